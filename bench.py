@@ -3,6 +3,7 @@
 configs[1]), 16 kHz output samples / s over the whole job + RTF.
 
     python bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR    # also write the last timed step's (audio, source) as DIR/<name>.npy
 
 N > 1 works both ways: under a launcher (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`, one rank per GPU over RCCL) and on its own --
@@ -69,7 +70,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-extra", action="store_true", help="skip extra_configs (configs[2] and configs[3])")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--dump-launches", default=None, help="write a per-shape table of the conv launches here")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's shard) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample beyond that)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------ self-launch
@@ -224,6 +231,7 @@ def run_bench(args, make_workload, backend="nccl", device=None):
     elapsed = parallel.barrier_max(time.perf_counter() - t0, dev)
     per_rank = parallel.gather_floats(1e3 * local / args.steps, dev)
     wl.check(out)
+    wl.last_out = out
 
     samples_per_step = n_utt * wl.samples_per_utterance
     audio_s_per_step = samples_per_step / 16000.0
@@ -249,6 +257,32 @@ def run_bench(args, make_workload, backend="nccl", device=None):
             import numpy as np
             result["event_median_ms"] = float(np.median([a.elapsed_time(b) for a, b in events]))
     return result, wl
+
+
+# ------------------------------------------------------------------------ output dump
+OUTPUT_NAMES = ("audio", "source")      # SynthesizerTrn.infer -> (o [B, 1, 320 T], e_ [B, 1, 4 T])
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, path, names=OUTPUT_NAMES, max_bytes=DUMP_MAX_BYTES):
+    """Write the arrays a caller of the timed step received as `path`/<name>.npy in float32.  When they exceed
+    `max_bytes` together, each array is cut to the same fraction of its elements, picked by a fixed seed (sorted
+    flat indices), so that two runs with the same arguments write the same positions.  Returns a description."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = [t.detach().float().cpu().numpy() for t in out]
+    total = sum(a.size * 4 for a in arrays)
+    keep = min(1.0, max_bytes / total)
+    desc = {"dir": path, "arrays": {}}
+    for name, a in zip(names, arrays):
+        entry = {"shape": list(a.shape), "dtype": "float32"}
+        if keep < 1.0:
+            n = int(a.size * keep)
+            entry["sample"] = f"{n} of {a.size} elements, seed 0, sorted flat indices"
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        desc["arrays"][name] = entry
+    return desc
 
 
 # ------------------------------------------------------------------------ roofline (vocoder, live)
@@ -559,6 +593,8 @@ def main(argv=None):
     import torch.distributed as dist
     if result is not None:
         _progress(f"timed region done: {result['ms_per_step']:.2f} ms per step")
+        if args.dump_outputs:
+            result["dump_outputs"] = dump_outputs(wl.last_out, args.dump_outputs)
         if not args.no_roofline:
             vocoder_roofline(args, wl, result)
             _progress(f"roofline pass done: frac {result['roofline']['frac']:.3f}")

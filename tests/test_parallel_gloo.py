@@ -26,7 +26,16 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _cpu_only_rank():
+    """These ranks are CPU stand-ins and must not open the GPU.  dist.barrier() asks torch._C._get_accelerator()
+    which device to use, and on a ROCm build that query counts devices, i.e. initialises HIP and opens the GPU in
+    every rank -- eight of them beside a test process that already holds the device are more than a shared GPU host
+    allows.  Answering "cpu" takes barrier()'s own CPU branch, which gloo runs anyway."""
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _worker(rank, world, port, out):
+    _cpu_only_rank()
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     from megatts2_hierspeechpp_amd import parallel
@@ -107,6 +116,7 @@ class _StandInWorkload:
 
 
 def _bench_worker(rank, world, port, out):
+    _cpu_only_rank()
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
@@ -142,6 +152,7 @@ def test_bench_control_flow_world2_cpu_stand_in():
 
 
 def _force_worker(port, out):
+    _cpu_only_rank()
     os.environ.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
     import bench
@@ -166,6 +177,7 @@ def test_force_dist_runs_the_collectives_at_world_size_1():
 
 
 def _bench_worker8(rank, world, port, out, global_batch):
+    _cpu_only_rank()
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port), OMP_NUM_THREADS="1")
     sys.path.insert(0, ROOT)
@@ -240,3 +252,57 @@ def test_bench_gpus_n_starts_its_own_ranks(tmp_path):
     assert argv[argv.index("--master-addr") + 1] == "127.0.0.1"
     assert argv[-4:] == ["--gpus", "2", "--steps", "4"] and argv[-5].endswith("bench.py")
     assert "some launcher chatter" in p.stderr            # everything else is relayed on stderr
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs / --steps on CPU
+class _CountingWorkload(_StandInWorkload):
+    """Each call of the step returns a new value: what run_bench keeps must be the last timed step's output."""
+
+    def make_step(self):
+        self.calls = 0
+
+        def step():
+            self.calls += 1
+            return (torch.full((2, 1, 6), float(self.calls)), torch.full((2, 1, 3), -float(self.calls)))
+        return step
+
+    def check(self, out):
+        pass
+
+
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """`--steps` is the number of timed steps (`ms_per_step` is their mean), the last timed step's outputs are what
+    `--dump-outputs` writes, float32, and --steps below 1 is refused."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    args = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "2",
+                             "--dump-outputs", str(tmp_path / "d")])
+    result, wl = bench.run_bench(args, _CountingWorkload, backend="gloo", device=torch.device("cpu"))
+    assert wl.calls == 2 + 4 and result["steps"] == 4 and result["ms_per_step"] > 0
+    desc = bench.dump_outputs(wl.last_out, args.dump_outputs)
+    audio, source = np.load(tmp_path / "d" / "audio.npy"), np.load(tmp_path / "d" / "source.npy")
+    assert audio.dtype == np.float32 and audio.shape == (2, 1, 6) and (audio == 6.0).all()
+    assert source.dtype == np.float32 and source.shape == (2, 1, 3) and (source == -6.0).all()
+    assert desc["arrays"]["audio"]["shape"] == [2, 1, 6] and "sample" not in desc["arrays"]["audio"]
+    json.dumps(desc)
+
+
+def test_bench_dump_outputs_sample_is_bounded_and_fixed(tmp_path):
+    """Outputs above the byte cap are cut to a seeded sample: under the cap in all, the same elements every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    out = (torch.arange(3000, dtype=torch.float32).view(3, 1, 1000), torch.arange(300, dtype=torch.float64).view(3, 1, 100))
+    written = []
+    for run in ("a", "b"):
+        desc = bench.dump_outputs(out, str(tmp_path / run), max_bytes=4000)
+        arrs = [np.load(tmp_path / run / f"{n}.npy") for n in bench.OUTPUT_NAMES]
+        assert all(a.dtype == np.float32 for a in arrs) and sum(a.nbytes for a in arrs) <= 4000
+        assert all("sample" in e for e in desc["arrays"].values())
+        written.append(arrs)
+    assert all(np.array_equal(x, y) for x, y in zip(*written))
+    audio = written[0][0]
+    assert len(audio) > 0 and np.all(np.diff(audio) > 0)       # sorted positions of the flat array, no repeats
