@@ -42,7 +42,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HSP_VERSION 102 /* 0.1.2: round 6 -- hsp_dftseg_pair_f32 takes the pass-through form (inv->y / inv->res); 0.1.1: round 5
+#define HSP_VERSION 102 /* unchanged by hsp_resample_f32, which only adds to the ABI; 0.1.2: round 6 -- hsp_dftseg_pair_f32 takes the pass-through form (inv->y / inv->res); 0.1.1: round 5
                            * -- hsp_dftseg_args grew a field (prod3); hsp_cprod3_f32, hsp_cprod3_supported,
                            * hsp_dftseg_weight_spectrum_f32, hsp_dftseg_supported are new */
 #define HSP_EINVAL (-1)
@@ -456,6 +456,23 @@ int hsp_zero_below_f32(const float* x, float thr, float* y, int64_t n, void* str
  * astype('int16') (inference_plm.py:183-190) */
 int hsp_peak_int16(const float* x, int64_t x_bs, const int64_t* lengths, float gain, int16_t* out, int64_t o_bs,
                    int32_t B, int64_t n, void* stream);
+
+/* ------------------------------------------------ prompt ingest: sinc resampling to 16 kHz
+ * torchaudio.functional.resample (0.13.1: _get_sinc_resample_kernel + _apply_sinc_resample_kernel) of the reference
+ * harnesses (inference_plm.py:124-126, inference.py:122-124, inference_vc.py:76-78,101-103, inference_speechsr.py:32-34):
+ *   y[b][i n + p] = sum_{j < n_taps} bank[p * n_taps + j] * xz[b][i o + tap0[p] + j - width],  i n + p < T_b,
+ *   xz[b] = x[b] on [0, len_b), zero elsewhere; T_b = ceil(n len_b / o); y[b][t] = 0 for T_b <= t < T_out.
+ * o / n = the two rates divided by their gcd; width and the compacted bank (per phase p the n_taps coefficients from
+ * tap k = tap0[p] of torchaudio's [n][K = 2 width + o] bank, zero-padded) come from the host builder
+ * (functional.sinc_resample_bank).  x rows of stride x_bs >= L, y rows of stride y_bs >= T_out (contiguous in time);
+ * lengths int64 [B] (device; NULL = all L): lengths[b] <= L is the caller's contract (values are clamped to [0, L]),
+ * as is 0 <= tap0[p] <= K - n_taps (clamped into that range).
+ * HSP_EINVAL: o, n < 1, gcd(o, n) != 1, n_taps < 1 or > K, T_out < ceil(n L / o), x_bs < L, y_bs < T_out, B > 65535,
+ * or a bank + tap0 + one frame's K input samples above 64 KB of LDS (n n_taps + n + K <= 16384 words; every rate pair
+ * of the reference's prompts -- 8 ... 96 kHz -- is far below). */
+int hsp_resample_f32(const float* x, int64_t x_bs, const int64_t* lengths, int32_t B, int32_t L, const float* bank,
+                     const int32_t* tap0, int32_t n_taps, int32_t o, int32_t n, int32_t width, float* y, int64_t y_bs,
+                     int32_t T_out, void* stream);
 
 /* ------------------------------------------------ prompt front-end */
 /* torchaudio MelSpectrogram as wrapped by MelSpectrogramFixed (Mels_preprocess.py:8-18; built with the

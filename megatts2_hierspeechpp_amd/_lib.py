@@ -165,6 +165,8 @@ SIGNATURES = {
     "hsp_add_cbias_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_zero_below_f32": (C.c_int, [_fp, C.c_float, _fp, C.c_int64, _fp]),
     "hsp_peak_int16": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
+    "hsp_resample_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, _fp, C.c_int64, C.c_int32, _fp]),
     "hsp_copy_strided_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32,
                                        _fp]),
     "hsp_conv1d_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),

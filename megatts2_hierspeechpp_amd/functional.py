@@ -264,3 +264,119 @@ def f0_convert(f0_src, f0_trg):
     L.check(L.lib().hsp_f0_convert_f32(L.fptr(s), s.numel(), L.fptr(t), t.numel(), L.fptr(out), L.stream_ptr()),
             "hsp_f0_convert_f32")
     return out.reshape(f0_src.shape)
+
+
+# ---------------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
+KAISER_BETA = 14.769656459379492   # torchaudio's beta for resampling_method="kaiser_window", beta=None
+
+
+class ResampleBank:
+    """The filter bank of one rate pair, as torchaudio builds it (full) and as the kernel reads it (compacted)."""
+
+    def __init__(self, o, n, width, full, bank, tap0):
+        self.o, self.n, self.width = o, n, width
+        self.K = 2 * width + o
+        self.full = full            # float64 [n, K]: torchaudio's bank before its fp32 cast
+        self.bank = bank            # float32 [n, n_taps]: taps tap0[p] ... tap0[p] + n_taps - 1 of phase p
+        self.tap0 = tap0            # int32 [n]
+        self.n_taps = bank.shape[1]
+
+    def out_length(self, length: int) -> int:
+        """torchaudio's target length ceil(n * length / o)."""
+        return -(-self.n * int(length) // self.o)
+
+
+def sinc_resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                       resampling_method: str = "sinc_interpolation", beta: Optional[float] = None) -> ResampleBank:
+    """torchaudio 0.13.1 _get_sinc_resample_kernel in float64 (phase / new_freq formed in fp32 first, as there), then
+    compacted: per phase only the taps whose argument t was not clamped to +-lowpass_filter_width are kept (a clamped tap
+    is sinc(+-lpw) * window(+-lpw), below 1e-15), padded with zeros to a common count n_taps."""
+    import math
+    import numpy as np
+    g = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // g, int(new_freq) // g
+    lpw = lowpass_filter_width
+    base = min(o, n) * rolloff
+    width = math.ceil(lpw * o / base)
+    K = 2 * width + o
+    idx = np.arange(-width, width + o, dtype=np.float64)[None, :] / o
+    ph = (np.arange(0, -n, -1, dtype=np.int64).astype(np.float32) / np.float32(n)).astype(np.float64)[:, None]
+    t_raw = (ph + idx) * base
+    t = np.clip(t_raw, -lpw, lpw)
+    if resampling_method == "sinc_interpolation":
+        window = np.cos(t * math.pi / lpw / 2) ** 2
+    elif resampling_method == "kaiser_window":
+        b_ = KAISER_BETA if beta is None else float(beta)
+        window = np.i0(b_ * np.sqrt(1 - (t / lpw) ** 2)) / np.i0(b_)
+    else:
+        raise L.HspError(f"unknown resampling_method {resampling_method!r} (sinc_interpolation or kaiser_window)")
+    t = t * math.pi
+    with np.errstate(invalid="ignore", divide="ignore"):
+        full = np.where(t == 0, 1.0, np.sin(t) / t)
+    full = full * window * (base / o)
+    sig = np.abs(t_raw) < lpw                       # unclamped taps: one contiguous run per phase
+    first = np.argmax(sig, axis=1)
+    count = sig.sum(axis=1)
+    n_taps = max(1, int(count.max()))
+    tap0 = np.minimum(first, K - n_taps).astype(np.int32)
+    cols = tap0[:, None] + np.arange(n_taps)[None, :]
+    rows = np.arange(n)[:, None]
+    bank = np.where(sig[rows, cols], full[rows, cols], 0.0).astype(np.float32)
+    return ResampleBank(o, n, width, full, np.ascontiguousarray(bank), tap0)
+
+
+_RESAMPLE_BANKS = {}
+
+
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+             resampling_method: str = "sinc_interpolation", beta: Optional[float] = None, lengths=None):
+    """torchaudio.functional.resample (0.13.1; same signature and defaults) on the GPU: one hsp_resample_f32 launch.
+
+    ``waveform`` [..., L] fp32 on the GPU -> [..., ceil(new * L / orig)] (gcd-reduced rates); the input tensor itself
+    when the two rates are equal.  ``lengths`` int64 [B] (B = rows of ``waveform.reshape(-1, L)``, device tensor,
+    each <= L) resamples a ragged batch: row b equals the call on ``waveform[b, :lengths[b]]`` alone, then zeros.
+    The reference harnesses pass ``resampling_method="kaiser_window"``; the default stays torchaudio's Hann window.
+
+    The bank is built on the host in float64 (``sinc_resample_bank``) and uploaded once per (rates, method, lpw,
+    rolloff, beta, device); a call inside a stream capture needs that upload done by an eager call first.
+    Pinned by the tests against a float64 restatement of torchaudio's formulas (max error 1e-5 at fp32) and against
+    an analytic band-limited sine; it has not been compared with torchaudio itself (not in this image).  torchaudio's
+    ``resample`` passes the waveform's dtype to its bank builder, so its own fp32 bank may be formed in fp32 arithmetic:
+    any difference from this float64 build is at the fp32 rounding of the coefficients (~1e-7 relative), unmeasured."""
+    for f in (orig_freq, new_freq):
+        if not float(f).is_integer() or f <= 0:
+            raise L.HspError(f"resample needs positive integer rates, got {orig_freq} -> {new_freq}")
+    if resampling_method not in ("sinc_interpolation", "kaiser_window"):
+        raise L.HspError(f"unknown resampling_method {resampling_method!r} (sinc_interpolation or kaiser_window)")
+    if not waveform.is_cuda:
+        raise L.HspError("resample runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if waveform.dtype != torch.float32:
+        raise L.HspError(f"resample expects float32, got {waveform.dtype}")
+    if int(orig_freq) == int(new_freq):
+        return waveform
+    key = (int(orig_freq), int(new_freq), resampling_method, int(lowpass_filter_width), float(rolloff),
+           None if beta is None else float(beta), waveform.device)
+    dev_bank = _RESAMPLE_BANKS.get(key)
+    if dev_bank is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.HspError("resample: the bank of this rate pair is not uploaded yet; make one eager call before "
+                             "capturing the stream")
+        hb = sinc_resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        dev_bank = (hb, torch.from_numpy(hb.bank).to(waveform.device), torch.from_numpy(hb.tap0).to(waveform.device))
+        _RESAMPLE_BANKS[key] = dev_bank
+    hb, bank, tap0 = dev_bank
+    shp = waveform.shape
+    Lx = shp[-1]
+    x = _c(waveform.reshape(-1, Lx))
+    B = x.shape[0]
+    T_out = hb.out_length(Lx)
+    y = torch.empty(B, T_out, dtype=torch.float32, device=x.device)
+    lens = None
+    if lengths is not None:
+        lens = _c(lengths.reshape(-1).to(device=x.device, dtype=torch.int64))
+        if lens.shape[0] != B:
+            raise L.HspError(f"resample: lengths has {lens.shape[0]} entries for {B} rows")
+    L.check(L.lib().hsp_resample_f32(L.fptr(x), x.stride(0), L.ptr(lens), B, Lx, L.fptr(bank), L.ptr(tap0), hb.n_taps,
+                                     hb.o, hb.n, hb.width, L.fptr(y), y.stride(0), T_out, L.stream_ptr()),
+            "hsp_resample_f32")
+    return y.reshape(*shp[:-1], T_out)

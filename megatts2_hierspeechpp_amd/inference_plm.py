@@ -1,19 +1,22 @@
 """HIP mirror of the tensor core of the reference's inference_plm.py (its ``tts()`` between mel
 extraction and wav writing, :156-190, and the model bundle of ``model_load`` :203-263).
 
-Out of scope here (host plumbing, not the hot path): text cleaning / phonemisation
-(``get_text``), audio file IO and resampling -- callers hand over phone ids and the prompt waveform (or its mels),
-exactly the tensors ``tts()`` feeds its models.  The prompt mel transform is ``Mels_preprocess.MelSpectrogramFixed``,
+The prompt file ingest (:120-126: ``torchaudio.load``, first channel, kaiser-window resampling to 16 kHz) is
+``audio.load`` + ``functional.resample`` (``tts_from_prompt_file``; ``tts_from_prompt(prompt_sr=...)``), and
+``scale_norm='prompt'`` (:127-128,185-186) is ``tts_from_prompt(scale_norm="prompt")``.  Out of scope here (host
+plumbing, not the hot path): text cleaning / phonemisation (``get_text``) -- callers hand over phone ids.  The prompt mel transform is ``Mels_preprocess.MelSpectrogramFixed``,
 the optional prompt denoiser ``denoiser.generator.MPNet`` + ``denoiser.infer.denoise`` (:142-147)."""
 from __future__ import annotations
 
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 from torch import nn
 
 from . import _lib as L
+from . import functional as Fh
 from .hierspeechpp_speechsynthesizer import SynthesizerTrn
 from .hip_layers import finalize as _finalize
 from .ttv_v1.t2w2v_transformer import Megatts2PLM1
@@ -99,14 +102,14 @@ def write_wav(path, sample_rate: int, pcm):
 @torch.no_grad()
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
-        return_float: bool = False):
+        return_float: bool = False, gain: float = 0.999):
     """inference_plm.py:tts :156-190 on tensors.
 
     text / tone / language int64 [B, N], text_length [B]; src_mel_ttv [B, 80, Tm'] (prompt mel for the
     front-end) with lengths; src_mel [2B, 80, Tm] = the B prompt mels followed by the B denoised prompt
     mels (the reference's ``torch.cat([audio, denoised])`` at B = 1) with ``src_length2`` [2B].
     Returns int16 audio [B, n] (n = 320 * frames, x3 / x1.5 with SpeechSR), rows peak-normalised over
-    their own length.  B > 1 runs the utterances side by side; rows are independent up to the
+    their own length (times ``gain``: 0.999, or the prompt's peak for scale_norm='prompt').  B > 1 runs the utterances side by side; rows are independent up to the
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
     B = text.shape[0]
@@ -132,21 +135,47 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         audio = models.sr(audio)
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
-    wav = peak_int16(audio, n_valid)
+    wav = peak_int16(audio, n_valid, gain)
     return (wav, audio) if return_float else wav
+
+
+@torch.no_grad()
+def prompt_peak(audio) -> float:
+    """``torch.max(audio.abs())`` of scale_norm='prompt' (inference_plm.py:127-128, inference_vc.py:104-105): the
+    reference takes it on the CPU copy of the 16 kHz prompt, so does this (one device-to-host copy of the prompt and a
+    host synchronise: not for use inside a captured graph)."""
+    return float(np.abs(audio.detach().cpu().numpy()).max())
+
+
+def output_gain(scale_norm: str, prompt_audio) -> float:
+    """The gain of the int16 conversion (inference_plm.py:185-188): 0.999 for 'max', the prompt's peak for 'prompt'.
+    A prompt whose peak is above 1 (full scale) is outside the contract: the reference's astype('int16') wraps such
+    samples around, hsp_peak_int16 saturates them."""
+    if scale_norm == "max":
+        return 0.999
+    if scale_norm == "prompt":
+        return prompt_peak(prompt_audio)
+    raise L.HspError(f"unknown scale_norm {scale_norm!r} ('max' or 'prompt')")
 
 
 @torch.no_grad()
 def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audio, output_path=None,
                     noise_scale_vc: float = 0.333, output_sr: int = 16000, dur=None, noise=None,
-                    denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None):
-    """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: prompt mels (:130-150, `prompt_mels`; with
-    ``denoise_ratio`` > 0 the second prompt mel comes from the denoised prompt and the style vectors are mixed by
-    voice_conversion_noise_control), text -> w2v / f0 -> waveform (`tts`), optional 16-bit WAV (:195-200).
-    text / tone / language int64 [1, N] on the GPU; prompt_audio fp32 [1, n] at 16 kHz on the GPU;
-    ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed.  Returns int16 [n_out]."""
+                    denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
+                    scale_norm: str = "max", return_float: bool = False):
+    """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
+    (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
+    comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
+    f0 -> waveform (`tts`), int16 with the gain of ``scale_norm`` (:185-188, `output_gain`: 'prompt' reads the prompt's
+    peak back to the host), optional 16-bit WAV (:195-200).
+    text / tone / language int64 [1, N] on the GPU; prompt_audio fp32 [1, n] at ``prompt_sr`` on the GPU;
+    ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed.  Returns int16 [n_out] (and the float audio with
+    ``return_float``)."""
     if denoise_ratio != 0 and denoiser is None:
         raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as inference_plm.py:144-147")
+    if int(prompt_sr) != 16000:
+        prompt_audio = Fh.resample(prompt_audio, prompt_sr, 16000, resampling_method="kaiser_window")
+    gain = output_gain(scale_norm, prompt_audio)
     src_mel_ttv, src_mel = prompt_mels(mel_fn, prompt_audio, denoiser if denoise_ratio != 0 else None, hps_denoiser)
     dev = prompt_audio.device
     B = text.shape[0]
@@ -154,8 +183,20 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
-    wav = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
-              noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur, noise=noise)[0]
+    wav, audio = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
+                     noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
+                     noise=noise, gain=gain, return_float=True)
+    wav = wav[0]
     if output_path is not None:
         write_wav(output_path, output_sr if output_sr in (24000, 48000) else 16000, wav)
-    return wav
+    return (wav, audio) if return_float else wav
+
+
+def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None, **kwargs):
+    """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
+    ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``kwargs`` go to
+    `tts_from_prompt`."""
+    from . import audio as A
+    prompt, rate = A.load(prompt_path)
+    return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
+                           prompt_sr=rate, **kwargs)

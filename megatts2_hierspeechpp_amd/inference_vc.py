@@ -2,16 +2,18 @@
 -> reflect pad 40 -> wav2vec2 hidden state 7 -> (with the source's and the prompt's F0 tracks) F0 conversion ->
 prompt mels -> ``voice_conversion_noise_control`` -> peak-normalised int16.
 
-Outside this module, as in inference_plm: audio file decoding / resampling (torchaudio plumbing) and the YAAPT pitch
-tracker (third-party ``amfm_decompy``, CPU numpy code, absent from this image): the F0 tracks are inputs here, at the
-tracker's rate of 200 Hz (4 per w2v frame), zeros where unvoiced."""
+File ingest (:76-78,98-103: ``torchaudio.load`` + kaiser-window resampling to 16 kHz) is ``load_source`` for the
+source and ``audio.load_16k`` for the target prompt; ``scale_norm='prompt'`` (:104-105,157-158) is
+``vc(scale_norm="prompt")``.  Outside this module: the YAAPT pitch tracker (third-party ``amfm_decompy``, CPU numpy
+code, absent from this image).  The F0 tracks are inputs here, computed by the caller from the 16 kHz audio (the padded
+source, the unpadded target) at the tracker's rate of 200 Hz (4 per w2v frame), zeros where unvoiced."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
 from . import functional as Fh
-from .inference_plm import peak_int16
+from .inference_plm import output_gain, peak_int16
 
 
 class VcModels(nn.Module):
@@ -39,13 +41,22 @@ def pad_source(audio, hop: int = 1280):
     return out
 
 
+def load_source(path, device):
+    """inference_vc.py:76-78: the source file at 16 kHz (``audio.load_16k``: channel 0, kaiser-window resampling),
+    padded by `pad_source` -> fp32 [1, Ls] on ``device``."""
+    from .audio import load_16k
+    return pad_source(load_16k(path, device))
+
+
 @torch.no_grad()
 def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noise_scale_vc=0.333, denoise_ratio=0.0,
-       denoised_audio=None, noise=None, return_float=False):
+       denoised_audio=None, noise=None, return_float=False, scale_norm="max"):
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which is
-    what the reference does at denoise_ratio == 0."""
+    what the reference does at denoise_ratio == 0.  ``scale_norm`` 'prompt': the int16 gain is the peak of
+    ``target_audio`` (inference_vc.py:104-105; read back to the host, see inference_plm.output_gain) instead of 0.999."""
+    gain = output_gain(scale_norm, target_audio)
     x_w2v = models.w2v(Fh.reflect_pad(source_audio, 40))                       # :85-86
     T = x_w2v.shape[2]
     x_length = torch.tensor([T], dtype=torch.int64, device=x_w2v.device)
@@ -58,5 +69,5 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     trg_len = torch.tensor([trg_mel.shape[2]] * 2, dtype=torch.int64, device=x_w2v.device)
     audio = models.voc.voice_conversion_noise_control(x_w2v, x_length, trg_mel, trg_len, lf0.reshape(1, -1)[:, :4 * T],
                                                       noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio, noise=noise)
-    wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device))
+    wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device), gain)
     return (wav.reshape(-1), audio) if return_float else wav.reshape(-1)
