@@ -225,6 +225,34 @@ int hsp_reflect_pad_f32(const float* x, int64_t x_bs, float* y, int32_t B, int32
  * elsewhere.  One utterance per call (the statistics are per utterance): f0_src [n_src], f0_trg [n_trg]. */
 int hsp_f0_convert_f32(const float* f0_src, int32_t n_src, const float* f0_trg, int32_t n_trg, float* out, void* stream);
 
+/* ------------------------------------------------ batched voice conversion (inference_vc.vc_batch; csrc/hsp_vcbatch.hip)
+ * Per-row-length forms of the single-utterance steps above and below.  Row lengths are device int64 [B] (values are
+ * clamped into [0, the buffer's capacity]), so a fixed-shape batch is capturable with no host read-back.
+ * hsp_reflect_pad_ragged_f32: y[b, t] = x[b, reflect(t - pad)] over t < len_b + 2 pad with the reflection at row b's
+ *   own end len_b (F.pad(x[b, :len_b], (pad, pad), "reflect")), y[b, t] = 0 on [len_b + 2 pad, Lo).  x rows of stride
+ *   x_bs >= L, y rows of stride y_bs >= Lo; Lo <= L + 2 pad, pad < L; lengths NULL = all L; pad < len_b is the
+ *   caller's contract.
+ * hsp_f0_convert_batch_f32: hsp_f0_convert_f32 on row b = (f0_src[b, :n_src[b]], f0_trg[b, :n_trg[b]]) into
+ *   out[b, :n_src[b]], zeros on out[b, n_src[b] : n_max); one launch, row b bit-identical to the single call.
+ *   f0_src rows of stride src_bs >= n_max, out rows of stride out_bs >= n_max, f0_trg rows of stride trg_bs
+ *   (0 = one track shared by every row; else >= nt_max) holding up to nt_max samples.
+ * hsp_stft_frames_ragged_f32: hsp_stft_frames_f32 with row b's own length len_b <= L: T_b = 1 + len_b / hop frames
+ *   reflecting at len_b, zero columns on [T_b, f_ld).  T = 1 + L / hop, x rows of stride x_bs >= L; len_b > n_fft / 2
+ *   is the caller's contract.  After hsp_power_mel_log_f32 (T_out = T - 1) mel row b has T_b - 1 valid frames.
+ * hsp_abs_max_rows_f32: out[b] = max_{i < len_b} |x[b, i]| (0 for an empty row); lengths NULL = all n.
+ * hsp_peak_int16_gains: hsp_peak_int16 with row b's gain read from gains[b] (device fp32 [B]). */
+int hsp_reflect_pad_ragged_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* y, int64_t y_bs, int32_t B,
+                               int32_t L, int32_t pad, int32_t Lo, void* stream);
+int hsp_f0_convert_batch_f32(const float* f0_src, int64_t src_bs, const int64_t* n_src, const float* f0_trg,
+                             int64_t trg_bs, const int64_t* n_trg, int32_t nt_max, float* out, int64_t out_bs,
+                             int32_t B, int32_t n_max, void* stream);
+int hsp_stft_frames_ragged_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* window, float* frames,
+                               int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t T, int32_t f_ld, void* stream);
+int hsp_abs_max_rows_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* out, int32_t B, int64_t n,
+                         void* stream);
+int hsp_peak_int16_gains(const float* x, int64_t x_bs, const int64_t* lengths, const float* gains, int16_t* out,
+                         int64_t o_bs, int32_t B, int64_t n, void* stream);
+
 /* ----------------------------------------------- prompt denoiser (MP-SENet) */
 /* The parts of denoiser/ that are neither convolutions nor GEMMs (those run on hsp_conv1d_mfma_f32 /
  * hsp_conv1d_direct_f32 / hsp_mha_f32 / hsp_layernorm_mod_f32).  One utterance per call, as the reference

@@ -78,8 +78,13 @@ class MelSpectrogramFixed(nn.Module):
 
     @_entry
     @torch.no_grad()
-    def forward(self, x):
-        """x [..., L] fp32 on the GPU (L > n_fft / 2) -> log-mel [..., n_mels, L // hop_length]."""
+    def forward(self, x, lengths=None):
+        """x [..., L] fp32 on the GPU (L > n_fft / 2) -> log-mel [..., n_mels, L // hop_length].
+
+        With ``lengths`` (int64 [B], x [B, L] holding B zero-padded rows of lengths[b] > n_fft / 2 samples): every row
+        is framed at its own length (reflecting at lengths[b], ``hsp_stft_frames_ragged_f32``) and the call returns
+        (mels [B, n_mels, L // hop_length], mel lengths [B] = lengths // hop_length); frames past a row's mel length
+        are don't-care.  Over its valid frames row b equals the call on x[b, :lengths[b]] alone."""
         if self._window is None:
             raise L.HspError("MelSpectrogramFixed used before finalize(device)")
         if not x.is_cuda or x.dtype != torch.float32:
@@ -92,8 +97,16 @@ class MelSpectrogramFixed(nn.Module):
         T = 1 + Ls // self.hop_length
         f_ld = (T + 3) & ~3
         frames = torch.empty(B, self.n_fft, f_ld, dtype=torch.float32, device=xs.device)  # pitch columns zeroed by the kernel
-        L.check(L.lib().hsp_stft_frames_f32(L.fptr(xs), L.fptr(self._window), L.fptr(frames), B, Ls, self.n_fft,
-                                            self.hop_length, T, f_ld, L.stream_ptr()), "hsp_stft_frames_f32")
+        if lengths is None:
+            L.check(L.lib().hsp_stft_frames_f32(L.fptr(xs), L.fptr(self._window), L.fptr(frames), B, Ls, self.n_fft,
+                                                self.hop_length, T, f_ld, L.stream_ptr()), "hsp_stft_frames_f32")
+        else:
+            if x.dim() != 2 or lengths.shape != (B,):
+                raise L.HspError("MelSpectrogramFixed: lengths need x [B, L] and lengths [B]")
+            lengths = lengths.to(torch.int64).contiguous()
+            L.check(L.lib().hsp_stft_frames_ragged_f32(L.fptr(xs), xs.stride(0), L.ptr(lengths), L.fptr(self._window),
+                                                       L.fptr(frames), B, Ls, self.n_fft, self.hop_length, T, f_ld,
+                                                       L.stream_ptr()), "hsp_stft_frames_ragged_f32")
         spec = self.dft(frames)                                   # [B, 2 n_freqs, f_ld]: real | imaginary rows
         T_out = T - 1                                             # the wrapper drops the last frame
         out = torch.empty(B, self.n_mels, max(T_out, 0), dtype=torch.float32, device=xs.device)
@@ -101,4 +114,5 @@ class MelSpectrogramFixed(nn.Module):
             L.check(L.lib().hsp_power_mel_log_f32(L.fptr(spec), spec.stride(0), spec.stride(1), L.fptr(self._fb),
                                                   L.ptr(self._lo), L.ptr(self._hi), L.fptr(out), B, self.n_freqs,
                                                   self.n_mels, T_out, 0.001, L.stream_ptr()), "hsp_power_mel_log_f32")
-        return out.reshape(*lead, self.n_mels, max(T_out, 0))
+        out = out.reshape(*lead, self.n_mels, max(T_out, 0))
+        return out if lengths is None else (out, lengths // self.hop_length)

@@ -150,6 +150,14 @@ SIGNATURES = {
     "hsp_act_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int32, _fp]),
     "hsp_reflect_pad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_f0_convert_f32": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp]),
+    "hsp_reflect_pad_ragged_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, _fp]),
+    "hsp_f0_convert_batch_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int32, _fp, C.c_int64, C.c_int32,
+                                           C.c_int32, _fp]),
+    "hsp_stft_frames_ragged_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, _fp]),
+    "hsp_abs_max_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int64, _fp]),
+    "hsp_peak_int16_gains": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
     "hsp_sum_sq_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "hsp_mag_pha_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, C.c_float, _fp]),
     "hsp_instnorm_prelu_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int64, _fp, _fp, _fp, C.c_float, _fp]),

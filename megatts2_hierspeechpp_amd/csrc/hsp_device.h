@@ -109,3 +109,79 @@ __device__ __forceinline__ void hsp_epilogue_store(const hsp_conv1d_args& a, int
   if (a.accumulate) v += *yp;
   *yp = v * a.post_scale;
 }
+
+// F0 conversion of inference_vc.py:80-81,104-105 for one utterance, by one 256-thread workgroup: voiced statistics of
+// both tracks in double (the reference's numpy float32 mean / std differ from the exact values by ~1e-7 relative;
+// double keeps this side at the exact ones), then the conversion of src[0, ns) into out[0, ns) and zeros on
+// out[ns, n_out).  hsp_f0_convert_f32 and each row of hsp_f0_convert_batch_f32 run this one function, so a batch row is
+// bit-identical to the single-utterance call on that row.
+__device__ __forceinline__ void hsp_f0_convert_row(const float* src, int ns, const float* trg, int nt, float* out,
+                                                   int n_out) {
+  __shared__ double red[4][256];
+  __shared__ double stat[4];
+  double s1 = 0, c1 = 0, s2 = 0, c2 = 0;
+  for (int i = threadIdx.x; i < ns; i += 256) if (src[i] != 0.0f) { s1 += src[i]; c1 += 1; }
+  for (int i = threadIdx.x; i < nt; i += 256) if (trg[i] != 0.0f) { s2 += trg[i]; c2 += 1; }
+  red[0][threadIdx.x] = s1; red[1][threadIdx.x] = c1; red[2][threadIdx.x] = s2; red[3][threadIdx.x] = c2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
+    __syncthreads();
+  }
+  const double m1 = red[1][0] > 0 ? red[0][0] / red[1][0] : 0.0, m2 = red[3][0] > 0 ? red[2][0] / red[3][0] : 0.0;
+  const double n1 = red[1][0], n2 = red[3][0];
+  __syncthreads();
+  double v1 = 0, v2 = 0;
+  for (int i = threadIdx.x; i < ns; i += 256) if (src[i] != 0.0f) { const double d = src[i] - m1; v1 += d * d; }
+  for (int i = threadIdx.x; i < nt; i += 256) if (trg[i] != 0.0f) { const double d = trg[i] - m2; v2 += d * d; }
+  red[0][threadIdx.x] = v1; red[2][threadIdx.x] = v2;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[2][threadIdx.x] += red[2][threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stat[0] = m1; stat[1] = n1 > 0 ? sqrt(red[0][0] / n1) : 1.0; stat[2] = m2; stat[3] = n2 > 0 ? sqrt(red[2][0] / n2) : 0.0;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_out; i += 256) {
+    float o = 0.0f;
+    if (i < ns && src[i] != 0.0f) {
+      // the reference's steps, in float64 like its numpy arrays (get_yaapt_f0 works on float64), then the float32 cast
+      // of torch.FloatTensor(f0 + 1) and a float32 log
+      const double z = ((double)src[i] - stat[0]) / stat[1];
+      const double f = fmax(z * stat[3] + stat[2], 0.0);
+      o = logf((float)(f + 1.0));
+    }
+    out[i] = o;
+  }
+}
+
+// max |x[0, n)| of one row by a 1024-thread workgroup (wave64 butterfly, then the 16 wave maxima through LDS)
+__device__ __forceinline__ float hsp_block_abs_max_1024(const float* __restrict__ xb, int64_t n) {
+  __shared__ float red[16];
+  const int tid = threadIdx.x;
+  float mx = 0.0f;
+  for (int64_t i = tid; i < n; i += 1024) mx = fmaxf(mx, fabsf(xb[i]));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  mx = red[0];
+#pragma unroll
+  for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
+  return mx;
+}
+
+// ob[i] = (int16)(xb[i] / max_{j < L} |xb[j]| * 32767 * gain) for i < L, 0 for L <= i < n, by a 1024-thread workgroup:
+// `audio / max(abs(audio)) * 32767.0 * gain` then numpy's truncating astype(int16) (inference_plm.py:186).
+// hsp_peak_int16 and hsp_peak_int16_gains both run this function, so equal gains give equal rows.
+__device__ __forceinline__ void hsp_peak_int16_row(const float* __restrict__ xb, int64_t L, float gain,
+                                                   int16_t* __restrict__ ob, int64_t n) {
+  const float mx = hsp_block_abs_max_1024(xb, L);
+  for (int64_t i = threadIdx.x; i < n; i += 1024) {
+    float v = 0.0f;
+    if (i < L) v = xb[i] / mx * 32767.0f * gain;
+    ob[i] = (int16_t)fminf(fmaxf(v, -32768.0f), 32767.0f);
+  }
+}

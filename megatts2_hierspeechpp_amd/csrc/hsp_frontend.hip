@@ -212,25 +212,9 @@ __global__ __launch_bounds__(256) void zero_below_kernel(const float* __restrict
 __global__ __launch_bounds__(1024) void peak_int16_kernel(const float* __restrict__ x, int64_t x_bs,
                                                           const int64_t* __restrict__ len, float gain,
                                                           int16_t* __restrict__ out, int64_t o_bs, int64_t n) {
-  __shared__ float red[16];
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.x;
   const int64_t L = len ? min(n, max((int64_t)0, len[b])) : n;
-  const float* xb = x + b * x_bs;
-  float mx = 0.0f;
-  for (int64_t i = tid; i < L; i += 1024) mx = fmaxf(mx, fabsf(xb[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
-  int16_t* ob = out + b * o_bs;
-  for (int64_t i = tid; i < n; i += 1024) {
-    float v = 0.0f;
-    if (i < L) v = xb[i] / mx * 32767.0f * gain;
-    ob[i] = (int16_t)fminf(fmaxf(v, -32768.0f), 32767.0f);
-  }
+  hsp_peak_int16_row(x + b * x_bs, L, gain, out + b * o_bs, n);
 }
 
 

@@ -13,7 +13,10 @@ checkpoint keys ``wav2vec2.wav2vec2.*`` load unchanged):
                     so no final LayerNorm and no layer >= `layer` is ever run -- their checkpoint keys (and the
                     quantizer / projection heads of the pre-training model) are skipped on load.
 
-No attention mask: the harness feeds one utterance (B utterances of equal length work the same way)."""
+No attention mask for one utterance (B utterances of equal length work the same way).  ``forward(x, lengths)`` runs a
+ragged batch (vc_batch): the feature encoder's valid convolutions give a row's first T_b frames from its own samples
+only; frames >= T_b are zeroed before the positional conv (a solo call sees zero padding there) and masked out as keys
+of every attention, so row b over frames < T_b equals the call on that row alone."""
 from __future__ import annotations
 
 import torch
@@ -101,10 +104,11 @@ class _EncoderLayer(nn.Module):
         self.attention.qkv.fuse_input_layernorm(self.layer_norm)
         self.feed_forward.intermediate_dense.fuse_input_layernorm(self.final_layer_norm)
 
-    def forward(self, x):
+    def forward(self, x, mask=None):
         C = x.shape[1]
         qkv = self.attention.qkv(x)                       # LayerNorm fused into the stacked q / k / v GEMM
-        o = Fh.mha(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.attention.heads, self.attention.scale)
+        o = Fh.mha(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.attention.heads, self.attention.scale,
+                   mask_q=mask, mask_k=mask)
         x = self.attention.out_proj(o, res=x)
         h = self.feed_forward.intermediate_dense(x, act=L.ACT_GELU_ERF)
         return self.feed_forward.output_dense(h, res=x)
@@ -158,14 +162,30 @@ class Wav2vec2(nn.Module):
         self.arena = _finalize(self, device, materialize)
         return self
 
+    @staticmethod
+    def frames(samples):
+        """Frames of the feature encoder for ``samples`` input samples (an int, or an int64 tensor of row lengths):
+        the output length of its 7 valid strided convs."""
+        for k, s in zip(CONV_KERNEL, CONV_STRIDE):
+            samples = (samples - k) // s + 1
+        return samples
+
     @_entry
     @torch.no_grad()
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """x [B, 1, t] or [B, t] -> hidden state ``layer`` [B, 1024, T].  ``lengths`` (int64 [B], samples of each row,
+        <= t): row b over its first ``frames(lengths[b])`` frames equals the call on x[b, :lengths[b]] alone; the
+        frames after are don't-care."""
         m = self.wav2vec2.wav2vec2
         if x.dim() == 2:
             x = x.unsqueeze(1)
         h = m.feature_projection(m.feature_extractor(x))
+        mask = None
+        if lengths is not None:
+            mask = Fh.sequence_mask(self.frames(lengths.to(torch.int64)), h.shape[2])   # [B, 1, T]
+            h = Fh.mask_mul(h, mask)
+            mask = mask.reshape(h.shape[0], h.shape[2])
         h = m.encoder.pos_conv_embed.conv(h)              # h + GELU(pos_conv(h))
         for layer in m.encoder.layers:
-            h = layer(h)
+            h = layer(h, mask)
         return h

@@ -266,6 +266,55 @@ def f0_convert(f0_src, f0_trg):
     return out.reshape(f0_src.shape)
 
 
+# ---------------------------------------------------------------- batched voice conversion (ragged rows, device lengths)
+def _lengths(lengths):
+    return _c(lengths.to(torch.int64))
+
+
+def reflect_pad_ragged(x, lengths, pad: int):
+    """Row b of x [B, L] -> F.pad(x[b, :lengths[b]], (pad, pad), "reflect"), zero after lengths[b] + 2 pad: [B, L + 2 pad]."""
+    assert x.dim() == 2 and x.stride(1) == 1
+    B, Lx = x.shape
+    y = torch.empty(B, Lx + 2 * pad, dtype=torch.float32, device=x.device)
+    L.check(L.lib().hsp_reflect_pad_ragged_f32(L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)), L.fptr(y), y.stride(0), B,
+                                               Lx, pad, Lx + 2 * pad, L.stream_ptr()), "hsp_reflect_pad_ragged_f32")
+    return y
+
+
+def f0_convert_batch(f0_src, n_src, f0_trg, n_trg):
+    """`f0_convert` per row in one launch: f0_src [B, N] with n_src [B] valid samples, f0_trg [B, Nt] (or [1, Nt]: one
+    track shared by every row) with n_trg [B] -> [B, N], zero after n_src[b].  Row b equals f0_convert on that row's
+    tracks bit for bit."""
+    s, t = _c(f0_src), _c(f0_trg)
+    B, N = s.shape
+    assert t.dim() == 2 and t.shape[0] in (1, B)
+    out = torch.empty(B, N, dtype=torch.float32, device=s.device)
+    L.check(L.lib().hsp_f0_convert_batch_f32(L.fptr(s), s.stride(0), L.ptr(_lengths(n_src)), L.fptr(t),
+                                             0 if t.shape[0] == 1 else t.stride(0), L.ptr(_lengths(n_trg)), t.shape[1],
+                                             L.fptr(out), out.stride(0), B, N, L.stream_ptr()), "hsp_f0_convert_batch_f32")
+    return out
+
+
+def abs_max_rows(x, lengths=None):
+    """max |x[b, :lengths[b]]| of every row of x [B, n] -> fp32 [B] on the device (no host read-back)."""
+    assert x.dim() == 2 and x.stride(1) == 1
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    L.check(L.lib().hsp_abs_max_rows_f32(L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None,
+                                         L.fptr(out), x.shape[0], x.shape[1], L.stream_ptr()), "hsp_abs_max_rows_f32")
+    return out
+
+
+def peak_int16_gains(audio, lengths, gains):
+    """inference_plm.peak_int16 with a per-row device gain: [B, 1, n] / [B, n] fp32, gains fp32 [B] -> int16 [B, n]."""
+    a = audio.reshape(audio.shape[0], -1)
+    assert a.stride(1) == 1 and gains.shape == (a.shape[0],)
+    out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
+    L.check(L.lib().hsp_peak_int16_gains(L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None,
+                                         L.fptr(_c(gains)), L.ptr(out), out.stride(0), a.shape[0], a.shape[1],
+                                         L.stream_ptr()), "hsp_peak_int16_gains")
+    return out
+
+
 # ---------------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
 KAISER_BETA = 14.769656459379492   # torchaudio's beta for resampling_method="kaiser_window", beta=None
 

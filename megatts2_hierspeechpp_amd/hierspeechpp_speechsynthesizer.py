@@ -629,19 +629,34 @@ class SynthesizerTrn(nn.Module):
 
     @_entry
     @torch.no_grad()
+    def style_vector(self, trg_mel, trg_length, denoise_ratio=0):
+        """The style vector of voice_conversion_noise_control (:684-689): trg_mel [2B, 80, T] = B prompts, then the B
+        denoised prompts -> (1 - denoise_ratio) emb_g(prompt) + denoise_ratio emb_g(denoised) [B, 256, 1]."""
+        B = trg_mel.shape[0] // 2
+        trg_mask = commons.sequence_mask(trg_length, trg_mel.size(2))
+        g = self.emb_g(trg_mel, trg_mask)  # [2B, 256]
+        return Fh.axpby(g[:B], g[B:], 1.0 - denoise_ratio, float(denoise_ratio)).unsqueeze(-1)
+
+    @_entry
+    @torch.no_grad()
     def voice_conversion_noise_control(self, src, src_length, trg_mel, trg_length, f0, noise_scale=0.333,
-                                       uncond=False, denoise_ratio=0, noise: Optional[torch.Tensor] = None):
+                                       uncond=False, denoise_ratio=0, noise: Optional[torch.Tensor] = None,
+                                       style: Optional[torch.Tensor] = None):
         """:674-699.  trg_mel holds two prompts (original, denoised); their style vectors
         are interpolated with ``denoise_ratio`` (B = 1 by construction in the reference, SURVEY.md
         App. B1).  With B source utterances trg_mel is [2B, 80, T]: the B prompts, then the B denoised
-        prompts, and f0 is [B, 1, 4T]."""
+        prompts, and f0 is [B, 1, 4T].  ``style`` [B, 256, 1]: that interpolated style vector, precomputed
+        (inference_vc.vc_batch takes it per distinct prompt at the prompt's own length); emb_g and the
+        interpolation are skipped and trg_mel / trg_length are not read."""
         if uncond and not self.cfg:   # the reference evaluates self.emb here (:693-695) and then does not use the result
             raise AttributeError("'SynthesizerTrn' object has no attribute 'emb' (uncond needs a model built with cfg=True)")
         B = src.shape[0]
-        assert trg_mel.shape[0] == 2 * B
-        trg_mask = commons.sequence_mask(trg_length, trg_mel.size(2))
-        g = self.emb_g(trg_mel, trg_mask)  # [2B, 256]
-        g = Fh.axpby(g[:B], g[B:], 1.0 - denoise_ratio, float(denoise_ratio)).unsqueeze(-1)
+        if style is not None:
+            assert style.dim() == 3 and style.shape[0] == B and style.shape[2] == 1, style.shape
+            g = style
+        else:
+            assert trg_mel.shape[0] == 2 * B
+            g = self.style_vector(trg_mel, trg_length, denoise_ratio)
         y_mask = commons.sequence_mask(src_length, src.size(2))
         z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale)
         return self._decode(z, g)[0]
