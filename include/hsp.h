@@ -42,7 +42,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HSP_VERSION 102 /* unchanged by hsp_resample_f32, which only adds to the ABI; 0.1.2: round 6 -- hsp_dftseg_pair_f32 takes the pass-through form (inv->y / inv->res); 0.1.1: round 5
+#define HSP_VERSION 102 /* unchanged by hsp_resample_f32 and hsp_act1d_snakebeta_ragged_f32, which only add to the ABI.
+                           * NOT purely additive: hsp_mha_proj_args and hsp_dftseg_args grew a trailing field each (key_len,
+                           * act_len; NULL = the former behaviour) for the row-exact ragged vocoder -- a caller compiled
+                           * against an older header passes shorter structs and must be rebuilt (the version number is pinned by the suite's ABI test); 0.1.2: round 6 -- hsp_dftseg_pair_f32 takes the pass-through form (inv->y / inv->res); 0.1.1: round 5
                            * -- hsp_dftseg_args grew a field (prod3); hsp_cprod3_f32, hsp_cprod3_supported,
                            * hsp_dftseg_weight_spectrum_f32, hsp_dftseg_supported are new */
 #define HSP_EINVAL (-1)
@@ -297,6 +300,11 @@ int hsp_istft_ola_f32(const float* frames, int64_t f_ld, const float* window, fl
 int hsp_act1d_snakebeta_f32(const float* x, float* y, int32_t B, int32_t C, int32_t L,
                             const float* alpha_exp, const float* beta_inv, const float* filt,
                             void* stream);
+/* The same on a ragged batch: row b is valid over [0, lens[b]) (device int64 [B], clamped to [1, L]).  Reads clamp at
+ * lens[b] - 1 -- the replicate pad of the call on the row cut to that length, which row b then equals -- and the
+ * outputs at t >= lens[b] are written as 0.  Needs L % 4 == 0 and 16-B aligned x, y (else HSP_EINVAL). */
+int hsp_act1d_snakebeta_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t L, const int64_t* lens,
+                                   const float* alpha_exp, const float* beta_inv, const float* filt, void* stream);
 /* per-channel constants of SnakeBeta(alpha_logscale=True): activations.py:113-117 */
 int hsp_snake_consts_f32(const float* alpha_log, const float* beta_log, float* alpha_exp,
                          float* beta_inv, int32_t C, void* stream);
@@ -358,9 +366,11 @@ int hsp_mha_f32(const hsp_mha_args* a, void* stream);
  * = scaled_dot_product_attention + out_proj + the residual add of the Mega-TTS2 PLM layer
  * (ttv_v1/transformer_mega.py:63-87,121-123: 4 heads x 69) and timm Attention's softmax(q k^T) v + proj followed by
  * `x + gate_msa * attn(.)` of a DiT block (modules.py:397,409: 2 heads x 96).  Any Tk >= 4 (up to 2^20): rows of up to 256
- * keys take the one-pass form, longer ones stream the keys in groups with an online softmax (tested to 1 000 keys).  NO
- * masks inside the softmax -- neither key / query masks nor a dense or causal attn_mask: a caller that needs one uses
- * hsp_mha_f32 (mask_q / mask_k / mask_dense) and the projection as two launches.
+ * keys take the one-pass form, longer ones stream the keys in groups with an online softmax (tested to 1 000 keys).
+ * key_len (optional, device int64 [B]): the softmax of utterance b covers keys [0, key_len[b]) only (clamped to [1, Tk]);
+ * 64-key groups past it are skipped -- a ragged batch whose rows equal their B = 1 runs.  No other mask inside the
+ * softmax -- neither query masks nor a dense or causal attn_mask: a caller that needs one uses hsp_mha_f32
+ * (mask_q / mask_k / mask_dense) and the projection as two launches.
  * q / k / v: element (b, c, t) at base + b * bs + c * cs + t (channel-major; a batch may sit side by side on the columns
  * of one [C][B * T] matrix: bs = T, cs = row pitch).  wt = the nn.Linear / 1x1-conv weight AS STORED, [M][H D] row-major
  * with row pitch wt_ld (M == H D).  y / res: element (b, m, i) at base + b * bs + m * cs + i * ts, so that the
@@ -385,6 +395,7 @@ typedef struct hsp_mha_proj_args {
   float* y;
   int64_t y_bs, y_cs, y_ts;
   int32_t debug; /* must be 0 (tuning build only, as hsp_conv1d_args.debug) */
+  const int64_t* key_len; /* [B] keys per utterance, or NULL: all Tk */
 } hsp_mha_proj_args;
 int hsp_mha_proj_f32(const hsp_mha_proj_args* a, void* stream);
 int hsp_mha_proj_supported(int32_t H, int32_t D, int32_t M, int32_t Tk);
@@ -396,6 +407,11 @@ int hsp_mask_mul_f32(const float* x, const float* mask, float* y, int32_t B, int
 /* y = F.interpolate(x, Lout, mode='linear') along T (align_corners=False), fp32 index arithmetic
  * bit-compatible with torch-CPU: speechsr48k/speechsr.py:96 */
 int hsp_linear_interp_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout, void* stream);
+/* The same on a ragged batch (SpeechSR in row-exact mode): row b has lin[b] valid inputs and lout[b] valid outputs
+ * (device int64 [B]); output t < lout[b] is the call on the row alone when Lin / Lout is that call's ratio (its upper
+ * neighbour clamps at lin[b] - 1), outputs t >= lout[b] are 0. */
+int hsp_linear_interp_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout,
+                                 const int64_t* lin, const int64_t* lout, void* stream);
 /* y = a*x + b*z elementwise (style interpolation, hierspeechpp_speechsynthesizer.py:682) */
 int hsp_axpby_f32(const float* x, const float* z, float* y, float a, float b, int64_t n, void* stream);
 
@@ -562,6 +578,10 @@ typedef struct hsp_dftseg_args {
    * transforms of the even / odd samples at bin 0 -- instead of (DC, Nyquist) = (E0 + O0, E0 - O0).  0 = the layout above
    * (the [2C x 2C] block product on hsp_conv1d_mfma_f32). */
   int32_t prod3;
+  /* forward with act_* (and the forward half of the pair launch): device int64 [B] valid lengths, or NULL.  Row b's
+   * activation clamps its reads at act_len[b] - 1 and the transformed input is zero from act_len[b] on: the forward of
+   * the row cut to that length (the ragged activation of hsp_act1d_snakebeta_ragged_f32). */
+  const int64_t* act_len;
 } hsp_dftseg_args;
 int hsp_dftseg_fwd_f32(const hsp_dftseg_args* a, void* stream);
 int hsp_dftseg_inv_f32(const hsp_dftseg_args* a, void* stream);

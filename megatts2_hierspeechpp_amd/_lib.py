@@ -74,6 +74,7 @@ class MhaProjArgs(C.Structure):
         ("bias", _fp), ("mask", _fp), ("mask_bs", C.c_int64), ("cscale", _fp), ("cscale_bs", C.c_int64),
         ("res", _fp), ("res_bs", C.c_int64), ("res_cs", C.c_int64), ("res_ts", C.c_int64),
         ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64), ("y_ts", C.c_int64), ("debug", C.c_int32),
+        ("key_len", _fp),
     ]
 
 
@@ -88,6 +89,7 @@ class DftSegArgs(C.Structure):
         ("bias", _fp), ("res", _fp), ("res_bs", C.c_int64), ("res_cs", C.c_int64),
         ("accumulate", C.c_int32), ("post_scale", C.c_float),
         ("act_alpha_exp", _fp), ("act_beta_inv", _fp), ("act_filt", _fp), ("prod3", C.c_int32),
+        ("act_len", _fp),
     ]
 
 
@@ -110,6 +112,7 @@ SIGNATURES = {
     "hsp_conv1d_direct_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),
     "hsp_conv1d_mfma_plan": (C.c_int, [C.POINTER(Conv1dArgs), C.POINTER(C.c_int32 * 4)]),
     "hsp_act1d_snakebeta_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
+    "hsp_act1d_snakebeta_ragged_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
     "hsp_snake_consts_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, _fp]),
     "hsp_fold_weight_norm_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, _fp]),
     "hsp_gather_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
@@ -133,6 +136,7 @@ SIGNATURES = {
     "hsp_masked_mean_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_mask_mul_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_linear_interp_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "hsp_linear_interp_ragged_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     "hsp_axpby_f32": (C.c_int, [_fp, _fp, _fp, C.c_float, C.c_float, C.c_int64, _fp]),
     "hsp_plm_embed_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32, C.c_int32,
                                     _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp]),

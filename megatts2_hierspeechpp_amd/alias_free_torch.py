@@ -8,6 +8,7 @@ from torch import nn
 
 from . import _lib as L
 from . import functional as Fh
+from . import hip_layers
 from .hip_layers import HipLayer
 from .synth import kaiser_sinc_filter12
 
@@ -60,4 +61,5 @@ class Activation1d(HipLayer):
     def forward(self, x):
         if self._ea is None:
             raise L.HspError("Activation1d used before finalize()")
-        return Fh.act1d(x, self._ea, self._binv, self._filt)
+        rows = hip_layers.row_lengths()   # a row-exact ragged batch: the ragged launch at this tensor's resolution
+        return Fh.act1d(x, self._ea, self._binv, self._filt, lens=None if rows is None else rows.at(x.shape[2]))

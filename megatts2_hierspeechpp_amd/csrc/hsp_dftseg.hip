@@ -191,27 +191,40 @@ __device__ __forceinline__ void da_fence() { asm volatile("" ::: "memory"); }
 struct DaItem {
   int pa, pb, pa4, nsg, nsegs;                                  // outputs [pa, pb) of every row, segments of DA_SEG from pa4
 };
-__device__ __forceinline__ DaItem da_item(const hsp_dftseg_args& a, const DsItem& I, const DsStage& s) {
+// RAG (hsp_dftseg_args.act_len): the row of item I is valid over [0, lb): the activation clamps at lb - 1 and the
+// stretch holds zeros from lb on (the conv's zero padding of the row cut to lb).  RAG = false: lb is a.L.
+template <bool RAG = false>
+__device__ __forceinline__ DaItem da_item(const hsp_dftseg_args& a, const DsItem& I, const DsStage& s, int lb = 0) {
+  const int L = RAG ? lb : a.L;
   DaItem A;
   A.pa = max(s.t0, 0);
-  A.pb = min(s.t0 + s.len, a.L);
+  A.pb = min(s.t0 + s.len, L);
   A.pa4 = A.pa & ~3;
   A.nsg = (A.pb - A.pa4 + DA_SEG - 1) / DA_SEG;
   A.nsegs = I.ncg * A.nsg;
+  if constexpr (RAG) {                                          // an item wholly past the row's end: no segment
+    A.nsg = max(A.nsg, 1);
+    A.nsegs = A.pb > A.pa ? I.ncg * A.nsg : 0;
+  }
   return A;
 }
 // the raw window of segment sI (clamped to the item's last one: always a legal address, no branch around the load)
+template <bool RAG = false>
 __device__ __forceinline__ ds_f32x4 da_load(const hsp_dftseg_args& a, const DsItem& I, const DaItem& A, int sI, int lane) {
-  const int q = min(sI, A.nsegs - 1), ch = q / A.nsg, p0 = A.pa4 + DA_SEG * (q - ch * A.nsg);
+  const int q = RAG ? max(min(sI, A.nsegs - 1), 0) : min(sI, A.nsegs - 1), ch = q / A.nsg, p0 = A.pa4 + DA_SEG * (q - ch * A.nsg);
   const float* xr = a.x + (int64_t)I.b * a.x_bs + (int64_t)(I.c0 + ch) * a.x_cs;
   return *reinterpret_cast<const ds_f32x4*>(xr + hsp_clampi(p0 - 8 + 4 * lane, 0, a.L - 4));
 }
 // one segment: raw window in registers -> act -> the stretch (row[j + sh] = act(x)[t0 + j] for t0 + j in [pa, pb))
+// RAG: `last` points at the row's last valid input x[lb - 1] (global memory or LDS), replicated from lb on
+template <bool RAG = false>
 __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeom& G, const DsItem& I, const DsStage& s,
                                            const DaItem& A, int sI, int lane, ds_f32x4 rv, float* slice, float* buf,
-                                           const float* flt, float add = 0.0f) {
+                                           const float* flt, float add = 0.0f, int lb = 0, const float* last = nullptr,
+                                           int64_t last_cs = 0) {
   const int ch = sI / A.nsg, p0 = A.pa4 + DA_SEG * (sI - ch * A.nsg);
-  const int n_out = min(DA_SEG, a.L - p0);                      // a multiple of 4
+  const int L = RAG ? lb : a.L;
+  const int n_out = min(DA_SEG, L - p0);                        // a multiple of 4 (RAG: any count >= 1)
   const int c = I.c0 + ch;
   const float kf = a.act_alpha_exp[c] * 0.318309886183790672f, kb = 0.5f * a.act_beta_inv[c];
   float* raw = slice;
@@ -229,6 +242,13 @@ __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeo
     ds_f32x4 t = rv + add;                                      // (the pair kernel: the first conv's bias)
     t = idx < 0 ? ds_f32x4{t.x, t.x, t.x, t.x} : t;
     t = idx >= a.L ? ds_f32x4{t.w, t.w, t.w, t.w} : t;
+    if constexpr (RAG) {
+      const float rl = last[ch * last_cs] + add;
+      t.x = idx >= L ? rl : t.x;
+      t.y = idx + 1 >= L ? rl : t.y;
+      t.z = idx + 2 >= L ? rl : t.z;
+      t.w = idx + 3 >= L ? rl : t.w;
+    }
     *reinterpret_cast<ds_f32x4*>(raw + 4 * lane) = t;
   }
   da_fence();
@@ -253,7 +273,17 @@ __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeo
   }
   da_fence();
   // replicate padding of the 2x-rate signal: a[-5 .. -1] = a[0], a[2L .. 2L + 4] = a[2L - 1]
-  if (p0 == 0 || p0 + n_out == a.L) {
+  if constexpr (RAG) {
+    // a[2 lb - 1] sits at slot e; the slots after it that this segment's outputs read take its value -- also in the
+    // segment before the row's end when lb is not a multiple of 4 and the end lies within its taps' reach
+    const int e = 2 * (L - p0) + 4;
+    const bool tail = e < 2 * n_out + 9;
+    if (p0 == 0 || tail) {
+      if (p0 == 0 && lane < 5) a2[lane] = a2[5];
+      if (tail && lane >= 8 && lane < 13) a2[e + lane - 7] = a2[e];
+      da_fence();
+    }
+  } else if (p0 == 0 || p0 + n_out == a.L) {
     if (p0 == 0 && lane < 5) a2[lane] = a2[5];
     if (p0 + n_out == a.L && lane >= 8 && lane < 13) a2[2 * n_out + lane - 3] = a2[2 * n_out + 4];
     da_fence();
@@ -282,7 +312,8 @@ __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeo
   da_fence();                                                   // raw / a2 are rewritten by the next segment
 }
 
-template <bool ACT>
+// RAG (ACT only): per-row lengths hsp_dftseg_args.act_len -- the ragged activation (see da_item)
+template <bool ACT, bool RAG = false>
 __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) void dftseg_fwd_kernel(const hsp_dftseg_args a, const DsGeom G) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // [cg][pitch]: zero-padded input stretch of every row
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -335,12 +366,16 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   if (act) __syncthreads();                                     // the first item's staging reads the taps
   DsItem I = ds_item(blockIdx.x, a, G);
   DsStage sg = ds_stage_of(a, I);
-  DaItem da = da_item(a, I, sg);
+  auto row_len = [&](const DsItem& It) __attribute__((always_inline)) {
+    return RAG ? (int)min(max(a.act_len[It.b], (int64_t)1), (int64_t)a.L) : a.L;
+  };
+  int lb = row_len(I);
+  DaItem da = da_item<RAG>(a, I, sg, lb);
   ds_f32x4 pv[16];
   auto prefetch = [&]() __attribute__((always_inline)) {
     if (act) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) pv[i] = da_load(a, I, da, wave + 4 * i, lane);   // this wave's first sixteen segments
+      for (int i = 0; i < 16; ++i) pv[i] = da_load<RAG>(a, I, da, wave + 4 * i, lane);   // this wave's first sixteen segments
     } else if (vec) {
       ds_stage_load(a, I, sg, 0, tid, pv);
     }
@@ -350,15 +385,17 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (it) ds_barrier();                                       // the previous item's stretch has been read
     // ---- finish the staging of item `it`
     if (act) {
+      const float* last = RAG ? a.x + (int64_t)I.b * a.x_bs + (int64_t)I.c0 * a.x_cs + (lb - 1) : nullptr;
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (wave + 4 * i < da.nsegs) da_segment(a, G, I, sg, da, wave + 4 * i, lane, pv[i], slice, lds, flt);
+        if (wave + 4 * i < da.nsegs)
+          da_segment<RAG>(a, G, I, sg, da, wave + 4 * i, lane, pv[i], slice, lds, flt, 0.0f, lb, last, a.x_cs);
       for (int sI = wave + 64; sI < da.nsegs; sI += 4)          // beyond the prefetch depth
-        da_segment(a, G, I, sg, da, sI, lane, da_load(a, I, da, sI, lane), slice, lds, flt);
+        da_segment<RAG>(a, G, I, sg, da, sI, lane, da_load<RAG>(a, I, da, sI, lane), slice, lds, flt, 0.0f, lb, last, a.x_cs);
       for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
         float* row = lds + ch * pitch + sg.sh;
         for (int j = tid; j < min(-sg.t0, sg.len); j += DS_MEM) row[j] = 0.0f;
-        for (int j = max(a.L - sg.t0, 0) + tid; j < sg.len; j += DS_MEM) row[j] = 0.0f;
+        for (int j = max((RAG ? lb : a.L) - sg.t0, 0) + tid; j < sg.len; j += DS_MEM) row[j] = 0.0f;
       }
     } else if (vec) {
       ds_stage_write(G, sg, 0, tid, lds, pv);
@@ -394,7 +431,8 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (it + 1 < nmine) {                                       // the next item's loads go out now
       I = ds_item(blockIdx.x + (it + 1) * gridDim.x, a, G);
       sg = ds_stage_of(a, I);
-      da = da_item(a, I, sg);
+      lb = row_len(I);
+      da = da_item<RAG>(a, I, sg, lb);
       prefetch();
     }
     // ---- the transform of item `it`
@@ -743,6 +781,8 @@ struct DpGeom {
   int cg, ngrp, S1, pitchA, S2, pitchB, offB, offX, offT;
 };
 
+// RAG: af.act_len holds per-row lengths -- the activation between the convs is the ragged one (see da_item)
+template <bool RAG = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void dftseg_pair_kernel(
     const hsp_dftseg_args ai, const hsp_dftseg_args af, const DpGeom G) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -870,16 +910,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       sg.g_lo = 0;
       sg.ng = 0;
       sg.tot = 0;
-      const DaItem da = da_item(af, I, sg);
+      const int lb = RAG ? (int)min(max(af.act_len[I.b], (int64_t)1), (int64_t)af.L) : af.L;
+      const DaItem da = da_item<RAG>(af, I, sg, lb);
       for (int sI = wave; sI < da.nsegs; sI += 8) {
         const int ch = sI / da.nsg, p0 = da.pa4 + DA_SEG * (sI - ch * da.nsg);
         const ds_f32x4 rv = *reinterpret_cast<const ds_f32x4*>(sA + ch * G.pitchA + hsp_clampi(p0 - 8 + 4 * lane, 0, af.L - 4));
-        da_segment(af, Gf, I, sg, da, sI, lane, rv, slice, sB, flt, (ai.bias && !through) ? ai.bias[I.c0 + ch] : 0.0f);
+        da_segment<RAG>(af, Gf, I, sg, da, sI, lane, rv, slice, sB, flt, (ai.bias && !through) ? ai.bias[I.c0 + ch] : 0.0f,
+                        lb, sA + (lb - 1), G.pitchA);
       }
       for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
         float* row = sB + ch * G.pitchB + sg.sh;
         for (int j = tid; j < min(-sg.t0, sg.len); j += 512) row[j] = 0.0f;
-        for (int j = max(af.L - sg.t0, 0) + tid; j < sg.len; j += 512) row[j] = 0.0f;
+        for (int j = max(lb - sg.t0, 0) + tid; j < sg.len; j += 512) row[j] = 0.0f;
       }
       ds_barrier();
       // ---------------- phase 3: forward of c2 out of B
@@ -1098,6 +1140,16 @@ extern "C" int hsp_dftseg_fwd_f32(const hsp_dftseg_args* ap, void* stream) {
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
   if (a.xf_bs * 64 * 4 > 0xffffffffll) return HSP_EINVAL;      // the kernel addresses the spectrum with 32-bit byte offsets
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
+  if (a.act_len && !act) return HSP_EINVAL;                    // per-row lengths belong to the fused activation
+  if (a.act_len) {
+    static hsp_lds_flags flags_rag;
+    if (lds_bytes > 32 * 1024)
+      if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_fwd_kernel<true, true>), 160 * 1024, flags_rag))
+        return e;
+    hipLaunchKernelGGL((dftseg_fwd_kernel<true, true>), dim3((unsigned)blocks), dim3(DS_MEM), lds_bytes,
+                       static_cast<hipStream_t>(stream), a, G);
+    return (int)hipGetLastError();
+  }
   static hsp_lds_flags flags[2];
   const void* kern = act ? reinterpret_cast<const void*>(dftseg_fwd_kernel<true>) : reinterpret_cast<const void*>(dftseg_fwd_kernel<false>);
   if (lds_bytes > 32 * 1024)
@@ -1139,9 +1191,16 @@ extern "C" int hsp_dftseg_pair_f32(const hsp_dftseg_args* inv, const hsp_dftseg_
   const int64_t items = (int64_t)inv->B * G.ngrp;
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
+  if (fwd->act_len) {
+    static hsp_lds_flags flags_rag;
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_pair_kernel<true>), 160 * 1024, flags_rag)) return e;
+    hipLaunchKernelGGL(dftseg_pair_kernel<true>, dim3((unsigned)blocks), dim3(512), lds_bytes, static_cast<hipStream_t>(stream),
+                       *inv, *fwd, G);
+    return (int)hipGetLastError();
+  }
   static hsp_lds_flags flags;
-  if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_pair_kernel), 160 * 1024, flags)) return e;
-  hipLaunchKernelGGL(dftseg_pair_kernel, dim3((unsigned)blocks), dim3(512), lds_bytes, static_cast<hipStream_t>(stream), *inv,
+  if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_pair_kernel<false>), 160 * 1024, flags)) return e;
+  hipLaunchKernelGGL(dftseg_pair_kernel<false>, dim3((unsigned)blocks), dim3(512), lds_bytes, static_cast<hipStream_t>(stream), *inv,
                      *fwd, G);
   return (int)hipGetLastError();
 }

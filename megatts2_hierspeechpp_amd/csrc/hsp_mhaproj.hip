@@ -86,7 +86,8 @@ __device__ __forceinline__ void mp_barrier() {
   asm volatile("" ::: "memory");
 }
 
-template <class Cfg>
+// KL: per-row key lengths (hsp_mha_proj_args.key_len); the KL = false instantiations never read the field
+template <class Cfg, bool KL>
 __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj_args a, int n_qt) {
   constexpr int D = Cfg::D, C = Cfg::C, KS = Cfg::KS, NK = Cfg::NK, NDB = Cfg::NDB, VE = Cfg::VE;
   constexpr int NCB = Cfg::NCB, NRBT = Cfg::NRBT, NRB = Cfg::NRB, PF = Cfg::PF;
@@ -107,7 +108,11 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
   // heads vary fastest so that every SIMD hosts a first split (split-major order left SIMDs 1 and 3 idle through the
   // attention phases of the PLM's first 64 steps while 0 and 2 multiplied two heads each)
   const int h = wave % Cfg::H, ksp = wave / Cfg::H;
-  const int Tq = a.Tq, Tk = a.Tk;
+  // keys of this utterance: [0, key_len[b]) (clamped to [1, Tk]) when the caller gives per-row lengths, else all Tk --
+  // key groups past the row's end are not visited at all, the group that holds it is the ragged tail
+  const int Tq = a.Tq;
+  int Tk = a.Tk;
+  if constexpr (KL) Tk = (int)min(max(a.key_len[b], (int64_t)1), (int64_t)a.Tk);
   const int qi = min(i0 + x, Tq - 1);                 // this lane's query (clamped: surplus columns compute garbage nobody stores)
 #ifdef HSP_TUNING
   // tuning build, debug bit 1: cycle-counter stamps of the middle workgroup's wave 0 -> a.cscale (10 x uint64; cscale unused)
@@ -379,7 +384,7 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
 #undef MP_STAMP
 }
 
-template <class Cfg>
+template <class Cfg, bool KL>
 int mp_launch(const hsp_mha_proj_args& a, hipStream_t s) {
   const int n_qt = (a.Tq + MP_QT - 1) / MP_QT;
   const int64_t blocks = (int64_t)n_qt * a.B;
@@ -388,8 +393,8 @@ int mp_launch(const hsp_mha_proj_args& a, hipStream_t s) {
   static_assert(lds_bytes <= 160 * 1024, "LDS");
   static hsp_lds_flags flags;
   if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_proj_kernel<Cfg>), lds_bytes, flags)) return e;
-  hipLaunchKernelGGL((mha_proj_kernel<Cfg>), dim3((unsigned)blocks), dim3(64 * MP_NW), lds_bytes, s, a, n_qt);
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_proj_kernel<Cfg, KL>), lds_bytes, flags)) return e;
+  hipLaunchKernelGGL((mha_proj_kernel<Cfg, KL>), dim3((unsigned)blocks), dim3(64 * MP_NW), lds_bytes, s, a, n_qt);
   return (int)hipGetLastError();
 }
 }  // namespace
@@ -414,6 +419,7 @@ extern "C" int hsp_mha_proj_f32(const hsp_mha_proj_args* ap, void* stream) {
         (int64_t)a.M * a.y_cs >= lim || (a.res && (int64_t)a.M * a.res_cs >= lim)) return HSP_EINVAL;
   }
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a.H == 4) return mp_launch<MpCfg<4, 69>>(a, s);
-  return mp_launch<MpCfg<2, 96>>(a, s);
+  if (a.key_len) return a.H == 4 ? mp_launch<MpCfg<4, 69>, true>(a, s) : mp_launch<MpCfg<2, 96>, true>(a, s);
+  if (a.H == 4) return mp_launch<MpCfg<4, 69>, false>(a, s);
+  return mp_launch<MpCfg<2, 96>, false>(a, s);
 }

@@ -190,11 +190,21 @@ __device__ __forceinline__ void act2_load(const float* __restrict__ x, const Act
   }
 }
 
+// the valid length of the row of work item w: len[b] clamped to [1, L] (ragged form)
+__device__ __forceinline__ int act2_row_len(const int64_t* __restrict__ lens, unsigned w, int nseg, int C, int L) {
+  const unsigned b = (w / (unsigned)nseg) / (unsigned)C;
+  return (int)min(max(lens[b], (int64_t)1), (int64_t)L);
+}
+
+// RAG (hsp_act1d_snakebeta_ragged_f32): row b is valid over [0, lens[b]).  Reads clamp at lens[b] - 1 -- the replicate
+// pad of the call on the row cut to that length -- and the outputs at t >= lens[b] are written as 0.  RAG = false is the
+// plain kernel (`lens` unread).
+template <bool RAG>
 __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                     int C, int L, const float* __restrict__ alpha_exp,
                                                                     const float* __restrict__ beta_inv,
                                                                     const float* __restrict__ filt, int nseg,
-                                                                    unsigned nwork) {
+                                                                    unsigned nwork, const int64_t* __restrict__ lens) {
   __shared__ __attribute__((aligned(16))) float raw_all[ACT2_WAVES][ACT2_RAW];
   __shared__ __attribute__((aligned(16))) float a2_all[ACT2_WAVES][ACT2_A2];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -219,6 +229,12 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
   Act2Item cur = act2_item(w0, nseg, C, L);
   float4 rv[2];
   act2_load(x, cur, L, lane, rv);
+  int lb = L;         // (RAG) valid length of the current item's row and its last valid sample
+  float rl = 0.0f;
+  if constexpr (RAG) {
+    lb = act2_row_len(lens, w0, nseg, C, L);
+    rl = x[cur.row_off + lb - 1];
+  }
   constexpr int NC = (ACT2_SEG / 2 + 63) / 64;  // phase-C iterations of a full segment
   float2 yo[NC];
   float* yprev = nullptr;
@@ -234,6 +250,9 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
   };
   for (unsigned w = w0; w < w1; ++w) {
     const int p0 = cur.p0, n_out = cur.n_out;
+    const int lbc = lb;
+    const float rlc = rl;
+    const int n_in = RAG ? max(0, min(n_out, lbc - p0)) : n_out;   // outputs inside the valid part of the row
     float* yrow = y + cur.row_off;
     const float kf = alpha_exp[cur.c] * 0.318309886183790672f, kb = 0.5f * beta_inv[cur.c];
     // ---- phase A: registers -> LDS, then start the next item's loads
@@ -244,6 +263,12 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
       float4 t = rv[k];
       t = idx < 0 ? make_float4(t.x, t.x, t.x, t.x) : t;    // clamped address was 0:     x[0]
       t = idx >= L ? make_float4(t.w, t.w, t.w, t.w) : t;   // clamped address was L - 4: x[L-1]
+      if constexpr (RAG) {                                  // replicate x[lb - 1] from the row's valid end on
+        t.x = idx >= lbc ? rlc : t.x;
+        t.y = idx + 1 >= lbc ? rlc : t.y;
+        t.z = idx + 2 >= lbc ? rlc : t.z;
+        t.w = idx + 3 >= lbc ? rlc : t.w;
+      }
       *reinterpret_cast<float4*>(raw + 4 * v) = t;
     }
     act2_compiler_fence();  // keeps the deferred stores behind the wait for rv (the scheduler hoists them into the latch otherwise)
@@ -251,6 +276,10 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
     if (w + 1 < w1) {
       cur = act2_item(w + 1, nseg, C, L);
       act2_load(x, cur, L, lane, rv);
+      if constexpr (RAG) {
+        lb = act2_row_len(lens, w + 1, nseg, C, L);
+        rl = x[cur.row_off + lb - 1];
+      }
     }
     act2_compiler_fence();
 
@@ -272,7 +301,17 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
     }
     act2_compiler_fence();
     // replicate padding of the 2x-rate signal: a[-5 .. -1] = a[0], a[2L .. 2L+4] = a[2L-1]
-    if (p0 == 0 || p0 + n_out == L) {
+    if constexpr (RAG) {
+      // a[2 lb - 1] sits at slot e; every slot after it that an output of this item reads (up to 2 n_out + 9) takes its
+      // value -- in the item that holds the row's end AND in the one before it when the end lies within its taps' reach
+      const int e = 2 * (lbc - p0) + 4;
+      const bool tail = e >= 0 && e < 2 * n_out + 9;
+      if (p0 == 0 || tail) {
+        if (p0 == 0 && lane < 5) a2[lane] = a2[5];
+        if (tail && lane >= 8 && lane < 13) a2[e + lane - 7] = a2[e];
+        act2_compiler_fence();
+      }
+    } else if (p0 == 0 || p0 + n_out == L) {
       if (p0 == 0 && lane < 5) a2[lane] = a2[5];
       if (p0 + n_out == L && lane >= 8 && lane < 13) a2[2 * n_out + lane - 3] = a2[2 * n_out + 4];
       act2_compiler_fence();
@@ -294,6 +333,10 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
         s1 = __builtin_elementwise_fma(aw[k + 1], hd[k], s1);
       }
       yo[it] = make_float2(s0.x + s0.y, s1.x + s1.y);
+      if constexpr (RAG) {
+        yo[it].x = 2 * l2 < n_in ? yo[it].x : 0.0f;
+        yo[it].y = 2 * l2 + 1 < n_in ? yo[it].y : 0.0f;
+      }
     }
     yprev = yrow + p0;
     nprev = n_out;
@@ -390,6 +433,33 @@ __global__ void linear_interp_kernel(const float* __restrict__ x, float* __restr
     src = src < 0.0f ? 0.0f : src;
     const int i0 = (int)src;
     const int i1 = i0 + (i0 < Lin - 1 ? 1 : 0);
+    const float l1 = src - (float)i0, l0 = 1.0f - l1;
+    const float* xr = x + r * Lin;
+    y[i] = l0 * xr[i0] + l1 * xr[i1];
+  }
+}
+
+// the same on a ragged batch: row b holds lin[b] valid inputs and lout[b] valid outputs (rows = B * C, b = r / C).  Same
+// source position as the call on the row alone (the caller keeps Lin / Lout equal to that call's ratio), the upper
+// neighbour clamped at the row's last valid input, zeros past its last valid output
+__global__ void linear_interp_ragged_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int C, int Lin,
+                                            int Lout, float scale, const int64_t* __restrict__ lin,
+                                            const int64_t* __restrict__ lout) {
+  const int64_t n = rows * Lout;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int t = (int)(i % Lout);
+    const int64_t r = i / Lout;
+    const int64_t b = r / C;
+    const int lb_in = (int)min(max(lin[b], (int64_t)1), (int64_t)Lin);
+    const int lb_out = (int)min(max(lout[b], (int64_t)0), (int64_t)Lout);
+    if (t >= lb_out) {
+      y[i] = 0.0f;
+      continue;
+    }
+    float src = fmaf(scale, (float)t + 0.5f, -0.5f);
+    src = src < 0.0f ? 0.0f : src;
+    const int i0 = min((int)src, lb_in - 1);
+    const int i1 = i0 + (i0 < lb_in - 1 ? 1 : 0);
     const float l1 = src - (float)i0, l0 = 1.0f - l1;
     const float* xr = x + r * Lin;
     y[i] = l0 * xr[i0] + l1 * xr[i1];
@@ -561,8 +631,8 @@ extern "C" int hsp_act1d_snakebeta_f32(const float* x, float* y, int32_t B, int3
     const int64_t nwork = (int64_t)nseg * B * C;
     const int64_t blocks = (nwork + ACT2_WAVES * ACT2_ITEMS - 1) / (ACT2_WAVES * ACT2_ITEMS);
     if (nwork > 0x7fffffff - ACT2_WAVES * ACT2_ITEMS) return HSP_EINVAL;
-    hipLaunchKernelGGL(act1d_seg_kernel, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, HSP_STREAM, x, y, C, L,
-                       alpha_exp, beta_inv, filt, nseg, (unsigned)nwork);
+    hipLaunchKernelGGL(act1d_seg_kernel<false>, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, HSP_STREAM, x, y, C, L,
+                       alpha_exp, beta_inv, filt, nseg, (unsigned)nwork, nullptr);
     return (int)hipGetLastError();
   }
   const int n_tiles = (L + ACT_TILE - 1) / ACT_TILE;
@@ -570,6 +640,21 @@ extern "C" int hsp_act1d_snakebeta_f32(const float* x, float* y, int32_t B, int3
   if (blocks > 0x7fffffff) return HSP_EINVAL;
   hipLaunchKernelGGL(act1d_kernel, dim3((unsigned)blocks), dim3(ACT_THREADS), 0, HSP_STREAM, x, y, C, L, alpha_exp,
                      beta_inv, filt, n_tiles);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_act1d_snakebeta_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t L, const int64_t* lens,
+                                              const float* alpha_exp, const float* beta_inv, const float* filt,
+                                              void* stream) {
+  if (!x || !y || !lens || !alpha_exp || !beta_inv || !filt || B <= 0 || C <= 0 || L <= 0) return HSP_EINVAL;
+  // the wave-per-segment form only: 16-B addressable rows, L % 4 == 0 (the caller pads the batch to such a length)
+  if ((L & 3) != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0) return HSP_EINVAL;
+  const int nseg = (L + ACT2_SEG - 1) / ACT2_SEG;
+  const int64_t nwork = (int64_t)nseg * B * C;
+  const int64_t blocks = (nwork + ACT2_WAVES * ACT2_ITEMS - 1) / (ACT2_WAVES * ACT2_ITEMS);
+  if (nwork > 0x7fffffff - ACT2_WAVES * ACT2_ITEMS) return HSP_EINVAL;
+  hipLaunchKernelGGL(act1d_seg_kernel<true>, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, HSP_STREAM, x, y, C, L,
+                     alpha_exp, beta_inv, filt, nseg, (unsigned)nwork, lens);
   return (int)hipGetLastError();
 }
 
@@ -627,6 +712,15 @@ extern "C" int hsp_linear_interp_f32(const float* x, float* y, int32_t B, int32_
   const float scale = (float)Lin / (float)Lout;  // torch: area_pixel_compute_scale, align_corners=False
   hipLaunchKernelGGL(linear_interp_kernel, dim3(grid_for((int64_t)B * C * Lout, 256)), dim3(256), 0, HSP_STREAM, x, y,
                      (int64_t)B * C, Lin, Lout, scale);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_linear_interp_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout,
+                                           const int64_t* lin, const int64_t* lout, void* stream) {
+  if (!x || !y || !lin || !lout || B <= 0 || C <= 0 || Lin <= 0 || Lout <= 0) return HSP_EINVAL;
+  const float scale = (float)Lin / (float)Lout;
+  hipLaunchKernelGGL(linear_interp_ragged_kernel, dim3(grid_for((int64_t)B * C * Lout, 256)), dim3(256), 0, HSP_STREAM,
+                     x, y, (int64_t)B * C, C, Lin, Lout, scale, lin, lout);
   return (int)hipGetLastError();
 }
 

@@ -32,7 +32,9 @@ def sequence_mask(length: torch.Tensor, max_length: int) -> torch.Tensor:
 ACT_HOOK = None  # measurement hook (bench.py): hook(algorithmic_bytes, ev_start, ev_end) around every stand-alone activation
 
 
-def act1d(x, ea, binv, filt, out=None):
+def act1d(x, ea, binv, filt, out=None, lens=None):
+    """``lens`` (device int64 [B]): ragged form (hsp_act1d_snakebeta_ragged_f32) -- row b is the call on the row cut
+    to lens[b], zero beyond it."""
     x = _c(x)
     B, Cc, T = x.shape
     out = _new_like(x) if out is None else out
@@ -40,8 +42,14 @@ def act1d(x, ea, binv, filt, out=None):
     if hook is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    L.check(L.lib().hsp_act1d_snakebeta_f32(L.fptr(x), L.fptr(out), B, Cc, T, L.fptr(ea), L.fptr(binv), L.fptr(filt),
-                                            L.stream_ptr()), "hsp_act1d_snakebeta_f32")
+    if lens is not None:
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == B
+        L.check(L.lib().hsp_act1d_snakebeta_ragged_f32(L.fptr(x), L.fptr(out), B, Cc, T, L.ptr(lens), L.fptr(ea),
+                                                       L.fptr(binv), L.fptr(filt), L.stream_ptr()),
+                "hsp_act1d_snakebeta_ragged_f32")
+    else:
+        L.check(L.lib().hsp_act1d_snakebeta_f32(L.fptr(x), L.fptr(out), B, Cc, T, L.fptr(ea), L.fptr(binv), L.fptr(filt),
+                                                L.stream_ptr()), "hsp_act1d_snakebeta_f32")
     if hook is not None:
         e1.record()
         hook(8 * B * Cc * T, e0, e1)   # one fp32 read + one fp32 write per element
@@ -131,11 +139,13 @@ def mha_proj_supported(n_heads: int, head_dim: int, m: int, tk: int) -> bool:
     return FUSE_MHA_PROJ and bool(L.lib().hsp_mha_proj_supported(n_heads, head_dim, m, tk))
 
 
-def mha_proj(q, k, v, n_heads: int, qk_scale: float, wt, bias=None, mask=None, cscale=None, res=None, out=None):
+def mha_proj(q, k, v, n_heads: int, qk_scale: float, wt, bias=None, mask=None, cscale=None, res=None, out=None,
+             key_len=None):
     """Attention over all heads + output projection + epilogue in one launch (hsp_mha_proj_f32):
     y = ((wt @ attention(q, k, v) + bias) * mask) * cscale + res.  q [B, H*D, Tq], k / v [B, H*D, Tk] with unit time
     stride (strided views as for ``mha``); ``wt`` [M, H*D] row-major (the nn.Linear weight as stored); ``res`` / ``out``
-    [B, M, Tq] with ANY strides; ``mask`` [B, 1, Tq] or [B, Tq]; ``cscale`` [B, M]."""
+    [B, M, Tq] with ANY strides; ``mask`` [B, 1, Tq] or [B, Tq]; ``cscale`` [B, M]; ``key_len`` (device int64 [B]): the
+    softmax of row b covers keys [0, key_len[b]) only."""
     B, HD, Tq = q.shape
     Tk = k.shape[2]
     M = wt.shape[0]
@@ -162,6 +172,9 @@ def mha_proj(q, k, v, n_heads: int, qk_scale: float, wt, bias=None, mask=None, c
         assert res.shape == y.shape
         a.res, a.res_bs, a.res_cs, a.res_ts = L.fptr(res), res.stride(0), res.stride(1), max(res.stride(2), 1)
     a.y, a.y_bs, a.y_cs, a.y_ts = L.fptr(y), y.stride(0), y.stride(1), max(y.stride(2), 1)
+    if key_len is not None:
+        assert key_len.dtype == torch.int64 and key_len.is_contiguous() and key_len.numel() == B
+        a.key_len = L.ptr(key_len)
     L.check(L.lib().hsp_mha_proj_f32(C.byref(a), L.stream_ptr()), "hsp_mha_proj_f32")
     return y
 
@@ -192,11 +205,19 @@ def axpby(x, z, a: float, b: float):
     return y
 
 
-def linear_interp(x, out_len: int):
-    """F.interpolate(x, out_len, mode='linear') along the last axis of [B, C, L]."""
+def linear_interp(x, out_len: int, lens_in=None, lens_out=None):
+    """F.interpolate(x, out_len, mode='linear') along the last axis of [B, C, L].  ``lens_in`` / ``lens_out`` (device
+    int64 [B]): ragged form (hsp_linear_interp_ragged_f32) -- row b is the call on its first lens_in[b] samples to
+    lens_out[b] outputs, zero after."""
     x = _c(x)
     B, Cc, Lin = x.shape
     y = torch.empty(B, Cc, out_len, dtype=torch.float32, device=x.device)
+    if lens_in is not None:
+        for t_ in (lens_in, lens_out):
+            assert t_.dtype == torch.int64 and t_.is_contiguous() and t_.numel() == B
+        L.check(L.lib().hsp_linear_interp_ragged_f32(L.fptr(x), L.fptr(y), B, Cc, Lin, out_len, L.ptr(lens_in),
+                                                     L.ptr(lens_out), L.stream_ptr()), "hsp_linear_interp_ragged_f32")
+        return y
     L.check(L.lib().hsp_linear_interp_f32(L.fptr(x), L.fptr(y), B, Cc, Lin, out_len, L.stream_ptr()),
             "hsp_linear_interp_f32")
     return y

@@ -84,8 +84,9 @@ class ResidualCouplingBlock_Transformer(nn.Module):
             for i in range(n_flows):
                 self.flows[2 * i].set_flipped((n_flows - i) % 2 == 1)
 
-    def forward(self, x, x_mask, g=None, reverse=False, owned=False):
-        """``owned``: the caller hands x over (a temporary of its own): the first coupling layer may update it in place."""
+    def forward(self, x, x_mask, g=None, reverse=False, owned=False, key_len=None):
+        """``owned``: the caller hands x over (a temporary of its own): the first coupling layer may update it in place.
+        ``key_len`` (device int64 [B], row-exact mode): the DiT blocks' attention sees keys [0, key_len[b]) only."""
         if not reverse:
             raise NotImplementedError("training direction is out of scope")
         c = self.cond_block[0](g.reshape(g.shape[0], -1), act=L.ACT_SILU)
@@ -104,7 +105,7 @@ class ResidualCouplingBlock_Transformer(nn.Module):
                 flipped = not flipped                                                           # Flip, not launched
             q0 = self._modq_base
             x = layer(x, x_mask, g=None, mods=mods[:, i * R:(i + 1) * R], reverse=True, inplace=owned,
-                      modq=None if q0 is None else mods[:, q0 + i * R:q0 + (i + 1) * R])                 # coupling
+                      modq=None if q0 is None else mods[:, q0 + i * R:q0 + (i + 1) * R], key_len=key_len)  # coupling
             owned = True
         return Fh.flip_channels(x) if flipped else x
 
@@ -369,7 +370,18 @@ def _side_streams(device, n):
 
 
 def _amp_stage(resblocks, first, num_kernels, x):
-    """xs = sum_j block_j(x); x = xs / num_kernels (hierspeechpp_speechsynthesizer.py:440-446)."""
+    """xs = sum_j block_j(x); x = xs / num_kernels (hierspeechpp_speechsynthesizer.py:440-446).  Row-exact mode: the
+    stage output is zeroed past every row's end (a ConvTranspose or conv_post reads it directly; inside the blocks
+    every conv reads a ragged Activation1d's output)."""
+    rows = hip_layers.row_lengths()
+    if rows is None:
+        return _amp_stage_sum(resblocks, first, num_kernels, x)
+    rows.prepare(x.shape[2])          # on this stream, before the side streams fork
+    xs = _amp_stage_sum(resblocks, first, num_kernels, x)
+    return Fh.mask_mul(xs, rows.mask(xs.shape[2]))
+
+
+def _amp_stage_sum(resblocks, first, num_kernels, x):
     if not AMP_STREAMS or SERIAL_STREAMS or num_kernels == 1:
         xs = None
         for j in range(num_kernels):
@@ -415,8 +427,10 @@ class DBlock(nn.Module):
             raise L.HspError("DBlock needs a length divisible by its factor (pitch is 4 frames per w2v frame)")
         xs = x[..., ::self.factor]
         res = self.residual_dense(xs)
-        h = self.conv[0](xs, lrelu=modules.LRELU_SLOPE)
-        h = self.conv[1](h, lrelu=modules.LRELU_SLOPE)
+        rows = hip_layers.row_lengths()   # row-exact: the inputs of conv[1] / conv[2] are zero past each row's end
+        mk = dict(mask=rows.mask(xs.shape[2]), mask_mode=L.MASK_POST) if rows is not None else {}
+        h = self.conv[0](xs, lrelu=modules.LRELU_SLOPE, **mk)
+        h = self.conv[1](h, lrelu=modules.LRELU_SLOPE, **mk)
         return self.conv[2](h, lrelu=modules.LRELU_SLOPE, res=res)
 
 
@@ -442,12 +456,14 @@ class SourceNetwork(nn.Module):
         self.cond = Conv1d(256, c0, 1)
 
     def forward(self, x, g):
-        x = self.conv_pre(x, cbias=self.cond(g))
+        rows = hip_layers.row_lengths()   # row-exact: conv outputs read by a conv are zero past each row's end
+        mk = (lambda t: dict(mask=rows.mask(t), mask_mode=L.MASK_POST)) if rows is not None else (lambda t: {})
+        x = self.conv_pre(x, cbias=self.cond(g), **mk(x.shape[2]))
         for i in range(self.num_upsamples):
             x = self.ups[i](x)
             x = _amp_stage(self.resblocks, i * self.num_kernels, self.num_kernels, x)
         x = self.activation_post(x)
-        return x, self.conv_post(x)
+        return x, self.conv_post(x, **mk(x.shape[2]))
 
 
 class Generator(nn.Module):
@@ -476,7 +492,9 @@ class Generator(nn.Module):
 
     @_entry
     def forward(self, x, pitch, g=None):
-        x = self.conv_pre(x, cbias=self.cond(g), res=self.downs(pitch))
+        rows = hip_layers.row_lengths()   # row-exact: conv outputs read by a conv are zero past each row's end
+        mk = (lambda t: dict(mask=rows.mask(t), mask_mode=L.MASK_POST)) if rows is not None else (lambda t: {})
+        x = self.conv_pre(x, cbias=self.cond(g), res=self.downs(pitch), **mk(x.shape[2]))
         first_grouped = self.num_upsamples
         if GEN_GROUPS > 1 and x.shape[0] >= 2 * GEN_GROUPS:
             # the first stage whose channel count is at most GEN_GROUP_MAX_C: from there on the batch walks the rest of
@@ -490,7 +508,7 @@ class Generator(nn.Module):
             x = _amp_stage(self.resblocks, i * self.num_kernels, self.num_kernels, x)
         if first_grouped == self.num_upsamples:
             x = self.activation_post(x)
-            return self.conv_post(x, act=L.ACT_TANH)
+            return self.conv_post(x, act=L.ACT_TANH, **mk(x.shape[2]))
         B = x.shape[0]
         total_up = 1
         for i in range(first_grouped, self.num_upsamples):
@@ -557,16 +575,23 @@ class SynthesizerTrn(nn.Module):
             noise = torch.randn(stats.shape[0], C, stats.shape[2], dtype=torch.float32, device=stats.device)
         return Fh.sample_prior(stats, noise, y_mask, noise_scale)
 
-    def _latent(self, w2v, f0, y_mask, g, noise, noise_scale):
+    def _latent(self, w2v, f0, y_mask, g, noise, noise_scale, lengths=None):
         """prior sample -> both reversed flows.  Everything here works on 50 Hz frames (a few
         hundred columns per utterance): ~250 small, latency-bound launches.  Utterances are
         independent, so the batch is cut into FRONT_SPLITS groups issued on separate streams;
-        their launches overlap on the GPU instead of each one draining the chip."""
+        their launches overlap on the GPU instead of each one draining the chip.
+        ``lengths`` (device int64 [B], row-exact mode): w2v and f0 are zeroed past each row's end (the prior encoder's
+        stride-4 k = 9 conv reads f0 there) and the flows' attention masks the keys past it."""
         B = w2v.shape[0]
         n = min(FRONT_SPLITS, B)
+        if lengths is not None:
+            w2v = Fh.mask_mul(w2v, y_mask)
+            f0 = Fh.mask_mul(f0, Fh.sequence_mask(4 * lengths, f0.shape[2]))
+        kl = (lambda lo, hi: None) if lengths is None else (lambda lo, hi: lengths[lo:hi])
         if n <= 1:
             z = self._prior(w2v, f0, y_mask, g, noise, noise_scale)
-            return self.flow(self.flow_l(z, y_mask, g=g, reverse=True, owned=True), y_mask, g=g, reverse=True, owned=True)
+            return self.flow(self.flow_l(z, y_mask, g=g, reverse=True, owned=True, key_len=kl(0, B)), y_mask, g=g,
+                             reverse=True, owned=True, key_len=kl(0, B))
         if noise is None:
             noise = torch.randn(B, self.inter_channels, w2v.shape[2], dtype=torch.float32, device=w2v.device)
         main = torch.cuda.current_stream(w2v.device)
@@ -582,8 +607,8 @@ class SynthesizerTrn(nn.Module):
                 if i > 0 and st is not main:
                     st.wait_event(fork)
                 zi = self._prior(w2v[lo:hi], f0[lo:hi], y_mask[lo:hi], g[lo:hi], noise[lo:hi], noise_scale)
-                zi = self.flow_l(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True)
-                zi = self.flow(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True)
+                zi = self.flow_l(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True, key_len=kl(lo, hi))
+                zi = self.flow(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True, key_len=kl(lo, hi))
                 z[lo:hi].copy_(zi)
                 if i > 0 and st is not main:
                     ev = torch.cuda.Event()
@@ -591,34 +616,55 @@ class SynthesizerTrn(nn.Module):
                     main.wait_event(ev)
         return z
 
-    def _decode(self, z, g):
-        e, e_ = self.sn(z, g)
-        return self.dec(z, e, g=g), e_
+    def _decode(self, z, g, lengths=None):
+        if lengths is None:
+            e, e_ = self.sn(z, g)
+            return self.dec(z, e, g=g), e_
+        # row-exact: the padded length is rounded up to a multiple of 4 frames, so that every resolution of the source
+        # network (2T, 4T) and the Generator holds whole 16-B groups (the ragged activation's form); the extra frames are
+        # padding like any other and are cut off again
+        B, Cz, T = z.shape
+        Tp = (T + 3) // 4 * 4
+        if Tp != T:
+            zp = torch.zeros(B, Cz, Tp, dtype=z.dtype, device=z.device)
+            zp[:, :, :T].copy_(z)
+            z = zp
+        with hip_layers.row_exact(hip_layers.RowLengths(lengths, Tp)):
+            e, e_ = self.sn(z, g)
+            o = self.dec(z, e, g=g)
+        if Tp != T:
+            o = o[:, :, :o.shape[2] // Tp * T].contiguous()
+            e_ = e_[:, :, :e_.shape[2] // Tp * T].contiguous()
+        return o, e_
 
     @_entry
     @torch.no_grad()
-    def infer(self, x_mel, w2v, length, f0, noise: Optional[torch.Tensor] = None):
+    def infer(self, x_mel, w2v, length, f0, noise: Optional[torch.Tensor] = None, row_exact: bool = False):
         """:635-651 -> (o [B,1,320T], e_ [B,1,4T]).  ``noise`` ([B,192,T]) replaces the
-        randn_like draw of :202 for reproducible parity runs."""
+        randn_like draw of :202 for reproducible parity runs.  ``row_exact`` (ragged batches): row b
+        equals this call on row b alone (its inputs cut to length[b] frames, noise[b:b+1, :, :length[b]]), zero past
+        320 length[b]; ``length`` counts w2v frames and is also the prompt mel's length, as in the reference."""
+        lengths = _row_exact_lengths(row_exact, length, w2v.shape[2], w2v.device)
         x_mask = commons.sequence_mask(length, x_mel.size(2))
-        g = self.emb_g(x_mel, x_mask).unsqueeze(-1)
-        z = self._latent(w2v, f0, x_mask, g, noise, 1.0)
-        return self._decode(z, g)
+        g = self.emb_g(x_mel, x_mask, per_utterance=row_exact).unsqueeze(-1)
+        z = self._latent(w2v, f0, x_mask, g, noise, 1.0, lengths=lengths)
+        return self._decode(z, g, lengths)
 
     @_entry
     @torch.no_grad()
     def voice_conversion(self, src, src_length, trg_mel, trg_length, f0, noise_scale=0.333, uncond=False,
-                         noise: Optional[torch.Tensor] = None):
+                         noise: Optional[torch.Tensor] = None, row_exact: bool = False):
         """:652-673.  ``uncond`` (a model built with cfg=True): the source network and the generator are conditioned
         on the null embedding ``emb(0) * sqrt(256)`` instead of the prompt's style vector (:669-671); the prior encoder
-        and the flows still see the prompt."""
+        and the flows still see the prompt.  ``row_exact``: as for ``infer`` (row b = the call on row b alone)."""
+        lengths = _row_exact_lengths(row_exact, src_length, src.shape[2], src.device)
         trg_mask = commons.sequence_mask(trg_length, trg_mel.size(2))
-        g = self.emb_g(trg_mel, trg_mask).unsqueeze(-1)
+        g = self.emb_g(trg_mel, trg_mask, per_utterance=row_exact).unsqueeze(-1)
         y_mask = commons.sequence_mask(src_length, src.size(2))
-        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale)
+        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths)
         if uncond:
             g = self._null_g(src.shape[0])
-        return self._decode(z, g)[0]
+        return self._decode(z, g, lengths)[0]
 
     def _null_g(self, B):
         """[B, 256, 1] = emb(0) * sqrt(256), one copy per utterance (the reference broadcasts a [1, 256, 1] tensor)."""
@@ -629,37 +675,71 @@ class SynthesizerTrn(nn.Module):
 
     @_entry
     @torch.no_grad()
-    def style_vector(self, trg_mel, trg_length, denoise_ratio=0):
+    def style_vector(self, trg_mel, trg_length, denoise_ratio=0, per_utterance=False):
         """The style vector of voice_conversion_noise_control (:684-689): trg_mel [2B, 80, T] = B prompts, then the B
-        denoised prompts -> (1 - denoise_ratio) emb_g(prompt) + denoise_ratio emb_g(denoised) [B, 256, 1]."""
+        denoised prompts -> (1 - denoise_ratio) emb_g(prompt) + denoise_ratio emb_g(denoised) [B, 256, 1].
+        ``per_utterance``: every row as at B = 1 (StyleEncoder.forward)."""
         B = trg_mel.shape[0] // 2
         trg_mask = commons.sequence_mask(trg_length, trg_mel.size(2))
-        g = self.emb_g(trg_mel, trg_mask)  # [2B, 256]
+        g = self.emb_g(trg_mel, trg_mask, per_utterance=per_utterance)  # [2B, 256]
         return Fh.axpby(g[:B], g[B:], 1.0 - denoise_ratio, float(denoise_ratio)).unsqueeze(-1)
 
     @_entry
     @torch.no_grad()
     def voice_conversion_noise_control(self, src, src_length, trg_mel, trg_length, f0, noise_scale=0.333,
                                        uncond=False, denoise_ratio=0, noise: Optional[torch.Tensor] = None,
-                                       style: Optional[torch.Tensor] = None):
+                                       style: Optional[torch.Tensor] = None, row_exact: bool = False):
         """:674-699.  trg_mel holds two prompts (original, denoised); their style vectors
         are interpolated with ``denoise_ratio`` (B = 1 by construction in the reference, SURVEY.md
         App. B1).  With B source utterances trg_mel is [2B, 80, T]: the B prompts, then the B denoised
         prompts, and f0 is [B, 1, 4T].  ``style`` [B, 256, 1]: that interpolated style vector, precomputed
         (inference_vc.vc_batch takes it per distinct prompt at the prompt's own length); emb_g and the
-        interpolation are skipped and trg_mel / trg_length are not read."""
+        interpolation are skipped and trg_mel / trg_length are not read.  ``row_exact``: as for ``infer`` (row b = the
+        call on row b alone with the same prompt pair)."""
         if uncond and not self.cfg:   # the reference evaluates self.emb here (:693-695) and then does not use the result
             raise AttributeError("'SynthesizerTrn' object has no attribute 'emb' (uncond needs a model built with cfg=True)")
         B = src.shape[0]
+        lengths = _row_exact_lengths(row_exact, src_length, src.shape[2], src.device)
         if style is not None:
             assert style.dim() == 3 and style.shape[0] == B and style.shape[2] == 1, style.shape
             g = style
         else:
             assert trg_mel.shape[0] == 2 * B
+            # (row-exact too: the style of row b is computed from its own prompt pair only, with the reference's masking
+            # inside the pair -- the B = 1 call on the same trg_mel rows)
             g = self.style_vector(trg_mel, trg_length, denoise_ratio)
         y_mask = commons.sequence_mask(src_length, src.size(2))
-        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale)
-        return self._decode(z, g)[0]
+        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths)
+        return self._decode(z, g, lengths)[0]
+
+
+def row_exact_refusal() -> Optional[str]:
+    """Why this process cannot run row-exact ragged batches, or None: the non-default experiment knobs whose launches
+    have no ragged form."""
+    if FUSE_ACT_MAX_CHANNELS > 0:
+        return "HSP_FUSE_ACT_MAX_C > 0 (the conv-prologue activation has no ragged form)"
+    if FFT_THROUGH:
+        return "HSP_FFT_THROUGH=1 (the chained transforms carry the activation; they have no ragged form)"
+    if GEN_GROUPS > 1:
+        return "HSP_GEN_GROUPS > 1"
+    return None
+
+
+def _row_exact_lengths(row_exact: bool, length, T: int, device) -> Optional[torch.Tensor]:
+    """The device int64 [B] frame counts of a row-exact call (None when ``row_exact`` is off).  Lengths given on the host
+    (a list or a CPU tensor) are checked against the padded length ``T``; device lengths are not read back (a fixed shape
+    stays capturable) -- the kernels clamp them to [1, T]."""
+    if not row_exact:
+        return None
+    why = row_exact_refusal()
+    if why is not None:
+        raise L.HspError(f"row_exact is not available with {why}")
+    if isinstance(length, torch.Tensor) and length.device.type != "cpu":
+        return length.reshape(-1).to(torch.int64).contiguous()
+    host = [int(v) for v in (length.reshape(-1).tolist() if isinstance(length, torch.Tensor) else length)]
+    if any(v < 1 or v > T for v in host):
+        raise L.HspError(f"row_exact: lengths {host} must lie in [1, {T}] (the padded frame count)")
+    return torch.tensor(host, dtype=torch.int64, device=device)
 
 
 def _f0_3d(f0):

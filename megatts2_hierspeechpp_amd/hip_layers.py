@@ -12,6 +12,7 @@ job can ship them with a single RCCL broadcast.
 """
 from __future__ import annotations
 
+import contextvars
 import ctypes as C
 import os
 from typing import Dict, List, Optional, Tuple
@@ -78,8 +79,75 @@ def _wspec_twiddles(device):
 FFT_PRODUCT = os.environ.get("HSP_FFT_PRODUCT", "three")
 
 
+# ---------------------------------------------------------------- row-exact ragged batches
+class RowLengths:
+    """The valid length of every row of a ragged batch at each resolution of the vocoder: ``frames`` (device int64 [B])
+    at the frame rate of the padded length ``T``; a tensor of L = f * T columns holds f * frames[b] valid ones.  Lengths
+    and masks stay on the device (no host read-back, so a fixed shape captures as one hipGraph) and are built once per
+    resolution: ``prepare(L)`` on the stream that later forks side streams, before the fork."""
+
+    def __init__(self, frames: torch.Tensor, T: int):
+        if frames.dtype != torch.int64 or frames.dim() != 1:
+            raise L.HspError(f"row lengths must be int64 [B], got {frames.dtype} {tuple(frames.shape)}")
+        self.frames, self.T = frames.contiguous(), int(T)
+        self._lens: Dict[int, torch.Tensor] = {}
+        self._masks: Dict[int, torch.Tensor] = {}
+
+    def factor(self, L_: int) -> int:
+        if L_ % self.T != 0:
+            raise L.HspError(f"row_exact: a tensor of {L_} columns is not a whole multiple of the {self.T} frames")
+        return L_ // self.T
+
+    def at(self, L_: int) -> torch.Tensor:
+        """int64 [B]: valid columns of every row of an L-column tensor."""
+        t = self._lens.get(L_)
+        if t is None:
+            f = self.factor(L_)
+            t = self._lens[L_] = self.frames if f == 1 else self.frames * f
+        return t
+
+    def mask(self, L_: int) -> torch.Tensor:
+        """float [B, 1, L]: 1 over each row's valid columns, 0 after."""
+        m = self._masks.get(L_)
+        if m is None:
+            from . import functional as Fh
+            m = self._masks[L_] = Fh.sequence_mask(self.at(L_), L_)
+        return m
+
+    def prepare(self, L_: int):
+        self.at(L_)
+        self.mask(L_)
+
+
+# a context variable, not a module global: two threads (or asyncio tasks) driving models see only their own lengths
+_ROWS: "contextvars.ContextVar[Optional[RowLengths]]" = contextvars.ContextVar("hsp_row_lengths", default=None)
+
+
+class row_exact:
+    """``with row_exact(RowLengths(...)):`` the vocoder layers run the ragged batch row-exactly: every Activation1d
+    clamps its reads at its row's end and writes 0 past it, and the callers zero every tensor a conv reads directly past
+    each row's end.  Nested use replaces the lengths for the inner block."""
+
+    def __init__(self, rows: Optional[RowLengths]):
+        self.rows = rows
+
+    def __enter__(self):
+        self._token = _ROWS.set(self.rows)
+        return self.rows
+
+    def __exit__(self, *exc):
+        _ROWS.reset(self._token)
+        return False
+
+
+def row_lengths() -> Optional[RowLengths]:
+    """The RowLengths of the enclosing ``row_exact`` block, or None (the default batched semantics)."""
+    return _ROWS.get()
+
+
 def fft_act_fusable(x) -> bool:
-    """hsp_dftseg_args.act_*: the fused activation reads 16-B groups of every row."""
+    """hsp_dftseg_args.act_*: the fused activation reads 16-B groups of every row (in a row-exact block its ragged form,
+    hsp_dftseg_args.act_len)."""
     return (x.stride(2) == 1 and x.shape[2] % 4 == 0 and x.stride(0) % 4 == 0 and x.stride(1) % 4 == 0
             and x.data_ptr() % 16 == 0)
 
@@ -505,6 +573,9 @@ class Conv1d(_ConvBase):
         if act1d._ea is None:
             raise L.HspError("Activation1d used before finalize()")
         da.act_alpha_exp, da.act_beta_inv, da.act_filt = L.fptr(act1d._ea), L.fptr(act1d._binv), L.fptr(act1d._filt)
+        rows = _ROWS.get()      # row-exact: the ragged activation (hsp_dftseg_args.act_len)
+        if rows is not None:
+            da.act_len = L.ptr(rows.at(x_like.shape[2]))
 
     def _fft_forward(self, x, act1d=None):
         """x [B, C, L] -> spectrum [64][2 C][Np] (hsp_dftseg_fwd_f32), the activation applied on the way if given."""
@@ -703,6 +774,8 @@ class Conv1d(_ConvBase):
         (unit inner stride) the per-utterance vectors of include/hsp.h, ``mask`` [B, 1, T] or None.  Returns None when the
         library has no kernel for the shape (the caller then runs LayerNorm + modulate as its own launch)."""
         self._require_ready()
+        if act1d is not None and _ROWS.get() is not None:
+            raise L.HspError("row_exact: the conv-prologue Activation1d (HSP_FUSE_ACT_MAX_C > 0) has no ragged form")
         B, Cin, Lin = x.shape
         assert Cin == self.cin, (Cin, self.cin)
         gated = self.rows in (L.ROWS_GATE_WN, L.ROWS_GATE_GLU)

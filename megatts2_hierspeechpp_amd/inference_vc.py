@@ -21,6 +21,7 @@ from torch import nn
 
 from . import _lib as L
 from . import functional as Fh
+from . import hip_layers
 from .inference_plm import output_gain, peak_int16
 
 SOURCE_HOP = 1280   # pad_source's multiple (inference_vc.py:74-75)
@@ -253,7 +254,8 @@ def _rows(arg, device, what):
 
 @torch.no_grad()
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
-             denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False):
+             denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
+             row_exact=False):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -269,7 +271,9 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
     (320 T_b at 16 kHz, x1.5 / x3 with SpeechSR), zeros after; with ``return_float`` also the float audio
     [B, 1, n_max].  Row b up to the vocoder equals ``vc`` on row b alone; the vocoder and SpeechSR run the ragged batch
-    with per-row frame counts as ``tts`` does at B > 1."""
+    with per-row frame counts as ``tts`` does at B > 1.  ``row_exact``: the vocoder runs each row as
+    at B = 1 too (key-masked flows, ragged activations, zeros past every row's end), so every row equals ``vc`` on it
+    alone, at 16, 24 and 48 kHz."""
     voc = models.voc
     dev = sources[0].device
     x, src_len, src_host = _rows(sources, dev, "sources")
@@ -343,10 +347,15 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     _tap("style", style)
     _stage("vocoder")
     audio = voc.voice_conversion_noise_control(x_w2v, frames, None, None, lf0, noise_scale=noise_scale_vc,
-                                               denoise_ratio=denoise_ratio, noise=noise, style=style)
+                                               denoise_ratio=denoise_ratio, noise=noise, style=style,
+                                               row_exact=row_exact)
     if output_sr in (24000, 48000):
         _stage("speechsr")
-        audio = models.sr(audio)                                               # :147-151
+        if row_exact:                  # SpeechSR on the ragged rows, each as on its own (lengths at 16 kHz: 320 T_b)
+            with hip_layers.row_exact(hip_layers.RowLengths(frames, audio.shape[2] // 320)):
+                audio = models.sr(audio)                                       # :147-151
+        else:
+            audio = models.sr(audio)                                           # :147-151
     _stage("int16")
     n_valid = output_length(frames, output_sr)
     # int16 with each row's gain (:157-160): 0.999, or the peak of the row's own prompt
@@ -362,7 +371,7 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
 
 @torch.no_grad()
 def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir=None, f0=None, device=None,
-                   group_by_length: bool = True, **kw):
+                   group_by_length: Optional[bool] = None, **kw):
     """The reference's per-file loop (inference_vc.py:70-170, one process call per file) as batches: every source and
     prompt WAV at any sample rate (``audio.load_16k``; sources padded by pad_source), F0 tracks from ``f0`` (a mapping
     path -> track) or else from the '.hf0.npy' file extract_f0.py writes beside each WAV (a missing track is an error
@@ -373,7 +382,8 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     ``group_by_length`` True: one vc_batch call per padded source length (`length_groups`), so every batch has equal
     rows and each output matches the one-file conversion (contract item 2).  False: ONE ragged batch,
     faster, but every row shorter than the longest differs from its one-file conversion over its whole length (the
-    flows' attention sees the batch's padding; contract item 3).
+    flows' attention sees the batch's padding; contract item 3).  None (the default): True, unless ``row_exact=True``
+    is given -- then ONE ragged batch whose rows each match their one-file conversion.
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device); the files hold wav[b, :lengths[b]]."""
     from .audio import load_16k
     from .inference_plm import write_wav
@@ -388,6 +398,8 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     if kw.get("return_float"):
         raise L.HspError("vc_batch_files returns int16 rows only (use vc_batch for the float audio)")
     f0 = {} if f0 is None else {str(k): v for k, v in f0.items()}
+    if group_by_length is None:
+        group_by_length = not kw.get("row_exact", False)
 
     def track(path):
         t = f0[path] if path in f0 else load_f0(path)

@@ -181,11 +181,13 @@ class DiTConVBlock(nn.Module):
         # nn.Sequential(SiLU, Linear) in the reference: index 1 carries the parameters
         self.adaLN_modulation = nn.ModuleList([nn.Identity(), Linear(hidden_size, 6 * hidden_size)])
 
-    def forward(self, x, c, x_mask, c_silu=None, mod=None, premasked=False, modq=None):
+    def forward(self, x, c, x_mask, c_silu=None, mod=None, premasked=False, modq=None, key_len=None):
         """``c_silu`` = SiLU(c) precomputed by the caller (the same for every block of a flow); ``mod`` =
         this block's adaLN_modulation output [B, 6C, 1] when the caller ran all blocks' Linears as one GEMM;
         ``premasked``: x is already zero outside the mask (the output of a masked launch), so the leading
-        ``x * x_mask`` of modules.py:407 is the identity and is not launched."""
+        ``x * x_mask`` of modules.py:407 is the identity and is not launched.  ``key_len`` (device int64 [B]): the
+        row-exact mode -- the attention of row b sees keys [0, key_len[b]) only (the reference masks output rows only,
+        modules.py:408), and the FFN's k = 5 conv reads zeros past the row's end instead of modulate(0) = shift."""
         C = self.hidden_size
         if not premasked:
             x = Fh.mask_mul(x, x_mask)
@@ -207,11 +209,17 @@ class DiTConVBlock(nn.Module):
         if Fh.mha_proj_supported(self.attn.num_heads, C // self.attn.num_heads, C, x.shape[2]):
             # attention + proj + `x + gate_msa * (.) * mask` in ONE launch (round 4, csrc/hsp_mhaproj.hip)
             x = Fh.mha_proj(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.attn.num_heads, self.attn.scale,
-                            self.attn.proj._wt, bias=self.attn.proj._b, mask=x_mask, cscale=g_a, res=x)
+                            self.attn.proj._wt, bias=self.attn.proj._b, mask=x_mask, cscale=g_a, res=x, key_len=key_len)
         else:
-            o = Fh.mha(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.attn.num_heads, self.attn.scale)
+            # row-exact: the frame mask as key mask (hsp_mha_f32 takes mask_k together with mask_q; the rows a query mask
+            # blanks are zeroed by the projection's mask anyway)
+            km = x_mask if key_len is not None else None
+            o = Fh.mha(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.attn.num_heads, self.attn.scale, mask_q=km,
+                       mask_k=km)
             x = self.attn.proj(o, mask=x_mask, mask_mode=L.MASK_PRE, cscale=g_a, res=x)
         h = Fh.layernorm_mod(x, 1e-6, shift=sh_m, scale=sc_m)
+        if key_len is not None:
+            h = Fh.mask_mul(h, x_mask)
         # fc1 -> GELU -> fc2; fc2(y * mask) * mask == (W y + b) * mask for a 1x1 conv and a 0/1 mask
         fuse = _fuse(x)
         with (hip_layers.deferred() if fuse else contextlib.nullcontext()) as args:
@@ -250,7 +258,7 @@ class ResidualCouplingLayer_Transformer_simple(nn.Module):
         self.pre.pack_flipped(inputs=self.flipped)
         self.post.pack_flipped(outputs=self.flipped)
 
-    def forward(self, x, x_mask, g=None, reverse=False, inplace=False, c_silu=None, mods=None, modq=None):
+    def forward(self, x, x_mask, g=None, reverse=False, inplace=False, c_silu=None, mods=None, modq=None, key_len=None):
         """``mods`` [B, n_layers * 6 * hidden, 1]: the adaLN outputs of this layer's blocks, stacked; ``modq`` [B, n_layers *
         6 * hidden, 1]: their qkv layers' (c1_b | bias_b) rows (DiTConVBlock.forward), or None."""
         if not reverse:
@@ -262,7 +270,7 @@ class ResidualCouplingLayer_Transformer_simple(nn.Module):
         for j, blk in enumerate(self.enc_block):
             # `pre` and every block's last launch multiply by the mask before the residual add: h stays masked
             h = blk(h, g, x_mask, c_silu=c_silu, mod=None if mods is None else mods[:, j * R:(j + 1) * R],
-                    premasked=True, modq=None if modq is None else modq[:, j * R:(j + 1) * R])
+                    premasked=True, modq=None if modq is None else modq[:, j * R:(j + 1) * R], key_len=key_len)
         out = x if inplace else x.clone()
         # x1 <- (x1 - post(h) * mask) * mask          (modules.py:473,486)
         self.post(h, mask=x_mask, mask_mode=L.MASK_BOTH, scale=-1.0, res=x[:, wr], out=out[:, wr])

@@ -10,6 +10,7 @@ from torch import nn
 from .. import _lib as L
 from .. import activations
 from .. import functional as Fh
+from .. import hip_layers
 from ..alias_free_torch import Activation1d
 from ..hierspeechpp_speechsynthesizer import AMPBlock1, _amp_stage
 from ..hip_layers import Conv1d, entry as _entry, finalize as _finalize
@@ -36,13 +37,21 @@ class Generator(nn.Module):
             self.cond = Conv1d(gin_channels, ch, 1)
 
     def forward(self, x, g=None):
-        x = self.conv_pre(x, cbias=self.cond(g) if g is not None else None)
+        # inside hip_layers.row_exact (its RowLengths at any frame rate of which the input is a whole multiple): every
+        # row as on its own -- conv outputs zero past each row's end, ragged interpolation and activations
+        rows = hip_layers.row_lengths()
+        mk = (lambda t: dict(mask=rows.mask(t), mask_mode=L.MASK_POST)) if rows is not None else (lambda t: {})
+        x = self.conv_pre(x, cbias=self.cond(g) if g is not None else None, **mk(x.shape[2]))
         for i in range(self.num_upsamples):
             # the reference hard-codes `int(x.shape[-1] * 3)` (48k) / `* 1.5` (24k): speechsr.py:96
-            x = Fh.linear_interp(x, int(x.shape[-1] * self.upsample_rates[i]))
+            n = int(x.shape[-1] * self.upsample_rates[i])
+            if rows is None:
+                x = Fh.linear_interp(x, n)
+            else:
+                x = Fh.linear_interp(x, n, lens_in=rows.at(x.shape[2]), lens_out=rows.at(n))
             x = _amp_stage(self.resblocks, i * self.num_kernels, self.num_kernels, x)
         x = self.activation_post(x)
-        return self.conv_post(x, act=L.ACT_TANH)
+        return self.conv_post(x, act=L.ACT_TANH, **mk(x.shape[2]))
 
 
 class SynthesizerTrn(nn.Module):

@@ -4,7 +4,10 @@ B in {1, 4, 16, 32} x 4 s sources at equal length, and one ragged mix of 1-8 s s
 hipGraph replay per fixed shape (median of HIP-event pairs), a per-stage split from one eager pass with events
 (inference_vc.STAGE_HOOK; host submission included), and for the ragged mix the solo-versus-batch deviation of every
 row (contract item 3).  Prints one JSON line.
-    python tools/vc_batch_bench.py [--steps N] [--batches 1,4,16,32]"""
+    python tools/vc_batch_bench.py [--steps N] [--batches 1,4,16,32] [--row-exact]
+--row-exact adds, in the same process: the ragged mix with row_exact=True (and its deviation), the mix as
+length-grouped batches (vc_batch_files' default: one batch per padded length, times summed), and 16 x 4 s with
+row_exact=True against the default."""
 import argparse
 import json
 import os
@@ -46,9 +49,10 @@ def batch(dev, raw_lengths, prompt_seconds=3.0, seed=11):
                 fl=torch.tensor(fl, device=dev), noise=noise, seconds=sum(s.shape[-1] for s in srcs) / 16000.0)
 
 
-def measure(models, mel_fn, d, steps):
+def measure(models, mel_fn, d, steps, row_exact=False):
     from megatts2_hierspeechpp_amd import inference_vc as IV
-    run = lambda: IV.vc_batch(models, mel_fn, (d["x"], d["xl"]), (d["fs"], d["fl"]), d["trg"], d["f0t"], noise=d["noise"])
+    run = lambda: IV.vc_batch(models, mel_fn, (d["x"], d["xl"]), (d["fs"], d["fl"]), d["trg"], d["f0t"], noise=d["noise"],
+                              row_exact=row_exact)
     run()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
@@ -68,12 +72,12 @@ def measure(models, mel_fn, d, steps):
             "stage_ms_eager": stage}
 
 
-def ragged_deviation(models, mel_fn, d):
+def ragged_deviation(models, mel_fn, d, row_exact=False):
     """Solo vc() per row against the batch's float row (same noise slice): max |diff| / row peak over the whole row and
     over all but the last 0.5 s, and the distance from the row end beyond which |diff| stays below 1e-4 of the peak."""
     from megatts2_hierspeechpp_amd import inference_vc as IV
     _, n_out, audio = IV.vc_batch(models, mel_fn, d["srcs"], d["f0s"], d["trg"], d["f0t"], noise=d["noise"],
-                                  return_float=True)
+                                  return_float=True, row_exact=row_exact)
     rows = []
     for b, s in enumerate(d["srcs"]):
         n = int(n_out[b])
@@ -94,6 +98,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--batches", default="1,4,16,32")
+    ap.add_argument("--row-exact", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -109,6 +114,17 @@ def main():
         d = batch(dev, mix)
         out["ragged_1_8s"] = measure(models, mel_fn, d, a.steps)
         out["ragged_1_8s"]["solo_vs_batch"] = ragged_deviation(models, mel_fn, d)
+        if a.row_exact:
+            from megatts2_hierspeechpp_amd import inference_vc as IV
+            out["ragged_1_8s_row_exact"] = measure(models, mel_fn, d, a.steps, row_exact=True)
+            out["ragged_1_8s_row_exact"]["solo_vs_batch"] = ragged_deviation(models, mel_fn, d, row_exact=True)
+            groups = IV.length_groups([s.shape[-1] for s in d["srcs"]])
+            parts = [measure(models, mel_fn, batch(dev, [mix[b] for b in g]), a.steps) for g in groups]
+            out["ragged_1_8s_length_grouped"] = {"batches": len(groups), "ms_per_mix": sum(p["ms_per_batch"] for p in parts),
+                                                 "ms_per_batch": [p["ms_per_batch"] for p in parts]}
+            d16 = batch(dev, [n4] * 16)
+            out["equal_16x4s_default_vs_row_exact"] = {"default": measure(models, mel_fn, d16, a.steps)["ms_per_batch"],
+                                                       "row_exact": measure(models, mel_fn, d16, a.steps, row_exact=True)["ms_per_batch"]}
     print(json.dumps(out))
 
 
