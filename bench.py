@@ -4,6 +4,10 @@ configs[1]), 16 kHz output samples / s over the whole job + RTF.
 
     python bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR    # also write the last timed step's (audio, source) as DIR/<name>.npy
+    python bench.py ... --full                # also roofline, cpu_baseline and extra_configs (see below)
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump the outputs when asked, print
+the line.  Everything else it can measure takes runs of its own and waits for --full.
 
 N > 1 works both ways: under a launcher (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`, one rank per GPU over RCCL) and on its own --
@@ -20,6 +24,7 @@ Printed JSON (one line, rank 0): metric/value per the driver contract plus
   pack_ms (rank 0: fold + pack + upload of the weight arena), broadcast_ms (the dist.broadcast loop alone,
   barrier-bracketed; null at N = 1), broadcast_gbs, rank_ms_per_step {min, max}, rccl_world -- the multi-GPU side
   event_median_ms -- median of the K steps, each bracketed by a HIP-event pair (SURVEY.md 8d protocol)
+and with --full (each part can still be left out by its --no-* option):
   roofline      -- dominant kernel (conv1d_mfma_kernel): algorithmic FLOP of all its launches in one step /
                    their summed duration, timed live with events on the launch stream, against the
                    157.3 TFLOP/s fp32 MFMA peak; `traffic` from the committed PMC profile when it was
@@ -65,18 +70,35 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="form the RCCL process group and run every collective of the N > 1 path (weight broadcast, "
                          "barriers, timing reductions) at world size 1 as well")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_configs (configs[2] and configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the per-launch roofline pass, the CPU baseline and extra_configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-launch roofline pass")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip extra_configs (configs[2] and configs[3])")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
-    ap.add_argument("--dump-launches", default=None, help="write a per-shape table of the conv launches here")
+    ap.add_argument("--dump-launches", default=None,
+                    help="write a per-shape table of the conv launches here (taken by the roofline pass: needs --full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (rank 0's shard) as "
                          "DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample beyond that)")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.dump_launches and "roofline" not in full_parts(args, 1):
+        ap.error("--dump-launches is written by the roofline pass: give --full and leave out --no-roofline")
     return args
+
+
+def full_parts(args, n_gpus):
+    """What runs after the headline's timed steps: nothing on a plain run; with --full the per-launch roofline pass,
+    and at N = 1 the CPU baseline and extra_configs, less whatever a --no-* option leaves out."""
+    if not args.full:
+        return set()
+    parts = {"roofline"} if not args.no_roofline else set()
+    if n_gpus == 1:
+        parts |= {name for name, off in (("cpu_baseline", args.no_cpu_baseline), ("extra_configs", args.no_extra))
+                  if not off}
+    return parts
 
 
 # ------------------------------------------------------------------------ self-launch
@@ -595,12 +617,13 @@ def main(argv=None):
         _progress(f"timed region done: {result['ms_per_step']:.2f} ms per step")
         if args.dump_outputs:
             result["dump_outputs"] = dump_outputs(wl.last_out, args.dump_outputs)
-        if not args.no_roofline:
+        parts = full_parts(args, result["n_gpus"])
+        if "roofline" in parts:
             vocoder_roofline(args, wl, result)
             _progress(f"roofline pass done: frac {result['roofline']['frac']:.3f}")
-        if result["n_gpus"] == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in parts:
             cpu_baseline(args, wl, result)
-        if result["n_gpus"] == 1 and not args.no_extra:
+        if "extra_configs" in parts:
             from tools import bench_extra
             extra = {}
             _progress("extra_configs: vocoder 1 x 1 s")

@@ -306,3 +306,60 @@ def test_bench_dump_outputs_sample_is_bounded_and_fixed(tmp_path):
     assert all(np.array_equal(x, y) for x, y in zip(*written))
     audio = written[0][0]
     assert len(audio) > 0 and np.all(np.diff(audio) > 0)       # sorted positions of the flat array, no repeats
+
+
+# ------------------------------------------------------------------ bench.py: a plain run against --full
+def test_bench_full_parts():
+    """A plain run measures the headline alone; --full adds the roofline pass, and at N = 1 the CPU baseline and
+    extra_configs, each of which its --no-* option still leaves out.  --dump-launches needs the roofline pass."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert not plain.full and bench.full_parts(plain, 1) == set()
+    assert bench.full_parts(bench.parse_args(["--no-roofline", "--no-extra"]), 1) == set()
+    full = bench.parse_args(["--full"])
+    assert bench.full_parts(full, 1) == {"roofline", "cpu_baseline", "extra_configs"}
+    assert bench.full_parts(full, 2) == {"roofline"}
+    assert bench.full_parts(bench.parse_args(["--full", "--no-extra", "--no-cpu-baseline"]), 1) == {"roofline"}
+    assert bench.full_parts(bench.parse_args(["--full", "--no-roofline"]), 1) == {"cpu_baseline", "extra_configs"}
+    bench.parse_args(["--full", "--dump-launches", "t.txt"])
+    for argv in (["--dump-launches", "t.txt"], ["--full", "--no-roofline", "--dump-launches", "t.txt"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_main_runs_only_what_is_asked(monkeypatch, capfd, tmp_path, full):
+    """bench.main with the timed run stubbed out: a plain run goes from the timed steps to the dump and the line, and
+    starts none of the --full passes; with --full (extra_configs left out) the roofline pass and the CPU baseline run,
+    in that order, after the dump."""
+    sys.path.insert(0, ROOT)
+    import bench
+    calls = []
+    wl = _CountingWorkload(None, 0, 1, torch.device("cpu"))
+    wl.last_out = (torch.zeros(2, 1, 6), torch.ones(2, 1, 3))
+
+    def fake_run_bench(args, make_workload):
+        calls.append("timed")
+        return {"metric": bench.METRIC, "value": 1.0, "ms_per_step": 1.0, "n_gpus": 1}, wl
+
+    monkeypatch.setattr(bench, "run_bench", fake_run_bench)
+    monkeypatch.setattr(bench, "dump_outputs", lambda out, path: calls.append("dump") or {"dir": path})
+    monkeypatch.setattr(bench, "vocoder_roofline",
+                        lambda args, wl_, result: calls.append("roofline") or result.update(roofline={"frac": 0.5}))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda args, wl_, result: calls.append("cpu_baseline"))
+    argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")]
+    if full:
+        argv += ["--full", "--no-extra"]
+    saved = os.dup(1)                      # main() points descriptor 1 at stderr for the rest of the process
+    try:
+        assert bench.main(argv) == 0
+    finally:
+        os.dup2(saved, 1)
+        os.close(saved)
+    assert calls == (["timed", "dump", "roofline", "cpu_baseline"] if full else ["timed", "dump"])
+    lines = [ln for ln in capfd.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["dump_outputs"]["dir"] == str(tmp_path / "d")
+    assert ("roofline" in line) == full and "extra_configs" not in line

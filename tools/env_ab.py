@@ -4,9 +4,9 @@ HSP_FRONT_SPLITS, HSP_FFT_PAIR), alternating child processes as tools/lib_ab.py 
 
     python tools/env_ab.py --env "HSP_GEN_GROUPS=1" "HSP_GEN_GROUPS=2" "HSP_GEN_GROUPS=4" --rounds 2 [--roofline] [--json out.json]
 
-An entry may set several variables ("A=1,B=2") or none ("" = the defaults).  With --roofline the per-launch pass of
-bench.py stays on and the stand-alone activation's GB/s (roofline_activation) is reported beside the step time.  This
-process never touches the GPU."""
+An entry may set several variables ("A=1,B=2") or none ("" = the defaults).  With --roofline bench.py also runs its
+per-launch pass (`--full --no-extra --no-cpu-baseline`) and the stand-alone activation's GB/s (roofline_activation)
+is reported beside the step time.  This process never touches the GPU."""
 import argparse
 import json
 import os
@@ -29,9 +29,9 @@ for r in range(a.rounds):
         for kv in filter(None, e.split(",")):
             k, v = kv.split("=", 1)
             env[k] = v
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline", "--steps", str(a.steps)]
-        if not a.roofline:
-            cmd.append("--no-roofline")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps)]
+        if a.roofline:
+            cmd += ["--full", "--no-extra", "--no-cpu-baseline"]
         cmd += a.rest
         p = subprocess.run(cmd, capture_output=True, text=True, env=env)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -3,9 +3,9 @@
 
     python tools/lib_ab.py --libs /path/libhsp_a.so /path/libhsp_b.so --rounds 3 [--json out.json] [-- extra bench.py args]
 
-Each round runs `python bench.py --no-extra --no-cpu-baseline --no-roofline --steps 20` once per library (HSP_LIB
-selects it) as a child process, alternating A, B, A, B ... -- boxes and clocks drift, only alternating same-box
-numbers are comparable.  This process never touches the GPU."""
+Each round runs `python bench.py --steps 20` (with --roofline: `--full --no-extra --no-cpu-baseline`) once per
+library (HSP_LIB selects it) as a child process, alternating A, B, A, B ... -- boxes and clocks drift, only
+alternating same-box numbers are comparable.  This process never touches the GPU."""
 import argparse
 import json
 import os
@@ -25,9 +25,9 @@ out = {lib: [] for lib in a.libs}
 frac = {lib: [] for lib in a.libs}
 for r in range(a.rounds):
     for lib in a.libs:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline", "--steps", str(a.steps)]
-        if not a.roofline:
-            cmd.append("--no-roofline")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps)]
+        if a.roofline:
+            cmd += ["--full", "--no-extra", "--no-cpu-baseline"]
         cmd += a.rest
         p = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, HSP_LIB=os.path.abspath(lib)))
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
