@@ -443,6 +443,47 @@ int hsp_plm_embed_step_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_
  * logits.argmax(dim=-1) of the greedy loop (ttv_v1/t2w2v_transformer.py:716-717) */
 int hsp_argmax_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out,
                    int64_t out_bs, void* stream);
+
+/* ------------------------------------------------ sampled PLM decoding (additive: HSP_VERSION unchanged)
+ * The decision for row b choosing code column j (go token at column 0) from that step's N <= 1024 logits l, in the
+ * order of the GPT-SoVITS sampler logits_to_probs + multinomial_sample_one_no_sync (ttv_v1/utils_gptsovits.py):
+ *  1. repetition penalty r (1 = off): for every DISTINCT token c < N among the row's previous codes (columns 1 .. j-1),
+ *     l_c <- l_c < 0 ? l_c * r : l_c / r (once per token, however often it occurs);
+ *  2. top-p p (>= 1 = off) on the penalised logits: in descending order, ties ordered by LOWER INDEX FIRST (a stable
+ *     sort), a token is removed when the inclusive cumulative softmax mass exceeds p (no shift: the crossing token goes
+ *     too); the first token is always kept;
+ *  3. temperature: divide by max(T, 1e-5);
+ *  4. top-k k (0 = off): pivot = the min(k, N)-th largest tempered logit; only tokens strictly BELOW it are removed
+ *     (ties with the pivot stay);
+ *  5. draw: token = argmax over the kept tokens of (l'_i - ln q_i), lowest index on ties, q_i = -ln u_i ~ Exp(1) with
+ *     u_i = (w >> 8) 2^-24 + 2^-25 and w = word (i & 3) of Philox4x32-10(counter (i >> 2, j, 0, 0), key (low, high
+ *     32 bits of seeds[b])); u_i = (2 (w >> 8) + 1) 2^-25 is exact in float64, where q_i is computed (never 0).  A draw
+ *     depends on (seeds[b], j, i) only: independent of the batch and idempotent.
+ * `seeds` is read from device memory when the kernel runs (a captured graph replays with new seeds after a copy).
+ * probs (optional, NULL on the product path): probs[b * probs_bs + i] = the kept, normalised distribution after 4. */
+typedef struct hsp_sample_args {
+  float temperature;
+  int32_t top_k;               /* 0 = off */
+  float top_p;                 /* >= 1 = off */
+  float repetition_penalty;    /* 1 = off */
+  const int64_t* seeds;        /* [B] device int64 */
+  float* probs;                /* [B, N] or NULL */
+  int64_t probs_bs;
+} hsp_sample_args;
+/* The sampled twin of hsp_plm_embed_step_f32 (both its full and its n == 1 forms): workgroup (b, 0) takes
+ * codes[b, n - 1] = the decision above for column j (j = n - 1 in the full form, the position t in the n == 1 form),
+ * reading the row's previous codes from the j - 1 entries just before that slot, stores it and embeds.
+ * HSP_EINVAL (nothing launched) on top_k < 0, top_p <= 0, repetition_penalty <= 0, a non-finite temperature,
+ * n_logits > 1024, j < 1 or NULL seeds. */
+int hsp_plm_embed_sample_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t Dtc, int64_t* codes,
+                             int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb, const float* pe_t,
+                             int32_t P, const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B, int32_t n,
+                             const float* logits, int64_t l_bs, int64_t l_cs, int32_t n_logits, int32_t j,
+                             const hsp_sample_args* args, void* stream);
+/* The sampled twin of hsp_argmax_f32: out[b * out_bs] = the decision above for column j; the row's previous codes are
+ * the j - 1 entries just before out[b * out_bs] (out = &codes[0, j]).  One workgroup per row.  Same refusals. */
+int hsp_sample_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out, int64_t out_bs,
+                   int32_t j, const hsp_sample_args* args, void* stream);
 /* y[b, c, t] (contiguous) = x[b * s_bs + c * s_cs + t * s_ts] : strided gather, e.g. the last
  * position of every utterance (`[:, -1:, :]`, ttv_v1/t2w2v_transformer.py:716) */
 int hsp_copy_strided_f32(const float* x, int64_t s_bs, int64_t s_cs, int64_t s_ts, float* y, int32_t B,

@@ -101,6 +101,14 @@ class Cprod3Args(C.Structure):
     ]
 
 
+class SampleArgs(C.Structure):
+    """Mirror of ``hsp_sample_args``."""
+    _fields_ = [
+        ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+        ("seeds", _fp), ("probs", _fp), ("probs_bs", C.c_int64),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -144,6 +152,12 @@ SIGNATURES = {
                                          _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64,
                                          C.c_int64, C.c_int32, _fp]),
     "hsp_argmax_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, _fp]),
+    "hsp_plm_embed_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32,
+                                           C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32,
+                                           C.c_int32, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                           C.POINTER(SampleArgs), _fp]),
+    "hsp_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, C.c_int32,
+                                 C.POINTER(SampleArgs), _fp]),
     "hsp_embedding_sum_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp,
                                         C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

@@ -2,6 +2,8 @@
 // ttv_v1/t2w2v_transformer.py:702-718): the per-step input assembly and the greedy argmax
 // that feeds the next step.  Both read/write the code buffer in device memory so that the
 // whole T-step loop is a chain of launches without a host round trip (hipGraph-capturable).
+#include <cmath>
+
 #include "hsp_device.h"
 
 namespace {
@@ -144,6 +146,297 @@ __global__ __launch_bounds__(256) void copy_strided_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------- sampled decoding
+// The decision of hsp.h "sampled PLM decoding" for one row, by one 256-thread workgroup.  Thread t holds the logits
+// 4t .. 4t+3 (so its four Philox words are exactly one call at counter t).  No sort: the top-k pivot and the top-p
+// boundary are exact radix selects (four 8-bit digit passes) over the order-preserving uint32 key of each float.  The
+// top-p mass is carried as 2^-40 fixed point in 64-bit integers, so every sum is exact, order-free and deterministic
+// (the fused and the standalone launch agree bit for bit, and re-choosing a column is idempotent).
+constexpr int kSampleMaxN = 1024;
+
+struct SampleSmem {
+  unsigned long long hist[256];
+  unsigned long long wtot[4];
+  unsigned long long sel_above;
+  unsigned sel_bin;
+  int sel_found;
+  unsigned bits[kSampleMaxN / 32];
+  float redf[4];
+  int redi[4];
+  int token;
+};
+
+__device__ __forceinline__ unsigned order_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const unsigned lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+}
+
+// inclusive scan of v over the 256 threads in thread order; every thread gets its own prefix, *total the sum
+__device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long v, SampleSmem& s,
+                                                            unsigned long long* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) s.wtot[wave] = v;
+  __syncthreads();
+  unsigned long long before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const unsigned long long t = s.wtot[w];
+    before += w < wave ? t : 0ull;
+    all += t;
+  }
+  __syncthreads();   // wtot is reused by the next scan
+  *total = all;
+  return v + before;
+}
+
+__device__ __forceinline__ float block_max(float v, SampleSmem& s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) s.redf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = fmaxf(fmaxf(s.redf[0], s.redf[1]), fmaxf(s.redf[2], s.redf[3]));
+  __syncthreads();
+  return v;
+}
+
+// the same sum on every thread (the butterfly is symmetric, the four waves are added in a fixed order)
+__device__ __forceinline__ float block_sum(float v, SampleSmem& s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) s.redf[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = ((s.redf[0] + s.redf[1]) + s.redf[2]) + s.redf[3];
+  __syncthreads();
+  return v;
+}
+
+// Radix descent: the key v* of the first element, in DESCENDING key order, at which the running sum of the weights w
+// exceeds `target`, and the weight of all elements with a key above v*.  Elements with live[r] == false take no part.
+// Returns false (nothing crosses) when the total weight is <= target.
+__device__ bool radix_descend(const unsigned key[4], const unsigned long long w[4], const bool live[4],
+                              unsigned long long target, SampleSmem& s, unsigned* vstar, unsigned long long* above_out) {
+  const int tid = threadIdx.x;
+  unsigned prefix = 0, mask = 0;
+  unsigned long long above = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    s.hist[tid] = 0;
+    if (tid == 0) s.sel_found = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (live[r] && (key[r] & mask) == prefix) atomicAdd(&s.hist[(key[r] >> shift) & 255u], w[r]);
+    __syncthreads();
+    const unsigned bin = 255u - (unsigned)tid;   // thread order = descending digit
+    const unsigned long long h = s.hist[bin];
+    unsigned long long total;
+    const unsigned long long incl = block_scan_u64(h, s, &total);
+    const unsigned long long excl = incl - h;
+    if (above + excl <= target && above + incl > target) {
+      s.sel_bin = bin;
+      s.sel_above = above + excl;
+      s.sel_found = 1;
+    }
+    __syncthreads();
+    const int found = s.sel_found;
+    const unsigned sel_bin = s.sel_bin;
+    const unsigned long long sel_above = s.sel_above;
+    __syncthreads();   // every wave holds the selection before the next pass (or the next descent) clears it
+    if (!found) return false;                    // only possible in the first pass (uniform)
+    prefix |= sel_bin << shift;
+    mask |= 255u << shift;
+    above = sel_above;
+  }
+  *vstar = prefix;
+  *above_out = above;
+  return true;
+}
+
+// The whole decision for one row; every thread returns the token.  `prev` = the row's n_prev previous codes.
+__device__ int sample_decide(const float* __restrict__ row, int64_t l_cs, int N, const int64_t* prev, int n_prev,
+                             int j, const hsp_sample_args& a, float* probs, SampleSmem& s) {
+  const int tid = threadIdx.x;
+  const float rp = a.repetition_penalty;
+  const bool penalise = rp != 1.0f;
+  if (penalise) {
+    if (tid < kSampleMaxN / 32) s.bits[tid] = 0u;
+    __syncthreads();
+    for (int k = tid; k < n_prev; k += 256) {
+      const int64_t c = prev[k];
+      if (c >= 0 && c < N) atomicOr(&s.bits[c >> 5], 1u << (c & 31));   // the go token (>= N) is no candidate
+    }
+    __syncthreads();
+  }
+  // 1. penalty
+  float l[4];
+  bool valid[4];
+  unsigned key[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = 4 * tid + r;
+    valid[r] = i < N;
+    float v = valid[r] ? row[(int64_t)i * l_cs] : -INFINITY;
+    if (penalise && valid[r] && ((s.bits[i >> 5] >> (i & 31)) & 1u)) v = v < 0.0f ? v * rp : v / rp;
+    l[r] = v + 0.0f;                                   // -0 -> +0: equal floats get equal keys
+    key[r] = order_key(l[r]);
+  }
+  // 2. top-p on the penalised logits
+  if (a.top_p < 1.0f) {
+    const float m = block_max(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])), s);
+    unsigned long long w[4], mine = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      w[r] = valid[r] ? (unsigned long long)(expf(l[r] - m) * 1099511627776.0f) : 0ull;   // 2^40 fixed point
+      mine += w[r];
+    }
+    unsigned long long S;
+    block_scan_u64(mine, s, &S);
+    const unsigned long long thresh = (unsigned long long)((double)a.top_p * (double)S);
+    unsigned vstar;
+    unsigned long long above;
+    if (radix_descend(key, w, valid, thresh, s, &vstar, &above)) {
+      // ties at v* are kept in index order while their running mass stays <= thresh; the first token always stays
+      const bool at_max = vstar == order_key(m);
+      int nt = 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) nt += valid[r] && key[r] == vstar;
+      unsigned long long dummy;
+      unsigned long long rank = block_scan_u64((unsigned long long)nt, s, &dummy) - (unsigned long long)nt;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (!valid[r]) continue;
+        bool keep = key[r] > vstar;
+        if (key[r] == vstar) {
+          keep = above + (rank + 1) * w[r] <= thresh || (at_max && rank == 0);
+          ++rank;
+        }
+        if (!keep) l[r] = -INFINITY;
+      }
+    }
+  }
+  // 3. temperature
+  const float temp = fmaxf(a.temperature, 1e-5f);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    l[r] = l[r] / temp;
+    key[r] = order_key(l[r]);
+  }
+  // 4. top-k: pivot = the k-th largest tempered logit (the removed ones count, as -inf); keep everything >= pivot
+  if (a.top_k > 0 && a.top_k < N) {
+    const unsigned long long one[4] = {1ull, 1ull, 1ull, 1ull};
+    unsigned pivot;
+    unsigned long long above;
+    if (radix_descend(key, one, valid, (unsigned long long)(a.top_k - 1), s, &pivot, &above)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (key[r] < pivot) l[r] = -INFINITY;
+    }
+  }
+  // 5. softmax (for probs) and the exponential race in log form
+  const float mt = block_max(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])), s);
+  const int64_t seed = a.seeds[blockIdx.x];
+  unsigned c[4] = {(unsigned)tid, (unsigned)j, 0u, 0u};
+  philox4x32_10(c, (unsigned)(uint64_t)seed, (unsigned)((uint64_t)seed >> 32));
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (!valid[r] || l[r] == -INFINITY) continue;
+    // u = (2 (w >> 8) + 1) 2^-25 needs 25 bits: exact in double only (in float32 the top word rounds to u = 1, q = 0)
+    const double u = (double)(2u * (c[r] >> 8) + 1u) * 0x1p-25;
+    const float score = (l[r] - mt) - (float)log(-log(u));
+    if (score > best) best = score, bi = 4 * tid + r;   // ascending i within the thread: first wins ties
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) best = ov, bi = oi;
+  }
+  if ((tid & 63) == 0) s.redf[tid >> 6] = best, s.redi[tid >> 6] = bi;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (s.redf[w] > best || (s.redf[w] == best && s.redi[w] < bi)) best = s.redf[w], bi = s.redi[w];
+    s.token = bi == 0x7fffffff ? 0 : bi;
+  }
+  __syncthreads();
+  const int token = s.token;
+  if (probs) {
+    float e[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) e[r] = valid[r] ? expf(l[r] - mt) : 0.0f;
+    const float sum = block_sum((e[0] + e[1]) + (e[2] + e[3]), s);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (valid[r]) probs[(int64_t)blockIdx.x * a.probs_bs + 4 * tid + r] = e[r] / sum;
+  }
+  return token;
+}
+
+// hsp_sample_f32: one workgroup per row
+__global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ logits, int64_t l_bs, int64_t l_cs, int N,
+                                                     int64_t* __restrict__ out, int64_t out_bs, int j,
+                                                     hsp_sample_args a) {
+  __shared__ SampleSmem s;
+  const int b = blockIdx.x;
+  int64_t* slot = out + (int64_t)b * out_bs;
+  const int tok = sample_decide(logits + (int64_t)b * l_bs, l_cs, N, slot - (j - 1), j - 1, j, a, a.probs, s);
+  if (threadIdx.x == 0) *slot = tok;
+}
+
+// plm_embed_step_kernel with the sampled decision in place of the argmax (same grid, same writes)
+__global__ __launch_bounds__(256) void plm_embed_sample_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
+                                                               int Dtc, int64_t* __restrict__ codes, int64_t codes_bs,
+                                                               const float* __restrict__ emb, int Demb, int n_emb,
+                                                               const float* __restrict__ pe_t, int P,
+                                                               const float* __restrict__ alpha, float* __restrict__ x,
+                                                               int64_t x_bs, int64_t x_cs, int B, int n,
+                                                               const float* __restrict__ logits, int64_t l_bs,
+                                                               int64_t l_cs, int n_logits, int j, hsp_sample_args a) {
+  __shared__ SampleSmem s;
+  const int b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
+  const float al = alpha[0];
+  const int D = Dtc + Demb;
+  if (part == 0) {
+    int64_t* slot = codes + (int64_t)b * codes_bs + n - 1;
+    const int newest = sample_decide(logits + (int64_t)b * l_bs, l_cs, n_logits, slot - (j - 1), j - 1, j, a,
+                                     nullptr, s);
+    if (tid == 0) *slot = newest;
+    for (int e = tid; e < Demb * n; e += 256) {
+      const int jj = e % n, c = Dtc + e / n;
+      int64_t id = jj == n - 1 ? (int64_t)newest : codes[(int64_t)b * codes_bs + jj];
+      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);   // a corrupted code must not fault the GPU
+      x[b * x_bs + (int64_t)c * x_cs + jj] = fmaf(al, pe_t[(int64_t)c * P + jj], emb[id * Demb + (c - Dtc)]);
+    }
+    if (b == 0 && x_bs == n && x_cs > (int64_t)B * n) {
+      const int padc = (int)(x_cs - (int64_t)B * n);
+      for (int e = tid; e < D * padc; e += 256) x[(int64_t)(e / padc) * x_cs + (int64_t)B * n + e % padc] = 0.0f;
+    }
+  } else {
+    const int total = Dtc * n;
+    for (int e = (part - 1) * 1024 + tid; e < min(total, part * 1024); e += 256) {
+      const int jj = e % n, c = e / n;
+      x[b * x_bs + (int64_t)c * x_cs + jj] = fmaf(al, pe_t[(int64_t)c * P + jj], tc[b * tc_bs + c * tc_cs + jj]);
+    }
+  }
+}
+
 }  // namespace
 
 #define HSP_STREAM static_cast<hipStream_t>(stream)
@@ -192,5 +485,44 @@ extern "C" int hsp_copy_strided_f32(const float* x, int64_t s_bs, int64_t s_cs, 
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(copy_strided_kernel, dim3((unsigned)blocks), dim3(256), 0, HSP_STREAM, x, s_bs, s_cs, s_ts, y, B, C,
                      T);
+  return (int)hipGetLastError();
+}
+
+
+static bool sample_args_ok(const hsp_sample_args* a, int32_t N, int32_t j) {
+  if (!a || !a->seeds) return false;
+  if (a->top_k < 0 || !(a->top_p > 0.0f) || !(a->repetition_penalty > 0.0f) || !std::isfinite(a->temperature))
+    return false;
+  if (!std::isfinite(a->repetition_penalty)) return false;
+  if (N <= 0 || N > kSampleMaxN || j < 1) return false;
+  if (a->probs && a->probs_bs < N) return false;
+  return true;
+}
+
+extern "C" int hsp_plm_embed_sample_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t Dtc, int64_t* codes,
+                                        int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb,
+                                        const float* pe_t, int32_t P, const float* alpha, float* x, int64_t x_bs,
+                                        int64_t x_cs, int32_t B, int32_t n, const float* logits, int64_t l_bs,
+                                        int64_t l_cs, int32_t n_logits, int32_t j, const hsp_sample_args* args,
+                                        void* stream) {
+  if (!tc || !codes || !emb || !pe_t || !alpha || !x || !logits) return HSP_EINVAL;
+  if (B <= 0 || n < 1 || n > P || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || x_bs < 0 || x_cs < n) return HSP_EINVAL;
+  if (l_cs <= 0 || l_bs < 0 || !sample_args_ok(args, n_logits, j)) return HSP_EINVAL;
+  if (n > 1 && j != n - 1) return HSP_EINVAL;   // the full form chooses column n - 1
+  const int parts = 1 + (int)(((int64_t)Dtc * n + 1023) / 1024);
+  if (B > 65535 || parts > 65535) return HSP_EINVAL;
+  hsp_sample_args a = *args;
+  a.probs = nullptr;
+  hipLaunchKernelGGL(plm_embed_sample_kernel, dim3((unsigned)B, (unsigned)parts), dim3(256), 0, HSP_STREAM, tc, tc_bs,
+                     tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, B, n, logits, l_bs,
+                     l_cs, n_logits, j, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_sample_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out,
+                              int64_t out_bs, int32_t j, const hsp_sample_args* args, void* stream) {
+  if (!logits || !out || B <= 0 || B > 65535 || l_cs <= 0 || l_bs < 0 || !sample_args_ok(args, N, j)) return HSP_EINVAL;
+  hipLaunchKernelGGL(sample_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logits, l_bs, l_cs, N, out, out_bs, j,
+                     *args);
   return (int)hipGetLastError();
 }

@@ -102,8 +102,9 @@ def write_wav(path, sample_rate: int, pcm):
 @torch.no_grad()
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
-        return_float: bool = False, gain: float = 0.999):
-    """inference_plm.py:tts :156-190 on tensors.
+        return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None):
+    """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
+    make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
 
     text / tone / language int64 [B, N], text_length [B]; src_mel_ttv [B, 80, Tm'] (prompt mel for the
     front-end) with lengths; src_mel [2B, 80, Tm] = the B prompt mels followed by the B denoised prompt
@@ -115,7 +116,7 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
-    codes = models.plm.infer(x_frame)
+    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds)
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
     pitch = zero_below(pitch, math.log(55.0))                                  # :166 pitch clipping
     T2 = w2v_x.shape[2]
@@ -162,7 +163,8 @@ def output_gain(scale_norm: str, prompt_audio) -> float:
 def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audio, output_path=None,
                     noise_scale_vc: float = 0.333, output_sr: int = 16000, dur=None, noise=None,
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
-                    scale_norm: str = "max", return_float: bool = False):
+                    scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
+                    takes: int = 1):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -170,7 +172,18 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     peak back to the host), optional 16-bit WAV (:195-200).
     text / tone / language int64 [1, N] on the GPU; prompt_audio fp32 [1, n] at ``prompt_sr`` on the GPU;
     ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed.  Returns int16 [n_out] (and the float audio with
-    ``return_float``)."""
+    ``return_float``).
+
+    ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling): the prosody LM samples its codes with seed ``seed``.
+    ``takes`` = N > 1: one call synthesises N takes of the same text and prompt, take k with the PLM seed ``seed + k``
+    (each take equals the solo call with that seed: the rows of a batch are independent and have one length, since the
+    durations do not depend on the codes); returns int16 [N, n_out] and writes ``<stem>_take<k><ext>``.  An explicit
+    ``noise`` with one row is used by every take; None: every take draws its own."""
+    takes = int(takes)
+    if takes < 1:
+        raise L.HspError(f"takes must be >= 1, got {takes}")
+    if takes > 1 and plm_sampling is None:
+        raise L.HspError("takes > 1 needs plm_sampling: greedy decoding gives the same take every time")
     if denoise_ratio != 0 and denoiser is None:
         raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as inference_plm.py:144-147")
     if int(prompt_sr) != 16000:
@@ -178,25 +191,40 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     gain = output_gain(scale_norm, prompt_audio)
     src_mel_ttv, src_mel = prompt_mels(mel_fn, prompt_audio, denoiser if denoise_ratio != 0 else None, hps_denoiser)
     dev = prompt_audio.device
-    B = text.shape[0]
-    assert B == 1 and prompt_audio.shape[0] == 1, "the reference harness synthesises one utterance per call"
+    assert text.shape[0] == 1 and prompt_audio.shape[0] == 1, "the reference harness synthesises one utterance per call"
+    B = takes
+    if B > 1:
+        rep = lambda x: None if x is None else x.expand(B, *x.shape[1:]).contiguous()  # noqa: E731
+        text, tone, language, src_mel_ttv, dur = rep(text), rep(tone), rep(language), rep(src_mel_ttv), rep(dur)
+        src_mel = torch.cat([rep(src_mel[:1]), rep(src_mel[1:2])])     # the B prompt mels, then the B second mels
+        if noise is not None and noise.shape[0] == 1:
+            noise = rep(noise)
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
     wav, audio = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
                      noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
-                     noise=noise, gain=gain, return_float=True)
-    wav = wav[0]
-    if output_path is not None:
-        write_wav(output_path, output_sr if output_sr in (24000, 48000) else 16000, wav)
+                     noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
+                     seeds=int(seed) if plm_sampling is not None else None)
+    rate = output_sr if output_sr in (24000, 48000) else 16000
+    if B == 1:
+        wav = wav[0]
+        if output_path is not None:
+            write_wav(output_path, rate, wav)
+    elif output_path is not None:
+        import os
+        stem, ext = os.path.splitext(str(output_path))
+        for k in range(B):
+            write_wav(f"{stem}_take{k}{ext}", rate, wav[k])
     return (wav, audio) if return_float else wav
 
 
-def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None, **kwargs):
+def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
+                         plm_sampling=None, seed: int = 0, takes: int = 1, **kwargs):
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
-    ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``kwargs`` go to
-    `tts_from_prompt`."""
+    ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
+    ``takes`` and ``kwargs`` go to `tts_from_prompt`."""
     from . import audio as A
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
-                           prompt_sr=rate, **kwargs)
+                           prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, **kwargs)

@@ -1,8 +1,11 @@
 """HIP mirror of reference ttv_v1/t2w2v_transformer.py (inference members only)."""
 from __future__ import annotations
 
+import ctypes
+import dataclasses
 import math
 import os
+from typing import Optional
 
 import torch
 from torch import nn
@@ -79,6 +82,53 @@ class Embedding(HipLayer):
 PLM_CACHE_L0 = os.environ.get("HSP_PLM_CACHE_L0", "1") == "1"
 
 
+@dataclasses.dataclass(frozen=True)
+class PlmSampling:
+    """Sampled decoding of the prosody LM: the GPT-SoVITS sampler (ttv_v1/utils_gptsovits.py logits_to_probs +
+    multinomial_sample_one_no_sync) -- repetition penalty, then top-p on the penalised logits, then temperature
+    (clamped to >= 1e-5), then top-k -- drawn on the GPU with a counter-based stream (include/hsp.h "sampled PLM
+    decoding").  ``top_k`` / ``top_p`` None = off; ``top_k=1`` is greedy whatever the temperature."""
+
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    repetition_penalty: float = 1.0
+
+    def __post_init__(self):
+        if not (isinstance(self.temperature, (int, float)) and math.isfinite(self.temperature) and self.temperature >= 0):
+            raise ValueError(f"temperature must be a finite number >= 0, got {self.temperature!r}")
+        if self.top_k is not None and (isinstance(self.top_k, bool) or not isinstance(self.top_k, int) or self.top_k < 1):
+            raise ValueError(f"top_k must be None or an int >= 1, got {self.top_k!r}")
+        if self.top_p is not None and not (isinstance(self.top_p, (int, float)) and 0 < self.top_p <= 1):
+            raise ValueError(f"top_p must be None or in (0, 1], got {self.top_p!r}")
+        if not (isinstance(self.repetition_penalty, (int, float)) and math.isfinite(self.repetition_penalty)
+                and self.repetition_penalty > 0):
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {self.repetition_penalty!r}")
+
+    def c_args(self, seeds: torch.Tensor, probs: Optional[torch.Tensor] = None) -> L.SampleArgs:
+        """The hsp_sample_args of this setting; ``seeds`` int64 [B] on the GPU (read when the kernels run).  The struct
+        holds raw pointers: the caller keeps ``seeds`` and ``probs`` alive until the launches are enqueued."""
+        if seeds.dtype != torch.int64 or seeds.dim() != 1 or seeds.stride(0) != 1:
+            raise L.HspError("seeds must be a contiguous int64 [B] tensor")
+        return L.SampleArgs(float(self.temperature), int(self.top_k or 0),
+                            2.0 if self.top_p is None else float(self.top_p), float(self.repetition_penalty),
+                            L.ptr(seeds), L.fptr(probs), probs.stride(0) if probs is not None else 0)
+
+
+def plm_seeds(seeds, B: int, device) -> torch.Tensor:
+    """int64 [B] seeds on ``device``: an int s gives row b the seed s + b (one fill kernel, capturable); a tensor is used
+    as it is when it already is a contiguous int64 [B] device tensor -- so a captured loop replays with the values
+    a later ``seeds.copy_()`` put there."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.shape != (B,):
+            raise L.HspError(f"seeds must have shape ({B},), got {tuple(seeds.shape)}")
+        if seeds.dtype == torch.int64 and seeds.device == torch.device(device) and seeds.is_contiguous():
+            return seeds
+        return seeds.to(device=device, dtype=torch.int64).contiguous()
+    s = int(0 if seeds is None else seeds)
+    return torch.arange(s, s + B, dtype=torch.int64, device=device)
+
+
 class Megatts2PLM1(nn.Module):
     """t2w2v_transformer.Megatts2PLM1 (:627-718): greedy prosody-code generation.
 
@@ -108,10 +158,11 @@ class Megatts2PLM1(nn.Module):
         self.arena = _finalize(self, device, materialize)
         return self
 
-    def _embed(self, tc, codes, n, prev_logits=None):
+    def _embed(self, tc, codes, n, prev_logits=None, sample=None):
         """[1, d_model, Np]: utterance b occupies columns b*n .. b*n+n-1; Np = B*n rounded up to a multiple
         of 4 (16-B rows for the token GEMM's DMA), padding columns are zero.  ``prev_logits`` [1, vq_bins, B]: the
-        scores of step n-1, whose argmax this launch takes (and stores to ``codes[:, n-1]``) before it embeds."""
+        scores of step n-1, whose argmax (with ``sample``, a SampleArgs: whose sampled choice) this launch takes (and
+        stores to ``codes[:, n-1]``) before it embeds."""
         B = tc.shape[0]
         x = torch.empty(1, self.d_model, (B * n + 3) & ~3, dtype=torch.float32, device=tc.device)
         head = (L.fptr(tc), tc.stride(0), tc.stride(1), self.tc_latent_dim, L.ptr(codes), codes.stride(0),
@@ -119,14 +170,19 @@ class Megatts2PLM1(nn.Module):
                 self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x), n, x.shape[2], B, n)
         if prev_logits is None:
             L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
-        else:
+        elif sample is None:
             lg = prev_logits
             assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
             L.check(L.lib().hsp_plm_embed_step_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, L.stream_ptr()),
                     "hsp_plm_embed_step_f32")
+        else:
+            lg = prev_logits
+            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
+            L.check(L.lib().hsp_plm_embed_sample_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, n - 1,
+                                                     ctypes.byref(sample), L.stream_ptr()), "hsp_plm_embed_sample_f32")
         return x
 
-    def _embed_one(self, tc, codes, t, cache, prev_logits):
+    def _embed_one(self, tc, codes, t, cache, prev_logits, sample=None):
         """Position t of every utterance into ``cache.emb[:, :, t]`` ([D, B, Tp]: fixed pitch) -- the same launch as _embed
         with every per-position operand shifted to column t and n = 1 (the kernel then takes codes[:, t] = argmax of
         ``prev_logits`` first, as in the full form)."""
@@ -140,46 +196,66 @@ class Megatts2PLM1(nn.Module):
                 self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x_t), emb.stride(1), emb.stride(0), B, 1)
         if prev_logits is None:
             L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
-        else:
+        elif sample is None:
             lg = prev_logits
             assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
             L.check(L.lib().hsp_plm_embed_step_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, L.stream_ptr()),
                     "hsp_plm_embed_step_f32")
+        else:
+            lg = prev_logits
+            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
+            L.check(L.lib().hsp_plm_embed_sample_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, t,
+                                                     ctypes.byref(sample), L.stream_ptr()), "hsp_plm_embed_sample_f32")
 
     @_entry
-    def step_logits(self, tc_latent, codes, n, out=None, prev_logits=None, cache=None):
+    def step_logits(self, tc_latent, codes, n, out=None, prev_logits=None, cache=None, sampling=None, seeds=None):
         """Logits of position n-1 given the first n columns of ``tc_latent`` [B, 256, T] and of
         ``codes`` [B, >= n] (go token first): one pass of the loop body (:710-716) -> [1, vq_bins, B].
         With ``prev_logits`` (the result of the call for n-1) ``codes[:, n-1]`` is not read but first set to their
-        argmax, inside the embedding launch."""
+        argmax, inside the embedding launch -- or, with ``sampling`` (a PlmSampling; ``seeds`` as for `infer`), to a
+        sampled choice (hsp_plm_embed_sample_f32)."""
         B = tc_latent.shape[0]
+        sample = None
+        if sampling is not None and prev_logits is not None:
+            seeds = plm_seeds(seeds, B, tc_latent.device)   # held until the launches below are enqueued
+            sample = sampling.c_args(seeds)
         # the last layer only produces the last position of every utterance when those B columns form a
         # 16-B addressable matrix for the fused-LayerNorm GEMM; otherwise it runs in full
         last_only = B % 4 == 0
         att = self.plm.layers[0].attn
         if cache is not None:
             # layer 0 incrementally (PLM_CACHE_L0): only position n - 1 is embedded and projected, the older columns are kept
-            self._embed_one(tc_latent, codes, n - 1, cache, prev_logits)
+            self._embed_one(tc_latent, codes, n - 1, cache, prev_logits, sample)
         if cache is not None and Fh.mha_proj_supported(att.n_heads, att.head_dim, self.d_model, n):
             x = self.plm(None, batch=(B, n), last_only=last_only, cache=cache)
         elif cache is not None:
             # the first three steps (fewer than four keys: no fused attention kernel): the new column still enters the cache,
-            # the step itself runs in the full form (its embedding launch takes the same argmax again: idempotent)
+            # the step itself runs in the full form (its embedding launch takes the same argmax -- or the same draw, which
+            # depends on (seed, column, token) only -- again: idempotent)
             att.qkv(cache.emb[:, :, n - 1:n].permute(1, 0, 2), out=cache.qkv[:, :, n - 1:n].permute(1, 0, 2))
-            x = self.plm(self._embed(tc_latent, codes, n, prev_logits), batch=(B, n), last_only=last_only)
+            x = self.plm(self._embed(tc_latent, codes, n, prev_logits, sample), batch=(B, n), last_only=last_only)
         else:
-            x = self.plm(self._embed(tc_latent, codes, n, prev_logits), batch=(B, n), last_only=last_only)
+            x = self.plm(self._embed(tc_latent, codes, n, prev_logits, sample), batch=(B, n), last_only=last_only)
         if not last_only:
             x = Fh.copy_strided(x[0][:, :B * n].reshape(self.d_model, B, n)[:, :, n - 1].unsqueeze(0))
         return self.predict_layer(x, out=out)
 
     @_entry
     @torch.no_grad()
-    def infer(self, tc_latent: torch.Tensor, return_logits: bool = False):
-        """tc_latent (B, D, T) -> int64 codes (B, T)  [+ fp32 logits (B, T, vq_bins)]."""
+    def infer(self, tc_latent: torch.Tensor, return_logits: bool = False, sampling: Optional[PlmSampling] = None,
+              seeds=None):
+        """tc_latent (B, D, T) -> int64 codes (B, T)  [+ fp32 logits (B, T, vq_bins)].
+
+        ``sampling`` None: greedy (the reference).  A PlmSampling: every code is drawn instead (include/hsp.h "sampled
+        PLM decoding"); ``seeds`` an int (row b gets seed + b; None = 0) or an int64 [B] tensor (a device tensor is read
+        in place when the kernels run, so a captured loop replays with new seeds after ``seeds.copy_()``).  Row b
+        depends on its own seed only, not on the rest of the batch."""
         if self.pos_emb._pe_t is None:
             raise L.HspError("Megatts2PLM1 used before finalize()")
+        if sampling is not None and not isinstance(sampling, PlmSampling):
+            raise L.HspError("sampling must be a PlmSampling or None")
         B, D, T = tc_latent.shape
+        seeds = plm_seeds(seeds, B, tc_latent.device) if sampling is not None else None
         assert D == self.tc_latent_dim and tc_latent.stride(2) == 1 and T <= self.pos_emb.N_POS
         codes = torch.empty(B, T + 1, dtype=torch.int64, device=tc_latent.device)
         codes[:, 0] = self.GO_ID
@@ -197,9 +273,13 @@ class Megatts2PLM1(nn.Module):
         for t in range(T):
             # the greedy choice of step t-1 is taken inside step t's embedding launch; only the last step's needs its own
             lg = self.step_logits(tc_latent, codes, t + 1, out=all_logits[t:t + 1] if return_logits else None,
-                                  prev_logits=lg, cache=cache)
-        L.check(L.lib().hsp_argmax_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0),
-                                       L.stream_ptr()), "hsp_argmax_f32")
+                                  prev_logits=lg, cache=cache, sampling=sampling, seeds=seeds)
+        if sampling is None:
+            L.check(L.lib().hsp_argmax_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0),
+                                           L.stream_ptr()), "hsp_argmax_f32")
+        else:
+            L.check(L.lib().hsp_sample_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0), T,
+                                           ctypes.byref(sampling.c_args(seeds)), L.stream_ptr()), "hsp_sample_f32")
         return (codes[:, 1:], all_logits.permute(2, 0, 1)) if return_logits else codes[:, 1:]
 
 

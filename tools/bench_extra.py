@@ -119,8 +119,9 @@ def dominant_roofline(agg, workload=None):
 
 
 # ----------------------------------------------------------------------------- configs[2]
-def tts_b16(dev, steps=3, warmup=1, batch=16, phones=40, use_graph=True, models=None):
-    """16 utterances x 40 phones x 10 frames (durations pinned) -> 200 PLM steps, 4 s each."""
+def tts_b16(dev, steps=3, warmup=1, batch=16, phones=40, use_graph=True, models=None, plm_sampling=None):
+    """16 utterances x 40 phones x 10 frames (durations pinned) -> 200 PLM steps, 4 s each.
+    ``plm_sampling`` (a PlmSampling): the PLM loop samples (row b seed b) instead of taking the argmax."""
     from megatts2_hierspeechpp_amd import inference_plm as IP, synth
     B, N = batch, phones
     if models is None:
@@ -140,17 +141,19 @@ def tts_b16(dev, steps=3, warmup=1, batch=16, phones=40, use_graph=True, models=
     T2 = N * 10 // 2
     noise = torch.from_numpy(r.standard_normal((B, 192, T2)).astype(np.float32)).to(dev)
     plm_graph = {}
+    plm_kw = {} if plm_sampling is None else dict(sampling=plm_sampling,
+                                                  seeds=torch.arange(B, dtype=torch.int64, device=dev))
 
     def plm_infer(x_frame, eager=False):
         if eager or not use_graph:
-            return models.plm.infer(x_frame)
+            return models.plm.infer(x_frame, **plm_kw)
         if "g" not in plm_graph:
             plm_graph["x"] = x_frame.clone()
-            models.plm.infer(plm_graph["x"])
+            models.plm.infer(plm_graph["x"], **plm_kw)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                plm_graph["codes"] = models.plm.infer(plm_graph["x"])
+                plm_graph["codes"] = models.plm.infer(plm_graph["x"], **plm_kw)
             plm_graph["g"] = g
         plm_graph["x"].copy_(x_frame)
         plm_graph["g"].replay()
@@ -219,7 +222,7 @@ def tts_b16(dev, steps=3, warmup=1, batch=16, phones=40, use_graph=True, models=
     torch.cuda.synchronize()
     names = ["front_end(A16-A17)", "plm_loop(A18)", "w2v+pitch(A17)", "vocoder(A1-A14)", "int16_post(A19)"]
     stages = {n: ev[i].elapsed_time(ev[i + 1]) for i, n in enumerate(names)}
-    roof = dominant_roofline(conv_entry_profile(lambda: models.plm.infer(plm_graph["x"]) if "x" in plm_graph
+    roof = dominant_roofline(conv_entry_profile(lambda: models.plm.infer(plm_graph["x"], **plm_kw) if "x" in plm_graph
                                                 else step(None, eager=True)), "tts")
     if roof:
         roof["scope"] = "the PLM greedy loop (the dominant stage of this config), all launches behind the conv entry point"
