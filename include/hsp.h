@@ -42,12 +42,15 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HSP_VERSION 102 /* unchanged by hsp_resample_f32 and hsp_act1d_snakebeta_ragged_f32, which only add to the ABI.
-                           * NOT purely additive: hsp_mha_proj_args and hsp_dftseg_args grew a trailing field each (key_len,
-                           * act_len; NULL = the former behaviour) for the row-exact ragged vocoder -- a caller compiled
-                           * against an older header passes shorter structs and must be rebuilt (the version number is pinned by the suite's ABI test); 0.1.2: round 6 -- hsp_dftseg_pair_f32 takes the pass-through form (inv->y / inv->res); 0.1.1: round 5
-                           * -- hsp_dftseg_args grew a field (prod3); hsp_cprod3_f32, hsp_cprod3_supported,
-                           * hsp_dftseg_weight_spectrum_f32, hsp_dftseg_supported are new */
+#define HSP_VERSION 103 /* 0.1.3: hsp_conv1d_args lost the five trailing fields of the modulated input LayerNorm (the
+                           * round-6 experiment that 0.1.2 added after w_bs) -- a caller compiled against 102 passes a longer
+                           * struct and must be rebuilt; hsp_dftseg_pair_f32 no longer takes inv->y / inv->res (refused).
+                           * 0.1.2: hsp_conv1d_args grew those five fields; hsp_dftseg_pair_f32 took inv->y / inv->res and
+                           * wrote inv->y; hsp_mha_proj_args and hsp_dftseg_args grew a trailing field each (key_len,
+                           * act_len; NULL = the former behaviour) for the row-exact ragged vocoder (hsp_resample_f32 and
+                           * hsp_act1d_snakebeta_ragged_f32 only add to the ABI).  0.1.1: hsp_dftseg_args grew a field
+                           * (prod3); hsp_cprod3_f32, hsp_cprod3_supported, hsp_dftseg_weight_spectrum_f32,
+                           * hsp_dftseg_supported are new.  The version number is pinned by the suite's ABI test. */
 #define HSP_EINVAL (-1)
 
 int hsp_version(void);
@@ -183,23 +186,6 @@ typedef struct hsp_conv1d_args {
    * hsp_dftseg_*_f32 below), where the batch index is the frequency BIN and every bin has its own [Cin][M] matrix.
    * The implicit-GEMM conv kernel only (the token GEMMs refuse it). */
   int64_t w_bs;
-  /* Modulated input LayerNorm (round 6; with ln_c1, on the block token GEMM only -- any other launch that carries one of
-   * these fields is refused with HSP_EINVAL): the adaLN form of a DiT block's first half,
-   *   qkv = W ((LN(x) * mask) * (1 + scale_b) + shift_b) + bias        (modules.py:346-347,406-409: norm1 has no affine,
-   *                                                                     scale / shift differ per UTTERANCE b)
-   * as ONE launch on the un-normalised x:  v = rstd[t] mask[b, t] (acc[m, t] - mean[t] c1_b[m]) + bias_b[m]  with
-   *   acc = W diag(1 + scale_b) x          ln_scale[b * ln_scale_bs + ci] = scale_b[ci]: the kernel multiplies the staged
-   *                                        input fragments by (1 + scale) on their way into the MFMA
-   *   c1_b[m] = sum_ci W[m][ci] (1 + scale_b[ci])      = ln_c1[b * ln_c1_bs + m]        (ln_c1_bs = 0: one vector for all b)
-   *   bias_b[m] = sum_ci W[m][ci] shift_b[ci] + bias[m] = cbias[b * cbias_bs + m]       (bias NULL)
-   *   ln_mask[b * ln_mask_bs + t]: the 0 / 1 column mask applied to the normalised input (NULL = none).
-   * c1_b and bias_b are linear in the conditioning vector: the caller gets them as extra rows of the one GEMM that
-   * produces scale_b / shift_b (hip_layers / modules.DiTConVBlock).  Cin <= 1024.  NULL ln_scale = plain ln_c1 form. */
-  const float* ln_scale;
-  int64_t ln_scale_bs;
-  int64_t ln_c1_bs;
-  const float* ln_mask;
-  int64_t ln_mask_bs;
 } hsp_conv1d_args;
 
 /* MFMA (v_mfma_f32_32x32x2_f32, exact fp32) path; stride must be 1, M % 4 == 0.  Behind this entry point: the
@@ -601,7 +587,8 @@ typedef struct hsp_dftseg_args {
   int32_t B, C, L;
   int32_t k, dil, pad, nseg, Np;
   float* xf;        /* forward: written; inverse: read */
-  int64_t xf_bs;    /* plane (bin) stride >= 2 C Np */
+  int64_t xf_bs;    /* plane (bin) stride >= 2 C Np, and xf_bs * 256 <= 0xffffffff: the kernels address the spectrum with
+                       32-bit byte offsets, every hsp_dftseg_* entry point refuses a larger stride */
   const float* dft;
   const float* bias; /* inverse epilogue: optional */
   const float* res;
@@ -630,15 +617,10 @@ int hsp_dftseg_tables_f32(float* fwd, float* inv); /* host buffers of HSP_DFTSEG
 /* The two convs of an AMP pair (hierspeechpp_speechsynthesizer.py:380-384: xt = c1(a1(x)); xt = c2(a2(xt))) met in ONE
  * launch: `inv` describes the inverse transform of c1's product (xf = c1's product output, dft = the inverse table, bias;
  * no residual / running sum / post_scale), `fwd` the forward transform of c2's input (xf = c2's spectrum to write, dft =
- * the forward table, act_* = a2, required); same B, C, L.  y of `inv` and x of `fwd` are not read: the tensor between
- * the convs exists in LDS only.  hsp_dftseg_pair_supported: 1 if the pair fits (both unchunked, two row stretches in one
- * CU's LDS), else 0 and the caller runs hsp_dftseg_inv_f32 + hsp_dftseg_fwd_f32.
- * Pass-through form (round 6; version 102): `inv->y` given (with `inv->res` or without) -- the tensor between the two
- * transforms IS needed elsewhere: the seam between two iterations of an AMP block (hierspeechpp_speechsynthesizer.py:
- * 380-384: x = c2(...) + x; xt = a1'(x) ...), where x_new = inverse(c2's product) + bias + res is the residual of the next
- * iteration.  The launch then writes x_new to `inv->y` (16-B addressable rows) and transforms act(x_new) for the next
- * conv: the inverse launch, the forward launch and one read of x_new become one launch.  Same arithmetic in the same
- * order as the two launches. */
+ * the forward table, act_* = a2, required); same B, C, L.  y / res of `inv` are not used (refused) and x of `fwd` is not
+ * read: the tensor between the convs exists in LDS only.  hsp_dftseg_pair_supported: 1 if the pair fits (both unchunked,
+ * two row stretches in one CU's LDS, each spectrum below 4 GiB), else 0 and the caller runs hsp_dftseg_inv_f32 +
+ * hsp_dftseg_fwd_f32. */
 int hsp_dftseg_pair_supported(const hsp_dftseg_args* inv, const hsp_dftseg_args* fwd);
 int hsp_dftseg_pair_f32(const hsp_dftseg_args* inv, const hsp_dftseg_args* fwd, void* stream);
 

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   float* const twl = lds + G.bufsz;                             // (cos | sin)(2 pi k / 128), k < 32, behind the stretch
   if (tid < 64) twl[tid] = a.dft[DS_H * DS_H + tid];
   // the previous column block's outputs of this lane (bin register r: X[kb] Re, Im, X[64 - kb] Re, Im) and where they go:
-  // 32-bit byte offsets into the spectrum (the host checks that it is below 4 GB), lane part in two registers -- bins
+  // 32-bit byte offsets into the spectrum (ds_check bounds it below 4 GB), lane part in two registers -- bins
   // kb = lanek + c_r count up from lb1, bins 64 - kb down from lb2 -- and the register's part c_r xf_bs uniform (the
   // 32 full 64-bit offsets, hoisted out of the item loop by the compiler, cost 64 registers and with them the second
   // workgroup of the CU).
@@ -522,9 +522,7 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 // Epilogue of the conv this replaces, y = ((corr + bias + res) [+ y]) * post_scale, out of the LDS stretch of an item.
 // A UNIT = 64 U consecutive W-float vectors of one row; wave w of nw takes units w, w + nw, ...: the row's base addresses
 // (y, res) are wave-uniform 64-bit values, a lane adds one 32-bit byte offset per vector.
-// KEEP: the finished samples also go back into the stretch (the pair kernel's pass-through form: the activation of the
-// next conv reads them there)
-template <int W, int U, bool RES, bool ACC, bool KEEP = false>
+template <int W, int U, bool RES, bool ACC>
 __device__ __forceinline__ void ds_inv_epilogue_t(const hsp_dftseg_args& a, const DsGeom& G, const DsItem& I, const float* buf,
                                                   int w, int nw, int lane, int tb, int tl) {
   typedef float vec_t __attribute__((ext_vector_type(W)));
@@ -558,7 +556,6 @@ __device__ __forceinline__ void ds_inv_epilogue_t(const hsp_dftseg_args& a, cons
         if constexpr (ACC) v += o4[u];
         if (ps != 1.0f) v *= ps;
         *reinterpret_cast<vec_t*>(yb + (unsigned)(j * (W * 4))) = v;
-        if constexpr (KEEP) *reinterpret_cast<vec_t*>(const_cast<float*>(row) + W * j) = v;
       }
     }
     rr += nw;
@@ -891,16 +888,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       else step1(v1, q1);
       odd = !odd;
     }
-    // ---------------- phase 1.5 (pass-through form, round 6: ai.y given): the first conv's whole epilogue -- bias + residual --
-    // happens here, its output leaves for HBM (it is the residual of the NEXT iteration: x = xt + x,
-    // hierspeechpp_speechsynthesizer.py:384) and stays in A for the activation of the next conv
-    const bool through = ai.y != nullptr;
-    if (through) {
-      const DsGeom Ga = {G.cg, G.S1, G.pitchA, G.ngrp, 1, 0};
-      if (ai.res) ds_inv_epilogue_t<4, 4, true, false, true>(ai, Ga, I, sA, wave, 8, lane, 0, ai.L);
-      else ds_inv_epilogue_t<4, 4, false, false, true>(ai, Ga, I, sA, wave, 8, lane, 0, ai.L);
-      ds_barrier();
-    }
     // ---------------- phase 2: A -> act -> B
     {
       DsStage sg;
@@ -915,7 +902,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int sI = wave; sI < da.nsegs; sI += 8) {
         const int ch = sI / da.nsg, p0 = da.pa4 + DA_SEG * (sI - ch * da.nsg);
         const ds_f32x4 rv = *reinterpret_cast<const ds_f32x4*>(sA + ch * G.pitchA + hsp_clampi(p0 - 8 + 4 * lane, 0, af.L - 4));
-        da_segment<RAG>(af, Gf, I, sg, da, sI, lane, rv, slice, sB, flt, (ai.bias && !through) ? ai.bias[I.c0 + ch] : 0.0f,
+        da_segment<RAG>(af, Gf, I, sg, da, sI, lane, rv, slice, sB, flt, ai.bias ? ai.bias[I.c0 + ch] : 0.0f,
                         lb, sA + (lb - 1), G.pitchA);
       }
       for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
@@ -973,6 +960,7 @@ int ds_check(const hsp_dftseg_args& a) {
   const int per_phase = (a.L + a.dil - 1) / a.dil;
   if (a.nseg != (per_phase + hop - 1) / hop || a.pad < 0 || a.pad > (a.k - 1) * a.dil) return HSP_EINVAL;
   if ((int64_t)a.B * a.dil * a.nseg > a.Np || a.xf_bs < (int64_t)2 * a.C * a.Np) return HSP_EINVAL;
+  if (a.xf_bs * 64 * 4 > 0xffffffffll) return HSP_EINVAL;       // the kernels address the spectrum with 32-bit byte offsets
   return 0;
 }
 
@@ -1041,14 +1029,8 @@ DsGeom ds_geom(const hsp_dftseg_args& a, bool inverse) {
 DpGeom dp_geom(const hsp_dftseg_args& ai, const hsp_dftseg_args& af) {
   DpGeom G = {};
   if (ds_check(ai) || ds_check(af)) return G;
-  if (ai.B != af.B || ai.C != af.C || ai.L != af.L || ai.accumulate || ai.post_scale != 1.0f) return G;
-  if (ai.res && !ai.y) return G;                                // a residual belongs to the pass-through form (ai.y given)
-  if (ai.y) {                                                   // ... whose epilogue moves 16-B vectors
-    if (((ai.L | (int)ai.y_bs | (int)ai.y_cs) & 3) || (reinterpret_cast<uintptr_t>(ai.y) & 15)) return G;
-    if (ai.res && ((((int)ai.res_bs | (int)ai.res_cs) & 3) || (reinterpret_cast<uintptr_t>(ai.res) & 15))) return G;
-  }
+  if (ai.B != af.B || ai.C != af.C || ai.L != af.L || ai.y || ai.res || ai.accumulate || ai.post_scale != 1.0f) return G;
   if (!af.act_alpha_exp || !af.act_beta_inv || !af.act_filt || (af.L & 3)) return G;
-  if (af.xf_bs * 64 * 4 > 0xffffffffll) return G;
   const int hop1 = DS_N - (ai.k - 1), hop2 = DS_N - (af.k - 1);
   G.S1 = ai.nseg;
   G.S2 = af.nseg;
@@ -1083,7 +1065,6 @@ DpGeom dp_geom(const hsp_dftseg_args& ai, const hsp_dftseg_args& af) {
 }
 // what hsp_dftseg_fwd_f32 / hsp_dftseg_inv_f32 refuse beyond ds_check, from the geometry alone (hsp_dftseg_supported)
 int ds_limits(const hsp_dftseg_args& a, bool act) {
-  if (a.xf_bs * 64 * 4 > 0xffffffffll) return HSP_EINVAL;       // the kernels address the spectrum with 32-bit byte offsets
   const DsGeom Gf = ds_geom(a, false), Gi = ds_geom(a, true);
   const size_t lds_f = ((size_t)Gf.bufsz + 64 + (act ? 32 + 4 * DA_SLICE : 0)) * sizeof(float);
   const size_t lds_i = ((size_t)Gi.bufsz + 128 * 32) * sizeof(float);
@@ -1138,7 +1119,6 @@ extern "C" int hsp_dftseg_fwd_f32(const hsp_dftseg_args* ap, void* stream) {
   const size_t lds_bytes = ((size_t)G.bufsz + 64 + (act ? 32 + 4 * DA_SLICE : 0)) * sizeof(float);
   const int64_t items = (int64_t)a.B * G.ngrp * G.nchunk;
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
-  if (a.xf_bs * 64 * 4 > 0xffffffffll) return HSP_EINVAL;      // the kernel addresses the spectrum with 32-bit byte offsets
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
   if (a.act_len && !act) return HSP_EINVAL;                    // per-row lengths belong to the fused activation
   if (a.act_len) {

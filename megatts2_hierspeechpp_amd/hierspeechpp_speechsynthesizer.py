@@ -30,7 +30,7 @@ from . import activations
 from . import modules
 from .alias_free_torch import Activation1d
 from .commons import get_padding
-from .hip_layers import Conv1d, ConvTranspose1d, Linear, ModulatedNormRows, StackedLinearCT, entry as _entry, finalize as _finalize
+from .hip_layers import Conv1d, ConvTranspose1d, Linear, StackedLinearCT, entry as _entry, finalize as _finalize
 from .styleencoder import StyleEncoder
 
 UNUSED_PREFIXES = ("enc_p.", "enc_q.", "mel_decoder.", "emb.")  # training / analysis only
@@ -69,13 +69,6 @@ class ResidualCouplingBlock_Transformer(nn.Module):
         for lin in lins:
             lin.__dict__["_stacked_elsewhere"] = True
         self._mod_rows = lins[0].cout * n_layers   # rows per coupling layer
-        # (round 6) ... and, behind them, per block the (c1_b | bias_b) rows its qkv layer needs to run norm1 + modulate
-        # inside its own GEMM (hip_layers.ModulatedNormRows: 6 * hidden rows per block as well)
-        self._modq_base = None
-        if modules.FOLD_LN:
-            blocks = [blk for i in range(n_flows) for blk in self.flows[2 * i].enc_block]
-            self._modq_base = sum(l.cout for l in lins)
-            lins = lins + [ModulatedNormRows(blk.attn.qkv, blk.adaLN_modulation[1]) for blk in blocks]
         self.adaln_all = StackedLinearCT(lins)
         # (round 6)  The Flips cost no launch: reverse runs `Flip, coupling` for i = n_flows - 1 ... 0, so the tensor
         # reaches coupling i after n_flows - i flips; the layers that see an odd number of them work on the reversed
@@ -103,9 +96,8 @@ class ResidualCouplingBlock_Transformer(nn.Module):
                 owned = True
             else:
                 flipped = not flipped                                                           # Flip, not launched
-            q0 = self._modq_base
             x = layer(x, x_mask, g=None, mods=mods[:, i * R:(i + 1) * R], reverse=True, inplace=owned,
-                      modq=None if q0 is None else mods[:, q0 + i * R:q0 + (i + 1) * R], key_len=key_len)  # coupling
+                      key_len=key_len)                                                          # coupling
             owned = True
         return Fh.flip_channels(x) if flipped else x
 
@@ -166,72 +158,12 @@ class AMPBlock1(nn.Module):
         """``before_last``: an event the current stream waits on before the last launch (the one
         that accumulates into the shared ``out`` of the stage)."""
         n = len(self.convs1)
-        if FFT_THROUGH and fft_chain_ok(self, x):
-            return amp_block_fft_chain(self, x, out=out, accumulate=accumulate, post_scale=post_scale, before_last=before_last)
         for i, (c1, c2) in enumerate(zip(self.convs1, self.convs2)):
             last = i == n - 1
             x = amp_pair(c1, c2, self.activations[2 * i], self.activations[2 * i + 1], x,
                          before_last=before_last if last else None, res=x, out=out if last else None,
                          accumulate=accumulate and last, post_scale=post_scale if last else 1.0)
         return x
-
-
-# (round 6, VERDICT r05 item 1a)  A whole AMP block in the frequency domain as ONE chain of spectra: the seam between two
-# iterations -- inverse of c2's product + bias + residual -> x_new, then a1'(x_new) -> forward for the next c1 -- is one
-# launch too (hsp_dftseg_pair_f32, pass-through form: x_new is written once and never read back by a transform): 7 transform
-# launches per block instead of 9.  MEASURED AND NOT KEPT AS THE DEFAULT: same-box 56.84 (per-iteration form, amp_pair) against
-# 57.10 ms per 32 x 4 s step with the chain (profiles/r06_ab_fft_through.json) -- the pair kernel runs its phases one after
-# the other on one workgroup per CU, and the seam's residual read and x_new write join a phase that nothing overlaps, while
-# the separate inverse and forward launches run two workgroups per CU each.  HSP_FFT_THROUGH=1 switches it on; the parity
-# tests run both forms (tests/test_gpu_parity.py::test_amp_block_as_one_chain_of_spectra).
-FFT_THROUGH = os.environ.get("HSP_FFT_THROUGH", "0") == "1"
-
-
-def fft_chain_ok(block, x) -> bool:
-    """Every conv of the block takes the frequency-domain form for an input like x, every pair and every seam fuses."""
-    if not (FFT_PAIR and fft_act(x)) or x.shape[1] <= FUSE_ACT_MAX_CHANNELS:
-        return False
-    key = (x.shape[0], x.shape[2], x.stride(0), x.stride(1), x.data_ptr() & 15)
-    memo = block.__dict__.setdefault("_chain_ok", {})
-    ok = memo.get(key)
-    if ok is None:
-        n = len(block.convs1)
-        ok = all(fft_wins(c, x) for c in list(block.convs1) + list(block.convs2)) and \
-            all(block.convs1[i].fft_pair_ok(block.convs2[i], x) for i in range(n)) and \
-            all(block.convs2[i].fft_through_ok(block.convs1[i + 1], x) for i in range(n - 1))
-        if len(memo) >= 256:
-            memo.clear()
-        memo[key] = ok
-        return ok
-    # (fft_wins also guards the capture-before-first-use case: ask it again, it is cheap once the geometry is cached)
-    return ok and all(fft_wins(c, x) for c in list(block.convs1) + list(block.convs2))
-
-
-def amp_block_fft_chain(block, x, *, out=None, accumulate=False, post_scale=1.0, before_last=None):
-    """AMPBlock1.forward (hierspeechpp_speechsynthesizer.py:377-386) with every conv in the frequency domain:
-    forward(a1(x)) -> [product c1 -> inverse + a2 + forward -> product c2 -> inverse + residual + a1' + forward] x (n - 1)
-    -> product c1 -> inverse + a2 + forward -> product c2 -> inverse with the block's epilogue."""
-    n = len(block.convs1)
-    B, Cc, Lx = x.shape
-    acts = block.activations
-    hook = hip_layers.LAUNCH_HOOK
-    xf, e_first = block.convs1[0]._fft_forward(x, acts[0])
-    for i in range(n):
-        c1, c2 = block.convs1[i], block.convs2[i]
-        xf2, _ = c1._fft_pair_launch(c2, c1._fft_product(xf), B, Lx, acts[2 * i + 1], x)
-        yf2 = c2._fft_product(xf2)
-        if i < n - 1:
-            x_new = torch.empty_like(x)
-            xf, _ = c2._fft_pair_launch(block.convs1[i + 1], yf2, B, Lx, acts[2 * i + 2], x, res=x, y=x_new)
-            x = x_new
-        else:
-            out, e_last = c2._fft_inverse(yf2, B, Lx, res=x, out=out, accumulate=accumulate, post_scale=post_scale,
-                                          before_inverse=before_last)
-    if hook is not None:
-        ks = sum(c.k for c in list(block.convs1) + list(block.convs2))
-        nio = 2 * n + 1 + 2 * bool(accumulate)            # every iteration reads and writes x once more than a lone conv
-        hook("hsp_fftconv", 2 * B * Cc * Cc * ks * Lx, 4 * B * Cc * Lx * nio + 4 * ks * Cc * Cc, e_first, e_last, 2 * n)
-    return out
 
 
 def amp_pair(c1, c2, a1, a2, x, *, form=None, before_last=None, **kw):
@@ -345,14 +277,6 @@ def fft_act(x) -> bool:
 # chain touches the shared accumulator; events serialise those three launches in block order,
 # so the sum is formed in the reference's order ((b0 + b1) + b2) / 3.
 AMP_STREAMS = int(os.environ.get("HSP_AMP_STREAMS", "1"))
-# (round 6; SURVEY.md §7 "stage ordering for cache")  HSP_GEN_GROUPS = G > 1: the stages of the
-# Generator with at most HSP_GEN_GROUP_MAX_C channels (default 128: L = 16 000 ... 64 000, 262-MB tensors at 32 x 4 s, just
-# past the 256-MB Infinity Cache) run as G SEQUENTIAL utterance groups -- each group walks ups -> AMP stage -> ... ->
-# conv_post before the next one starts, on the same three AMP streams -- so that a group's intermediates (65 MB at G = 4)
-# can stay cache-resident between the launch that writes them and the one that reads them.  Same launches per utterance,
-# bit-identical results (utterances are independent); measured in DESIGN.md §5.6.
-GEN_GROUPS = int(os.environ.get("HSP_GEN_GROUPS", "1"))
-GEN_GROUP_MAX_C = int(os.environ.get("HSP_GEN_GROUP_MAX_C", "128"))
 FRONT_SPLITS = int(os.environ.get("HSP_FRONT_SPLITS", "4"))
 # measurement mode (bench.py's per-launch pass, tools/pmc_traffic.sh): the SAME launches as the product step -- the front
 # part still cut into FRONT_SPLITS batch groups, the AMP chains unchanged -- but issued one after the other on the
@@ -495,36 +419,13 @@ class Generator(nn.Module):
         rows = hip_layers.row_lengths()   # row-exact: conv outputs read by a conv are zero past each row's end
         mk = (lambda t: dict(mask=rows.mask(t), mask_mode=L.MASK_POST)) if rows is not None else (lambda t: {})
         x = self.conv_pre(x, cbias=self.cond(g), res=self.downs(pitch), **mk(x.shape[2]))
-        first_grouped = self.num_upsamples
-        if GEN_GROUPS > 1 and x.shape[0] >= 2 * GEN_GROUPS:
-            # the first stage whose channel count is at most GEN_GROUP_MAX_C: from there on the batch walks the rest of
-            # the Generator as sequential utterance groups (SURVEY.md §7 "stage ordering for cache")
-            chans = [self.ups[i].cout for i in range(self.num_upsamples)]
-            first_grouped = next((i for i, c in enumerate(chans) if c <= GEN_GROUP_MAX_C), self.num_upsamples)
-        for i in range(first_grouped):
+        for i in range(self.num_upsamples):
             x = self.ups[i](x)
             if i == 0:
                 x = self.proj(pitch, res=x, out=x)
             x = _amp_stage(self.resblocks, i * self.num_kernels, self.num_kernels, x)
-        if first_grouped == self.num_upsamples:
-            x = self.activation_post(x)
-            return self.conv_post(x, act=L.ACT_TANH, **mk(x.shape[2]))
-        B = x.shape[0]
-        total_up = 1
-        for i in range(first_grouped, self.num_upsamples):
-            total_up *= self.ups[i].up
-        out = torch.empty(B, 1, x.shape[2] * total_up, dtype=torch.float32, device=x.device)
-        bounds = [(B * j) // GEN_GROUPS for j in range(GEN_GROUPS + 1)]
-        for lo, hi in zip(bounds[:-1], bounds[1:]):
-            xg = x[lo:hi]
-            for i in range(first_grouped, self.num_upsamples):
-                xg = self.ups[i](xg)
-                if i == 0:
-                    xg = self.proj(pitch[lo:hi], res=xg, out=xg)
-                xg = _amp_stage(self.resblocks, i * self.num_kernels, self.num_kernels, xg)
-            xg = self.activation_post(xg)
-            self.conv_post(xg, act=L.ACT_TANH, out=out[lo:hi])
-        return out
+        x = self.activation_post(x)
+        return self.conv_post(x, act=L.ACT_TANH, **mk(x.shape[2]))
 
 
 class SynthesizerTrn(nn.Module):
@@ -718,10 +619,6 @@ def row_exact_refusal() -> Optional[str]:
     have no ragged form."""
     if FUSE_ACT_MAX_CHANNELS > 0:
         return "HSP_FUSE_ACT_MAX_C > 0 (the conv-prologue activation has no ragged form)"
-    if FFT_THROUGH:
-        return "HSP_FFT_THROUGH=1 (the chained transforms carry the activation; they have no ragged form)"
-    if GEN_GROUPS > 1:
-        return "HSP_GEN_GROUPS > 1"
     return None
 
 

@@ -171,7 +171,8 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(hsp_[a-z0-9_]+)\s*\(", hdr)))
 
 
-def test_library_loads_and_exports_every_declared_symbol():
+def test_abi_103_library_loads_and_exports_every_declared_symbol():
+    """libhsp.so loads, resolves every function include/hsp.h declares, and reports ABI version 103 for gfx950."""
     from megatts2_hierspeechpp_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__ as g
@@ -182,7 +183,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert set(declared) == set(_lib.SIGNATURES), set(declared) ^ set(_lib.SIGNATURES)
     for sym in declared:
         assert getattr(lib, sym) is not None
-    assert lib.hsp_version() == 102 and lib.hsp_arch() == b"gfx950"
+    assert lib.hsp_version() == 103 and lib.hsp_arch() == b"gfx950"
 
 
 def test_dynamic_symbol_table_is_exactly_the_header():
@@ -496,6 +497,33 @@ def test_frequency_domain_form_has_a_supported_predicate():
     da.nseg += 1
     assert lib.hsp_dftseg_supported(C.byref(da)) == 0
     assert lib.hsp_dftseg_supported(None) == 0
+
+    # One bound for every entry point (ds_check): a plane stride with xf_bs * 256 > 0xffffffff -- a padded or a huge
+    # spectrum -- is refused by the launchers as by the predicates, before anything reaches a device.  The pointers are
+    # dummies that are never read: each launcher below is called only with arguments its checks refuse.
+    buf = (C.c_float * 4)()
+    dummy = C.addressof(buf)
+    big = 0xffffffff // 256 + 1
+    da = geom(64, 11, 1, 2, 4000)[1]
+    da.x = da.y = da.xf = da.dft = dummy
+    da.xf_bs = big - 1
+    assert lib.hsp_dftseg_supported(C.byref(da)) == 1
+    da.xf_bs = big
+    assert lib.hsp_dftseg_supported(C.byref(da)) == 0
+    assert lib.hsp_dftseg_fwd_f32(C.byref(da), None) == -1
+    assert lib.hsp_dftseg_inv_f32(C.byref(da), None) == -1
+    ia, fa = geom(64, 11, 1, 2, 4000)[1], geom(64, 11, 1, 2, 4000)[1]
+    ia.xf = ia.dft = fa.xf = fa.dft = fa.act_alpha_exp = fa.act_beta_inv = fa.act_filt = dummy
+    assert lib.hsp_dftseg_pair_supported(C.byref(ia), C.byref(fa)) == 1
+    for side in (ia, fa):                                       # either side's spectrum past the bound
+        side.xf_bs = big
+        assert lib.hsp_dftseg_pair_supported(C.byref(ia), C.byref(fa)) == 0
+        assert lib.hsp_dftseg_pair_f32(C.byref(ia), C.byref(fa), None) == -1
+        side.xf_bs = 2 * 64 * side.Np
+    # the pair launch writes no tensor between its transforms: an inverse output (or residual) is refused
+    ia.y = dummy
+    assert lib.hsp_dftseg_pair_supported(C.byref(ia), C.byref(fa)) == 0
+    assert lib.hsp_dftseg_pair_f32(C.byref(ia), C.byref(fa), None) == -1
 
 
 def test_three_product_weights_reproduce_the_complex_product():

@@ -21,7 +21,7 @@ def test_lengths_are_checked_against_the_padded_length():
             HS._row_exact_lengths(True, bad, 10, "cpu")
 
 
-@pytest.mark.parametrize("knob,value", [("FUSE_ACT_MAX_CHANNELS", 64), ("FFT_THROUGH", True), ("GEN_GROUPS", 4)])
+@pytest.mark.parametrize("knob,value", [("FUSE_ACT_MAX_CHANNELS", 64)])
 def test_experiment_knobs_refuse_row_exact(monkeypatch, knob, value):
     from megatts2_hierspeechpp_amd import _lib as L
     from megatts2_hierspeechpp_amd import hierspeechpp_speechsynthesizer as HS

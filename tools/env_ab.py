@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the headline step under several ENVIRONMENT settings (host-side policy knobs such as HSP_GEN_GROUPS,
-HSP_FRONT_SPLITS, HSP_FFT_PAIR), alternating child processes as tools/lib_ab.py does for two builds of the library:
+"""Same-box A/B of the headline step under several ENVIRONMENT settings (host-side policy knobs such as HSP_FRONT_SPLITS,
+HSP_FFT_PAIR, HSP_AMP_STREAMS), alternating child processes as tools/lib_ab.py does for two builds of the library:
 
-    python tools/env_ab.py --env "HSP_GEN_GROUPS=1" "HSP_GEN_GROUPS=2" "HSP_GEN_GROUPS=4" --rounds 2 [--roofline] [--json out.json]
+    python tools/env_ab.py --env "HSP_FRONT_SPLITS=4" "HSP_FRONT_SPLITS=2" "HSP_FRONT_SPLITS=1" --rounds 2 [--roofline] [--json out.json]
 
 An entry may set several variables ("A=1,B=2") or none ("" = the defaults).  With --roofline bench.py also runs its
 per-launch pass (`--full --no-extra --no-cpu-baseline`) and the stand-alone activation's GB/s (roofline_activation)
