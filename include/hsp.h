@@ -524,7 +524,9 @@ int hsp_add_cbias_f32(const float* x, int64_t x_bs, int64_t x_cs, const float* c
 int hsp_zero_below_f32(const float* x, float thr, float* y, int64_t n, void* stream);
 /* out[b, i] = (int16) (x[b, i] / max_j |x[b, j]| * 32767 * gain) over the first lengths[b] samples
  * (NULL = all n), zeros after : `audio / max(abs(audio)) * 32767.0 * 0.999` then numpy
- * astype('int16') (inference_plm.py:183-190) */
+ * astype('int16') (inference_plm.py:183-190).  A row whose peak is 0 (all its lengths[b] samples are zero) is
+ * written as zeros, which is what the reference's NaN -> astype('int16') gives; values beyond the int16 range
+ * (a gain above 1) saturate.  hsp_peak_int16_gains (above) shares the row function and both rules. */
 int hsp_peak_int16(const float* x, int64_t x_bs, const int64_t* lengths, float gain, int16_t* out, int64_t o_bs,
                    int32_t B, int64_t n, void* stream);
 

@@ -176,12 +176,14 @@ __device__ __forceinline__ float hsp_block_abs_max_1024(const float* __restrict_
 // ob[i] = (int16)(xb[i] / max_{j < L} |xb[j]| * 32767 * gain) for i < L, 0 for L <= i < n, by a 1024-thread workgroup:
 // `audio / max(abs(audio)) * 32767.0 * gain` then numpy's truncating astype(int16) (inference_plm.py:186).
 // hsp_peak_int16 and hsp_peak_int16_gains both run this function, so equal gains give equal rows.
+// A row whose peak is 0 (silence) is written as zeros: the reference expression gives 0 / 0 = NaN there and numpy's
+// astype(int16) turns NaN into 0, whereas fmaxf(NaN, -32768) below would make it full-scale negative DC.
 __device__ __forceinline__ void hsp_peak_int16_row(const float* __restrict__ xb, int64_t L, float gain,
                                                    int16_t* __restrict__ ob, int64_t n) {
   const float mx = hsp_block_abs_max_1024(xb, L);
   for (int64_t i = threadIdx.x; i < n; i += 1024) {
     float v = 0.0f;
-    if (i < L) v = xb[i] / mx * 32767.0f * gain;
+    if (i < L && mx > 0.0f) v = xb[i] / mx * 32767.0f * gain;
     ob[i] = (int16_t)fminf(fmaxf(v, -32768.0f), 32767.0f);
   }
 }

@@ -20,9 +20,15 @@ __global__ __launch_bounds__(256) void embedding_sum_kernel(const int64_t* __res
     const int64_t bc = e / T;
     const int c = (int)(bc % C), b = (int)(bc / C);
     const int64_t p = (int64_t)b * T + t;
-    float v = t0[(int64_t)hsp_clampi((int)id0[p], 0, n0 - 1) * C + c] * scale;
-    if (t1) v += t1[(int64_t)hsp_clampi((int)id1[p], 0, n1 - 1) * C + c] * scale;
-    if (t2) v += t2[(int64_t)hsp_clampi((int)id2[p], 0, n2 - 1) * C + c] * scale;
+    // every term is rounded before it is added, as torch's `emb(x) * s + emb(t) * s` does: contracted into an fma the
+    // sum differs in the last bit when scale is not a power of two
+    float v;
+    {
+#pragma clang fp contract(off)
+      v = t0[(int64_t)hsp_clampi((int)id0[p], 0, n0 - 1) * C + c] * scale;
+      if (t1) v += t1[(int64_t)hsp_clampi((int)id1[p], 0, n1 - 1) * C + c] * scale;
+      if (t2) v += t2[(int64_t)hsp_clampi((int)id2[p], 0, n2 - 1) * C + c] * scale;
+    }
     out[b * o_bs + c * o_cs + t] = v;
   }
 }

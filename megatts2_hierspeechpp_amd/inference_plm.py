@@ -52,7 +52,8 @@ def zero_below(x, thr: float):
 
 
 def peak_int16(audio, lengths=None, gain: float = 0.999):
-    """[B, 1, n] / [B, n] fp32 -> int16 [B, n], every row scaled by its own peak (over ``lengths[b]`` samples)."""
+    """[B, 1, n] / [B, n] fp32 -> int16 [B, n], every row scaled by its own peak (over ``lengths[b]`` samples).
+    A silent row (peak 0) comes out as zeros, as the reference's ``(a / a.abs().max() ...).astype(int16)`` does."""
     a = audio.reshape(audio.shape[0], -1)
     assert a.stride(1) == 1
     out = torch.empty(a.shape, dtype=torch.int16, device=a.device)

@@ -524,7 +524,7 @@ class SynthesizerTrn(nn.Module):
     @_entry
     @torch.no_grad()
     def infer(self, x, x_lengths, mel_spk, mel_spk_lengths, tone, language, dur=None, mrte_mel=None, mrte_mel_lengths=None,
-              noise_scale=1, noise_scale_w=1, length_scale=1, denoise_ratio=0):
+              noise_scale=1, noise_scale_w=1, length_scale=1, denoise_ratio=0, return_codes=False):
         """The older non-PLM text -> (w2v, lf0) path (:996-1077; call site inference.py:158): the prosody codes come
         from the PROMPT mel (first 20 bins -> PLMConv -> max-pool 8 -> PLMConv -> nearest code of the 1024-entry
         codebook, every code held for 8 frames) instead of from the prosody LM.
@@ -534,7 +534,8 @@ class SynthesizerTrn(nn.Module):
         also needs ``dur`` 2-D) and the mel length is a multiple of 8 (:999); the same holds here, anything else raises.
         ``x_lengths`` of the encoder come from the PREDICTED durations (:1031-1035), as in the reference.  ``mrte_mel``
         is accepted and -- as in the reference, which overwrites g at :1009 -- does not change the style vector.
-        B = 1 (the reference's RangePredictor .squeeze()); a batch here is B independent utterances."""
+        B = 1 (the reference's RangePredictor .squeeze()); a batch here is B independent utterances.
+        ``return_codes`` (not in the reference's signature) also returns the prompt's prosody codes, int64 [B, Tm]."""
         if dur is None:
             raise L.HspError("infer(): the reference path needs explicit durations (dur [B, N]); see the docstring")
         B, N = x.shape
@@ -595,4 +596,6 @@ class SynthesizerTrn(nn.Module):
         x2v_enc, _ = self.w2v_encoder(xq, enc_len, g, x_mask=y_mask, cond_added=True)
         w2v_pred = self.w2v_decoder(x2v_enc, y_mask, g=g)
         lf0 = self.pp(w2v_pred, g)
+        if return_codes:
+            return w2v_pred, lf0.squeeze(1), codes
         return w2v_pred, lf0.squeeze(1)
