@@ -279,6 +279,44 @@ int hsp_polar_f32(const float* mag, const float* pha, float power, float* re, in
 int hsp_istft_ola_f32(const float* frames, int64_t f_ld, const float* window, float* out, int32_t n_fft, int32_t hop,
                       int32_t T, float scale, void* stream);
 
+/* ---- the packed ragged batch of the prompt denoiser (denoiser.infer.denoise_batch; additive:
+ * HSP_VERSION unchanged).  B utterances lie end to end along T in one [C, T_tot, F] tensor with zero gap rows between
+ * neighbours.  The segment table holds (first row, T_b) per utterance as int32 [B][2], ascending and disjoint: `seg` is
+ * the device copy the kernels read, `seg_host` the host copy the launcher checks -- HSP_EINVAL, before any HIP call,
+ * for a null pointer, B < 1, T_b < 1, a negative, descending or overlapping segment or one past T_tot.  Both copies
+ * must hold the same values.  Row lengths in samples are device int64 [B], clamped into [0, L] as in the batched
+ * voice conversion above.  Nothing here reads back, so a fixed set of lengths can be captured in a hipGraph. */
+/* scale[b] = sqrt(len_b / sum_i x[b][i]^2) (double accumulation, as hsp_sum_sq_f32) and inv[b] = 1 / scale[b]: the
+ * norm factor of denoiser/infer.py:4 per row.  A silent or empty row gets scale = inv = 0 (denoise() raises there). */
+int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* scale, float* inv, int32_t B,
+                             int64_t L, void* stream);
+/* hsp_stft_frames_ragged_f32 into ONE frame matrix [n_fft, f_ld]: row b's T_b = 1 + len_b / hop frames, reflected at
+ * len_b and multiplied by scale[b] (NULL = no scaling; bit-equal to hsp_stft_frames_f32 on the row then), at columns
+ * [first_b, first_b + T_b); every other column, gaps included, is written as 0.  x rows of stride x_bs >= L. */
+int hsp_stft_frames_packed_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* scale,
+                               const float* window, float* frames, const int32_t* seg, const int32_t* seg_host, int32_t B,
+                               int64_t L, int32_t n_fft, int32_t hop, int32_t T_tot, int32_t f_ld, void* stream);
+/* hsp_instnorm_prelu_f32 with statistics over the T_b x F values of each (segment, channel) of the C planes
+ * [T_tot, F] at x + c * x_cs, in place; every row outside the segments is WRITTEN as 0 (never read). */
+int hsp_instnorm_prelu_seg_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
+                               const int32_t* seg_host, int32_t B, const float* gamma, const float* beta,
+                               const float* slope, float eps, void* stream);
+/* Zeros on every row outside the segments of the C planes [T_tot, F] at x + c * x_cs; nothing is read. */
+int hsp_zero_gaps_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
+                      const int32_t* seg_host, int32_t B, void* stream);
+/* hsp_dwconv_bn_silu_f32 over contiguous [A, C, N] with N the packed axis (T_tot = N): taps outside the element's own
+ * segment read as 0 whatever the gap width; positions outside the segments are written as 0. */
+int hsp_dwconv_bn_silu_seg_f32(const float* x, const float* w, const float* bias, const float* bn_weight,
+                               const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, float* y,
+                               int32_t A, int32_t C, int32_t N, int32_t K, const int32_t* seg, const int32_t* seg_host,
+                               int32_t B, void* stream);
+/* hsp_istft_ola_f32 per segment of frames [n_fft, f_ld >= T_tot]: out[b][n] for n < hop (T_b - 1) sums the frames of
+ * segment b only and is multiplied by inv[b] (device fp32 [B]; NULL = 1, bit-equal to the solo call then); zeros on
+ * [hop (T_b - 1), n_max).  out rows of stride out_bs >= n_max >= hop (T_b - 1). */
+int hsp_istft_ola_seg_f32(const float* frames, int64_t f_ld, const float* window, const float* inv, float* out,
+                          int64_t out_bs, int64_t n_max, int32_t n_fft, int32_t hop, const int32_t* seg,
+                          const int32_t* seg_host, int32_t B, int32_t T_tot, void* stream);
+
 /* ------------------------------------------------------- anti-aliased activation */
 /* y = DownSample2x(SnakeBeta(UpSample2x(x))): alias_free_torch/act.py:23-28,
  * resample.py:25-33,47-49, filter.py:86-95, activations.py:107-119.  x, y contiguous

@@ -184,6 +184,16 @@ SIGNATURES = {
     "hsp_atan2_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
     "hsp_polar_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, C.c_int32, _fp]),
     "hsp_istft_ola_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
+    "hsp_norm_factor_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int64, _fp]),
+    "hsp_stft_frames_packed_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int64, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "hsp_instnorm_prelu_seg_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp,
+                                             _fp, C.c_float, _fp]),
+    "hsp_zero_gaps_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp]),
+    "hsp_dwconv_bn_silu_seg_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp]),
+    "hsp_istft_ola_seg_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, _fp,
+                                        C.c_int32, C.c_int32, _fp]),
     "hsp_maxpool1d_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_vq_nearest_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, _fp]),

@@ -149,7 +149,205 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
   out[n] = num / den * scale;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Packed ragged batch (denoise_batch): B utterances laid end to end along T with zero gap rows between
+// them.  seg = device int32 [B][2] = (first row, T_b), ascending and disjoint (the launchers check the host copy).
+// B is a handful of prompts: the table is scanned linearly, with addresses every lane shares.
+__device__ __forceinline__ int dn_seg_of(const int32_t* __restrict__ seg, int B, int t, int& t0, int& Tb) {
+  for (int b = 0; b < B; ++b) {
+    const int s = seg[2 * b], n = seg[2 * b + 1];
+    if (t < s) break;
+    if (t < s + n) {
+      t0 = s;
+      Tb = n;
+      return b;
+    }
+  }
+  return -1;
+}
+
+__device__ __forceinline__ int64_t dn_clamp_len(const int64_t* len, int b, int64_t cap) {
+  return min(cap, max((int64_t)0, len[b]));
+}
+
+// sum_sq_kernel per row, then scale = sqrt(len / ss) and 1 / scale formed in double from the fp32-rounded sum, as
+// denoise() forms them on the host; a silent (or empty) row gets 0 for both
+__global__ __launch_bounds__(1024) void norm_factor_rows_kernel(const float* __restrict__ x, int64_t x_bs,
+                                                                const int64_t* __restrict__ lengths, float* __restrict__ scale,
+                                                                float* __restrict__ inv, int64_t L) {
+  __shared__ double sh[16];
+  const int b = blockIdx.x;
+  const int64_t n = dn_clamp_len(lengths, b, L);
+  const float* p = x + (int64_t)b * x_bs;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += (double)p[i] * (double)p[i];
+  s = dn_block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    const float ss = (float)s;
+    const bool ok = n > 0 && ss > 0.0f;
+    const double norm = ok ? sqrt((double)n / (double)ss) : 0.0;
+    scale[b] = (float)norm;
+    inv[b] = ok ? (float)(1.0 / norm) : 0.0f;
+  }
+}
+
+// stft_frames_ragged_kernel of hsp_vcbatch.hip writing row b's frames at columns [t0_b, t0_b + T_b) of ONE
+// [n_fft, f_ld] matrix (times scale[b] when given: the norm factor folded into the framing); every other column 0
+__global__ __launch_bounds__(256) void stft_frames_packed_kernel(const float* __restrict__ x, int64_t x_bs,
+                                                                 const int64_t* __restrict__ lengths,
+                                                                 const float* __restrict__ scale, const float* __restrict__ w,
+                                                                 float* __restrict__ frames, const int32_t* __restrict__ seg,
+                                                                 int B, int64_t L, int n_fft, int hop, int f_ld) {
+  const int t = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int n0 = blockIdx.y * 256 + (threadIdx.x >> 6) * 64;
+  if (t >= f_ld) return;
+  int t0 = 0, Tb = 0;
+  const int b = dn_seg_of(seg, B, t, t0, Tb);
+  int64_t Lb = 0;
+  const float* xb = x;
+  float sc = 1.0f;
+  if (b >= 0) {
+    Lb = dn_clamp_len(lengths, b, L);
+    xb = x + (int64_t)b * x_bs;
+    if (scale) sc = scale[b];
+  }
+  const int64_t base = (int64_t)(t - t0) * hop - (n_fft >> 1);
+  for (int n = n0; n < min(n0 + 64, n_fft); ++n) {
+    float v = 0.0f;
+    if (b >= 0 && Lb > 0) {
+      int64_t i = base + n;
+      i = i < 0 ? -i : i;
+      i = i >= Lb ? 2 * (Lb - 1) - i : i;
+      i = min(max(i, (int64_t)0), Lb - 1);    // only for Lb <= n_fft / 2 or T_b > 1 + Lb / hop (outside the contract)
+      v = scale ? w[n] * (xb[i] * sc) : w[n] * xb[i];
+    }
+    frames[(int64_t)n * f_ld + t] = v;
+  }
+}
+
+// instnorm_prelu_kernel per (channel, segment): block (c, b) normalises the T_b x F values of segment b in place and
+// WRITES zeros on the gap rows that follow it (block b = 0 also on the rows ahead of the first segment), so every
+// row of the plane is written by exactly one block and no gap value is ever read
+__global__ __launch_bounds__(1024) void instnorm_prelu_seg_kernel(float* __restrict__ x, int64_t cs, int T_tot, int F,
+                                                                  const int32_t* __restrict__ seg, int B,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ slope, float eps) {
+  __shared__ double sh[16];
+  const int c = blockIdx.x, b = blockIdx.y;
+  const int t0 = seg[2 * b], Tb = seg[2 * b + 1];
+  float* plane = x + (int64_t)c * cs;
+  float* p = plane + (int64_t)t0 * F;
+  const int64_t N = (int64_t)Tb * F;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) s += (double)p[i];
+  const double mean = dn_block_sum(s, sh) / (double)N;
+  double q = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
+    const double d = (double)p[i] - mean;
+    q += d * d;
+  }
+  const double var = dn_block_sum(q, sh) / (double)N;   // biased, as F.instance_norm
+  const float inv = (float)(1.0 / sqrt(var + (double)eps));
+  const float m = (float)mean, g = gamma[c], bt = beta[c], sl = slope[c];
+  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
+    const float y = (p[i] - m) * inv * g + bt;
+    p[i] = y > 0.0f ? y : sl * y;
+  }
+  const int g_hi = b + 1 < B ? seg[2 * b + 2] : T_tot;
+  float* z = p + N;
+  const int64_t NZ = (int64_t)(g_hi - t0 - Tb) * F;
+  for (int64_t i = threadIdx.x; i < NZ; i += blockDim.x) z[i] = 0.0f;
+  if (b == 0) {
+    const int64_t N0 = (int64_t)t0 * F;
+    for (int64_t i = threadIdx.x; i < N0; i += blockDim.x) plane[i] = 0.0f;
+  }
+}
+
+// zeros on the gap rows of C channel planes [T_tot, F]; rows inside a segment are not touched (nothing is read)
+__global__ __launch_bounds__(256) void zero_gaps_kernel(float* __restrict__ x, int64_t cs, int T_tot, int F,
+                                                        const int32_t* __restrict__ seg, int B, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int64_t plane = (int64_t)T_tot * F;
+  const int64_t c = i / plane, r = i % plane;
+  int t0, Tb;
+  if (dn_seg_of(seg, B, (int)(r / F), t0, Tb) < 0) x[c * cs + r] = 0.0f;
+}
+
+// dwconv_bn_silu_kernel with N = the packed T axis: taps outside the element's own segment read as zero (bounded by the
+// table, whatever the gap width); gap positions are written as 0
+__global__ __launch_bounds__(256) void dwconv_bn_silu_seg_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ bias, const float* __restrict__ bn_w,
+                                                                 const float* __restrict__ bn_b, const float* __restrict__ bn_mean,
+                                                                 const float* __restrict__ bn_var, float bn_eps,
+                                                                 float* __restrict__ y, int C, int N, int K,
+                                                                 const int32_t* __restrict__ seg, int B, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int n = (int)(i % N);
+  int t0, Tb;
+  if (dn_seg_of(seg, B, n, t0, Tb) < 0) {
+    y[i] = 0.0f;
+    return;
+  }
+  const int c = (int)((i / N) % C);
+  const float* row = x + (i - n);
+  const float* wc = w + (int64_t)c * K;
+  const int half = K >> 1;
+  float acc = 0.0f;
+  for (int j = 0; j < K; ++j) {
+    const int m = n + j - half;
+    if (m >= t0 && m < t0 + Tb) acc = fmaf(wc[j], row[m], acc);
+  }
+  acc += bias[c];
+  const float alpha = bn_w[c] / sqrtf(bn_var[c] + bn_eps);
+  const float v = acc * alpha + (bn_b[c] - bn_mean[c] * alpha);
+  y[i] = v / (1.0f + expf(-v));
+}
+
+// istft_ola_kernel per segment: output row b (blockIdx.y) sums the frames of columns [t0_b, t0_b + T_b) only, holds
+// hop (T_b - 1) samples times inv[b] (1 when inv is NULL) and zeros up to n_max
+__global__ __launch_bounds__(256) void istft_ola_seg_kernel(const float* __restrict__ frames, int64_t f_ld,
+                                                            const float* __restrict__ window, const float* __restrict__ inv,
+                                                            float* __restrict__ out, int64_t out_bs, int64_t n_max, int n_fft,
+                                                            int hop, const int32_t* __restrict__ seg) {
+  const int b = blockIdx.y;
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= n_max) return;
+  const int t0 = seg[2 * b], T = seg[2 * b + 1];
+  float v = 0.0f;
+  if (n < (int64_t)hop * (T - 1)) {
+    const int64_t pos = n + (n_fft >> 1);
+    int64_t t_hi = pos / hop;
+    if (t_hi > T - 1) t_hi = T - 1;
+    int64_t t_lo = (pos - n_fft + hop) / hop;
+    if (pos - n_fft + 1 <= 0) t_lo = 0;
+    float num = 0.0f, den = 0.0f;
+    for (int64_t t = t_lo; t <= t_hi; ++t) {
+      const int k = (int)(pos - t * hop);
+      if (k < 0 || k >= n_fft) continue;
+      const float w = window[k];
+      num += frames[(int64_t)k * f_ld + t0 + t] * w;
+      den += w * w;
+    }
+    v = num / den * (inv ? inv[b] : 1.0f);
+  }
+  out[(int64_t)b * out_bs + n] = v;
+}
+
 }  // namespace
+
+// the host copy of a segment table: B >= 1 segments (first row >= 0, T_b >= 1), ascending, disjoint, inside T_tot
+static bool dn_seg_ok(const int32_t* seg, const int32_t* seg_host, int32_t B, int64_t T_tot) {
+  if (!seg || !seg_host || B < 1 || B > 65535 || T_tot < 1) return false;
+  int64_t end = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t s = seg_host[2 * b], n = seg_host[2 * b + 1];
+    if (s < end || n < 1 || s + n > T_tot) return false;
+    end = s + n;
+  }
+  return true;
+}
 
 #define HSP_STREAM static_cast<hipStream_t>(stream)
 
@@ -221,5 +419,72 @@ extern "C" int hsp_istft_ola_f32(const float* frames, int64_t f_ld, const float*
   if (!dn_fits(L, 256)) return HSP_EINVAL;
   hipLaunchKernelGGL(istft_ola_kernel, dim3(dn_grid(L, 256)), dim3(256), 0, HSP_STREAM, frames, f_ld, window, out, n_fft, hop, T,
                      L, scale);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* scale, float* inv,
+                                        int32_t B, int64_t L, void* stream) {
+  if (!x || !lengths || !scale || !inv || B < 1 || L <= 0 || x_bs < L) return HSP_EINVAL;
+  hipLaunchKernelGGL(norm_factor_rows_kernel, dim3((unsigned)B), dim3(1024), 0, HSP_STREAM, x, x_bs, lengths, scale, inv, L);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_stft_frames_packed_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* scale,
+                                          const float* window, float* frames, const int32_t* seg, const int32_t* seg_host,
+                                          int32_t B, int64_t L, int32_t n_fft, int32_t hop, int32_t T_tot, int32_t f_ld,
+                                          void* stream) {
+  if (!x || !lengths || !window || !frames || n_fft <= 0 || hop <= 0 || f_ld < T_tot || x_bs < L) return HSP_EINVAL;
+  if (L <= n_fft / 2 || (n_fft + 255) / 256 > 65535) return HSP_EINVAL;
+  if (!dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
+  for (int b = 0; b < B; ++b)                                  // no row holds more frames than the longest can: 1 + L / hop
+    if (seg_host[2 * b + 1] > 1 + L / hop) return HSP_EINVAL;
+  hipLaunchKernelGGL(stft_frames_packed_kernel, dim3((f_ld + 63) / 64, (n_fft + 255) / 256), dim3(256), 0, HSP_STREAM, x,
+                     x_bs, lengths, scale, window, frames, seg, B, L, n_fft, hop, f_ld);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_instnorm_prelu_seg_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
+                                          const int32_t* seg_host, int32_t B, const float* gamma, const float* beta,
+                                          const float* slope, float eps, void* stream) {
+  if (!x || !gamma || !beta || !slope || C <= 0 || F <= 0 || T_tot <= 0) return HSP_EINVAL;
+  if (x_cs < (int64_t)T_tot * F || !dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
+  hipLaunchKernelGGL(instnorm_prelu_seg_kernel, dim3((unsigned)C, (unsigned)B), dim3(1024), 0, HSP_STREAM, x, x_cs, T_tot, F,
+                     seg, B, gamma, beta, slope, eps);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_zero_gaps_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
+                                 const int32_t* seg_host, int32_t B, void* stream) {
+  if (!x || C <= 0 || F <= 0 || T_tot <= 0) return HSP_EINVAL;
+  if (x_cs < (int64_t)T_tot * F || !dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
+  const int64_t total = (int64_t)C * T_tot * F;
+  if (!dn_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(zero_gaps_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, x_cs, T_tot, F, seg, B, total);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_dwconv_bn_silu_seg_f32(const float* x, const float* w, const float* bias, const float* bn_weight,
+                                          const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps,
+                                          float* y, int32_t A, int32_t C, int32_t N, int32_t K, const int32_t* seg,
+                                          const int32_t* seg_host, int32_t B, void* stream) {
+  if (!x || !w || !bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !y) return HSP_EINVAL;
+  if (A <= 0 || C <= 0 || N <= 0 || K <= 0 || (K & 1) == 0 || !dn_seg_ok(seg, seg_host, B, N)) return HSP_EINVAL;
+  const int64_t total = (int64_t)A * C * N;
+  if (!dn_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(dwconv_bn_silu_seg_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, w, bias, bn_weight,
+                     bn_bias, bn_mean, bn_var, bn_eps, y, C, N, K, seg, B, total);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_istft_ola_seg_f32(const float* frames, int64_t f_ld, const float* window, const float* inv, float* out,
+                                     int64_t out_bs, int64_t n_max, int32_t n_fft, int32_t hop, const int32_t* seg,
+                                     const int32_t* seg_host, int32_t B, int32_t T_tot, void* stream) {
+  if (!frames || !window || !out || n_fft <= 0 || (n_fft & 1) || hop <= 0 || hop > n_fft) return HSP_EINVAL;
+  if (n_max < 1 || out_bs < n_max || f_ld < T_tot || !dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
+  for (int b = 0; b < B; ++b)
+    if ((int64_t)hop * (seg_host[2 * b + 1] - 1) > n_max) return HSP_EINVAL;
+  if (!dn_fits(n_max, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(istft_ola_seg_kernel, dim3(dn_grid(n_max, 256), (unsigned)B), dim3(256), 0, HSP_STREAM, frames, f_ld,
+                     window, inv, out, out_bs, n_max, n_fft, hop, seg);
   return (int)hipGetLastError();
 }

@@ -66,12 +66,21 @@ class ConformerConvModule(nn.Module):
                                   "4": _DepthwiseConv1d(inner, kernel_size), "5": _BatchNorm1d(inner),
                                   "7": Conv1d(inner, dim, 1)})
 
-    def forward(self, x):
-        """x + ccm(x)."""
+    def forward(self, x, seg=None):
+        """x + ccm(x).  ``seg`` (denoiser.packed.Segments): N is a packed axis, the depthwise conv stays inside each
+        segment (``hsp_dwconv_bn_silu_seg_f32``)."""
         h = self.ccm["2"](self.ccm["0"](x))                    # [A, inner, N]
         dw, bn = self.ccm["4"], self.ccm["5"]
         y = torch.empty_like(h)
         A, Cc, N = h.shape
+        if seg is not None:
+            assert N == seg.T_tot
+            L.check(L.lib().hsp_dwconv_bn_silu_seg_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
+                                                       L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
+                                                       L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
+                                                       float(bn.eps), L.fptr(y), A, Cc, N, dw.k, *seg.args(),
+                                                       L.stream_ptr()), "hsp_dwconv_bn_silu_seg_f32")
+            return self.ccm["7"](y, res=x)
         L.check(L.lib().hsp_dwconv_bn_silu_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
                                                L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
                                                L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
@@ -110,12 +119,21 @@ class AttentionModule(nn.Module):
         self.attn = _MultiheadAttention(dim, n_head)
         self.layernorm = LayerNorm(dim)
 
-    def forward(self, x):
-        """x + attn(layernorm(x)), attention along dim 0 of [A, C, N] for every n."""
+    def forward(self, x, seg=None):
+        """x + attn(layernorm(x)), attention along dim 0 of [A, C, N] for every n.  ``seg`` (denoiser.packed.Segments):
+        A is a packed axis and every segment attends to itself only -- one launch per segment on column slices of the
+        packed q / k / v, each the launch its utterance runs alone; rows outside the segments come out as zeros."""
         m = self.attn
         qkv = m._qkv(self.layernorm(x))                                   # [A, 3C, N]
         qkv_t = Fh.copy_strided(qkv.permute(2, 1, 0))                     # [N, 3C, A]: A is the sequence axis
         C_ = m.dim
+        if seg is not None:
+            assert qkv_t.shape[2] == seg.T_tot
+            o = torch.zeros(qkv_t.shape[0], C_, seg.T_tot, dtype=torch.float32, device=x.device)
+            for sl in seg.slices():
+                Fh.mha(qkv_t[:, :C_, sl], qkv_t[:, C_:2 * C_, sl], qkv_t[:, 2 * C_:, sl], m.n_head,
+                       (C_ // m.n_head) ** -0.5, out=o[:, :, sl])
+            return m.out_proj(Fh.copy_strided(o.permute(2, 1, 0)), res=x)
         o = Fh.mha(qkv_t[:, :C_], qkv_t[:, C_:2 * C_], qkv_t[:, 2 * C_:], m.n_head, (C_ // m.n_head) ** -0.5)
         return m.out_proj(Fh.copy_strided(o.permute(2, 1, 0)), res=x)     # back to [A, C, N]
 
@@ -132,9 +150,11 @@ class ConformerBlock(nn.Module):
         self.ffm2 = FeedForwardModule(dim, ffm_mult, dropout=ffm_dropout)
         self.post_norm = LayerNorm(dim)
 
-    def forward(self, x):
+    def forward(self, x, attn_seg=None, conv_seg=None):
+        """``attn_seg`` / ``conv_seg``: the segment table when the attention's axis (A) / the conv module's axis (N) is
+        the packed T axis of a ragged batch; None = one utterance."""
         x = self.ffm1(x, scale=0.5)
-        x = self.attn(x)
-        x = self.ccm(x)
+        x = self.attn(x, attn_seg)
+        x = self.ccm(x, conv_seg)
         x = self.ffm2(x, scale=0.5)
         return self.post_norm(x)

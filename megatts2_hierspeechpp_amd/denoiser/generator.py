@@ -1,5 +1,7 @@
 """denoiser/generator.py (MP-SENet ``MPNet``) with the reference's class names, constructor arguments and state-dict
-keys; every tensor stays ``[1, C, T, F]`` (the reference's layout) and all arithmetic is in libhsp.so.
+keys; every tensor stays ``[1, C, T, F]`` (the reference's layout) and all arithmetic is in libhsp.so.  A ragged batch
+runs as ONE such tensor with the rows packed along T (``MPNet.forward(..., lengths)``, denoiser/packed.py): the modules
+take the segment table as ``seg`` and only the operations that read across rows of T change.
 
 How the 2-D pieces map onto the 1-D kernels (one utterance, as denoiser/infer.py feeds it):
   * ``Conv2d(k = (kh, kw), dilation = (d, 1))``: the T rows are the batch of a Conv1d along F; tap row i reads the
@@ -91,10 +93,18 @@ class _PReLU(Vec):
         self.weight = nn.Parameter(torch.full((channels,), 0.25), requires_grad=False)
 
 
-def _norm_act(norm: _InstanceNorm2d, act: _PReLU, x):
-    """In place on x [1, C, T, F] (each channel plane contiguous)."""
+def _norm_act(norm: _InstanceNorm2d, act: _PReLU, x, seg=None):
+    """In place on x [1, C, T, F] (each channel plane contiguous).  ``seg``: statistics per segment of the packed T
+    axis, zeros written on the gap rows."""
     _, Cc, T, F_ = x.shape
     assert x.stride(3) == 1 and x.stride(2) == F_
+    if seg is not None:
+        assert T == seg.T_tot
+        L.check(L.lib().hsp_instnorm_prelu_seg_f32(L.fptr(x), x.stride(1), Cc, T, F_, *seg.args(),
+                                                   L.fptr(norm.dev("weight")), L.fptr(norm.dev("bias")),
+                                                   L.fptr(act.dev("weight")), float(norm.eps), L.stream_ptr()),
+                "hsp_instnorm_prelu_seg_f32")
+        return x
     L.check(L.lib().hsp_instnorm_prelu_f32(L.fptr(x), x.stride(1), Cc, T * F_, L.fptr(norm.dev("weight")),
                                            L.fptr(norm.dev("bias")), L.fptr(act.dev("weight")), float(norm.eps),
                                            L.stream_ptr()), "hsp_instnorm_prelu_f32")
@@ -120,9 +130,10 @@ class DenseBlock(nn.Module):
                         padding=get_padding_2d(kernel_size, (dil, 1))),
                 _InstanceNorm2d(h.dense_channel), _PReLU(h.dense_channel)))
 
-    def forward(self, x):
+    def forward(self, x, seg=None):
         """x [1, C, T, F] -> [1, C, T, F].  ``skip = cat([x_i, skip])`` lives in one buffer: slot depth holds the
-        input, slot depth - 1 - i the output of layer i, and layer i reads slots depth - i .. depth."""
+        input, slot depth - 1 - i the output of layer i, and layer i reads slots depth - i .. depth.  ``seg``: T is
+        packed; ``x`` must hold zeros on its gap rows, and each layer's norm writes them again."""
         _, Cc, T, F_ = x.shape
         assert x.stride(3) == 1 and x.stride(2) == F_
         buf = torch.empty(1, Cc * (self.depth + 1), T, F_, dtype=torch.float32, device=x.device)
@@ -132,7 +143,7 @@ class DenseBlock(nn.Module):
             blk = self.dense_block[i]
             o = buf[:, (self.depth - 1 - i) * Cc:(self.depth - i) * Cc]
             blk["0"](buf[:, (self.depth - i) * Cc:], out=o)
-            _norm_act(blk["1"], blk["2"], o)
+            _norm_act(blk["1"], blk["2"], o, seg)
         return buf[:, :Cc]
 
 
@@ -148,11 +159,11 @@ class DenseEncoder(nn.Module):
         self.dense_conv_2 = _seq(_Conv2d(h.dense_channel, h.dense_channel, (1, 3), (1, 2)),
                                  _InstanceNorm2d(h.dense_channel), _PReLU(h.dense_channel))
 
-    def forward(self, x):
+    def forward(self, x, seg=None):
         c1, c2 = self.dense_conv_1, self.dense_conv_2
-        x = _norm_act(c1["1"], c1["2"], c1["0"](x))
-        x = self.dense_block(x)
-        return _norm_act(c2["1"], c2["2"], c2["0"](x))
+        x = _norm_act(c1["1"], c1["2"], c1["0"](x), seg)
+        x = self.dense_block(x, seg)
+        return _norm_act(c2["1"], c2["2"], c2["0"](x), seg)
 
 
 class _ConvTranspose2d(HipLayer):
@@ -195,11 +206,11 @@ class MaskDecoder(nn.Module):
                               _PReLU(out_channel), _Conv2d(out_channel, out_channel, (1, 1)))
         self.lsigmoid = LearnableSigmoid_2d(h.n_fft // 2 + 1, beta=h.beta)
 
-    def forward(self, x, mag_tf):
+    def forward(self, x, mag_tf, seg=None):
         """x [1, C, T, F'], mag_tf [T, F] -> mag_tf * mask [T, F] (the product of generator.py:140 included)."""
         mc = self.mask_conv
-        m = mc["1"](mc["0"](self.dense_block(x)))
-        m = mc["4"](_norm_act(mc["2"], mc["3"], m))                  # [1, 1, T, F]
+        m = mc["1"](mc["0"](self.dense_block(x, seg)))
+        m = mc["4"](_norm_act(mc["2"], mc["3"], m, seg))             # [1, 1, T, F]
         T, F_ = mag_tf.shape
         out = torch.empty_like(mag_tf)
         L.check(L.lib().hsp_lsigmoid_mul_f32(L.fptr(m), L.fptr(self.lsigmoid.dev("slope")), float(self.lsigmoid.beta),
@@ -218,10 +229,10 @@ class PhaseDecoder(nn.Module):
         self.phase_conv_r = _Conv2d(h.dense_channel, out_channel, (1, 1))
         self.phase_conv_i = _Conv2d(h.dense_channel, out_channel, (1, 1))
 
-    def forward(self, x):
+    def forward(self, x, seg=None):
         """x [1, C, T, F'] -> atan2(x_i, x_r) [T, F]."""
         pc = self.phase_conv
-        p = _norm_act(pc["1"], pc["2"], pc["0"](self.dense_block(x)))
+        p = _norm_act(pc["1"], pc["2"], pc["0"](self.dense_block(x, seg)), seg)
         x_r, x_i = self.phase_conv_r(p), self.phase_conv_i(p)
         out = torch.empty(x_r.shape[2], x_r.shape[3], dtype=torch.float32, device=x.device)
         L.check(L.lib().hsp_atan2_f32(L.fptr(x_i), L.fptr(x_r), L.fptr(out), out.numel(), L.stream_ptr()), "hsp_atan2_f32")
@@ -240,12 +251,13 @@ class TSConformerBlock(nn.Module):
         self.freq_conformer = ConformerBlock(dim=h.dense_channel, n_head=4, ccm_kernel_size=31, ffm_dropout=0.2,
                                              attn_dropout=0.2)
 
-    def forward(self, x):
-        """x [1, C, T, F] -> [1, C, T, F]."""
+    def forward(self, x, seg=None):
+        """x [1, C, T, F] -> [1, C, T, F].  ``seg``: T is packed -- the time conformer's conv module (along T) and the
+        frequency conformer's attention (along T) stay inside each segment; everything else works per row of T."""
         xt = Fh.copy_strided(x[0].permute(2, 0, 1))                   # [F, C, T]   (reference: view(b f, t, c))
-        xt = Fh.axpby(self.time_conformer(xt), xt, 1.0, 1.0)
+        xt = Fh.axpby(self.time_conformer(xt, conv_seg=seg), xt, 1.0, 1.0)
         xf = Fh.copy_strided(xt.permute(2, 1, 0))                     # [T, C, F]   (reference: view(b t, f, c))
-        xf = Fh.axpby(self.freq_conformer(xf), xf, 1.0, 1.0)
+        xf = Fh.axpby(self.freq_conformer(xf, attn_seg=seg), xf, 1.0, 1.0)
         return Fh.copy_strided(xf.permute(1, 0, 2)).unsqueeze(0)      # [1, C, T, F]
 
 
@@ -269,20 +281,68 @@ class MPNet(nn.Module):
 
     @_entry
     @torch.no_grad()
-    def forward(self, noisy_mag, noisy_pha):
+    def forward(self, noisy_mag, noisy_pha, lengths=None):
+        """``lengths`` None: one utterance [1, F, T], as the reference.  ``lengths`` = HOST ints, frames per row:
+        ``[B, F, T_max]`` inputs run as one packed pass (denoiser/packed.py) and the three outputs are
+        ``[B, F, T_max]`` (``[B, F, T_max, 2]``) with row b equal to the call on ``[:, :, :lengths[b]]`` alone and zeros
+        past its frames.  Device-only lengths are refused: the shapes depend on them."""
+        if lengths is not None:
+            return self._forward_ragged(noisy_mag, noisy_pha, lengths)
         if noisy_mag.dim() != 3 or noisy_mag.shape[0] != 1 or noisy_mag.shape != noisy_pha.shape:
             raise L.HspError("MPNet takes one utterance: noisy_mag / noisy_pha [1, F, T]")
+        return self._run(noisy_mag, noisy_pha, None)
+
+    def _forward_ragged(self, noisy_mag, noisy_pha, lengths):
+        from .packed import host_ints, segments_for
+        frames = host_ints(lengths, "MPNet lengths")
+        if noisy_mag.dim() != 3 or noisy_mag.shape != noisy_pha.shape or noisy_mag.shape[0] != len(frames):
+            raise L.HspError("MPNet with lengths takes noisy_mag / noisy_pha [B, F, T_max] and one length per row")
+        B, F_, Tm = noisy_mag.shape
+        if max(frames) > Tm or min(frames) < 1:
+            raise L.HspError(f"MPNet lengths {frames} outside [1, {Tm}]")
+        seg = segments_for(frames, noisy_mag.device)
+        pk = [torch.zeros(1, F_, seg.T_tot, dtype=torch.float32, device=noisy_mag.device) for _ in range(2)]
+        for dst, src in zip(pk, (noisy_mag, noisy_pha)):
+            for b, sl in enumerate(seg.slices()):
+                dst[0, :, sl].copy_(src[b, :, :frames[b]])                     # copies, no arithmetic
+        d_mag, d_pha, _ = self.forward_packed(pk[0], pk[1], seg)
+        out = [torch.zeros(B, F_, Tm, dtype=torch.float32, device=noisy_mag.device) for _ in range(2)]
+        for dst, src in zip(out, (d_mag, d_pha)):
+            for b, sl in enumerate(seg.slices()):
+                dst[b, :, :frames[b]].copy_(src[0, :, sl])
+        re = torch.empty(B * F_, Tm, dtype=torch.float32, device=noisy_mag.device)
+        im = torch.empty(B * F_, Tm, dtype=torch.float32, device=noisy_mag.device)
+        L.check(L.lib().hsp_polar_f32(L.fptr(out[0]), L.fptr(out[1]), 1.0, L.fptr(re), Tm, L.fptr(im), Tm, B * F_, Tm,
+                                      L.stream_ptr()), "hsp_polar_f32")
+        return out[0], out[1], torch.stack((re, im), dim=-1).reshape(B, F_, Tm, 2)
+
+    @_entry
+    @torch.no_grad()
+    def forward_packed(self, noisy_mag, noisy_pha, seg):
+        """The packed pass itself: noisy_mag / noisy_pha [1, F, T_tot] in the layout of ``seg`` (a
+        denoiser.packed.Segments; gap columns finite) -> the same three outputs as ``forward``, packed alike.  Gap
+        columns of the outputs hold no meaning."""
+        if noisy_mag.dim() != 3 or noisy_mag.shape[0] != 1 or noisy_mag.shape != noisy_pha.shape \
+                or noisy_mag.shape[2] != seg.T_tot:
+            raise L.HspError("MPNet.forward_packed takes noisy_mag / noisy_pha [1, F, T_tot] of the segment table")
+        return self._run(noisy_mag, noisy_pha, seg)
+
+    def _run(self, noisy_mag, noisy_pha, seg):
         _, F_, T = noisy_mag.shape
         x = torch.empty(1, 2, T, F_, dtype=torch.float32, device=noisy_mag.device)      # cat((mag, pha), 1) as [1, 2, T, F]
         for i, src in enumerate((noisy_mag, noisy_pha)):
             v = src.permute(0, 2, 1)                                                    # [1, T, F] view of [1, F, T]
             L.check(L.lib().hsp_copy_strided_f32(L.fptr(v), v.stride(0), v.stride(1), v.stride(2), L.fptr(x[:, i]), 1, T, F_,
                                                  L.stream_ptr()), "hsp_copy_strided_f32")
-        h = self.dense_encoder(x)
+        h = self.dense_encoder(x, seg)
         for blk in self.TSConformer:
-            h = blk(h)
-        mag_tf = self.mask_decoder(h, x[0, 0])                                           # [T, F]
-        pha_tf = self.phase_decoder(h)                                                   # [T, F]
+            h = blk(h, seg)
+        if seg is not None:
+            # the decoders' dense blocks shift along T and read h before any norm: zeros on its gap rows
+            L.check(L.lib().hsp_zero_gaps_f32(L.fptr(h), h.stride(1), h.shape[1], T, h.shape[3], *seg.args(),
+                                              L.stream_ptr()), "hsp_zero_gaps_f32")
+        mag_tf = self.mask_decoder(h, x[0, 0], seg)                                      # [T, F]
+        pha_tf = self.phase_decoder(h, seg)                                              # [T, F]
         d_mag = Fh.copy_strided(mag_tf.t().unsqueeze(0))                                 # [1, F, T]
         d_pha = Fh.copy_strided(pha_tf.t().unsqueeze(0))
         re = torch.empty(F_, T, dtype=torch.float32, device=x.device)

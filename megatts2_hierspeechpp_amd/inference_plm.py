@@ -68,8 +68,9 @@ def prompt_mels(mel_fn, audio, denoiser=None, hps_denoiser=None):
     multiple of 1600 samples (always at least one sample of padding, :131-134), and ``src_mel`` [2, 80, T] from the
     un-padded prompt stacked with itself (denoise_ratio = 0, :142-143) or with its denoised version cut to the same
     length (``denoiser`` = a finalized denoiser.generator.MPNet, ``hps_denoiser`` its config: :144-150; the denoiser
-    sees the PADDED prompt, as in the reference).  ``audio`` [1, n] fp32 on the GPU; ``mel_fn`` a finalized
-    Mels_preprocess.MelSpectrogramFixed."""
+    sees the PADDED prompt, as in the reference).  ``audio`` [1, n] fp32 on the GPU, or [B, n] for B prompts of one
+    length (``src_mel`` is [2B, 80, T] then: the B prompts' mels followed by the B denoised ones, and the denoiser runs
+    them as one ``denoise_batch``); ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed."""
     n = audio.shape[-1]
     padded = torch.zeros(audio.shape[0], (n // 1600 + 1) * 1600, dtype=audio.dtype, device=audio.device)
     padded[:, :n].copy_(audio)
@@ -79,7 +80,11 @@ def prompt_mels(mel_fn, audio, denoiser=None, hps_denoiser=None):
         src_mel = src_mel.repeat(2, 1, 1) if src_mel.shape[0] == 1 else torch.cat([src_mel, src_mel], 0)
         return src_mel_ttv, src_mel
     if audio.shape[0] != 1:
-        raise L.HspError("the prompt denoiser takes one prompt per call, as the reference")
+        # B prompts of one length: each padded, denoised and cut as the single prompt below, in one packed pass
+        from .denoiser.infer import denoise_batch
+        den, _ = denoise_batch(padded, denoiser, hps_denoiser, lengths=[padded.shape[-1]] * audio.shape[0])
+        both = torch.cat([padded, den[:, :padded.shape[-1]]], 0)[:, :n]   # [2B, n]: the B prompts, then the B denoised
+        return src_mel_ttv, mel_fn(both.contiguous())
     from .denoiser.infer import denoise
     den = denoise(padded[0], denoiser, hps_denoiser)                  # [1, len(padded)] (1600 is a multiple of the hop)
     both = torch.cat([padded, den[:, :padded.shape[-1]]], 0)[:, :n]   # :147,150 (copies, no arithmetic)

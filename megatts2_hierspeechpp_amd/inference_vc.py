@@ -253,9 +253,29 @@ def _rows(arg, device, what):
 
 
 @torch.no_grad()
+def denoise_prompts(prompts, denoiser, hps):
+    """The denoised form of every prompt as inference_vc.py:117-133 makes it, for all of them in one
+    ``denoiser.infer.denoise_batch``: zero-pad each prompt to the next multiple of 1600 samples (always at least one
+    sample of padding, :117-119), denoise the padded prompts, cut to the padded length (:130) and to the prompt's own
+    length (:133).  ``prompts``: 1-D or [1, n] fp32 device tensors; ``denoiser`` a finalized denoiser.generator.MPNet,
+    ``hps`` its config.  Returns a list of 1-D tensors, the form ``vc_batch`` takes as ``denoised``."""
+    from .denoiser.infer import denoise_batch
+    rows = [_flat(p) for p in prompts]
+    if not rows:
+        raise L.HspError("denoise_prompts: no prompts")
+    lens = [r.shape[0] for r in rows]
+    padded_lens = [(n // 1600 + 1) * 1600 for n in lens]
+    padded, _ = _stack(rows, rows[0].device, max(padded_lens))
+    out, out_lens = denoise_batch(padded, denoiser, hps, lengths=padded_lens)
+    # 1600 is a multiple of the denoiser's hop, so row b holds all padded_lens[b] samples
+    assert all(o >= n for o, n in zip(out_lens, lens))
+    return [out[b, :n] for b, n in enumerate(lens)]
+
+
+@torch.no_grad()
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
              denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
-             row_exact=False):
+             row_exact=False, denoiser=None, hps_denoiser=None):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -266,6 +286,9 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
              share it: its mel and style vector are computed once, at its own length);
     f0_trgs  the prompts' tracks, in the same form as ``targets``;
     denoised the denoiser's output per prompt, in the same form as ``targets`` (None = the prompts themselves);
+    denoiser / hps_denoiser  a finalized denoiser.generator.MPNet and its config: with ``denoise_ratio != 0`` and no
+             ``denoised``, every distinct prompt is denoised here in one packed pass (``denoise_prompts``).  Giving
+             both ``denoised`` and ``denoiser``, or ``denoise_ratio != 0`` with neither, is an error;
     noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn.
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
@@ -275,6 +298,13 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     at B = 1 too (key-masked flows, ragged activations, zeros past every row's end), so every row equals ``vc`` on it
     alone, at 16, 24 and 48 kHz."""
     voc = models.voc
+    if denoised is not None and denoiser is not None:
+        raise L.HspError("vc_batch: give the denoised prompts or a denoiser, not both")
+    if denoise_ratio != 0 and denoised is None and denoiser is None:
+        raise L.HspError("vc_batch: denoise_ratio != 0 needs the denoised prompts (denoised=) or a denoiser (denoiser=, "
+                         "hps_denoiser=)")
+    if denoiser is not None and hps_denoiser is None:
+        raise L.HspError("vc_batch: a denoiser needs its config (hps_denoiser=)")
     dev = sources[0].device
     x, src_len, src_host = _rows(sources, dev, "sources")
     B, Ls = x.shape
@@ -297,7 +327,10 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
         return [arg]
 
     p_tracks = follow(f0_trgs, "f0_trgs")
-    seconds = prompts if denoised is None else follow(denoised, "denoised")
+    if denoised is None and denoiser is not None and denoise_ratio != 0:
+        seconds = denoise_prompts(prompts, denoiser, hps_denoiser)
+    else:
+        seconds = prompts if denoised is None else follow(denoised, "denoised")
     p_lens = [_flat(p).shape[0] for p in prompts]
     if src_host is not None and fs_host is not None:
         check_batch(src_host, fs_host, p_lens, [_flat(t).shape[0] for t in p_tracks])
@@ -375,7 +408,9 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     """The reference's per-file loop (inference_vc.py:70-170, one process call per file) as batches: every source and
     prompt WAV at any sample rate (``audio.load_16k``; sources padded by pad_source), F0 tracks from ``f0`` (a mapping
     path -> track) or else from the '.hf0.npy' file extract_f0.py writes beside each WAV (a missing track is an error
-    naming the file), ``vc_batch`` calls (keywords ``kw``; ``noise`` [B, 192, T_max] is sliced per batch), and with
+    naming the file), ``vc_batch`` calls (keywords ``kw``; ``noise`` [B, 192, T_max] is sliced per batch; ``denoiser=``
+    and ``hps_denoiser=`` with ``denoise_ratio != 0`` denoise every distinct prompt file of a batch in one packed pass,
+    the reference harness's step :117-133), and with
     ``out_dir`` one '<src>_to_<trg>.wav' per row at the output rate.  ``target_paths``: one prompt file for every source,
     or one per source.
 
