@@ -42,7 +42,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define HSP_VERSION 103 /* 0.1.3: hsp_conv1d_args lost the five trailing fields of the modulated input LayerNorm (the
+#define HSP_VERSION 104 /* 0.1.4: hsp_sum_sq_f32, hsp_instnorm_prelu_f32, hsp_dwconv_bn_silu_f32 and hsp_istft_ola_f32 are
+                           * removed: one prompt is a segment table with one row (hsp_norm_factor_rows_f32 with B = 1 and
+                           * the _seg entry points give the same bits); a caller of the four names must move to those.
+                           * 0.1.3: hsp_conv1d_args lost the five trailing fields of the modulated input LayerNorm (the
                            * round-6 experiment that 0.1.2 added after w_bs) -- a caller compiled against 102 passes a longer
                            * struct and must be rebuilt; hsp_dftseg_pair_f32 no longer takes inv->y / inv->res (refused).
                            * 0.1.2: hsp_conv1d_args grew those five fields; hsp_dftseg_pair_f32 took inv->y / inv->res and
@@ -244,25 +247,13 @@ int hsp_peak_int16_gains(const float* x, int64_t x_bs, const int64_t* lengths, c
 
 /* ----------------------------------------------- prompt denoiser (MP-SENet) */
 /* The parts of denoiser/ that are neither convolutions nor GEMMs (those run on hsp_conv1d_mfma_f32 /
- * hsp_conv1d_direct_f32 / hsp_mha_f32 / hsp_layernorm_mod_f32).  One utterance per call, as the reference
- * (denoiser/infer.py:3-10 takes a 1-D prompt). */
-/* out[0] = sum_i x[i]^2 (double accumulation): the norm factor sqrt(len / sum) of denoiser/infer.py:4. */
-int hsp_sum_sq_f32(const float* x, int64_t n, float* out, void* stream);
+ * hsp_conv1d_direct_f32 / hsp_mha_f32 / hsp_layernorm_mod_f32).  These four are pointwise; the operations that read
+ * across frames take a segment table and follow below. */
 /* mag[f][t] = |z|^compress, pha[f][t] = angle(z) for z = spec[f][t] + i spec[n_freqs + f][t] (row pitch s_ld):
  * mag_pha_stft of denoiser/infer.py:12-24 after the DFT product; the imaginary part of the DC and Nyquist rows is
  * taken as +0, as a real FFT returns it.  mag, pha contiguous [n_freqs, T]. */
 int hsp_mag_pha_f32(const float* spec, int64_t s_ld, float* mag, float* pha, int32_t n_freqs, int32_t T, float compress,
                     void* stream);
-/* In place: nn.InstanceNorm2d(C, affine=True) then nn.PReLU(C) over the N contiguous values of each of the C
- * channel planes at x + c * x_cs (biased variance, double accumulation as torch's CPU path):
- * denoiser/generator.py:22-23,40-41,47-48,65-66,83-84. */
-int hsp_instnorm_prelu_f32(float* x, int64_t x_cs, int32_t C, int64_t N, const float* gamma, const float* beta,
-                           const float* slope, float eps, void* stream);
-/* y = SiLU(BatchNorm1d_eval(depthwise Conv1d(x))) over contiguous [B, C, N]; w [C, K] (K odd, padding K / 2),
- * batch-norm as y = x alpha + (bias - mean alpha), alpha = weight / sqrt(var + eps): denoiser/conformer.py:34-37. */
-int hsp_dwconv_bn_silu_f32(const float* x, const float* w, const float* bias, const float* bn_weight,
-                           const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, float* y,
-                           int32_t B, int32_t C, int32_t N, int32_t K, void* stream);
 /* out[t][f] = mag[t][f] * beta * sigmoid(slope[f] * m[t][f]): LearnableSigmoid_2d (denoiser/utils.py:44-53) and the
  * mask product of generator.py:140; all [T, F] contiguous. */
 int hsp_lsigmoid_mul_f32(const float* m, const float* slope, float beta, const float* mag, float* out, int32_t T,
@@ -273,21 +264,18 @@ int hsp_atan2_f32(const float* y, const float* x, float* out, int64_t n, void* s
  * generator.py:142-143 (power 1) and the decompression of mag_pha_istft (infer.py:26-29, power 1 / compress). */
 int hsp_polar_f32(const float* mag, const float* pha, float power, float* re, int64_t re_ld, float* im, int64_t im_ld,
                   int32_t F, int32_t T, void* stream);
-/* torch.istft(center=True) after the inverse DFT: out[n] = scale * sum_t frames[k][t] w[k] / sum_t w[k]^2 with
- * k = n + n_fft / 2 - t hop in [0, n_fft), n < hop (T - 1); frames [n_fft, f_ld] (denoiser/infer.py:30-31 and the
- * division by the norm factor at :9). */
-int hsp_istft_ola_f32(const float* frames, int64_t f_ld, const float* window, float* out, int32_t n_fft, int32_t hop,
-                      int32_t T, float scale, void* stream);
 
-/* ---- the packed ragged batch of the prompt denoiser (denoiser.infer.denoise_batch; additive:
- * HSP_VERSION unchanged).  B utterances lie end to end along T in one [C, T_tot, F] tensor with zero gap rows between
- * neighbours.  The segment table holds (first row, T_b) per utterance as int32 [B][2], ascending and disjoint: `seg` is
- * the device copy the kernels read, `seg_host` the host copy the launcher checks -- HSP_EINVAL, before any HIP call,
- * for a null pointer, B < 1, T_b < 1, a negative, descending or overlapping segment or one past T_tot.  Both copies
- * must hold the same values.  Row lengths in samples are device int64 [B], clamped into [0, L] as in the batched
- * voice conversion above.  Nothing here reads back, so a fixed set of lengths can be captured in a hipGraph. */
-/* scale[b] = sqrt(len_b / sum_i x[b][i]^2) (double accumulation, as hsp_sum_sq_f32) and inv[b] = 1 / scale[b]: the
- * norm factor of denoiser/infer.py:4 per row.  A silent or empty row gets scale = inv = 0 (denoise() raises there). */
+/* ---- the operations of the prompt denoiser that read across frames.  B utterances lie end to end
+ * along T in one [C, T_tot, F] tensor with zero gap rows between neighbours (denoiser.infer.denoise_batch); one prompt
+ * (denoiser.infer.denoise) is the table with one row (0, T) and no gap.  The segment table holds (first row, T_b) per
+ * utterance as int32 [B][2], ascending and disjoint: `seg` is the device copy the kernels read, `seg_host` the host
+ * copy the launcher checks -- HSP_EINVAL, before any HIP call, for a null pointer, B < 1, T_b < 1, a negative,
+ * descending or overlapping segment or one past T_tot.  Both copies must hold the same values.  Row lengths in samples
+ * are device int64 [B], clamped into [0, L] as in the batched voice conversion above.  Nothing here reads back, so a
+ * fixed set of lengths can be captured in a hipGraph. */
+/* scale[b] = sqrt(len_b / sum_i x[b][i]^2) and inv[b] = 1 / scale[b]: the norm factor of denoiser/infer.py:4 per row
+ * (the sum accumulated in double and rounded to fp32, both factors formed in double from it and rounded once).  A
+ * silent or empty row gets scale = inv = 0 (denoise() reads scale[0] back and raises there). */
 int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* scale, float* inv, int32_t B,
                              int64_t L, void* stream);
 /* hsp_stft_frames_ragged_f32 into ONE frame matrix [n_fft, f_ld]: row b's T_b = 1 + len_b / hop frames, reflected at
@@ -296,23 +284,28 @@ int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int64_t* length
 int hsp_stft_frames_packed_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* scale,
                                const float* window, float* frames, const int32_t* seg, const int32_t* seg_host, int32_t B,
                                int64_t L, int32_t n_fft, int32_t hop, int32_t T_tot, int32_t f_ld, void* stream);
-/* hsp_instnorm_prelu_f32 with statistics over the T_b x F values of each (segment, channel) of the C planes
- * [T_tot, F] at x + c * x_cs, in place; every row outside the segments is WRITTEN as 0 (never read). */
+/* In place: nn.InstanceNorm2d(C, affine=True) then nn.PReLU(C) with statistics over the T_b x F values of each
+ * (segment, channel) of the C planes [T_tot, F] at x + c * x_cs (biased variance, double accumulation as torch's CPU
+ * path): denoiser/generator.py:22-23,40-41,47-48,65-66,83-84.  Every row outside the segments is WRITTEN as 0 (never
+ * read). */
 int hsp_instnorm_prelu_seg_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
                                const int32_t* seg_host, int32_t B, const float* gamma, const float* beta,
                                const float* slope, float eps, void* stream);
 /* Zeros on every row outside the segments of the C planes [T_tot, F] at x + c * x_cs; nothing is read. */
 int hsp_zero_gaps_f32(float* x, int64_t x_cs, int32_t C, int32_t T_tot, int32_t F, const int32_t* seg,
                       const int32_t* seg_host, int32_t B, void* stream);
-/* hsp_dwconv_bn_silu_f32 over contiguous [A, C, N] with N the packed axis (T_tot = N): taps outside the element's own
- * segment read as 0 whatever the gap width; positions outside the segments are written as 0. */
+/* y = SiLU(BatchNorm1d_eval(depthwise Conv1d(x))) over contiguous [A, C, N] with N the packed axis (T_tot = N); w [C, K]
+ * (K odd, padding K / 2), batch-norm as y = x alpha + (bias - mean alpha), alpha = weight / sqrt(var + eps):
+ * denoiser/conformer.py:34-37.  Taps outside the element's own segment read as 0 whatever the gap width; positions
+ * outside the segments are written as 0. */
 int hsp_dwconv_bn_silu_seg_f32(const float* x, const float* w, const float* bias, const float* bn_weight,
                                const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, float* y,
                                int32_t A, int32_t C, int32_t N, int32_t K, const int32_t* seg, const int32_t* seg_host,
                                int32_t B, void* stream);
-/* hsp_istft_ola_f32 per segment of frames [n_fft, f_ld >= T_tot]: out[b][n] for n < hop (T_b - 1) sums the frames of
- * segment b only and is multiplied by inv[b] (device fp32 [B]; NULL = 1, bit-equal to the solo call then); zeros on
- * [hop (T_b - 1), n_max).  out rows of stride out_bs >= n_max >= hop (T_b - 1). */
+/* torch.istft(center=True) after the inverse DFT, per segment of frames [n_fft, f_ld >= T_tot]: out[b][n] = inv[b] *
+ * sum_t frames[k][first_b + t] w[k] / sum_t w[k]^2 with k = n + n_fft / 2 - t hop in [0, n_fft) over the frames t of
+ * segment b only, n < hop (T_b - 1) (denoiser/infer.py:30-31 and the division by the norm factor at :9; inv device
+ * fp32 [B], NULL = 1); zeros on [hop (T_b - 1), n_max).  out rows of stride out_bs >= n_max >= hop (T_b - 1). */
 int hsp_istft_ola_seg_f32(const float* frames, int64_t f_ld, const float* window, const float* inv, float* out,
                           int64_t out_bs, int64_t n_max, int32_t n_fft, int32_t hop, const int32_t* seg,
                           const int32_t* seg_host, int32_t B, int32_t T_tot, void* stream);

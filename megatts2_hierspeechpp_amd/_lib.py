@@ -175,15 +175,10 @@ SIGNATURES = {
                                              C.c_int32, C.c_int32, _fp]),
     "hsp_abs_max_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int64, _fp]),
     "hsp_peak_int16_gains": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
-    "hsp_sum_sq_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "hsp_mag_pha_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, C.c_float, _fp]),
-    "hsp_instnorm_prelu_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int64, _fp, _fp, _fp, C.c_float, _fp]),
-    "hsp_dwconv_bn_silu_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_int32, C.c_int32, C.c_int32,
-                                         C.c_int32, _fp]),
     "hsp_lsigmoid_mul_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, _fp, C.c_int32, C.c_int32, _fp]),
     "hsp_atan2_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
     "hsp_polar_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, C.c_int32, _fp]),
-    "hsp_istft_ola_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
     "hsp_norm_factor_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int64, _fp]),
     "hsp_stft_frames_packed_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int64, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, _fp]),

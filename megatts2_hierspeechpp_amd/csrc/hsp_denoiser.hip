@@ -29,14 +29,6 @@ __device__ __forceinline__ double dn_block_sum(double v, double* sh) {
   return t;
 }
 
-__global__ __launch_bounds__(1024) void sum_sq_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
-  __shared__ double sh[16];
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += (double)x[i] * (double)x[i];
-  s = dn_block_sum(s, sh);
-  if (threadIdx.x == 0) out[0] = (float)s;
-}
-
 // spec rows [0, nf) real, [nf, 2 nf) imaginary, pitch s_ld  ->  mag[f][t] = |z|^c, pha[f][t] = angle(z)
 __global__ __launch_bounds__(256) void mag_pha_kernel(const float* __restrict__ spec, int64_t s_ld, float* __restrict__ mag,
                                                       float* __restrict__ pha, int nf, int T, float c) {
@@ -49,54 +41,6 @@ __global__ __launch_bounds__(256) void mag_pha_kernel(const float* __restrict__ 
   const float im = (f == 0 || f == nf - 1) ? 0.0f : spec[(int64_t)(nf + f) * s_ld + t];
   mag[i] = powf(hypotf(re, im), c);
   pha[i] = atan2f(im, re);
-}
-
-// InstanceNorm2d(affine) + PReLU over the N contiguous values of each channel plane (one utterance), in place
-__global__ __launch_bounds__(1024) void instnorm_prelu_kernel(float* __restrict__ x, int64_t cs, int64_t N,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float* __restrict__ slope, float eps) {
-  __shared__ double sh[16];
-  const int c = blockIdx.x;
-  float* p = x + (int64_t)c * cs;
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) s += (double)p[i];
-  const double mean = dn_block_sum(s, sh) / (double)N;
-  double q = 0.0;
-  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
-    const double d = (double)p[i] - mean;
-    q += d * d;
-  }
-  const double var = dn_block_sum(q, sh) / (double)N;   // biased, as F.instance_norm
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float m = (float)mean, g = gamma[c], b = beta[c], sl = slope[c];
-  for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
-    const float y = (p[i] - m) * inv * g + b;
-    p[i] = y > 0.0f ? y : sl * y;
-  }
-}
-
-// depthwise Conv1d (same padding, odd K) + BatchNorm1d in eval mode + SiLU over [B, C, N]
-__global__ __launch_bounds__(256) void dwconv_bn_silu_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, const float* __restrict__ bn_w,
-                                                             const float* __restrict__ bn_b, const float* __restrict__ bn_mean,
-                                                             const float* __restrict__ bn_var, float bn_eps,
-                                                             float* __restrict__ y, int C, int N, int K, int64_t total) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int n = (int)(i % N);
-  const int c = (int)((i / N) % C);
-  const float* row = x + (i - n);
-  const float* wc = w + (int64_t)c * K;
-  const int half = K >> 1;
-  float acc = 0.0f;
-  for (int j = 0; j < K; ++j) {
-    const int m = n + j - half;
-    if (m >= 0 && m < N) acc = fmaf(wc[j], row[m], acc);
-  }
-  acc += bias[c];
-  const float alpha = bn_w[c] / sqrtf(bn_var[c] + bn_eps);
-  const float v = acc * alpha + (bn_b[c] - bn_mean[c] * alpha);
-  y[i] = v / (1.0f + expf(-v));
 }
 
 // out[t][f] = mag[t][f] * beta * sigmoid(slope[f] * m[t][f])
@@ -127,32 +71,11 @@ __global__ __launch_bounds__(256) void polar_kernel(const float* __restrict__ ma
   im[f * im_ld + t] = m * sinf(pha[i]);
 }
 
-// torch.istft after the inverse DFT: out[n] = sum_t frames[n + N/2 - t hop][t] w[.] / sum_t w[.]^2, n < hop (T - 1)
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, int64_t f_ld,
-                                                        const float* __restrict__ window, float* __restrict__ out, int n_fft,
-                                                        int hop, int T, int64_t L, float scale) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= L) return;
-  const int64_t pos = n + (n_fft >> 1);
-  int64_t t_hi = pos / hop;
-  if (t_hi > T - 1) t_hi = T - 1;
-  int64_t t_lo = (pos - n_fft + hop) / hop;   // smallest t with pos - t hop <= n_fft - 1
-  if (pos - n_fft + 1 <= 0) t_lo = 0;
-  float num = 0.0f, den = 0.0f;
-  for (int64_t t = t_lo; t <= t_hi; ++t) {
-    const int k = (int)(pos - t * hop);
-    if (k < 0 || k >= n_fft) continue;
-    const float w = window[k];
-    num += frames[(int64_t)k * f_ld + t] * w;
-    den += w * w;
-  }
-  out[n] = num / den * scale;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Packed ragged batch (denoise_batch): B utterances laid end to end along T with zero gap rows between
-// them.  seg = device int32 [B][2] = (first row, T_b), ascending and disjoint (the launchers check the host copy).
-// B is a handful of prompts: the table is scanned linearly, with addresses every lane shares.
+// The T-crossing operations read their bounds from a segment table: B utterances laid end to end along
+// T with zero gap rows between them; one prompt is the table with one row.  seg = device int32 [B][2] = (first row,
+// T_b), ascending and disjoint (the launchers check the host copy).  B is a handful of prompts: the table is scanned
+// linearly, with addresses every lane shares.
 __device__ __forceinline__ int dn_seg_of(const int32_t* __restrict__ seg, int B, int t, int& t0, int& Tb) {
   for (int b = 0; b < B; ++b) {
     const int s = seg[2 * b], n = seg[2 * b + 1];
@@ -170,8 +93,8 @@ __device__ __forceinline__ int64_t dn_clamp_len(const int64_t* len, int b, int64
   return min(cap, max((int64_t)0, len[b]));
 }
 
-// sum_sq_kernel per row, then scale = sqrt(len / ss) and 1 / scale formed in double from the fp32-rounded sum, as
-// denoise() forms them on the host; a silent (or empty) row gets 0 for both
+// per row: ss = sum x^2 (double accumulation, rounded to fp32), then scale = sqrt(len / ss) and 1 / scale formed in
+// double and rounded once; a silent (or empty) row gets 0 for both
 __global__ __launch_bounds__(1024) void norm_factor_rows_kernel(const float* __restrict__ x, int64_t x_bs,
                                                                 const int64_t* __restrict__ lengths, float* __restrict__ scale,
                                                                 float* __restrict__ inv, int64_t L) {
@@ -225,8 +148,8 @@ __global__ __launch_bounds__(256) void stft_frames_packed_kernel(const float* __
   }
 }
 
-// instnorm_prelu_kernel per (channel, segment): block (c, b) normalises the T_b x F values of segment b in place and
-// WRITES zeros on the gap rows that follow it (block b = 0 also on the rows ahead of the first segment), so every
+// InstanceNorm2d(affine) + PReLU per (channel, segment): block (c, b) normalises the T_b x F values of segment b in place
+// and WRITES zeros on the gap rows that follow it (block b = 0 also on the rows ahead of the first segment), so every
 // row of the plane is written by exactly one block and no gap value is ever read
 __global__ __launch_bounds__(1024) void instnorm_prelu_seg_kernel(float* __restrict__ x, int64_t cs, int T_tot, int F,
                                                                   const int32_t* __restrict__ seg, int B,
@@ -274,8 +197,9 @@ __global__ __launch_bounds__(256) void zero_gaps_kernel(float* __restrict__ x, i
   if (dn_seg_of(seg, B, (int)(r / F), t0, Tb) < 0) x[c * cs + r] = 0.0f;
 }
 
-// dwconv_bn_silu_kernel with N = the packed T axis: taps outside the element's own segment read as zero (bounded by the
-// table, whatever the gap width); gap positions are written as 0
+// depthwise Conv1d (same padding, odd K) + BatchNorm1d in eval mode + SiLU over [A, C, N] with N = the packed T axis: taps
+// outside the element's own segment read as zero (bounded by the table, whatever the gap width); gap positions are
+// written as 0
 __global__ __launch_bounds__(256) void dwconv_bn_silu_seg_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                  const float* __restrict__ bias, const float* __restrict__ bn_w,
                                                                  const float* __restrict__ bn_b, const float* __restrict__ bn_mean,
@@ -305,8 +229,9 @@ __global__ __launch_bounds__(256) void dwconv_bn_silu_seg_kernel(const float* __
   y[i] = v / (1.0f + expf(-v));
 }
 
-// istft_ola_kernel per segment: output row b (blockIdx.y) sums the frames of columns [t0_b, t0_b + T_b) only, holds
-// hop (T_b - 1) samples times inv[b] (1 when inv is NULL) and zeros up to n_max
+// torch.istft after the inverse DFT, per segment: out[b][n] = sum_t frames[n + N/2 - t hop][t0_b + t] w[.] / sum_t w[.]^2
+// over the frames t of segment b (blockIdx.y) only, for n < hop (T_b - 1), times inv[b] (1 when inv is NULL); zeros up
+// to n_max
 __global__ __launch_bounds__(256) void istft_ola_seg_kernel(const float* __restrict__ frames, int64_t f_ld,
                                                             const float* __restrict__ window, const float* __restrict__ inv,
                                                             float* __restrict__ out, int64_t out_bs, int64_t n_max, int n_fft,
@@ -351,12 +276,6 @@ static bool dn_seg_ok(const int32_t* seg, const int32_t* seg_host, int32_t B, in
 
 #define HSP_STREAM static_cast<hipStream_t>(stream)
 
-extern "C" int hsp_sum_sq_f32(const float* x, int64_t n, float* out, void* stream) {
-  if (!x || !out || n <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(sum_sq_kernel, dim3(1), dim3(1024), 0, HSP_STREAM, x, n, out);
-  return (int)hipGetLastError();
-}
-
 extern "C" int hsp_mag_pha_f32(const float* spec, int64_t s_ld, float* mag, float* pha, int32_t n_freqs, int32_t T,
                                float compress, void* stream) {
   if (!spec || !mag || !pha || n_freqs < 2 || T <= 0 || s_ld < T) return HSP_EINVAL;
@@ -364,25 +283,6 @@ extern "C" int hsp_mag_pha_f32(const float* spec, int64_t s_ld, float* mag, floa
   if (!dn_fits(total, 256)) return HSP_EINVAL;
   hipLaunchKernelGGL(mag_pha_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, spec, s_ld, mag, pha, n_freqs, T,
                      compress);
-  return (int)hipGetLastError();
-}
-
-extern "C" int hsp_instnorm_prelu_f32(float* x, int64_t x_cs, int32_t C, int64_t N, const float* gamma, const float* beta,
-                                      const float* slope, float eps, void* stream) {
-  if (!x || !gamma || !beta || !slope || C <= 0 || N <= 0 || x_cs < N) return HSP_EINVAL;
-  hipLaunchKernelGGL(instnorm_prelu_kernel, dim3((unsigned)C), dim3(1024), 0, HSP_STREAM, x, x_cs, N, gamma, beta, slope, eps);
-  return (int)hipGetLastError();
-}
-
-extern "C" int hsp_dwconv_bn_silu_f32(const float* x, const float* w, const float* bias, const float* bn_weight,
-                                      const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, float* y,
-                                      int32_t B, int32_t C, int32_t N, int32_t K, void* stream) {
-  if (!x || !w || !bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !y) return HSP_EINVAL;
-  if (B <= 0 || C <= 0 || N <= 0 || K <= 0 || (K & 1) == 0) return HSP_EINVAL;
-  const int64_t total = (int64_t)B * C * N;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(dwconv_bn_silu_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, w, bias, bn_weight, bn_bias,
-                     bn_mean, bn_var, bn_eps, y, C, N, K, total);
   return (int)hipGetLastError();
 }
 
@@ -409,16 +309,6 @@ extern "C" int hsp_polar_f32(const float* mag, const float* pha, float power, fl
   if (!dn_fits(total, 256)) return HSP_EINVAL;
   hipLaunchKernelGGL(polar_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, mag, pha, power, re, re_ld, im, im_ld, T,
                      total);
-  return (int)hipGetLastError();
-}
-
-extern "C" int hsp_istft_ola_f32(const float* frames, int64_t f_ld, const float* window, float* out, int32_t n_fft,
-                                 int32_t hop, int32_t T, float scale, void* stream) {
-  if (!frames || !window || !out || n_fft <= 0 || (n_fft & 1) || hop <= 0 || hop > n_fft || T < 2 || f_ld < T) return HSP_EINVAL;
-  const int64_t L = (int64_t)hop * (T - 1);
-  if (!dn_fits(L, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(istft_ola_kernel, dim3(dn_grid(L, 256)), dim3(256), 0, HSP_STREAM, frames, f_ld, window, out, n_fft, hop, T,
-                     L, scale);
   return (int)hipGetLastError();
 }
 

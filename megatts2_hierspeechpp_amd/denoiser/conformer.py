@@ -11,6 +11,7 @@ from .. import _lib as L
 from .. import functional as Fh
 from ..hip_layers import Conv1d, HipLayer, LinearCT, _SubArena
 from ..ttv_v1.transformer_mega import LayerNorm
+from .packed import one_segment
 from .utils import Vec
 
 
@@ -67,25 +68,18 @@ class ConformerConvModule(nn.Module):
                                   "7": Conv1d(inner, dim, 1)})
 
     def forward(self, x, seg=None):
-        """x + ccm(x).  ``seg`` (denoiser.packed.Segments): N is a packed axis, the depthwise conv stays inside each
-        segment (``hsp_dwconv_bn_silu_seg_f32``)."""
+        """x + ccm(x).  ``seg`` (denoiser.packed.Segments): the segments of N the depthwise conv stays inside; None = one
+        utterance, all of N."""
         h = self.ccm["2"](self.ccm["0"](x))                    # [A, inner, N]
         dw, bn = self.ccm["4"], self.ccm["5"]
         y = torch.empty_like(h)
         A, Cc, N = h.shape
-        if seg is not None:
-            assert N == seg.T_tot
-            L.check(L.lib().hsp_dwconv_bn_silu_seg_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
-                                                       L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
-                                                       L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
-                                                       float(bn.eps), L.fptr(y), A, Cc, N, dw.k, *seg.args(),
-                                                       L.stream_ptr()), "hsp_dwconv_bn_silu_seg_f32")
-            return self.ccm["7"](y, res=x)
-        L.check(L.lib().hsp_dwconv_bn_silu_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
-                                               L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
-                                               L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
-                                               float(bn.eps), L.fptr(y), A, Cc, N, dw.k, L.stream_ptr()),
-                "hsp_dwconv_bn_silu_f32")
+        seg = one_segment(seg, N, x.device)
+        L.check(L.lib().hsp_dwconv_bn_silu_seg_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
+                                                   L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
+                                                   L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
+                                                   float(bn.eps), L.fptr(y), A, Cc, N, dw.k, *seg.args(),
+                                                   L.stream_ptr()), "hsp_dwconv_bn_silu_seg_f32")
         return self.ccm["7"](y, res=x)
 
 
@@ -121,20 +115,19 @@ class AttentionModule(nn.Module):
 
     def forward(self, x, seg=None):
         """x + attn(layernorm(x)), attention along dim 0 of [A, C, N] for every n.  ``seg`` (denoiser.packed.Segments):
-        A is a packed axis and every segment attends to itself only -- one launch per segment on column slices of the
-        packed q / k / v, each the launch its utterance runs alone; rows outside the segments come out as zeros."""
+        every segment of A attends to itself only -- one launch per segment on column slices of the packed q / k / v,
+        each the launch its utterance runs alone; rows outside the segments come out as zeros.  None = one utterance,
+        all of A."""
         m = self.attn
         qkv = m._qkv(self.layernorm(x))                                   # [A, 3C, N]
         qkv_t = Fh.copy_strided(qkv.permute(2, 1, 0))                     # [N, 3C, A]: A is the sequence axis
         C_ = m.dim
-        if seg is not None:
-            assert qkv_t.shape[2] == seg.T_tot
-            o = torch.zeros(qkv_t.shape[0], C_, seg.T_tot, dtype=torch.float32, device=x.device)
-            for sl in seg.slices():
-                Fh.mha(qkv_t[:, :C_, sl], qkv_t[:, C_:2 * C_, sl], qkv_t[:, 2 * C_:, sl], m.n_head,
-                       (C_ // m.n_head) ** -0.5, out=o[:, :, sl])
-            return m.out_proj(Fh.copy_strided(o.permute(2, 1, 0)), res=x)
-        o = Fh.mha(qkv_t[:, :C_], qkv_t[:, C_:2 * C_], qkv_t[:, 2 * C_:], m.n_head, (C_ // m.n_head) ** -0.5)
+        seg = one_segment(seg, qkv_t.shape[2], x.device)
+        new = torch.zeros if seg.has_gaps else torch.empty
+        o = new(qkv_t.shape[0], C_, seg.T_tot, dtype=torch.float32, device=x.device)
+        for sl in seg.slices():
+            Fh.mha(qkv_t[:, :C_, sl], qkv_t[:, C_:2 * C_, sl], qkv_t[:, 2 * C_:, sl], m.n_head,
+                   (C_ // m.n_head) ** -0.5, out=o[:, :, sl])
         return m.out_proj(Fh.copy_strided(o.permute(2, 1, 0)), res=x)     # back to [A, C, N]
 
 
@@ -152,7 +145,7 @@ class ConformerBlock(nn.Module):
 
     def forward(self, x, attn_seg=None, conv_seg=None):
         """``attn_seg`` / ``conv_seg``: the segment table when the attention's axis (A) / the conv module's axis (N) is
-        the packed T axis of a ragged batch; None = one utterance."""
+        the packed T axis; None = that axis is one utterance."""
         x = self.ffm1(x, scale=0.5)
         x = self.attn(x, attn_seg)
         x = self.ccm(x, conv_seg)

@@ -1,9 +1,11 @@
 """denoiser/generator.py (MP-SENet ``MPNet``) with the reference's class names, constructor arguments and state-dict
 keys; every tensor stays ``[1, C, T, F]`` (the reference's layout) and all arithmetic is in libhsp.so.  A ragged batch
 runs as ONE such tensor with the rows packed along T (``MPNet.forward(..., lengths)``, denoiser/packed.py): the modules
-take the segment table as ``seg`` and only the operations that read across rows of T change.
+take the segment table as ``seg``, which only the operations that read across rows of T look at.  There is one path:
+one utterance is the table with one row (``seg`` None stands for it), and those operations always run their
+segment-table kernels.
 
-How the 2-D pieces map onto the 1-D kernels (one utterance, as denoiser/infer.py feeds it):
+How the 2-D pieces map onto the 1-D kernels:
   * ``Conv2d(k = (kh, kw), dilation = (d, 1))``: the T rows are the batch of a Conv1d along F; tap row i reads the
     input rows shifted by (i - kh // 2) d -- kh launches on row-shifted views, accumulating into the output (rows the
     shift pushes outside [0, T) are the conv's zero padding: those launches simply cover fewer rows);
@@ -11,7 +13,7 @@ How the 2-D pieces map onto the 1-D kernels (one utterance, as denoiser/infer.py
     input is a channel slice of it and nothing is copied;
   * ``Conv2d((1, 3), stride (1, 2))`` / ``ConvTranspose2d((1, 3), stride (1, 2))``: the polyphase strided conv /
     transposed conv of the vocoder along F;
-  * ``InstanceNorm2d + PReLU``: one launch per layer (``hsp_instnorm_prelu_f32``), in place."""
+  * ``InstanceNorm2d + PReLU``: one launch per layer (``hsp_instnorm_prelu_seg_f32``: statistics per segment), in place."""
 from __future__ import annotations
 
 import torch
@@ -21,7 +23,8 @@ from .. import _lib as L
 from .. import functional as Fh
 from ..hip_layers import Conv1d, ConvTranspose1d, HipLayer, PolyphaseConv1d, _SubArena, entry as _entry, finalize as _finalize
 from .conformer import ConformerBlock
-from .utils import LearnableSigmoid_2d, Vec, get_padding_2d
+from .packed import host_ints, one_segment, segments_for
+from .utils import LearnableSigmoid_2d, Vec, get_padding_2d, polar_pair
 
 
 class _Conv2d(HipLayer):
@@ -94,20 +97,15 @@ class _PReLU(Vec):
 
 
 def _norm_act(norm: _InstanceNorm2d, act: _PReLU, x, seg=None):
-    """In place on x [1, C, T, F] (each channel plane contiguous).  ``seg``: statistics per segment of the packed T
-    axis, zeros written on the gap rows."""
+    """In place on x [1, C, T, F] (each channel plane contiguous).  ``seg``: statistics per segment of the T axis, zeros
+    written on the gap rows; None = one utterance, all of T."""
     _, Cc, T, F_ = x.shape
     assert x.stride(3) == 1 and x.stride(2) == F_
-    if seg is not None:
-        assert T == seg.T_tot
-        L.check(L.lib().hsp_instnorm_prelu_seg_f32(L.fptr(x), x.stride(1), Cc, T, F_, *seg.args(),
-                                                   L.fptr(norm.dev("weight")), L.fptr(norm.dev("bias")),
-                                                   L.fptr(act.dev("weight")), float(norm.eps), L.stream_ptr()),
-                "hsp_instnorm_prelu_seg_f32")
-        return x
-    L.check(L.lib().hsp_instnorm_prelu_f32(L.fptr(x), x.stride(1), Cc, T * F_, L.fptr(norm.dev("weight")),
-                                           L.fptr(norm.dev("bias")), L.fptr(act.dev("weight")), float(norm.eps),
-                                           L.stream_ptr()), "hsp_instnorm_prelu_f32")
+    seg = one_segment(seg, T, x.device)
+    L.check(L.lib().hsp_instnorm_prelu_seg_f32(L.fptr(x), x.stride(1), Cc, T, F_, *seg.args(),
+                                               L.fptr(norm.dev("weight")), L.fptr(norm.dev("bias")),
+                                               L.fptr(act.dev("weight")), float(norm.eps), L.stream_ptr()),
+            "hsp_instnorm_prelu_seg_f32")
     return x
 
 
@@ -251,20 +249,21 @@ class TSConformerBlock(nn.Module):
         self.freq_conformer = ConformerBlock(dim=h.dense_channel, n_head=4, ccm_kernel_size=31, ffm_dropout=0.2,
                                              attn_dropout=0.2)
 
-    def forward(self, x, seg=None):
+    def forward(self, x, seg=None, seg_f=None):
         """x [1, C, T, F] -> [1, C, T, F].  ``seg``: T is packed -- the time conformer's conv module (along T) and the
-        frequency conformer's attention (along T) stay inside each segment; everything else works per row of T."""
+        frequency conformer's attention (along T) stay inside each segment; everything else works per row of T.
+        ``seg_f``: the one-segment table of the F axis, when the caller already holds it (a pass builds it once)."""
         xt = Fh.copy_strided(x[0].permute(2, 0, 1))                   # [F, C, T]   (reference: view(b f, t, c))
-        xt = Fh.axpby(self.time_conformer(xt, conv_seg=seg), xt, 1.0, 1.0)
+        xt = Fh.axpby(self.time_conformer(xt, attn_seg=seg_f, conv_seg=seg), xt, 1.0, 1.0)
         xf = Fh.copy_strided(xt.permute(2, 1, 0))                     # [T, C, F]   (reference: view(b t, f, c))
-        xf = Fh.axpby(self.freq_conformer(xf, attn_seg=seg), xf, 1.0, 1.0)
+        xf = Fh.axpby(self.freq_conformer(xf, attn_seg=seg, conv_seg=seg_f), xf, 1.0, 1.0)
         return Fh.copy_strided(xf.permute(1, 0, 2)).unsqueeze(0)      # [1, C, T, F]
 
 
 class MPNet(nn.Module):
     """generator.py:118-147.  ``forward(noisy_mag [1, F, T], noisy_pha [1, F, T])`` ->
-    ``(denoised_mag [1, F, T], denoised_pha [1, F, T], denoised_com [1, F, T, 2])`` as the reference; one utterance
-    per call (B = 1 is what denoiser/infer.py passes)."""
+    ``(denoised_mag [1, F, T], denoised_pha [1, F, T], denoised_com [1, F, T, 2])`` as the reference; with ``lengths``
+    a ragged batch."""
 
     def __init__(self, h, num_tscblocks=4):
         super().__init__()
@@ -286,35 +285,20 @@ class MPNet(nn.Module):
         ``[B, F, T_max]`` inputs run as one packed pass (denoiser/packed.py) and the three outputs are
         ``[B, F, T_max]`` (``[B, F, T_max, 2]``) with row b equal to the call on ``[:, :, :lengths[b]]`` alone and zeros
         past its frames.  Device-only lengths are refused: the shapes depend on them."""
-        if lengths is not None:
-            return self._forward_ragged(noisy_mag, noisy_pha, lengths)
-        if noisy_mag.dim() != 3 or noisy_mag.shape[0] != 1 or noisy_mag.shape != noisy_pha.shape:
-            raise L.HspError("MPNet takes one utterance: noisy_mag / noisy_pha [1, F, T]")
-        return self._run(noisy_mag, noisy_pha, None)
-
-    def _forward_ragged(self, noisy_mag, noisy_pha, lengths):
-        from .packed import host_ints, segments_for
+        if lengths is None:
+            if noisy_mag.dim() != 3 or noisy_mag.shape[0] != 1 or noisy_mag.shape != noisy_pha.shape:
+                raise L.HspError("MPNet takes one utterance: noisy_mag / noisy_pha [1, F, T]")
+            return self._run(noisy_mag, noisy_pha, one_segment(None, noisy_mag.shape[2], noisy_mag.device))
         frames = host_ints(lengths, "MPNet lengths")
         if noisy_mag.dim() != 3 or noisy_mag.shape != noisy_pha.shape or noisy_mag.shape[0] != len(frames):
             raise L.HspError("MPNet with lengths takes noisy_mag / noisy_pha [B, F, T_max] and one length per row")
-        B, F_, Tm = noisy_mag.shape
+        Tm = noisy_mag.shape[2]
         if max(frames) > Tm or min(frames) < 1:
             raise L.HspError(f"MPNet lengths {frames} outside [1, {Tm}]")
         seg = segments_for(frames, noisy_mag.device)
-        pk = [torch.zeros(1, F_, seg.T_tot, dtype=torch.float32, device=noisy_mag.device) for _ in range(2)]
-        for dst, src in zip(pk, (noisy_mag, noisy_pha)):
-            for b, sl in enumerate(seg.slices()):
-                dst[0, :, sl].copy_(src[b, :, :frames[b]])                     # copies, no arithmetic
-        d_mag, d_pha, _ = self.forward_packed(pk[0], pk[1], seg)
-        out = [torch.zeros(B, F_, Tm, dtype=torch.float32, device=noisy_mag.device) for _ in range(2)]
-        for dst, src in zip(out, (d_mag, d_pha)):
-            for b, sl in enumerate(seg.slices()):
-                dst[b, :, :frames[b]].copy_(src[0, :, sl])
-        re = torch.empty(B * F_, Tm, dtype=torch.float32, device=noisy_mag.device)
-        im = torch.empty(B * F_, Tm, dtype=torch.float32, device=noisy_mag.device)
-        L.check(L.lib().hsp_polar_f32(L.fptr(out[0]), L.fptr(out[1]), 1.0, L.fptr(re), Tm, L.fptr(im), Tm, B * F_, Tm,
-                                      L.stream_ptr()), "hsp_polar_f32")
-        return out[0], out[1], torch.stack((re, im), dim=-1).reshape(B, F_, Tm, 2)
+        d_mag, d_pha, _ = self._run(seg.pack(noisy_mag), seg.pack(noisy_pha), seg)
+        d_mag, d_pha = seg.unpack(d_mag, Tm), seg.unpack(d_pha, Tm)
+        return d_mag, d_pha, polar_pair(d_mag, d_pha)
 
     @_entry
     @torch.no_grad()
@@ -335,9 +319,11 @@ class MPNet(nn.Module):
             L.check(L.lib().hsp_copy_strided_f32(L.fptr(v), v.stride(0), v.stride(1), v.stride(2), L.fptr(x[:, i]), 1, T, F_,
                                                  L.stream_ptr()), "hsp_copy_strided_f32")
         h = self.dense_encoder(x, seg)
+        # the conformers' other axis: once per pass, because a table made while a graph is captured is not cached
+        seg_f = one_segment(None, h.shape[3], h.device)
         for blk in self.TSConformer:
-            h = blk(h, seg)
-        if seg is not None:
+            h = blk(h, seg, seg_f)
+        if seg.has_gaps:
             # the decoders' dense blocks shift along T and read h before any norm: zeros on its gap rows
             L.check(L.lib().hsp_zero_gaps_f32(L.fptr(h), h.stride(1), h.shape[1], T, h.shape[3], *seg.args(),
                                               L.stream_ptr()), "hsp_zero_gaps_f32")
@@ -345,8 +331,4 @@ class MPNet(nn.Module):
         pha_tf = self.phase_decoder(h, seg)                                              # [T, F]
         d_mag = Fh.copy_strided(mag_tf.t().unsqueeze(0))                                 # [1, F, T]
         d_pha = Fh.copy_strided(pha_tf.t().unsqueeze(0))
-        re = torch.empty(F_, T, dtype=torch.float32, device=x.device)
-        im = torch.empty(F_, T, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_polar_f32(L.fptr(d_mag), L.fptr(d_pha), 1.0, L.fptr(re), T, L.fptr(im), T, F_, T, L.stream_ptr()),
-                "hsp_polar_f32")
-        return d_mag, d_pha, torch.stack((re, im), dim=-1).unsqueeze(0)       # a copy, no arithmetic
+        return d_mag, d_pha, polar_pair(d_mag, d_pha)

@@ -1,20 +1,19 @@
 """denoiser/infer.py: ``denoise(noisy_wav, model, hps)`` with the reference's signature.  torch.stft / torch.istft
-(third party) are restated as the framing kernel of the prompt mel front-end, a DFT product on the MFMA GEMM against a
-host-built (float64 -> fp32) basis, and an overlap-add kernel; magnitude compression, phase and the polar
-re-composition are pointwise launches.  One host synchronisation: the norm factor ``sqrt(len / sum(x^2))`` is read
-back once (prompt pre-processing, outside any timed path).  ``denoise_batch`` is the same call for B prompts in one
-packed pass with no read-back at all."""
+(third party) are restated as a framing kernel, a DFT product on the MFMA GEMM against a host-built (float64 -> fp32)
+basis, and an overlap-add kernel; magnitude compression, phase and the polar re-composition are pointwise launches.
+``denoise_batch`` runs B prompts in one packed pass with no read-back at all; ``denoise`` is that pass
+on a segment table of one row, after its one host synchronisation: the norm factor ``sqrt(len / sum(x^2))`` is read
+back once (prompt pre-processing, outside any timed path) so that a silent prompt can raise."""
 from __future__ import annotations
-
-import math
 
 import numpy as np
 import torch
 from torch import nn
 
 from .. import _lib as L
-from .. import functional as Fh
 from ..hip_layers import Conv1d, finalize as _finalize
+from .packed import device_lengths, host_ints, segments_for, split_rows
+from .utils import polar_pair
 
 
 class _Stft(nn.Module):
@@ -64,32 +63,12 @@ def mag_pha_stft(y, n_fft, hop_size, win_size, compress_factor=1.0, center=True)
         raise L.HspError("mag_pha_stft: one utterance [1, L], center=True")
     if not y.is_cuda or y.dtype != torch.float32:
         raise L.HspError("the denoiser runs on the GPU in float32 only; there is no CPU fallback")
-    st = _stft_for(y.device, n_fft, hop_size, win_size)
-    y = y.contiguous()
     Ls = y.shape[1]
     if Ls <= n_fft // 2:
         raise L.HspError(f"mag_pha_stft: reflect padding needs more than {n_fft // 2} samples, got {Ls}")
-    T = 1 + Ls // hop_size
-    f_ld = (T + 3) & ~3
-    frames = torch.empty(1, n_fft, f_ld, dtype=torch.float32, device=y.device)
-    L.check(L.lib().hsp_stft_frames_f32(L.fptr(y), L.fptr(st._window), L.fptr(frames), 1, Ls, n_fft, hop_size, T, f_ld,
-                                        L.stream_ptr()), "hsp_stft_frames_f32")
-    spec = st.dft(frames)                                          # [1, 2 F, f_ld]: real | imaginary rows
-    nf = st.n_freqs
-    mag = torch.empty(1, nf, T, dtype=torch.float32, device=y.device)
-    pha = torch.empty(1, nf, T, dtype=torch.float32, device=y.device)
-    L.check(L.lib().hsp_mag_pha_f32(L.fptr(spec), spec.stride(1), L.fptr(mag), L.fptr(pha), nf, T, float(compress_factor),
-                                    L.stream_ptr()), "hsp_mag_pha_f32")
-    return mag, pha, _com(mag, pha)
-
-
-def _com(mag, pha):
-    _, nf, T = mag.shape
-    re = torch.empty(nf, T, dtype=torch.float32, device=mag.device)
-    im = torch.empty(nf, T, dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0, L.fptr(re), T, L.fptr(im), T, nf, T, L.stream_ptr()),
-            "hsp_polar_f32")
-    return torch.stack((re, im), dim=-1).unsqueeze(0)
+    st = _stft_for(y.device, n_fft, hop_size, win_size)
+    mag, pha = _stft_packed(y.contiguous(), [Ls], segments_for([1 + Ls // hop_size], y.device), st, compress_factor)
+    return mag, pha, polar_pair(mag, pha)
 
 
 def mag_pha_istft(mag, pha, n_fft, hop_size, win_size, compress_factor=1.0, center=True, scale=1.0):
@@ -97,19 +76,11 @@ def mag_pha_istft(mag, pha, n_fft, hop_size, win_size, compress_factor=1.0, cent
     if not center or mag.dim() != 3 or mag.shape[0] != 1 or mag.shape != pha.shape:
         raise L.HspError("mag_pha_istft: one utterance [1, F, T], center=True")
     st = _stft_for(mag.device, n_fft, hop_size, win_size)
-    mag, pha = mag.contiguous(), pha.contiguous()
     _, nf, T = mag.shape
     if nf != st.n_freqs or T < 2:
         raise L.HspError(f"mag_pha_istft: expected {st.n_freqs} bins and at least two frames")
-    t_ld = (T + 3) & ~3
-    spec = torch.zeros(1, 2 * nf, t_ld, dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0 / float(compress_factor), L.fptr(spec), t_ld,
-                                  L.fptr(spec[0, nf:]), t_ld, nf, T, L.stream_ptr()), "hsp_polar_f32")
-    frames = st.idft(spec)                                         # [1, n_fft, t_ld]
-    wav = torch.empty(1, hop_size * (T - 1), dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_istft_ola_f32(L.fptr(frames), frames.stride(1), L.fptr(st._window), L.fptr(wav), n_fft, hop_size, T,
-                                      float(scale), L.stream_ptr()), "hsp_istft_ola_f32")
-    return wav
+    inv = None if scale == 1.0 else torch.full((1,), float(scale), dtype=torch.float32, device=mag.device)
+    return _istft_packed(mag, pha, segments_for([T], mag.device), st, compress_factor, inv)[0]
 
 
 @torch.no_grad()
@@ -119,24 +90,17 @@ def denoise(noisy_wav, model, hps):
         raise L.HspError("denoise takes one 1-D waveform, as the reference")
     if not noisy_wav.is_cuda or noisy_wav.dtype != torch.float32:
         raise L.HspError("the denoiser runs on the GPU in float32 only; there is no CPU fallback")
-    x = noisy_wav.contiguous()
-    ss = torch.empty(1, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_sum_sq_f32(L.fptr(x), x.numel(), L.fptr(ss), L.stream_ptr()), "hsp_sum_sq_f32")
-    ssv = float(ss.item())
-    if not ssv > 0.0:
+    x, lens = noisy_wav.contiguous().unsqueeze(0), [noisy_wav.shape[0]]
+    scale, inv = _norm_factors(x, lens, hps, "denoise")
+    if not float(scale[0]) > 0.0:                                   # the one read-back; a silent row has scale 0
         raise L.HspError("denoise(): the prompt is silent (sum of squares 0); the reference's norm factor is inf there "
                          "and its output NaN")
-    norm = math.sqrt(x.numel() / ssv)
-    y = Fh.axpby(x, x, norm, 0.0).unsqueeze(0)
-    amp, pha, _ = mag_pha_stft(y, hps.n_fft, hps.hop_size, hps.win_size, hps.compress_factor)
-    amp_g, pha_g, _ = model(amp, pha)
-    return mag_pha_istft(amp_g, pha_g, hps.n_fft, hps.hop_size, hps.win_size, hps.compress_factor, scale=1.0 / norm)
+    return _denoise_rows(x, lens, scale, inv, model, hps)[0]
 
 
 # ------------------------------------------------------------------ ragged batches
 def _pad_rows(wavs, lengths):
     """A list of 1-D device rows, or padded [B, L_max] + HOST lengths -> (padded fp32 [B, L_max], host lengths)."""
-    from .packed import host_ints
     if isinstance(wavs, torch.Tensor):
         if wavs.dim() != 2 or lengths is None:
             raise L.HspError("denoise_batch takes a list of 1-D waveforms, or padded [B, L_max] with host lengths")
@@ -161,14 +125,6 @@ def _pad_rows(wavs, lengths):
     return x.contiguous(), lens
 
 
-def _unpack(t, seg, T_max):
-    """packed [1, F, T_tot] -> [B, F, T_max], zero past each row's frames (copies, no arithmetic)."""
-    out = torch.zeros(seg.B, t.shape[1], T_max, dtype=torch.float32, device=t.device)
-    for b, sl in enumerate(seg.slices()):
-        out[b, :, :seg.frames[b]].copy_(t[0, :, sl])
-    return out
-
-
 def _stft_packed(y, lens, seg, st, compress_factor, scale=None):
     """y [B, L_max] with host lengths -> packed (mag, pha) [1, F, T_tot] in the layout of ``seg``; ``scale`` (device
     fp32 [B]) multiplies row b inside the framing.  Gap columns come out as magnitude 0, phase 0."""
@@ -176,7 +132,6 @@ def _stft_packed(y, lens, seg, st, compress_factor, scale=None):
     n_fft, hop, nf = st.n_fft, st.hop, st.n_freqs
     if min(lens) <= n_fft // 2:
         raise L.HspError(f"mag_pha_stft_batch: reflect padding needs more than {n_fft // 2} samples per row, got {lens}")
-    from .packed import device_lengths
     dlen = device_lengths(lens, y.device)
     f_ld = (seg.T_tot + 3) & ~3
     frames = torch.empty(1, n_fft, f_ld, dtype=torch.float32, device=y.device)
@@ -214,7 +169,6 @@ def mag_pha_stft_batch(y, lengths, n_fft, hop_size, win_size, compress_factor=1.
     """``mag_pha_stft`` on the rows of y [B, L_max] at their own HOST ``lengths`` (samples), in one packed pass: ->
     (mag [B, F, T_max], pha [B, F, T_max], com [B, F, T_max, 2]), T_b = 1 + lengths[b] // hop frames per row, zeros
     after.  ``scale`` (device fp32 [B]): row b is multiplied by scale[b] first."""
-    from .packed import host_ints, segments_for
     if not center or y.dim() != 2:
         raise L.HspError("mag_pha_stft_batch: padded rows [B, L_max], center=True")
     if not y.is_cuda or y.dtype != torch.float32:
@@ -226,19 +180,13 @@ def mag_pha_stft_batch(y, lengths, n_fft, hop_size, win_size, compress_factor=1.
     seg = segments_for([1 + n // hop_size for n in lens], y.device)
     mag, pha = _stft_packed(y.contiguous(), lens, seg, st, compress_factor, scale)
     T_max = max(seg.frames)
-    mag, pha = _unpack(mag, seg, T_max), _unpack(pha, seg, T_max)
-    B, nf = seg.B, st.n_freqs
-    re = torch.empty(B * nf, T_max, dtype=torch.float32, device=y.device)
-    im = torch.empty(B * nf, T_max, dtype=torch.float32, device=y.device)
-    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0, L.fptr(re), T_max, L.fptr(im), T_max, B * nf, T_max,
-                                  L.stream_ptr()), "hsp_polar_f32")
-    return mag, pha, torch.stack((re, im), dim=-1).reshape(B, nf, T_max, 2)
+    mag, pha = seg.unpack(mag, T_max), seg.unpack(pha, T_max)
+    return mag, pha, polar_pair(mag, pha)
 
 
 def mag_pha_istft_batch(mag, pha, lengths, n_fft, hop_size, win_size, compress_factor=1.0, center=True, scale=None):
     """``mag_pha_istft`` on the rows of mag, pha [B, F, T_max] at their own HOST ``lengths`` (frames, >= 2) -> (wav
     [B, n_max], lengths hop (T_b - 1)); row b is multiplied by scale[b] (device fp32 [B]) and zero past its end."""
-    from .packed import host_ints, segments_for
     if not center or mag.dim() != 3 or mag.shape != pha.shape:
         raise L.HspError("mag_pha_istft_batch: mag / pha [B, F, T_max], center=True")
     frames = host_ints(lengths, "mag_pha_istft_batch lengths")
@@ -246,11 +194,7 @@ def mag_pha_istft_batch(mag, pha, lengths, n_fft, hop_size, win_size, compress_f
     if len(frames) != mag.shape[0] or mag.shape[1] != st.n_freqs or max(frames) > mag.shape[2] or min(frames) < 2:
         raise L.HspError(f"mag_pha_istft_batch: expected {st.n_freqs} bins and 2 .. T_max frames per row, got {frames}")
     seg = segments_for(frames, mag.device)
-    pk = [torch.zeros(1, st.n_freqs, seg.T_tot, dtype=torch.float32, device=mag.device) for _ in range(2)]
-    for dst, src in zip(pk, (mag, pha)):
-        for b, sl in enumerate(seg.slices()):
-            dst[0, :, sl].copy_(src[b, :, :frames[b]])
-    return _istft_packed(pk[0], pk[1], seg, st, compress_factor, scale)
+    return _istft_packed(seg.pack(mag), seg.pack(pha), seg, st, compress_factor, scale)
 
 
 # a packed row of T holds, in floats: the dense buffers 5 x 64 x F (encoder at F = 201, the two decoders at F' = 100),
@@ -276,36 +220,50 @@ def denoise_batch(wavs, model, hps, lengths=None, max_rows: int = 8192, return_s
     ``BYTES_PER_ROW`` = 0.9 MB of activations at its peak -- the dense buffers alone are 5 x 64 x F floats per row.
     When the packed row count would exceed ``max_rows`` (8192: about 50 s of prompts, 7.4 GB) the batch runs as
     consecutive sub-batches of whole prompts."""
-    from .packed import device_lengths, segments_for, split_rows
     x, lens = _pad_rows(wavs, lengths)
-    hop = hps.hop_size
-    st = _stft_for(x.device, hps.n_fft, hop, hps.win_size)
+    scale, inv = _norm_factors(x, lens, hps, "denoise_batch")
+    out, spec = _denoise_rows(x, lens, scale, inv, model, hps, max_rows, return_spectrogram)
+    out_len = [hps.hop_size * (n // hps.hop_size) for n in lens]
+    return (out, out_len, spec) if return_spectrogram else (out, out_len)
+
+
+def _norm_factors(x, lens, hps, who):
+    """x [B, L_max] with host lengths -> the norm factor sqrt(len / sum x^2) of every row and its inverse, device fp32
+    [B] each (0 for a silent row); nothing is read back."""
     if min(lens) <= hps.n_fft // 2:
-        raise L.HspError(f"denoise_batch: reflect padding needs more than {hps.n_fft // 2} samples per row, got {lens}")
+        raise L.HspError(f"{who}: reflect padding needs more than {hps.n_fft // 2} samples per row, got {lens}")
     B, Lm = x.shape
-    frames = [1 + n // hop for n in lens]
-    dlen = device_lengths(lens, x.device)
     scale = torch.empty(B, dtype=torch.float32, device=x.device)
     inv = torch.empty(B, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_norm_factor_rows_f32(L.fptr(x), x.stride(0), L.ptr(dlen), L.fptr(scale), L.fptr(inv), B, Lm,
-                                             L.stream_ptr()), "hsp_norm_factor_rows_f32")
-    out_len = [hop * (n - 1) for n in frames]
-    n_max, T_max = max(out_len), max(frames)
+    L.check(L.lib().hsp_norm_factor_rows_f32(L.fptr(x), x.stride(0), L.ptr(device_lengths(lens, x.device)), L.fptr(scale),
+                                             L.fptr(inv), B, Lm, L.stream_ptr()), "hsp_norm_factor_rows_f32")
+    return scale, inv
+
+
+def _denoise_rows(x, lens, scale, inv, model, hps, max_rows: int = 8192, want_spec: bool = False):
+    """The packed pass on x [B, L_max]: STFT of ``scale[b]`` times row b, the network, inverse STFT times ``inv[b]``, in
+    sub-batches of at most ``max_rows`` packed rows -> (out [B, n_max], the (mag, pha) [B, F, T_max] the network was
+    given if ``want_spec``, else None)."""
+    hop = hps.hop_size
+    st = _stft_for(x.device, hps.n_fft, hop, hps.win_size)
+    B = x.shape[0]
+    frames = [1 + n // hop for n in lens]
+    n_max, T_max = hop * (max(frames) - 1), max(frames)
     groups = split_rows(frames, max_rows)
     out = torch.zeros(B, n_max, dtype=torch.float32, device=x.device) if len(groups) > 1 else None
-    spec = [torch.zeros(B, st.n_freqs, T_max, dtype=torch.float32, device=x.device) for _ in range(2)] \
-        if return_spectrogram else None
+    spec = tuple(torch.zeros(B, st.n_freqs, T_max, dtype=torch.float32, device=x.device) for _ in range(2)) \
+        if want_spec else None
     for rows in groups:
         b0, b1 = rows[0], rows[-1] + 1
         seg = segments_for(frames[b0:b1], x.device)
         amp, pha = _stft_packed(x[b0:b1], lens[b0:b1], seg, st, hps.compress_factor, scale[b0:b1])
         if spec is not None:
             for dst, src in zip(spec, (amp, pha)):
-                dst[b0:b1, :, :max(seg.frames)].copy_(_unpack(src, seg, max(seg.frames)))
+                dst[b0:b1, :, :max(seg.frames)].copy_(seg.unpack(src, max(seg.frames)))
         amp_g, pha_g, _ = model.forward_packed(amp, pha, seg)
         wav, _ = _istft_packed(amp_g, pha_g, seg, st, hps.compress_factor, inv[b0:b1])
         if out is None:
             out = wav
         else:
             out[b0:b1, :wav.shape[1]].copy_(wav)
-    return (out, out_len, tuple(spec)) if return_spectrogram else (out, out_len)
+    return out, spec

@@ -1,4 +1,4 @@
-"""The packed ragged layout of the batched prompt denoiser.
+"""The packed ragged layout of the prompt denoiser; one prompt is the layout with one row and no gap.
 
 Row b of a batch has ``T_b`` STFT frames; the B rows lie end to end along T in one ``[1, C, T_tot, F]`` tensor with
 ``GAP`` zero rows between neighbours.  A ``Segments`` object is the segment table ``(first row, T_b)`` of that layout,
@@ -67,6 +67,25 @@ class Segments:
     def slices(self):
         return [slice(s, s + n) for s, n in zip(self.first, self.frames)]
 
+    @property
+    def has_gaps(self):
+        """Whether the layout holds rows outside every segment (never for one segment): only then is there a row to zero."""
+        return self.T_tot != sum(self.frames)
+
+    def pack(self, x):
+        """x [B, F, >= max(frames)] -> packed [1, F, T_tot], zeros on the gap columns (copies, no arithmetic)."""
+        out = torch.zeros(1, x.shape[1], self.T_tot, dtype=torch.float32, device=x.device)
+        for b, sl in enumerate(self.slices()):
+            out[0, :, sl].copy_(x[b, :, :self.frames[b]])
+        return out
+
+    def unpack(self, t, T_max):
+        """packed [1, F, T_tot] -> [B, F, T_max], zero past each row's frames (copies, no arithmetic)."""
+        out = torch.zeros(self.B, t.shape[1], T_max, dtype=torch.float32, device=t.device)
+        for b, sl in enumerate(self.slices()):
+            out[b, :, :self.frames[b]].copy_(t[0, :, sl])
+        return out
+
 
 _CACHE = {}
 
@@ -89,6 +108,13 @@ def segments_for(frames, device, gap: int = GAP) -> Segments:
     """``Segments`` cached by (frames, gap, device)."""
     frames = host_ints(frames, "frames per row")
     return _cached(("seg", tuple(frames), gap, device.type, device.index), lambda: Segments(frames, device, gap))
+
+
+def one_segment(seg, n, device) -> Segments:
+    """``seg``, or for None the table of one utterance that fills the whole axis of ``n`` rows."""
+    seg = segments_for([n], device) if seg is None else seg
+    assert seg.T_tot == n
+    return seg
 
 
 def device_lengths(lens, device):

@@ -1,9 +1,11 @@
-"""denoiser/utils.py: padding helpers and the learnable sigmoid (parameters only; the arithmetic is in libhsp)."""
+"""denoiser/utils.py: padding helpers, the learnable sigmoid (parameters only; the arithmetic is in libhsp) and the
+polar re-composition of a (magnitude, phase) pair."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
+from .. import _lib as L
 from ..hip_layers import HipLayer
 
 
@@ -33,7 +35,6 @@ class Vec(HipLayer):
     def dev(self, n):
         v = self.__dict__.get("_" + n)
         if v is None:
-            from .. import _lib as L
             raise L.HspError(f"{type(self).__name__} used before finalize()")
         return v
 
@@ -47,3 +48,15 @@ class LearnableSigmoid_2d(Vec):
         super().__init__()
         self.beta = beta
         self.slope = nn.Parameter(torch.ones(in_features, 1), requires_grad=False)
+
+
+def polar_pair(mag, pha):
+    """Contiguous mag, pha [B, F, T] -> stack((mag cos(pha), mag sin(pha)), -1) [B, F, T, 2]: ``denoised_com`` of
+    generator.py:142-143 and ``com`` of infer.py:23."""
+    B, F_, T = mag.shape
+    assert mag.is_contiguous() and pha.is_contiguous()
+    re = torch.empty(B * F_, T, dtype=torch.float32, device=mag.device)
+    im = torch.empty(B * F_, T, dtype=torch.float32, device=mag.device)
+    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0, L.fptr(re), T, L.fptr(im), T, B * F_, T, L.stream_ptr()),
+            "hsp_polar_f32")
+    return torch.stack((re, im), dim=-1).reshape(B, F_, T, 2)       # a copy, no arithmetic

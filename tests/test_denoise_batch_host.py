@@ -169,7 +169,9 @@ def test_packed_abi_rejects_bad_counts_and_null_pointers():
 def test_header_declares_the_packed_entry_points():
     from megatts2_hierspeechpp_amd import _lib
     text = open(os.path.join(ROOT, "include", "hsp.h")).read()
-    assert "#define HSP_VERSION 103" in text          # the ABI only grows
+    assert "#define HSP_VERSION 104" in text          # 104: the four one-prompt twins of the _seg entry points left
+    for gone in ("hsp_sum_sq_f32", "hsp_instnorm_prelu_f32", "hsp_dwconv_bn_silu_f32", "hsp_istft_ola_f32"):
+        assert not re.search(r"\bint\s+%s\s*\(" % gone, text) and gone not in _lib.SIGNATURES, gone
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, text), name
         assert name in _lib.SIGNATURES, name

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the batched prompt denoiser.  The packed-layout kernels through the C ABI against
-float64 numpy or their solo twins, the packed network against the network on each row alone, ``denoise_batch`` against
+float64 numpy or the same launch on a row alone, the packed network against the network on each row alone, ``denoise_batch`` against
 the oracle, the silent row, the capture with no read-back, and the wiring into prompt_mels / vc_batch."""
 import ctypes as C
 
@@ -170,6 +170,9 @@ def test_packed_framing_bit_equal_to_solo_rows(device):
 
 
 def test_segmented_overlap_add_bit_equal_to_solo_rows(device):
+    """A row of the batch equals the same launch on that row's frames alone (a one-segment table), bit for bit; and
+    every row equals a float64 overlap-add of the same fp32 frames and window: at most four window-weighted terms per
+    sum, one divide and one multiply, so 16 roundings of 2^-24 on sum_t |frames w| / den |inv| bound the error."""
     from megatts2_hierspeechpp_amd import _lib as L
     from megatts2_hierspeechpp_amd.denoiser.packed import Segments
     n_fft, hop = 400, 100
@@ -180,29 +183,60 @@ def test_segmented_overlap_add_bit_equal_to_solo_rows(device):
     win = torch.hann_window(n_fft, periodic=True, dtype=torch.float32).to(device)
     n_max, pitch = hop * 80, hop * 80 + 5
     buf, out = _guarded(4 * pitch, device)
+
+    def alone(b, inv):
+        """The launch on row b's frames alone: one segment (0, T), frames [n_fft, T], output [hop (T - 1)]."""
+        T = seg.frames[b]
+        n = hop * (T - 1)
+        own = frames[:, seg.slices()[b]].contiguous()
+        one = Segments([T], device)
+        solo = torch.empty(n, dtype=torch.float32, device=device)
+        L.check(L.lib().hsp_istft_ola_seg_f32(own.data_ptr(), T, win.data_ptr(), None if inv is None else inv.data_ptr(),
+                                              solo.data_ptr(), n, n, n_fft, hop, *one.args(), T, L.stream_ptr()),
+                "hsp_istft_ola_seg_f32")
+        return solo
+
+    fr64, w64 = frames.cpu().numpy().astype(np.float64), win.cpu().numpy().astype(np.float64)
+
+    def against_float64(got, inv):
+        for b, sl in enumerate(seg.slices()):
+            T = seg.frames[b]
+            n = hop * (T - 1)
+            num, mass, den = np.zeros(n), np.zeros(n), np.zeros(n)
+            k = np.arange(n_fft)
+            for t in range(T):
+                at = k + t * hop - n_fft // 2          # frame t, tap k lands on sample k + t hop - n_fft / 2
+                ok = (at >= 0) & (at < n)
+                term = fr64[k[ok], sl.start + t] * w64[k[ok]]
+                num[at[ok]] += term
+                mass[at[ok]] += np.abs(term)
+                den[at[ok]] += w64[k[ok]] ** 2
+            want = num / den * inv[b]
+            tol = 16 * 2.0 ** -24 * mass / den * abs(inv[b])
+            err = np.abs(got[b, :n].cpu().numpy().astype(np.float64) - want)
+            worst = float((err / np.maximum(tol, 1e-300)).max()) if n else 0.0
+            print(f"overlap-add row {b} (T = {T}, inv {inv[b]}): worst err / tol {worst:.3f}")
+            assert (err <= tol).all(), (b, worst)
+
     L.check(L.lib().hsp_istft_ola_seg_f32(frames.data_ptr(), f_ld, win.data_ptr(), None, out.data_ptr(), pitch, n_max, n_fft,
                                           hop, *seg.args(), seg.T_tot, L.stream_ptr()), "hsp_istft_ola_seg_f32")
     got = out.reshape(4, pitch)
     assert _canaries_intact(buf) and bool((got[:, n_max:] == CANARY).all())
-    for b, sl in enumerate(seg.slices()):
+    for b in range(4):
         T = seg.frames[b]
         n = hop * (T - 1)
         if T >= 2:
-            own = frames[:, sl].contiguous()
-            solo = torch.empty(n, dtype=torch.float32, device=device)
-            L.check(L.lib().hsp_istft_ola_f32(own.data_ptr(), T, win.data_ptr(), solo.data_ptr(), n_fft, hop, T, 1.0,
-                                              L.stream_ptr()), "hsp_istft_ola_f32")
-            assert torch.equal(got[b, :n], solo), b
+            assert torch.equal(got[b, :n], alone(b, None)), b
         assert not got[b, n:n_max].any(), b
-    # with inverse scales: the solo call at that scale
-    inv = torch.tensor([2.0, 1.0, 0.0, 0.37], dtype=torch.float32).to(device)
+    against_float64(got, [1.0, 1.0, 1.0, 1.0])
+    # with inverse scales: the row alone at that scale
+    scales = [2.0, 1.0, 0.0, 0.37]
+    inv = torch.tensor(scales, dtype=torch.float32).to(device)
     L.check(L.lib().hsp_istft_ola_seg_f32(frames.data_ptr(), f_ld, win.data_ptr(), inv.data_ptr(), out.data_ptr(), pitch,
                                           n_max, n_fft, hop, *seg.args(), seg.T_tot, L.stream_ptr()), "hsp_istft_ola_seg_f32")
-    own = frames[:, seg.slices()[3]].contiguous()
-    solo = torch.empty(hop * 80, dtype=torch.float32, device=device)
-    L.check(L.lib().hsp_istft_ola_f32(own.data_ptr(), 81, win.data_ptr(), solo.data_ptr(), n_fft, hop, 81, 0.37,
-                                      L.stream_ptr()), "hsp_istft_ola_f32")
-    assert torch.equal(got[3, :n_max], solo) and not got[2, :n_max].any()
+    assert torch.equal(got[3, :n_max], alone(3, inv[3:4])) and not got[2, :n_max].any()
+    assert torch.equal(got[0, :hop * 3], alone(0, inv[0:1]))
+    against_float64(got, [float(v) for v in inv.cpu()])
 
 
 def test_norm_factor_rows_against_numpy(device):
@@ -306,6 +340,25 @@ def test_mpnet_refuses_device_lengths(device, net):
         net(z, z)                                      # without lengths: one utterance, as before
     with pytest.raises(L.HspError):
         net(z, z, [10, 11])
+
+
+def test_one_prompt_is_the_one_segment_batch(device, net):
+    """``denoise`` / ``net(mag, pha)`` are the packed pass on a table of one row: bit-equal to the batch of one, at 4
+    frames (below every T dilation of the dense blocks), 10 (across dilation 8) and 81 (a golden row)."""
+    from megatts2_hierspeechpp_amd import _lib as L
+    from megatts2_hierspeechpp_amd.denoiser.infer import denoise, denoise_batch, mag_pha_stft
+    for n in (300, 900, 8000):
+        w = torch.from_numpy(DI.row(n)).to(device)
+        T = 1 + n // 100
+        one = denoise(w, net, H.DENOISER_H)
+        many, n_out = denoise_batch([w], net, H.DENOISER_H)
+        assert one.shape == (1, 100 * (T - 1)) and n_out == [100 * (T - 1)]
+        assert torch.equal(one[0], many[0, :n_out[0]]), n
+        mag, pha, _ = mag_pha_stft(w.unsqueeze(0), 400, 100, 400, 0.3)
+        for a_, b_ in zip(net(mag, pha), net(mag, pha, [T])):
+            assert a_.shape == b_.shape and torch.equal(a_, b_), n
+    with pytest.raises(L.HspError):
+        denoise(torch.zeros(900, device=device), net, H.DENOISER_H)
 
 
 # ------------------------------------------------------------------------------------------ end to end

@@ -171,8 +171,8 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(hsp_[a-z0-9_]+)\s*\(", hdr)))
 
 
-def test_abi_103_library_loads_and_exports_every_declared_symbol():
-    """libhsp.so loads, resolves every function include/hsp.h declares, and reports ABI version 103 for gfx950."""
+def test_abi_104_library_loads_and_exports_every_declared_symbol():
+    """libhsp.so loads, resolves every function include/hsp.h declares, and reports ABI version 104 for gfx950."""
     from megatts2_hierspeechpp_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__ as g
@@ -183,7 +183,7 @@ def test_abi_103_library_loads_and_exports_every_declared_symbol():
     assert set(declared) == set(_lib.SIGNATURES), set(declared) ^ set(_lib.SIGNATURES)
     for sym in declared:
         assert getattr(lib, sym) is not None
-    assert lib.hsp_version() == 103 and lib.hsp_arch() == b"gfx950"
+    assert lib.hsp_version() == 104 and lib.hsp_arch() == b"gfx950"
 
 
 def test_dynamic_symbol_table_is_exactly_the_header():
