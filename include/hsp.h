@@ -561,6 +561,40 @@ int hsp_zero_below_f32(const float* x, float thr, float* y, int64_t n, void* str
 int hsp_peak_int16(const float* x, int64_t x_bs, const int64_t* lengths, float gain, int16_t* out, int64_t o_bs,
                    int32_t B, int64_t n, void* stream);
 
+/* ------------------------------------------------ loudness-normalised output (additive: HSP_VERSION unchanged;
+ * csrc/hsp_loudness.hip).  Neither harness of the reference has a loudness rule: scale_norm="lufs" of
+ * inference_plm / inference_vc / inference_speechsr replaces the gain of the int16 conversion above by one that
+ * brings every row to a target loudness.  Nothing here reads back: meter -> gains -> hsp_peak_int16_gains is three
+ * calls on one stream and can be captured in a hipGraph.
+ *
+ * The meter: ITU-R BS.1770-4 integrated loudness of B mono rows.  K-weighting = the standard's high shelf and
+ * high-pass biquads, designed on the host in double from the sample rate (at 48 kHz the standard's own table);
+ * 400 ms blocks every 100 ms that lie wholly inside the row; absolute gate at -70 LUFS, relative gate 10 LU below the
+ * loudness of the absolute-gated blocks; lufs[b] = -0.691 + 10 log10(mean power of the gated blocks).  A row shorter
+ * than 400 ms has no block: its loudness is that of its whole length taken as one block, ungated.  A row with no
+ * block above -70 LUFS (and an empty row) reports -inf.  peak[b] = max |x[b, i]| over the row, as
+ * hsp_abs_max_rows_f32 gives it.  Row b covers x[b * x_bs + i], i < lengths[b] (device int64 [B], clamped into [0, n];
+ * NULL = all n): samples at and after the length are never read, and row b of a batch is bit-identical to the call
+ * on row b alone.  The filter recurrence and every sum run in fp64 in a fixed order; lufs and peak are fp32 [B].
+ * sample_rate: a multiple of 8000 from 8000 to 48000.  `workspace`: 8-B aligned device memory of at least the byte
+ * count the size query returns for (B, n), contents irrelevant; it must stay alive until the call has run.
+ * HSP_EINVAL: a null pointer (lengths excepted), B < 1 or > 65535, n < 1, x_bs < n, an unsupported rate, a workspace
+ * that is too small or misaligned.
+ * The size query returns the byte count, or HSP_EINVAL for B / n outside the ranges above.
+ * The coefficient query writes the 10 doubles (b0, b1, b2, a1, a2; a0 = 1) of the shelf, then of the high-pass, as the
+ * meter uses them at that rate, into host memory (HSP_EINVAL: NULL or an unsupported rate). */
+int64_t hsp_loudness_workspace_bytes(int32_t B, int64_t n);
+int hsp_loudness_coefs_f64(int32_t sample_rate, double* coefs);
+int hsp_loudness_f32(const float* x, int64_t x_bs, const int64_t* lengths, int32_t B, int64_t n, int32_t sample_rate,
+                     void* workspace, int64_t workspace_bytes, float* lufs, float* peak, void* stream);
+/* gains[b] = min(10^((target_lufs - lufs[b]) / 20) * peak[b], ceiling): the peak fraction hsp_peak_int16_gains takes as
+ * row b's gain, so that the int16 row comes out at target_lufs; limited[b] (int32) = 1 where the ceiling was taken,
+ * else 0.  A row whose loudness is not finite (-inf: silence) takes the ceiling -- the 'max' rule -- with limited = 1;
+ * its int16 row is zeros either way.  Formed in double, rounded once.  HSP_EINVAL: a null pointer, B < 1, a target
+ * that is not finite, a ceiling that is not finite and positive. */
+int hsp_loudness_gains_f32(const float* lufs, const float* peak, float target_lufs, float ceiling, float* gains,
+                           int32_t* limited, int32_t B, void* stream);
+
 /* ------------------------------------------------ prompt ingest: sinc resampling to 16 kHz
  * torchaudio.functional.resample (0.13.1: _get_sinc_resample_kernel + _apply_sinc_resample_kernel) of the reference
  * harnesses (inference_plm.py:124-126, inference.py:122-124, inference_vc.py:76-78,101-103, inference_speechsr.py:32-34):

@@ -195,6 +195,10 @@ SIGNATURES = {
     "hsp_add_cbias_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_zero_below_f32": (C.c_int, [_fp, C.c_float, _fp, C.c_int64, _fp]),
     "hsp_peak_int16": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
+    "hsp_loudness_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "hsp_loudness_coefs_f64": (C.c_int, [C.c_int32, _fp]),
+    "hsp_loudness_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp]),
+    "hsp_loudness_gains_f32": (C.c_int, [_fp, _fp, C.c_float, C.c_float, _fp, _fp, C.c_int32, _fp]),
     "hsp_resample_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, _fp, C.c_int64, C.c_int32, _fp]),
     "hsp_copy_strided_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32,

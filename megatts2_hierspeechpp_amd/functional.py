@@ -336,6 +336,51 @@ def peak_int16_gains(audio, lengths, gains):
     return out
 
 
+# ---------------------------------------------------------------- loudness (ITU-R BS.1770-4; scale_norm="lufs")
+def loudness(audio, sample_rate: int, lengths=None):
+    """Integrated loudness and peak of every row: [B, 1, n] / [B, n] fp32 (unit stride in time, any row stride) at
+    ``sample_rate`` (a multiple of 8000 up to 48000), ``lengths`` int64 [B] valid samples (None = all n) ->
+    (lufs fp32 [B], peak fp32 [B]) on the device, no host read-back.  A row under 400 ms is metered whole and ungated;
+    a row with nothing above -70 LUFS reads -inf.  Row b equals the call on row b alone bit for bit."""
+    a = audio.reshape(audio.shape[0], -1) if audio.dim() == 3 else audio
+    assert a.dim() == 2 and a.stride(1) == 1
+    B, n = a.shape
+    lib = L.lib()
+    nbytes = lib.hsp_loudness_workspace_bytes(B, n)
+    if nbytes < 0:
+        raise L.HspError(f"hsp_loudness_workspace_bytes: no workspace for a batch of {B} rows x {n} samples")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
+    lufs = torch.empty(B, dtype=torch.float32, device=a.device)
+    peak = torch.empty(B, dtype=torch.float32, device=a.device)
+    L.check(lib.hsp_loudness_f32(L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None, B, n,
+                                 int(sample_rate), L.ptr(ws), ws.numel() * 8, L.fptr(lufs), L.fptr(peak), L.stream_ptr()),
+            "hsp_loudness_f32")
+    return lufs, peak
+
+
+def loudness_gains(lufs, peak, target_lufs: float = -23.0, ceiling: float = 0.999):
+    """The per-row gain of `peak_int16_gains` that brings a row metered by `loudness` to ``target_lufs``:
+    min(10^((target - lufs) / 20) * peak, ceiling) -> (gains fp32 [B], limited int32 [B]: 1 where the ceiling was
+    taken; a silent row, lufs = -inf, takes it too)."""
+    assert lufs.dim() == 1 and peak.shape == lufs.shape
+    B = lufs.shape[0]
+    gains = torch.empty(B, dtype=torch.float32, device=lufs.device)
+    limited = torch.empty(B, dtype=torch.int32, device=lufs.device)
+    L.check(L.lib().hsp_loudness_gains_f32(L.fptr(_c(lufs)), L.fptr(_c(peak)), float(target_lufs), float(ceiling),
+                                           L.fptr(gains), L.ptr(limited), B, L.stream_ptr()), "hsp_loudness_gains_f32")
+    return gains, limited
+
+
+def lufs_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.0, ceiling: float = 0.999):
+    """The int16 stage of scale_norm="lufs": meter -> gains -> `peak_int16_gains`, three launches-only steps on the
+    current stream.  [B, 1, n] / [B, n] fp32 -> int16 [B, n], row b at ``target_lufs`` over its lengths[b] samples unless
+    its peak would pass ``ceiling`` of full scale."""
+    a = audio.reshape(audio.shape[0], -1)
+    lufs, peak = loudness(a, sample_rate, lengths)
+    gains, _ = loudness_gains(lufs, peak, target_lufs, ceiling)
+    return peak_int16_gains(a, lengths, gains)
+
+
 # ---------------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
 KAISER_BETA = 14.769656459379492   # torchaudio's beta for resampling_method="kaiser_window", beta=None
 

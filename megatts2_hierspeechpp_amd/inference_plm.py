@@ -24,6 +24,8 @@ from .ttv_v1.t2w2v_transformer import SynthesizerTrn as Text2W2V
 
 # text/symbols_lmdh.py: len(symbols), len(tone_symbols), len(language_symbols)
 N_VOCAB, N_TONE, N_LANGUAGE = 126, 11, 4
+# the rules of the int16 stage: the reference's two peak rules (inference_plm.py:185-188) and the loudness target
+SCALE_NORMS = ("max", "prompt", "lufs")
 
 
 class TtsModels(nn.Module):
@@ -108,9 +110,13 @@ def write_wav(path, sample_rate: int, pcm):
 @torch.no_grad()
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
-        return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None):
+        return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
+        target_lufs: float = -23.0):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
     make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
+    ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
+    peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
+    length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
 
     text / tone / language int64 [B, N], text_length [B]; src_mel_ttv [B, 80, Tm'] (prompt mel for the
     front-end) with lengths; src_mel [2B, 80, Tm] = the B prompt mels followed by the B denoised prompt
@@ -119,6 +125,8 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     their own length (times ``gain``: 0.999, or the prompt's peak for scale_norm='prompt').  B > 1 runs the utterances side by side; rows are independent up to the
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
+    if scale_norm not in SCALE_NORMS:
+        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
@@ -142,7 +150,10 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         audio = models.sr(audio)
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
-    wav = peak_int16(audio, n_valid, gain)
+    if scale_norm == "lufs":
+        wav = Fh.lufs_int16(audio, n_valid, output_sr if output_sr in (24000, 48000) else 16000, target_lufs)
+    else:
+        wav = peak_int16(audio, n_valid, gain)
     return (wav, audio) if return_float else wav
 
 
@@ -157,12 +168,13 @@ def prompt_peak(audio) -> float:
 def output_gain(scale_norm: str, prompt_audio) -> float:
     """The gain of the int16 conversion (inference_plm.py:185-188): 0.999 for 'max', the prompt's peak for 'prompt'.
     A prompt whose peak is above 1 (full scale) is outside the contract: the reference's astype('int16') wraps such
-    samples around, hsp_peak_int16 saturates them."""
-    if scale_norm == "max":
+    samples around, hsp_peak_int16 saturates them.  'lufs' has no fixed gain (it is metered per row on the device,
+    ``functional.lufs_int16``); 0.999, its ceiling, is returned."""
+    if scale_norm in ("max", "lufs"):
         return 0.999
     if scale_norm == "prompt":
         return prompt_peak(prompt_audio)
-    raise L.HspError(f"unknown scale_norm {scale_norm!r} ('max' or 'prompt')")
+    raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
 
 
 @torch.no_grad()
@@ -170,12 +182,13 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     noise_scale_vc: float = 0.333, output_sr: int = 16000, dur=None, noise=None,
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
-                    takes: int = 1):
+                    takes: int = 1, target_lufs: float = -23.0):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
     f0 -> waveform (`tts`), int16 with the gain of ``scale_norm`` (:185-188, `output_gain`: 'prompt' reads the prompt's
-    peak back to the host), optional 16-bit WAV (:195-200).
+    peak back to the host; 'lufs': every row -- each take on its own -- at ``target_lufs``, see `tts`), optional 16-bit
+    WAV (:195-200).
     text / tone / language int64 [1, N] on the GPU; prompt_audio fp32 [1, n] at ``prompt_sr`` on the GPU;
     ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed.  Returns int16 [n_out] (and the float audio with
     ``return_float``).
@@ -211,7 +224,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     wav, audio = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
                      noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
                      noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
-                     seeds=int(seed) if plm_sampling is not None else None)
+                     seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
+                     target_lufs=target_lufs)
     rate = output_sr if output_sr in (24000, 48000) else 16000
     if B == 1:
         wav = wav[0]

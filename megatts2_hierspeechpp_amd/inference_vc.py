@@ -22,7 +22,7 @@ from torch import nn
 from . import _lib as L
 from . import functional as Fh
 from . import hip_layers
-from .inference_plm import output_gain, peak_int16
+from .inference_plm import SCALE_NORMS, output_gain, peak_int16
 
 SOURCE_HOP = 1280   # pad_source's multiple (inference_vc.py:74-75)
 W2V_PAD = 40        # reflect pad before wav2vec2 (:85)
@@ -72,13 +72,14 @@ def load_source(path, device):
 
 @torch.no_grad()
 def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noise_scale_vc=0.333, denoise_ratio=0.0,
-       denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000):
+       denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000, target_lufs=-23.0):
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``output_sr`` 24000 / 48000: SpeechSR (``models.sr``) runs after the vocoder (:147-151) -> [480 T] / [960 T].
     ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which is
     what the reference does at denoise_ratio == 0.  ``scale_norm`` 'prompt': the int16 gain is the peak of
-    ``target_audio`` (inference_vc.py:104-105; read back to the host, see inference_plm.output_gain) instead of 0.999."""
+    ``target_audio`` (inference_vc.py:104-105; read back to the host, see inference_plm.output_gain) instead of 0.999;
+    'lufs': the output is brought to ``target_lufs`` (BS.1770-4 at the output rate, ``functional.lufs_int16``)."""
     gain = output_gain(scale_norm, target_audio)
     x_w2v = models.w2v(Fh.reflect_pad(source_audio, 40))                       # :85-86
     T = x_w2v.shape[2]
@@ -94,7 +95,10 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
                                                       noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio, noise=noise)
     if output_sr in (24000, 48000):
         audio = _sr_model(models)(audio)                                       # :147-151
-    wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device), gain)
+    if scale_norm == "lufs":
+        wav = Fh.lufs_int16(audio.reshape(1, -1), None, output_rate(output_sr), target_lufs)
+    else:
+        wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device), gain)
     return (wav.reshape(-1), audio) if return_float else wav.reshape(-1)
 
 
@@ -275,7 +279,7 @@ def denoise_prompts(prompts, denoiser, hps):
 @torch.no_grad()
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
              denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
-             row_exact=False, denoiser=None, hps_denoiser=None):
+             row_exact=False, denoiser=None, hps_denoiser=None, target_lufs=-23.0):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -289,7 +293,9 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     denoiser / hps_denoiser  a finalized denoiser.generator.MPNet and its config: with ``denoise_ratio != 0`` and no
              ``denoised``, every distinct prompt is denoised here in one packed pass (``denoise_prompts``).  Giving
              both ``denoised`` and ``denoiser``, or ``denoise_ratio != 0`` with neither, is an error;
-    noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn.
+    noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn;
+    scale_norm  'max' / 'prompt' as in ``vc``; 'lufs': every row is brought to ``target_lufs`` over its own length
+             (``functional.loudness`` -> ``loudness_gains``: still no host read-back).
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
     (320 T_b at 16 kHz, x1.5 / x3 with SpeechSR), zeros after; with ``return_float`` also the float audio
@@ -339,8 +345,8 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
         if Ls % SOURCE_HOP or fs.shape[1] < Ls // F0_HOP:
             raise L.HspError(f"vc_batch: padded sources [B, {Ls}] need Ls % {SOURCE_HOP} == 0 and tracks of >= "
                              f"{Ls // F0_HOP} columns, got {fs.shape[1]}")
-    if scale_norm not in ("max", "prompt"):
-        raise L.HspError(f"unknown scale_norm {scale_norm!r} ('max' or 'prompt')")
+    if scale_norm not in SCALE_NORMS:
+        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
     if output_sr in (24000, 48000):
         _sr_model(models)
 
@@ -391,9 +397,11 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
             audio = models.sr(audio)                                           # :147-151
     _stage("int16")
     n_valid = output_length(frames, output_sr)
-    # int16 with each row's gain (:157-160): 0.999, or the peak of the row's own prompt
+    # int16 with each row's gain (:157-160): 0.999, the peak of the row's own prompt, or the one that meets target_lufs
     if scale_norm == "max":
         gains = torch.full((B,), 0.999, dtype=torch.float32, device=dev)
+    elif scale_norm == "lufs":
+        gains, _ = Fh.loudness_gains(*Fh.loudness(audio, output_rate(output_sr), n_valid), target_lufs)
     else:
         peaks = Fh.abs_max_rows(pm[0::2].contiguous(), pm_len[0::2].contiguous())
         gains = peaks.expand(B).contiguous() if P == 1 else torch.cat([peaks[index[b]:index[b] + 1] for b in range(B)])
