@@ -416,7 +416,10 @@ typedef struct hsp_mha_proj_args {
 } hsp_mha_proj_args;
 int hsp_mha_proj_f32(const hsp_mha_proj_args* a, void* stream);
 int hsp_mha_proj_supported(int32_t H, int32_t D, int32_t M, int32_t Tk);
-/* out[b, c] = sum_t x[b, c, t] / sum_t mask[b, t] : styleencoder.py:83-91 */
+/* out[b, c] = sum_t x[b, c, t] / sum_t mask[b, t] : styleencoder.py:83-91.  The numerator runs over ALL T frames, the
+ * padded ones included, as the reference's temporal_avg_pool does (a caller that wants the padding left out masks x
+ * first; a 0/1 mask is not applied to x here).  A row whose mask sums to
+ * 0 gets the IEEE quotient the reference's torch.div gives (+-inf, or NaN for 0 / 0); the other rows are unaffected. */
 int hsp_masked_mean_f32(const float* x, const float* mask, float* out, int32_t B, int32_t C,
                         int32_t T, void* stream);
 /* y[b, c, t] = x[b, c, t] * mask[b, t] : the `x * x_mask` steps (modules.py:407) */
@@ -426,7 +429,8 @@ int hsp_mask_mul_f32(const float* x, const float* mask, float* y, int32_t B, int
 int hsp_linear_interp_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout, void* stream);
 /* The same on a ragged batch (SpeechSR in row-exact mode): row b has lin[b] valid inputs and lout[b] valid outputs
  * (device int64 [B]); output t < lout[b] is the call on the row alone when Lin / Lout is that call's ratio (its upper
- * neighbour clamps at lin[b] - 1), outputs t >= lout[b] are 0. */
+ * neighbour clamps at lin[b] - 1), outputs t >= lout[b] are 0.  lin[b] is clamped into [1, Lin] and lout[b] into
+ * [0, Lout] before use, so no length reads or writes outside the two buffers. */
 int hsp_linear_interp_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout,
                                  const int64_t* lin, const int64_t* lout, void* stream);
 /* y = a*x + b*z elementwise (style interpolation, hierspeechpp_speechsynthesizer.py:682) */

@@ -374,6 +374,9 @@ def entry(fn):
 
 
 def _gather(src: torch.Tensor, idx_map: np.ndarray, dst: torch.Tensor):
+    # the kernel walks dst.numel() consecutive floats and one int32 map entry for each of them
+    assert dst.is_contiguous() and src.is_contiguous(), "hsp_gather_f32 reads and writes flat buffers"
+    assert idx_map.dtype == np.int32 and idx_map.size == dst.numel() and idx_map.flags["C_CONTIGUOUS"]
     mp = torch.from_numpy(idx_map).to(src.device)
     L.check(L.lib().hsp_gather_f32(L.fptr(src), L.ptr(mp), L.fptr(dst), dst.numel(), L.stream_ptr()), "hsp_gather_f32")
     # `mp` must outlive the asynchronous gather on the current stream
@@ -383,9 +386,13 @@ def _gather(src: torch.Tensor, idx_map: np.ndarray, dst: torch.Tensor):
 def _fold(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     rows = v.shape[0]
     cols = v.numel() // rows
-    w = torch.empty_like(v)
-    L.check(L.lib().hsp_fold_weight_norm_f32(L.fptr(v.contiguous()), L.fptr(g.contiguous()), L.fptr(w), rows, cols,
-                                             L.stream_ptr()), "hsp_fold_weight_norm_f32")
+    # contiguous whatever v's strides are: the kernel writes rows of `cols` consecutive floats (empty_like would keep
+    # the strides of a permuted v and the rows would land in the wrong places)
+    w = torch.empty(v.shape, dtype=v.dtype, device=v.device)
+    vc, gc = v.contiguous(), g.contiguous()          # named: a copy made here must live until the launch is issued
+    assert gc.numel() == rows
+    L.check(L.lib().hsp_fold_weight_norm_f32(L.fptr(vc), L.fptr(gc), L.fptr(w), rows, cols, L.stream_ptr()),
+            "hsp_fold_weight_norm_f32")
     return w
 
 
