@@ -118,7 +118,9 @@ enum { HSP_MASK_NONE = 0, HSP_MASK_PRE = 1, HSP_MASK_POST = 2, HSP_MASK_BOTH = 3
  *           v *= mask[...]                   if mask_mode & POST
  *           v += y[...]                      if accumulate
  *           y[b*y_bs + co*y_cs + t] = v * post_scale
- *           (SHUFFLE: co = m / up, t -> up*t + m % up - shuf_pad, bounds-checked to Lout)
+ *           (SHUFFLE: co = m / up, t -> up*t + m % up - shuf_pad, bounds-checked to Lout; bias, cbias and cscale
+ *            are indexed by co.  M = Cout * up rounded up to a multiple of 4: rows m >= Cout * up are padding and
+ *            write nothing.  GATE modes: Cout == gate_half and M == 2 * gate_half, anything else is refused.)
  */
 typedef struct hsp_conv1d_args {
   /* input */

@@ -35,7 +35,9 @@ int validate(const hsp_conv1d_args& a) {
     if (a.gate_half <= 0 || (a.gate_half & 31) || a.M != 2 * a.gate_half || a.Cout != a.gate_half) return HSP_EINVAL;
     if (a.prologue == HSP_PRO_ACT1D) return HSP_EINVAL;
   } else if (a.rows == HSP_ROWS_SHUFFLE) {
-    if (a.up <= 0 || a.up > 16 || a.M != a.Cout * a.up || a.M > (1 << 16)) return HSP_EINVAL;
+    // M = Cout * up rounded up to a multiple of 4 (hip_layers.convtr_pack_map): the up to three padding rows hold
+    // zero weights and are never stored (every SHUFFLE epilogue checks co < Cout)
+    if (a.up <= 0 || a.up > 16 || a.M < a.Cout * a.up || a.M - a.Cout * a.up > 3 || a.M > (1 << 16)) return HSP_EINVAL;
   } else if (a.rows != HSP_ROWS_PLAIN) {
     return HSP_EINVAL;
   }
