@@ -67,7 +67,7 @@ class ResidualCouplingBlock_Transformer(nn.Module):
         # stacked into ONE GEMM per forward (12 launches -> 1); the blocks keep the parameters (checkpoint keys).
         lins = [blk.adaLN_modulation[1] for i in range(n_flows) for blk in self.flows[2 * i].enc_block]
         for lin in lins:
-            lin.__dict__["_stacked_elsewhere"] = True
+            lin.packed = False
         self._mod_rows = lins[0].cout * n_layers   # rows per coupling layer
         self.adaln_all = StackedLinearCT(lins)
         # (round 6)  The Flips cost no launch: reverse runs `Flip, coupling` for i = n_flows - 1 ... 0, so the tensor
@@ -240,12 +240,12 @@ def fft_wins(conv, x) -> bool:
     for the form to pay (fft_min_cols), a geometry the transform kernels address (hsp_dftseg_supported: the reference has no
     batch or length limit, hierspeechpp_speechsynthesizer.py:377-386,635-651, so beyond it the direct conv runs), and --
     inside a stream capture -- per-bin matrices that already exist (they are derived on first eager use)."""
-    if not (FFT_CONV and conv.__dict__.get("_fft") and x.stride(2) == 1):
+    if not (FFT_CONV and conv._fft and x.stride(2) == 1):
         return False
     B, _, Lx = x.shape
     if B * Lx < fft_min_cols(conv.cin, conv.k):
         return False
-    ok = conv.__dict__.setdefault("_fft_ok", {})
+    ok = conv._fft_ok
     sup = ok.get((B, Lx))
     if sup is None:
         if len(ok) >= 1024:          # a long-running process with ragged batches: the cache is a convenience, not a log

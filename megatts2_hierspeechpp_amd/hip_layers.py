@@ -9,6 +9,10 @@ reference instead re-derives ``g*v/||v||`` on every forward.
 
 All packed tensors of a model live in one contiguous fp32 arena so that a multi-GPU
 job can ship them with a single RCCL broadcast.
+
+Every launch leaves through ``_bracket``, the one place that knows the measurement hook
+(``LAUNCH_HOOK``): a conv's argument struct by way of ``_launch``, which inside
+``deferred()`` records it for ``launch_group`` instead (per context, like ``row_exact``).
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import functional as Fh
 from .synth import kaiser_sinc_filter12
 
 
@@ -110,7 +115,6 @@ class RowLengths:
         """float [B, 1, L]: 1 over each row's valid columns, 0 after."""
         m = self._masks.get(L_)
         if m is None:
-            from . import functional as Fh
             m = self._masks[L_] = Fh.sequence_mask(self.at(L_), L_)
         return m
 
@@ -155,10 +159,14 @@ def fft_act_fusable(x) -> bool:
 # SURVEY.md §8(b) names its minimum C ABI (hsp_conv1d_f32, hsp_convtr1d_f32, hsp_wn_layer_f32,
 # hsp_layernorm_modulate_f32).  Those entry points dispatch to the kernel-level ones this module calls by
 # default; with SURVEY_ABI set (HSP_SURVEY_ABI=1) every launch goes through them instead - same kernels, same
-# results (tests/test_gpu_parity.py::test_survey_abi_names_give_identical_results).
+# results (tests/test_gpu_parity.py::test_survey_abi_names_give_identical_results): _launch() swaps the entry point of a
+# single conv, and modules.WN / modules.DiTConVBlock collect their layers' structs under deferred() for launch_group().
 SURVEY_ABI = os.environ.get("HSP_SURVEY_ABI", "0") == "1"
-_DEFER = None  # a list while a caller collects the argument structs of several layers for ONE fused entry point
-# (modules.WN -> hsp_wn_layer_f32, modules.DiTConVBlock -> hsp_ffn_conv_f32): _launch() then records instead of launching
+# The list of the enclosing deferred() block, or None: while a caller collects the argument structs of several layers for
+# ONE fused entry point (modules.WN -> hsp_wn_layer_f32, modules.DiTConVBlock -> hsp_ffn_conv_f32; both only under
+# SURVEY_ABI) _launch() records instead of launching.  A context variable for the reason _ROWS is one: a second thread
+# that launches while the first is inside deferred() must launch.
+_DEFER: "contextvars.ContextVar[Optional[list]]" = contextvars.ContextVar("hsp_deferred", default=None)
 
 
 class deferred:
@@ -166,62 +174,65 @@ class deferred:
     allocated as usual); the caller passes the collected structs to a fused entry point with launch_group()."""
 
     def __enter__(self):
-        global _DEFER
-        assert _DEFER is None
-        _DEFER = []
-        return _DEFER
+        assert _DEFER.get() is None, "deferred() does not nest"
+        structs = []
+        self._token = _DEFER.set(structs)
+        return structs
 
     def __exit__(self, *exc):
-        global _DEFER
-        _DEFER = None
+        _DEFER.reset(self._token)
         return False
+
+
+def _bracket(kind: str, call, flops: int, nbytes: int, arg, soft: bool = False, span=None):
+    """The measurement bracket of every launch, and the only code that knows LAUNCH_HOOK: ``call()`` performs the C call
+    and returns its status; with a hook set it runs between two timing events on the launch stream and is reported as
+    hook(kind, flops, nbytes, ev_start, ev_end, arg).  Without a hook no event is created.  ``soft``: a launch the
+    library refuses with HSP_EINVAL reports nothing and its status is returned; every other failure raises.
+    ``call=None`` launches nothing: a summary record over ``span`` = (ev_start, ev_end) of earlier brackets.
+    Returns (status, ev_start, ev_end), the events None without a hook."""
+    hook = LAUNCH_HOOK
+    if call is None:
+        if hook is not None and span[0] is not None:
+            hook(kind, flops, nbytes, span[0], span[1], arg)
+        return 0, span[0], span[1]
+    e0 = e1 = None
+    if hook is not None:
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+    rc = call()
+    if soft and rc == L.EINVAL:
+        return rc, None, None
+    L.check(rc, kind)
+    if hook is not None:
+        e1.record()
+        hook(kind, flops, nbytes, e0, e1, arg)
+    return 0, e0, e1
 
 
 def launch_group(kind: str, fn, structs, *extra):
     """One call into a fused entry point taking several hsp_conv1d_args; measurement hook as for _launch().
-    ``structs``: the (args, flops, bytes) entries collected by deferred(); a None entry is passed as NULL."""
+    ``structs``: the (args, flops, bytes, keep) entries collected by deferred(); a None entry is passed as NULL."""
     flops = sum(e[1] for e in structs if e is not None)
     nbytes = sum(e[2] for e in structs if e is not None)
     ptrs = [C.byref(e[0]) if e is not None else None for e in structs]
-    hook = LAUNCH_HOOK
-    if hook is None:
-        L.check(fn(*ptrs, *extra, L.stream_ptr()), kind)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    L.check(fn(*ptrs, *extra, L.stream_ptr()), kind)
-    e1.record()
-    hook(kind, flops, nbytes, e0, e1, structs[0][0])
+    _bracket(kind, lambda: fn(*ptrs, *extra, L.stream_ptr()), flops, nbytes, structs[0][0])
 
 
 def _launch(kind: str, fn, a, flops: int, nbytes: int, soft: bool = False, keep=()):
     """``soft``: return the status instead of raising on HSP_EINVAL (a shape the requested fusion does not
     cover; the caller then issues the un-fused launches)."""
     a.debug = DEBUG_FLAGS
-    if _DEFER is not None:
+    structs = _DEFER.get()
+    if structs is not None:
         # the struct holds raw device pointers: `keep` pins the tensors behind them until launch_group() has run
         if soft or a.ln_c1 or a.split_row:    # not an assert: python -O would pass a fused-LayerNorm struct through
             raise L.HspError("deferred(): no soft / fused-LayerNorm / split launches")
-        _DEFER.append((a, flops, nbytes, keep))
+        structs.append((a, flops, nbytes, keep))
         return 0
     if SURVEY_ABI:
         fn = L.lib().hsp_convtr1d_f32 if a.rows == L.ROWS_SHUFFLE else L.lib().hsp_conv1d_f32
-    hook = LAUNCH_HOOK
-    if hook is None:
-        rc = fn(C.byref(a), L.stream_ptr())
-        if soft and rc == L.EINVAL:
-            return rc
-        L.check(rc, kind)
-        return 0
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    rc = fn(C.byref(a), L.stream_ptr())
-    if soft and rc == L.EINVAL:
-        return rc
-    L.check(rc, kind)
-    e1.record()
-    hook(kind, flops, nbytes, e0, e1, a)
-    return 0
+    return _bracket(kind, lambda: fn(C.byref(a), L.stream_ptr()), flops, nbytes, a, soft=soft)[0]
 
 
 # ------------------------------------------------------------------ index maps (host logic)
@@ -447,6 +458,13 @@ class Conv1d(_ConvBase):
         else:
             self.row_map = plain_rows(cout)
         self.M = int(self.row_map.shape[0])
+        # options (each set by the method named) and the buffers derived from them, all "off"
+        self.packed = True                           # False: parameters only, the rows are packed into a StackedLinearCT
+        self._pre_norm, self._c1 = None, None        # fuse_input_layernorm
+        self._rowmajor, self._wt = False, None       # keep_rowmajor_weight
+        self._flip_in = self._flip_out = False       # pack_flipped
+        self._fft, self._wf_form = False, None       # enable_fft; the form `_wf` holds (ensure_wf)
+        self._fft_ok: Dict[Tuple[int, int], bool] = {}     # fft_supported by (B, L): hierspeechpp_speechsynthesizer.fft_wins
 
     def fuse_input_layernorm(self, norm):
         """Run ``norm`` (an affine LayerNorm over the input channels: attributes ``weight``/``gamma``,
@@ -454,7 +472,9 @@ class Conv1d(_ConvBase):
         bias W beta + b, and ``ln_c1`` the row sums of the packed weight (hsp_conv1d_args.ln_c1).  The layer is
         then called on the UN-normalised input."""
         assert self.k == 1 and self.rows == L.ROWS_PLAIN
-        self.__dict__["_pre_norm"] = norm   # not registered: the norm stays where the reference keeps it
+        # past nn.Module.__setattr__, which would register the norm as a sub-module: it stays where the reference keeps
+        # it, and a second registration would duplicate its state_dict keys under this layer's prefix
+        self.__dict__["_pre_norm"] = norm
 
     def _ln_params(self):
         n = self._pre_norm
@@ -466,7 +486,7 @@ class Conv1d(_ConvBase):
         """Also keep the folded weight as stored -- [cout][cin] row-major -- in the arena (``_wt``): the A operand of
         the projection inside hsp_mha_proj_f32 (attention + output projection in one launch)."""
         assert self.k == 1 and self.rows == L.ROWS_PLAIN
-        self.__dict__["_rowmajor"] = True
+        self._rowmajor = True
 
     def pack_flipped(self, inputs: bool = False, outputs: bool = False):
         """Pack this layer for a tensor whose channel axis is stored REVERSED: ``inputs`` -- the input channels arrive in
@@ -475,18 +495,18 @@ class Conv1d(_ConvBase):
         reference stores them; only the packed copy changes.  This is how modules.Flip (modules.py:270-277) between two
         coupling layers costs no launch: the layer after a Flip reads and writes the un-flipped tensor through a packed
         weight that has the permutation in it (modules.ResidualCouplingLayer_Transformer_simple.flipped)."""
-        assert self.rows == L.ROWS_PLAIN and not self.__dict__.get("_pre_norm") and not self.__dict__.get("_rowmajor")
-        self.__dict__["_flip_in"], self.__dict__["_flip_out"] = bool(inputs), bool(outputs)
+        assert self.rows == L.ROWS_PLAIN and self._pre_norm is None and not self._rowmajor
+        self._flip_in, self._flip_out = bool(inputs), bool(outputs)
         self.__dict__["_hsp_stale"] = True
         _bump_epoch()
 
     def hsp_requests(self):
-        if self.__dict__.get("_stacked_elsewhere"):   # rows live in a StackedLinearCT: parameters only
+        if not self.packed:
             return []
-        fused = self.__dict__.get("_pre_norm") is not None
+        fused = self._pre_norm is not None
         return [("w", self.k * self.cin * self.M)] + ([("b", self.cout)] if self.has_bias or fused else []) + \
             ([("c1", self.cout)] if fused else []) + \
-            ([("wt", self.cout * self.cin)] if self.__dict__.get("_rowmajor") else [])
+            ([("wt", self.cout * self.cin)] if self._rowmajor else [])
 
     def enable_fft(self):
         """This same-length stride-1 conv may also run in its frequency-domain form (round 4, csrc/hsp_dftseg.hip):
@@ -498,7 +518,7 @@ class Conv1d(_ConvBase):
         allocates them (201 MB per conv at 512 channels)."""
         assert self.stride == 1 and self.rows == L.ROWS_PLAIN and self.cin == self.cout and 2 <= self.k <= 64
         assert self.padding * 2 == (self.k - 1) * self.dilation, "same-length conv"
-        self.__dict__["_fft"] = True
+        self._fft = True
 
     def fft_form(self) -> str:
         return "three" if FFT_PRODUCT == "three" and self.cin % 64 == 0 else "block"
@@ -521,19 +541,19 @@ class Conv1d(_ConvBase):
         return wf
 
     def hsp_fill(self, arena, materialize):
-        if self.__dict__.get("_stacked_elsewhere"):
+        if not self.packed:
             return
-        fused = self.__dict__.get("_pre_norm") is not None
+        fused = self._pre_norm is not None
         self._w = arena.view(self, "w")
         self._b = arena.view(self, "b") if self.has_bias or fused else None
         self._c1 = arena.view(self, "c1") if fused else None
-        self._wt = arena.view(self, "wt").view(self.cout, self.cin) if self.__dict__.get("_rowmajor") else None
+        self._wt = arena.view(self, "wt").view(self.cout, self.cin) if self._rowmajor else None
         self._wf = None                                   # derived from _w on first use (ensure_wf)
         if materialize:
             w = self._folded()
-            if self.__dict__.get("_flip_in"):
+            if self._flip_in:
                 w = w.flip(1).contiguous()
-            if self.__dict__.get("_flip_out"):
+            if self._flip_out:
                 w = w.flip(0).contiguous()
             if self._wt is not None:
                 assert not fused
@@ -550,7 +570,7 @@ class Conv1d(_ConvBase):
                 w = wg.float().reshape(w.shape).contiguous()
             _gather(w, conv_pack_map(self.cout, self.cin, self.k, self.row_map), self._w)
             if self._b is not None and not fused:
-                self._b.copy_(self._bias_src().flip(0) if self.__dict__.get("_flip_out") else self._bias_src())
+                self._b.copy_(self._bias_src().flip(0) if self._flip_out else self._bias_src())
 
     # The frequency-domain form in pieces (forward_fft strings them together; an AMP pair fuses the inverse of its first
     # conv with the forward transform of its second: forward_fft_pair)
@@ -569,7 +589,7 @@ class Conv1d(_ConvBase):
     def fft_supported(self, B, Lx) -> bool:
         """Do the transform kernels take this geometry (hsp_dftseg_supported: dilation <= 8, a spectrum below 4 GiB per
         launch, item counts within int)?  fft_wins asks before choosing the form; beyond it the direct conv runs."""
-        if not self.__dict__.get("_fft"):
+        if not self._fft:
             return False
         da = self._fft_args(B, Lx)
         da.xf_bs = 2 * self.cin * da.Np
@@ -587,7 +607,7 @@ class Conv1d(_ConvBase):
     def _fft_forward(self, x, act1d=None):
         """x [B, C, L] -> spectrum [64][2 C][Np] (hsp_dftseg_fwd_f32), the activation applied on the way if given."""
         B, Cc, Lx = x.shape
-        assert Cc == self.cin and x.stride(2) == 1 and self.__dict__.get("_fft")
+        assert Cc == self.cin and x.stride(2) == 1 and self._fft
         da = self._fft_args(B, Lx)
         xf = _spectrum(Cc, da.Np, x.device)
         da.x, da.x_bs, da.x_cs = L.fptr(x), x.stride(0), x.stride(1)
@@ -596,15 +616,9 @@ class Conv1d(_ConvBase):
             if not fft_act_fusable(x):
                 raise L.HspError("forward_fft(act1d=...) needs 16-B addressable rows")
             self._fft_set_act(da, x, act1d)
-        hook, ev = LAUNCH_HOOK, None
-        if hook is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        L.check(L.lib().hsp_dftseg_fwd_f32(C.byref(da), L.stream_ptr()), "hsp_dftseg_fwd_f32")
-        if hook is not None:
-            ev[1].record()
-            hook("hsp_dftseg_fwd_f32", 2 * 2 * 64 * 64 * B * Cc * da.dil * da.nseg, 4 * (B * Cc * Lx + 128 * Cc * da.Np), ev[0], ev[1], None)
-        return xf, (ev[0] if ev else None)
+        _, e0, _ = _bracket("hsp_dftseg_fwd_f32", lambda: L.lib().hsp_dftseg_fwd_f32(C.byref(da), L.stream_ptr()),
+                            2 * 2 * 64 * 64 * B * Cc * da.dil * da.nseg, 4 * (B * Cc * Lx + 128 * Cc * da.Np), None)
+        return xf, e0
 
     def _fft_product(self, xf):
         """ONE batched launch over the 64 bins: yf[bin] = conj(W)[bin] xf[bin] -- three real C x C products per bin
@@ -616,25 +630,15 @@ class Conv1d(_ConvBase):
             pa = L.Cprod3Args()
             pa.xf, pa.yf, pa.w, pa.zeros = L.fptr(xf), L.fptr(yf), L.fptr(wf), L.fptr(_zeros(xf.device))
             pa.xf_bs, pa.yf_bs, pa.bins, pa.C, pa.Np, pa.debug = xf.stride(0), yf.stride(0), 64, Cc, Np, DEBUG_FLAGS
-            hook = LAUNCH_HOOK
-            if hook is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            L.check(L.lib().hsp_cprod3_f32(C.byref(pa), L.stream_ptr()), "hsp_cprod3_f32")
-            if hook is not None:
-                e1.record()
-                hook("hsp_cprod3_f32", 2 * 64 * 3 * Cc * Cc * Np, 4 * (64 * 2 * 2 * Cc * Np + 64 * 3 * Cc * Cc), e0, e1, None)
+            _bracket("hsp_cprod3_f32", lambda: L.lib().hsp_cprod3_f32(C.byref(pa), L.stream_ptr()),
+                     2 * 64 * 3 * Cc * Cc * Np, 4 * (64 * 2 * 2 * Cc * Np + 64 * 3 * Cc * Cc), None)
             return yf
         a = L.Conv1dArgs()
-        a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(xf), xf.stride(0), xf.stride(1), 1
-        a.B, a.Cin, a.Lin = 64, 2 * Cc, Np
+        _set_in(a, xf)                               # the 64 bins are the batch: [64][2 C][Np]
         a.w, a.K, a.dil, a.pad, a.stride = L.fptr(wf), 1, 1, 0, 1
         a.M, a.w_ld, a.w_bs = 2 * Cc, 2 * Cc, 4 * Cc * Cc
-        a.zeros = L.fptr(_zeros(xf.device))
         _set_out(a, yf, 64, 2 * Cc, Np)
         a.ncols, a.rows, a.scale, a.post_scale = Np, L.ROWS_PLAIN, 1.0, 1.0
-        # the launches are booked with the flops / bytes they EXECUTE; the conv they stand for is reported once more, as
-        # a whole, under the kind "hsp_fftconv" (algorithmic flops and bytes of the direct form over all its launches)
         _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, 2 * 64 * 4 * Cc * Cc * Np,
                 4 * (64 * 2 * 2 * Cc * Np + 64 * 4 * Cc * Cc))
         return yf
@@ -657,16 +661,22 @@ class Conv1d(_ConvBase):
         if res is not None:
             da.res, da.res_bs, da.res_cs = L.fptr(res), res.stride(0), res.stride(1)
         da.accumulate, da.post_scale = int(bool(accumulate)), float(post_scale)
-        hook, e1 = LAUNCH_HOOK, None
-        if hook is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        L.check(L.lib().hsp_dftseg_inv_f32(C.byref(da), L.stream_ptr()), "hsp_dftseg_inv_f32")
-        if hook is not None:
-            e1.record()
-            nio = 2 + bool(res is not None) + 2 * bool(accumulate)
-            hook("hsp_dftseg_inv_f32", 2 * 2 * 64 * 64 * B * Cc * da.dil * da.nseg, 4 * (B * Cc * Lx * (nio - 1) + 128 * Cc * da.Np), e0, e1, None)
+        _, _, e1 = _bracket("hsp_dftseg_inv_f32", lambda: L.lib().hsp_dftseg_inv_f32(C.byref(da), L.stream_ptr()),
+                            2 * 2 * 64 * 64 * B * Cc * da.dil * da.nseg,
+                            4 * (B * Cc * Lx * (self._fft_nio(res, accumulate) - 1) + 128 * Cc * da.Np), None)
         return out, e1
+
+    @staticmethod
+    def _fft_nio(res, accumulate) -> int:      # [B, C, L] tensors moved through HBM: in, out, residual, running sum twice
+        return 2 + bool(res is not None) + 2 * bool(accumulate)
+
+    def _fft_report(self, x, taps, res, accumulate, e_first, e_last, arg):
+        """The summary record "hsp_fftconv": the launches of the form are booked with the flops / bytes they EXECUTE, the
+        conv(s) they stand for once more as a whole -- algorithmic flops and bytes of the direct form with ``taps`` taps,
+        from the first launch's start event to the last launch's end event."""
+        B, Cc, Lx = x.shape
+        _bracket("hsp_fftconv", None, 2 * B * Cc * Cc * taps * Lx,
+                 4 * B * Cc * Lx * self._fft_nio(res, accumulate) + 4 * taps * Cc * Cc, arg, span=(e_first, e_last))
 
     def forward_fft(self, x, *, res=None, out=None, accumulate=False, post_scale=1.0, act1d=None, before_inverse=None):
         """The conv in its frequency-domain form (enable_fft()): three launches -- forward DFT of 128-sample segments,
@@ -676,20 +686,18 @@ class Conv1d(_ConvBase):
         fft_act_fusable).  ``before_inverse``: an event the stream waits on before the inverse transform, the only launch
         that touches ``out``."""
         self._require_ready()
-        B, Cc, Lx = x.shape
+        B, _, Lx = x.shape
         xf, e_first = self._fft_forward(x, act1d)
         yf = self._fft_product(xf)
         out, e_last = self._fft_inverse(yf, B, Lx, res=res, out=out, accumulate=accumulate, post_scale=post_scale,
                                         before_inverse=before_inverse)
-        if LAUNCH_HOOK is not None:
-            nio = 2 + bool(res is not None) + 2 * bool(accumulate)
-            LAUNCH_HOOK("hsp_fftconv", 2 * B * Cc * Cc * self.k * Lx, 4 * B * Cc * Lx * nio + 4 * self.k * Cc * Cc, e_first, e_last, None)
+        self._fft_report(x, self.k, res, accumulate, e_first, e_last, None)
         return out
 
     def fft_pair_ok(self, second, x) -> bool:
         """Can the inverse transform of this conv be fused with the activation and the forward transform of ``second``
         (hsp_dftseg_pair_f32) for an input like x?  Both unchunked and their two LDS stretches within one CU's 160 KB."""
-        if not self.__dict__.get("_fft") or not second.__dict__.get("_fft") or second.cin != self.cin or x.shape[2] % 4:
+        if not self._fft or not second._fft or second.cin != self.cin or x.shape[2] % 4:
             return False
         B, _, Lx = x.shape
         ia, fa = self._fft_args(B, Lx), second._fft_args(B, Lx)
@@ -700,24 +708,16 @@ class Conv1d(_ConvBase):
 
     def _fft_pair_launch(self, second, yf, B, Lx, act_second, like):
         """ONE launch (hsp_dftseg_pair_f32): inverse transform of this conv's product ``yf`` + bias -> ``act_second`` ->
-        forward transform for ``second``.  Returns second's spectrum and the launch's (start, end) events when a
-        LAUNCH_HOOK is set."""
+        forward transform for ``second``.  Returns second's spectrum."""
         Cc = self.cin
         ia = self._fft_inverse_args(yf, B, Lx)
         fa = second._fft_args(B, Lx)
         xf2 = _spectrum(Cc, fa.Np, yf.device)
         fa.xf, fa.xf_bs, fa.dft = L.fptr(xf2), xf2.stride(0), L.fptr(_dft_tables(yf.device)[0])
         self._fft_set_act(fa, like, act_second)
-        hook, ev = LAUNCH_HOOK, (None, None)
-        if hook is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        L.check(L.lib().hsp_dftseg_pair_f32(C.byref(ia), C.byref(fa), L.stream_ptr()), "hsp_dftseg_pair_f32")
-        if hook is not None:
-            ev[1].record()
-            hook("hsp_dftseg_pair_f32", 2 * 2 * 64 * 64 * B * Cc * (ia.dil * ia.nseg + fa.dil * fa.nseg),
-                 4 * 128 * Cc * (ia.Np + fa.Np), ev[0], ev[1], None)
-        return xf2, ev
+        _bracket("hsp_dftseg_pair_f32", lambda: L.lib().hsp_dftseg_pair_f32(C.byref(ia), C.byref(fa), L.stream_ptr()),
+                 2 * 2 * 64 * 64 * B * Cc * (ia.dil * ia.nseg + fa.dil * fa.nseg), 4 * 128 * Cc * (ia.Np + fa.Np), None)
+        return xf2
 
     def forward_fft_pair(self, second, x, *, act_first, act_second, res=None, out=None, accumulate=False, post_scale=1.0,
                          before_inverse=None):
@@ -726,18 +726,14 @@ class Conv1d(_ConvBase):
         inverse with second's epilogue.  Five launches instead of six (eight with the activations)."""
         self._require_ready()
         second._require_ready()
-        B, Cc, Lx = x.shape
+        B, _, Lx = x.shape
         xf, e_first = self._fft_forward(x, act_first)
         yf = self._fft_product(xf)
-        hook = LAUNCH_HOOK
-        xf2, _ = self._fft_pair_launch(second, yf, B, Lx, act_second, x)
+        xf2 = self._fft_pair_launch(second, yf, B, Lx, act_second, x)
         yf2 = second._fft_product(xf2)
         out, e_last = second._fft_inverse(yf2, B, Lx, res=res, out=out, accumulate=accumulate, post_scale=post_scale,
                                           before_inverse=before_inverse)
-        if hook is not None:
-            nio = 2 + bool(res is not None) + 2 * bool(accumulate)
-            hook("hsp_fftconv", 2 * B * Cc * Cc * (self.k + second.k) * Lx, 4 * B * Cc * Lx * nio + 4 * (self.k + second.k) * Cc * Cc,
-                 e_first, e_last, 2)   # (two convs)
+        self._fft_report(x, self.k + second.k, res, accumulate, e_first, e_last, 2)   # (two convs)
         return out
 
     # ----------------------------------------------------------------------------
@@ -774,12 +770,10 @@ class Conv1d(_ConvBase):
         if out is None:
             out = torch.empty(B, cout, Lout, dtype=torch.float32, device=x.device)
         a = L.Conv1dArgs()
-        a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(x), x.stride(0), x.stride(1), x.stride(2)
-        a.B, a.Cin, a.Lin = B, Cin, Lin
+        _set_in(a, x)
         a.w, a.K, a.dil, a.pad, a.stride = L.fptr(self._w) + 4 * r0, self.k, self.dilation, self.padding, self.stride
         a.M = self.M if row_range is None else _round_up(cout, 4)
         a.w_ld = self.M
-        a.zeros = L.fptr(_zeros(x.device))
         _set_out(a, out, B, cout, Lout)
         a.ncols = Lout
         a.rows, a.gate_half = self.rows, (cout if gated else 0)
@@ -792,15 +786,13 @@ class Conv1d(_ConvBase):
             a.prologue, a.slope = L.PRO_LRELU, float(lrelu)
         elif silu_in:
             a.prologue = L.PRO_SILU
-        if self.__dict__.get("_pre_norm") is not None:
+        if self._pre_norm is not None:
             a.ln_c1, a.ln_eps = L.fptr(self._c1), float(self._pre_norm.eps)
             assert not force_direct and row_range is None
-        direct = (force_direct or self.stride != 1 or self.cin < 8 or cout < 8 or Lout < 8 or silu_in) \
-            and not gated and act1d is None and self.__dict__.get("_pre_norm") is None
+        direct = _wants_direct(a, force_direct, silu_in)
         if direct and a.res_ts > 1:
             # the VALU kernel reads its residual at unit column stride (hsp_conv1d_args.res_ts is the register-path
             # token GEMM's): gather it first -- e.g. the PLM's last layer at B = 4, whose [D, 4] product is below the MFMA path
-            from . import functional as Fh
             res = Fh.copy_strided(res)
             a.res, a.res_bs, a.res_cs, a.res_ts = L.fptr(res), res.stride(0), res.stride(1), 0
         rows_full = cout * (2 if gated else 1)
@@ -808,39 +800,31 @@ class Conv1d(_ConvBase):
         # algorithmic traffic: input once, output once (+ residual / accumulate reads), weights once
         nbytes = 4 * (B * Cin * Lin + B * cout * Lout * (1 + (res is not None) + bool(accumulate))
                       + rows_full * Cin * self.k)
+        # every tensor the struct points at that a caller may drop before a deferred() group is launched (`res`: the
+        # gathered copy where one was made)
+        keep = (x, out, out2, res, cbias, mask, cscale)
+        kind, fn = ("hsp_conv1d_direct_f32", L.lib().hsp_conv1d_direct_f32) if direct else \
+            ("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32)
         if split_out is not None:
             a.Cout = self.cout                      # rows [split_row, cout) go to the second output
             a.split_row, a.accumulate2, a.mask_mode2 = split_row, int(bool(acc2)), mask_mode2   # (the second output shares `mask`)
             a.y2, a.y2_bs, a.y2_cs = L.fptr(out2), out2.stride(0), out2.stride(1)
             flops = 2 * B * self.cout * Cin * Lout
             nbytes += 4 * B * (self.cout - split_row) * Lout * (1 + bool(acc2))
-            rc = _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, soft=True)
+            rc = _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, soft=True, keep=keep)
             return None if rc else (out, out2)
-        if direct:
-            _launch("hsp_conv1d_direct_f32", L.lib().hsp_conv1d_direct_f32, a, flops, nbytes)
-        elif self.__dict__.get("_pre_norm") is not None and _DEFER is not None:
-            # inside deferred(): the normalisation (affine part folded into the packed weights) runs now as its own
-            # launch, the plain GEMM joins the group
-            from . import functional as Fh
+        if self._pre_norm is not None:
+            # fused input LayerNorm: token-GEMM shapes only (16-B addressable columns), and not inside deferred() (the
+            # fused entry points take plain GEMMs).  Anything else runs the normalisation as its own launch -- WITHOUT the
+            # affine part, which is folded into the packed weights (W diag(gamma), W beta + b) -- and then the same GEMM:
+            # identical arithmetic, one launch more.
+            if _DEFER.get() is None and not _launch(kind, fn, a, flops, nbytes, soft=True, keep=keep):
+                return out
             xn = Fh.layernorm_mod(x, float(self._pre_norm.eps))
-            a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(xn), xn.stride(0), xn.stride(1), xn.stride(2)
+            _set_in(a, xn)
             a.ln_c1 = None
-            _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes,
-                    keep=(xn, out, res, cbias, mask, cscale))
-        elif self.__dict__.get("_pre_norm") is not None:
-            # fused input LayerNorm: token-GEMM shapes only (16-B addressable columns).  Any other shape runs the
-            # normalisation as its own launch -- WITHOUT the affine part, which is folded into the packed weights
-            # (W diag(gamma), W beta + b) -- and then the same GEMM: identical arithmetic, one launch more.
-            rc = _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, soft=True)
-            if rc:
-                from . import functional as Fh
-                xn = Fh.layernorm_mod(x, float(self._pre_norm.eps))
-                a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(xn), xn.stride(0), xn.stride(1), xn.stride(2)
-                a.ln_c1 = None
-                _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes)
-        else:
-            _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes,
-                    keep=(x, out, res, cbias, mask, cscale))
+            keep += (xn,)
+        _launch(kind, fn, a, flops, nbytes, keep=keep)
         return out
 
 
@@ -871,11 +855,9 @@ class ConvTranspose1d(_ConvBase):
         if out is None:
             out = torch.empty(B, self.cout, Lout, dtype=torch.float32, device=x.device)
         a = L.Conv1dArgs()
-        a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(x), x.stride(0), x.stride(1), x.stride(2)
-        a.B, a.Cin, a.Lin = B, Cin, Lin
+        _set_in(a, x)
         a.w, a.K, a.M, a.dil, a.pad, a.stride = L.fptr(self._w), self.kp, self.M, 1, self.kp - 1, 1
         a.w_ld = self.M
-        a.zeros = L.fptr(_zeros(x.device))
         _set_out(a, out, B, self.cout, Lout)
         a.ncols = (Lout - 1 + self.padding) // self.up + 1
         a.rows, a.up, a.shuf_pad = L.ROWS_SHUFFLE, self.up, self.padding
@@ -984,7 +966,6 @@ class GroupedPosConv1d(HipLayer):
             c.hsp_fill(_SubArena(arena, self, f"s{i}."), materialize)
 
     def forward(self, x):
-        from . import functional as Fh
         nb = self.k // self.TAPS
         conv = torch.empty_like(x)
         for i, c in enumerate(self._subs):
@@ -1015,13 +996,6 @@ class LinearCT(Conv1d):
         super().__init__(cin, cout, 1, bias=bias, weight_2d=True)
         self.packed = packed
 
-    def hsp_requests(self):
-        return super().hsp_requests() if self.packed else []
-
-    def hsp_fill(self, arena, materialize):
-        if self.packed:
-            super().hsp_fill(arena, materialize)
-
 
 class StackedLinearCT(Conv1d):
     """Several nn.Linear layers reading the same input, run as ONE GEMM with their output rows
@@ -1038,6 +1012,24 @@ class StackedLinearCT(Conv1d):
 
     def _bias_src(self):
         return torch.cat([p.bias.data for p in self._parts], 0)
+
+
+def _set_in(a, x):
+    """The input side of hsp_conv1d_args for x [B, Cin, Lin] at any strides."""
+    a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(x), x.stride(0), x.stride(1), x.stride(2)
+    a.B, a.Cin, a.Lin = x.shape
+    a.zeros = L.fptr(_zeros(x.device))
+
+
+def _wants_direct(a, force_direct: bool, silu_in: bool) -> bool:
+    """Does this launch take the VALU kernel (hsp_conv1d_direct_f32) instead of the MFMA one?  Shapes the MFMA kernels do
+    not take: stride, degenerate channel / length counts, a SiLU prologue.  The same rule as wants_direct() in
+    csrc/hsp_abi.hip, which decides again for a struct that arrives through hsp_conv1d_f32 (SURVEY_ABI) -- change the two
+    together.  ``force_direct`` (a Linear's L = 1 products) is the host's alone.  Reads rows, prologue, ln_c1, stride,
+    Cin, Cout and Lout of ``a`` as Conv1d.forward has set them."""
+    gated = a.rows in (L.ROWS_GATE_WN, L.ROWS_GATE_GLU)
+    return (not gated and a.prologue != L.PRO_ACT1D and not a.ln_c1 and
+            bool(force_direct or a.stride != 1 or a.Cin < 8 or a.Cout < 8 or a.Lout < 8 or silu_in))
 
 
 def _set_out(a, out, B, cout, Lout):
@@ -1076,7 +1068,7 @@ def prepare_fft(model: nn.Module) -> int:
     the number of floats the side buffers hold."""
     n = 0
     for m in model.modules():
-        if isinstance(m, Conv1d) and m.__dict__.get("_fft"):
+        if isinstance(m, Conv1d) and m._fft:
             n += m.ensure_wf().numel()
     return n
 
