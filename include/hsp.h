@@ -25,7 +25,7 @@
  *   - hsp_conv1d_mfma_f32: stride 1; halo (K - 1) * dil + 3 <= 125 columns (plain and gated rows); one utterance of
  *     a tensor and the packed weight each below 2^31 elements
  *   - hsp_mha_f32: no sequence-length ceiling (score rows that do not fit LDS are walked in key blocks); head dim
- *     <= 128 without a relative-position window, <= 256 with one
+ *     <= 256, with or without a relative-position window (the matrix-core kernels serve D <= 128 without a window)
  *   - hsp_lstm_bidir_f32: hidden size H <= 256 (one workgroup of 4 H <= 1024 threads holds the gate rows)
  */
 #ifndef HSP_H_
@@ -356,8 +356,9 @@ int hsp_layernorm_mod_f32(const float* x, float* y, int32_t B, int32_t C, int32_
  * [B, T]: scores where mask_q*mask_k == 0 are set to -1e4 (attentions.py:174-175).
  * Without mask: timm 0.6.13 Attention (modules.py:409).  Optional relative-position
  * window (emb_rel_k/v [2w+1, D]): attentions.py:165-170,183-186.
- * No length ceiling: score rows that do not fit the CU's LDS are walked in key blocks with an online softmax
- * (head dim <= 128 without a window, <= 256 with one). */
+ * No length ceiling: score rows that do not fit the CU's LDS are walked in key blocks with an online softmax.
+ * Head dim D <= 256 on every path (D > 256 is refused with HSP_EINVAL, windowed or not, at any length): the
+ * matrix-core kernels serve D <= 128 without a window, the scalar kernels a window or D in 129 .. 256. */
 typedef struct hsp_mha_args {
   const float *q, *k, *v;
   float* o;
@@ -379,6 +380,17 @@ typedef struct hsp_mha_args {
   int64_t mask_dense_bs;
 } hsp_mha_args;
 int hsp_mha_f32(const hsp_mha_args* a, void* stream);
+/* Which kernel hsp_mha_f32 would launch for the struct, without launching (host only): 0 or the refusal
+ * hsp_mha_f32 gives, and out4 = {kernel (HSP_MHA_*), NDB, dynamic LDS bytes, workgroups}.  NDB = head-dim blocks the
+ * kernel is built for: ceil(D / 32) of the matrix-core kernels (TOK 1..3, the MFMA kernels 1..4), the passes over 128
+ * channels (1 or 2) of the scalar ROW kernels.  Both entry points read one decision function. */
+#define HSP_MHA_TOK 0         /* mha_tok_kernel: no mask, no window, 4 <= Tk <= 256, D <= 96 */
+#define HSP_MHA_MFMA_WHOLE 1  /* mha_mfma_kernel, all of V staged in LDS */
+#define HSP_MHA_MFMA_SLAB 2   /* mha_mfma_kernel, V in 64-key slabs */
+#define HSP_MHA_MFMA_STREAM 3 /* mha_mfma_stream_kernel: online softmax over 128-key blocks */
+#define HSP_MHA_ROW 4         /* mha_kernel: relative-position window, or D > 128 */
+#define HSP_MHA_ROW_STREAM 5  /* mha_stream_kernel: the same over 256-key blocks */
+int hsp_mha_plan(const hsp_mha_args* a, int32_t out4[4]);
 /* Self-attention over ALL heads + the output projection + its epilogue in ONE launch (csrc/hsp_mhaproj.hip):
  *   o[b, h D + d, i] = sum_j softmax_j(qk_scale q[b, h D + :, i] . k[b, h D + :, j]) v[b, h D + d, j]
  *   y[b, m, i] = ((sum_c wt[m, c] o[b, c, i] + bias[m]) * mask[b, i]) * cscale[b, m] + res[b, m, i]
@@ -387,7 +399,8 @@ int hsp_mha_f32(const hsp_mha_args* a, void* stream);
  * `x + gate_msa * attn(.)` of a DiT block (modules.py:397,409: 2 heads x 96).  Any Tk >= 4 (up to 2^20): rows of up to 256
  * keys take the one-pass form, longer ones stream the keys in groups with an online softmax (tested to 1 000 keys).
  * key_len (optional, device int64 [B]): the softmax of utterance b covers keys [0, key_len[b]) only (clamped to [1, Tk]);
- * 64-key groups past it are skipped -- a ragged batch whose rows equal their B = 1 runs.  No other mask inside the
+ * 64-key groups past it are skipped -- a ragged batch whose rows equal their B = 1 runs; what k / v hold past key_len[b]
+ * never reaches a sum (rows of fewer than 4 keys included).  No other mask inside the
  * softmax -- neither query masks nor a dense or causal attn_mask: a caller that needs one uses hsp_mha_f32
  * (mask_q / mask_k / mask_dense) and the projection as two launches.
  * q / k / v: element (b, c, t) at base + b * bs + c * cs + t (channel-major; a batch may sit side by side on the columns

@@ -20,6 +20,7 @@ ACT_NONE, ACT_TANH, ACT_GELU_TANH, ACT_RELU, ACT_MISH, ACT_SILU, ACT_SOFTPLUS, A
 ROWS_PLAIN, ROWS_GATE_WN, ROWS_GATE_GLU, ROWS_SHUFFLE = 0, 1, 2, 3
 MASK_NONE, MASK_PRE, MASK_POST, MASK_BOTH = 0, 1, 2, 3
 EINVAL = -1
+MHA_TOK, MHA_MFMA_WHOLE, MHA_MFMA_SLAB, MHA_MFMA_STREAM, MHA_ROW, MHA_ROW_STREAM = range(6)   # hsp_mha_plan kernel ids
 
 _fp = C.c_void_p
 
@@ -129,6 +130,7 @@ SIGNATURES = {
     "hsp_layernorm_mod_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp, _fp,
                                         C.c_int64, _fp, _fp, _fp]),
     "hsp_mha_f32": (C.c_int, [C.POINTER(MhaArgs), _fp]),
+    "hsp_mha_plan": (C.c_int, [C.POINTER(MhaArgs), C.POINTER(C.c_int32 * 4)]),
     "hsp_mha_proj_f32": (C.c_int, [C.POINTER(MhaProjArgs), _fp]),
     "hsp_dftseg_fwd_f32": (C.c_int, [C.POINTER(DftSegArgs), _fp]),
     "hsp_dftseg_inv_f32": (C.c_int, [C.POINTER(DftSegArgs), _fp]),

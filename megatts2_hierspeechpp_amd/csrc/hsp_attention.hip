@@ -290,30 +290,25 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
   }
 }
 
+// What mha_decide (end of this file) settled for a launch: the kernel (HSP_MHA_*), its head-dim blocks, the launch
+// shape and the LDS pitches.  The launchers below only carry it out; hsp_mha_plan reports it.
+struct mha_choice {
+  int kernel, ndb, n_qt, sp, vp, dpad;
+  int64_t lds, blocks;
+};
+
 template <int NDB>
-int mha_mfma_launch(const hsp_mha_args& a, hipStream_t stream) {
-  constexpr int DP = NDB * 32;
-  const int sp = ((a.Tk + 31) & ~31) + 33;  // odd pitch, room for one zero slab column block
-  const int vp = ((a.Tk + 63) & ~63) + 1;
-  const int64_t base = ((int64_t)DP * 32 + 32 * (int64_t)sp) * (int64_t)sizeof(float);
-  const int64_t lds_whole = base + (int64_t)DP * vp * (int64_t)sizeof(float);
-  const int64_t lds_slab = base + (int64_t)DP * 65 * (int64_t)sizeof(float);
-  const int n_qt32 = (a.Tq + MQT - 1) / MQT;
-  const unsigned blocks = (unsigned)((int64_t)n_qt32 * a.H * a.B);
-  // whole-V needs one round trip less per 64 keys but more LDS: with more workgroups than CUs prefer the
-  // footprint that lets two of them share a CU (their latencies then overlap instead of queueing)
-  const bool whole = lds_whole <= 160 * 1024 && (blocks <= 256 || lds_whole <= 80 * 1024 || lds_slab > 80 * 1024);
-  if (!whole && lds_slab > 160 * 1024) return -1;
-  if (whole) {
+int mha_mfma_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
+  if (c.kernel == HSP_MHA_MFMA_WHOLE) {
     static hsp_lds_flags flags;
-    if (lds_whole > 32 * 1024)
+    if (c.lds > 32 * 1024)
       if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_kernel<NDB, true>), 160 * 1024, flags)) return e;
-    hipLaunchKernelGGL((mha_mfma_kernel<NDB, true>), dim3(blocks), dim3(256), (size_t)lds_whole, stream, a, n_qt32, sp, vp);
+    hipLaunchKernelGGL((mha_mfma_kernel<NDB, true>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt, c.sp, c.vp);
   } else {
     static hsp_lds_flags flags;
-    if (lds_slab > 32 * 1024)
+    if (c.lds > 32 * 1024)
       if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_kernel<NDB, false>), 160 * 1024, flags)) return e;
-    hipLaunchKernelGGL((mha_mfma_kernel<NDB, false>), dim3(blocks), dim3(256), (size_t)lds_slab, stream, a, n_qt32, sp, 65);
+    hipLaunchKernelGGL((mha_mfma_kernel<NDB, false>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt, c.sp, c.vp);
   }
   return (int)hipGetLastError();
 }
@@ -449,16 +444,11 @@ __global__ __launch_bounds__(256) void mha_mfma_stream_kernel(const hsp_mha_args
 }
 
 template <int NDB>
-int mha_mfma_stream_launch(const hsp_mha_args& a, hipStream_t stream) {
-  constexpr int DP = NDB * 32;
-  const size_t lds_bytes = ((size_t)DP * 32 + 32 * (SKB + 1) + (size_t)DP * (SKB + 1) + 96) * sizeof(float);
-  const int n_qt = (a.Tq + MQT - 1) / MQT;
-  const int64_t blocks = (int64_t)n_qt * a.H * a.B;
-  if (blocks <= 0 || blocks > 0x7fffffff) return HSP_EINVAL;
+int mha_mfma_stream_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
   static hsp_lds_flags flags;
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_stream_kernel<NDB>), (int)lds_bytes, flags)) return e;
-  hipLaunchKernelGGL((mha_mfma_stream_kernel<NDB>), dim3((unsigned)blocks), dim3(256), lds_bytes, stream, a, n_qt);
+  if (c.lds > 32 * 1024)
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_stream_kernel<NDB>), (int)c.lds, flags)) return e;
+  hipLaunchKernelGGL((mha_mfma_stream_kernel<NDB>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt);
   return (int)hipGetLastError();
 }
 
@@ -619,17 +609,19 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
   }
 }
 
-int mha_stream_launch(const hsp_mha_args& a, hipStream_t stream) {
-  if (a.D > 256) return HSP_EINVAL;
-  const int n_qt = (a.Tq + QT - 1) / QT;
-  const int dpad = (a.D < 128 ? a.D : 128) | 1;
-  const size_t lds_bytes = ((size_t)a.D * QT + (size_t)QT * (WKB + 1) + 64 * (size_t)dpad + 3 * QT) * sizeof(float);
-  const int64_t blocks = (int64_t)n_qt * a.H * a.B;
-  if (blocks <= 0 || blocks > 0x7fffffff) return HSP_EINVAL;
+int mha_stream_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
   static hsp_lds_flags flags;
-  if (lds_bytes > 32 * 1024)
+  if (c.lds > 32 * 1024)
     if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_stream_kernel), 160 * 1024, flags)) return e;   // once per device: the maximum
-  hipLaunchKernelGGL(mha_stream_kernel, dim3((unsigned)blocks), dim3(ATT_THREADS), lds_bytes, stream, a, n_qt, dpad);
+  hipLaunchKernelGGL(mha_stream_kernel, dim3((unsigned)c.blocks), dim3(ATT_THREADS), (size_t)c.lds, stream, a, c.n_qt, c.dpad);
+  return (int)hipGetLastError();
+}
+
+int mha_row_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
+  static hsp_lds_flags flags;
+  if (c.lds > 32 * 1024)
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_kernel), 160 * 1024, flags)) return e;
+  hipLaunchKernelGGL(mha_kernel, dim3((unsigned)c.blocks), dim3(ATT_THREADS), (size_t)c.lds, stream, a, c.n_qt, c.dpad, c.sp);
   return (int)hipGetLastError();
 }
 
@@ -857,97 +849,142 @@ __global__ __launch_bounds__(64 * NW) void mha_tok_kernel(const hsp_mha_args a, 
 #undef MT_STAMP
 }
 
-template <int NDB, int NW>
-int mha_tok_launch_nw(const hsp_mha_args& a, hipStream_t stream, int64_t blocks, int n_qt) {
-  constexpr int KH = NW / NDB >= 2 ? 2 : 1;
-  const int nkb = (a.Tk + 31) >> 5;
-  const int sp = ((nkb * 32 + 7) & ~7) + 1;
-  const size_t lds_bytes = ((size_t)32 * sp + (KH == 2 ? NDB * 16 * 64 : 0) + 32) * sizeof(float);
+// eight waves: one key block each, two key halves in the PV phase.  (A four-wave form, of which a CU holds more,
+// was measured on 448 / 896 workgroups: 38.7 / 53.5 us against 32.6 / 58.1 -- its per-workgroup chain is twice as
+// long -- and is not built.)
+constexpr int TOK_NW = 8;
+
+template <int NDB>
+int mha_tok_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
   static hsp_lds_flags flags;   // raised ONCE per device, so to the kernel's maximum (Tk = 256), not to this launch's size
   constexpr int kMaxLds = (32 * 265 + NDB * 16 * 64 + 32) * (int)sizeof(float);
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_tok_kernel<NDB, NW>), kMaxLds, flags)) return e;
-  hipLaunchKernelGGL((mha_tok_kernel<NDB, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds_bytes, stream, a, n_qt, sp);
+  if (c.lds > 32 * 1024)
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_tok_kernel<NDB, TOK_NW>), kMaxLds, flags)) return e;
+  hipLaunchKernelGGL((mha_tok_kernel<NDB, TOK_NW>), dim3((unsigned)c.blocks), dim3(64 * TOK_NW), (size_t)c.lds, stream, a, c.n_qt, c.sp);
   return (int)hipGetLastError();
 }
 
-template <int NDB>
-int mha_tok_launch(const hsp_mha_args& a, hipStream_t stream) {
-  const int n_qt = (a.Tq + TQT - 1) / TQT;
-  const int64_t blocks = (int64_t)n_qt * a.H * a.B;
-  if (blocks <= 0 || blocks > 0x7fffffff) return HSP_EINVAL;
-  // eight waves: one key block each, two key halves in the PV phase.  (A four-wave form, of which a CU holds more,
-  // was measured on 448 / 896 workgroups: 38.7 / 53.5 us against 32.6 / 58.1 -- its per-workgroup chain is twice as
-  // long -- and is not built.)
-  return mha_tok_launch_nw<NDB, 8>(a, stream, blocks, n_qt);
-}
-
-}  // namespace
-
-extern "C" int hsp_mha_f32(const hsp_mha_args* ap, void* stream) {
-  if (!ap) return HSP_EINVAL;
-  hsp_mha_args a = *ap;
+// ---------------------------------------------------------------------------------------
+// THE decision: validation, defaults, and which kernel with which launch shape serves the struct.  hsp_mha_f32 launches
+// what this returns and hsp_mha_plan reports it; nothing else chooses.  `a` comes back with the defaults filled in and
+// the force-stream hook decoded (window >= 0).
+int mha_decide(hsp_mha_args& a, mha_choice& c) {
   if (a.q_cs == 0) a.q_cs = a.Tq;
   if (a.k_cs == 0) a.k_cs = a.Tk;
   if (a.v_cs == 0) a.v_cs = a.Tk;
   if (a.o_cs == 0) a.o_cs = a.Tq;
   if (a.q_cs < a.Tq || a.k_cs < a.Tk || a.v_cs < a.Tk || a.o_cs < a.Tq) return HSP_EINVAL;
   if (!a.q || !a.k || !a.v || !a.o || a.B <= 0 || a.H <= 0 || a.D <= 0 || a.Tq <= 0 || a.Tk <= 0) return HSP_EINVAL;
+  if (a.D > 256) return HSP_EINVAL;   // every path: the key-streaming window kernel holds two 128-channel accumulator sets
   if ((a.mask_q == nullptr) != (a.mask_k == nullptr)) return HSP_EINVAL;
   // test hook: window = -(w + 1) selects the key-streaming kernels at any Tk, with window w
   const bool force_stream = a.window < 0;
   if (force_stream) a.window = -(a.window + 1);
+  const int ndb32 = (a.D + 31) / 32;
+  auto grid = [&](int qt) {
+    c.n_qt = (a.Tq + qt - 1) / qt;
+    c.blocks = (int64_t)c.n_qt * a.H * a.B;
+    return c.blocks > 0 && c.blocks <= 0x7fffffff;
+  };
+  auto tok = [&]() {
+    constexpr int KH = TOK_NW / 3 >= 2 ? 2 : 1;   // NDB <= 3: two key halves x head-dim blocks = 6 of the 8 waves
+    const int nkb = (a.Tk + 31) >> 5;
+    c.kernel = HSP_MHA_TOK;
+    c.ndb = ndb32 < 3 ? ndb32 : 3;
+    c.sp = ((nkb * 32 + 7) & ~7) + 1;
+    c.lds = ((int64_t)32 * c.sp + (KH == 2 ? c.ndb * 16 * 64 : 0) + 32) * (int64_t)sizeof(float);
+    return grid(TQT) ? 0 : HSP_EINVAL;
+  };
+  c = mha_choice{};
 #ifdef HSP_TUNING
-  if (a.window == 1003 && a.rel_v && !a.rel_k) {   // in-kernel phase stamps of workgroup 0 -> rel_v (8 x uint64): tools/mha_stamps.py
-    switch ((a.D + 31) / 32) {
-      case 1: return mha_tok_launch<1>(a, static_cast<hipStream_t>(stream));
-      case 2: return mha_tok_launch<2>(a, static_cast<hipStream_t>(stream));
-      default: return mha_tok_launch<3>(a, static_cast<hipStream_t>(stream));
-    }
-  }
+  if (a.window == 1003 && a.rel_v && !a.rel_k) return tok();   // in-kernel phase stamps of workgroup 0 -> rel_v (8 x uint64): tools/mha_stamps.py
 #endif
   if ((a.rel_k || a.rel_v) && (a.window <= 0 || a.Tq != a.Tk)) return HSP_EINVAL;
   if (a.mask_dense && a.mask_dense_bs < (int64_t)a.Tq * a.Tk) return HSP_EINVAL;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  // (the force_stream hook was decoded above, before validation)
   // matrix-core path: no relative-position window, head dim <= 128.  The whole-row kernel while the scores of 32
   // queries fit LDS, the key-streaming one (online softmax) beyond
   if (!a.rel_k && !a.rel_v && a.D <= 128) {
-    int e = -1;
-    // no masks, at most 256 keys: the latency-oriented kernel (NDB <= 3: two key halves x head-dim blocks = 6 waves)
-    if (!force_stream && !a.mask_q && !a.mask_dense && a.Tk >= 4 && a.Tk <= 256 && a.D <= 96) {
-      switch ((a.D + 31) / 32) {
-        case 1: return mha_tok_launch<1>(a, st);
-        case 2: return mha_tok_launch<2>(a, st);
-        default: return mha_tok_launch<3>(a, st);
-      }
-    }
+    // no masks, at most 256 keys: the latency-oriented kernel
+    if (!force_stream && !a.mask_q && !a.mask_dense && a.Tk >= 4 && a.Tk <= 256 && a.D <= 96) return tok();
+    if (!grid(MQT)) return HSP_EINVAL;
+    c.ndb = ndb32;
+    const int DP = ndb32 * 32;
     if (!force_stream) {
-      switch ((a.D + 31) / 32) {
-        case 1: e = mha_mfma_launch<1>(a, st); break;
-        case 2: e = mha_mfma_launch<2>(a, st); break;
-        case 3: e = mha_mfma_launch<3>(a, st); break;
-        default: e = mha_mfma_launch<4>(a, st); break;
+      c.sp = ((a.Tk + 31) & ~31) + 33;  // odd pitch, room for one zero slab column block
+      const int vp = ((a.Tk + 63) & ~63) + 1;
+      const int64_t base = ((int64_t)DP * 32 + 32 * (int64_t)c.sp) * (int64_t)sizeof(float);
+      const int64_t lds_whole = base + (int64_t)DP * vp * (int64_t)sizeof(float);
+      const int64_t lds_slab = base + (int64_t)DP * 65 * (int64_t)sizeof(float);
+      // whole-V needs one round trip less per 64 keys but more LDS: with more workgroups than CUs prefer the
+      // footprint that lets two of them share a CU (their latencies then overlap instead of queueing)
+      const bool whole = lds_whole <= 160 * 1024 && (c.blocks <= 256 || lds_whole <= 80 * 1024 || lds_slab > 80 * 1024);
+      if (whole || lds_slab <= 160 * 1024) {
+        c.kernel = whole ? HSP_MHA_MFMA_WHOLE : HSP_MHA_MFMA_SLAB;
+        c.vp = whole ? vp : 65;
+        c.lds = whole ? lds_whole : lds_slab;
+        return 0;
       }
-      if (e >= 0) return e;
     }
-    switch ((a.D + 31) / 32) {
-      case 1: return mha_mfma_stream_launch<1>(a, st);
-      case 2: return mha_mfma_stream_launch<2>(a, st);
-      case 3: return mha_mfma_stream_launch<3>(a, st);
-      default: return mha_mfma_stream_launch<4>(a, st);
-    }
+    c.kernel = HSP_MHA_MFMA_STREAM;
+    c.sp = SKB + 1;
+    c.vp = SKB + 1;
+    c.lds = ((int64_t)DP * 32 + 32 * (SKB + 1) + (int64_t)DP * (SKB + 1) + 96) * (int64_t)sizeof(float);
+    return 0;
   }
-  const int n_qt = (a.Tq + QT - 1) / QT;
-  const int dpad = (a.D < 128 ? a.D : 128) | 1;
-  const int spad = a.Tk + 1;
-  const int64_t lds_bytes = ((int64_t)a.D * QT + (int64_t)QT * spad + 64 * dpad) * (int64_t)sizeof(float);
-  if (lds_bytes > 160 * 1024 || force_stream) return mha_stream_launch(a, st);
-  static hsp_lds_flags flags;
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_kernel), 160 * 1024, flags)) return e;
-  const int64_t blocks = (int64_t)n_qt * a.H * a.B;
-  hipLaunchKernelGGL(mha_kernel, dim3((unsigned)blocks), dim3(ATT_THREADS), (size_t)lds_bytes,
-                     static_cast<hipStream_t>(stream), a, n_qt, dpad, spad);
-  return (int)hipGetLastError();
+  // scalar kernels: a relative-position window, or head dim 129 .. 256
+  if (!grid(QT)) return HSP_EINVAL;
+  c.ndb = (a.D + 127) / 128;
+  c.dpad = (a.D < 128 ? a.D : 128) | 1;
+  c.sp = a.Tk + 1;
+  c.lds = ((int64_t)a.D * QT + (int64_t)QT * c.sp + 64 * c.dpad) * (int64_t)sizeof(float);
+  c.kernel = HSP_MHA_ROW;
+  if (c.lds > 160 * 1024 || force_stream) {
+    c.kernel = HSP_MHA_ROW_STREAM;
+    c.sp = WKB + 1;
+    c.lds = ((int64_t)a.D * QT + (int64_t)QT * (WKB + 1) + 64 * (int64_t)c.dpad + 3 * QT) * (int64_t)sizeof(float);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int hsp_mha_plan(const hsp_mha_args* ap, int32_t out4[4]) {
+  if (!ap || !out4) return HSP_EINVAL;
+  hsp_mha_args a = *ap;
+  mha_choice c;
+  if (int e = mha_decide(a, c)) return e;
+  out4[0] = c.kernel;
+  out4[1] = c.ndb;
+  out4[2] = (int32_t)c.lds;
+  out4[3] = (int32_t)c.blocks;
+  return 0;
+}
+
+extern "C" int hsp_mha_f32(const hsp_mha_args* ap, void* stream) {
+  if (!ap) return HSP_EINVAL;
+  hsp_mha_args a = *ap;
+  mha_choice c;
+  if (int e = mha_decide(a, c)) return e;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+#define MHA_NDB(launch)                                   \
+  switch (c.ndb) {                                        \
+    case 1: return launch<1>(a, c, st);                   \
+    case 2: return launch<2>(a, c, st);                   \
+    case 3: return launch<3>(a, c, st);                   \
+    default: return launch<4>(a, c, st);                  \
+  }
+  switch (c.kernel) {
+    case HSP_MHA_TOK:
+      switch (c.ndb) {
+        case 1: return mha_tok_launch<1>(a, c, st);
+        case 2: return mha_tok_launch<2>(a, c, st);
+        default: return mha_tok_launch<3>(a, c, st);
+      }
+    case HSP_MHA_MFMA_WHOLE:
+    case HSP_MHA_MFMA_SLAB: MHA_NDB(mha_mfma_launch)
+    case HSP_MHA_MFMA_STREAM: MHA_NDB(mha_mfma_stream_launch)
+    case HSP_MHA_ROW: return mha_row_launch(a, c, st);
+    default: return mha_stream_launch(a, c, st);
+  }
+#undef MHA_NDB
 }

@@ -242,6 +242,14 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
         for (int i = 0; i < 4; ++i) {
           const int key0 = 64 * kg + 16 * g + 4 * i;
           vf[db][i] = mp_shift(vf[db][i], key0 - max(min(key0, Tk - 4), 0));
+          if constexpr (KL) {
+            // a row of fewer than 4 keys (key_len[b] < 4): the window [0, 4) could not be moved back, so its components
+            // past the row's end are another key's V -- zeroed by hand, or 0 * (whatever lies there) reaches the sum
+            if (Tk < 4) {                               // wave-uniform
+#pragma unroll
+              for (int j = 0; j < 4; ++j) vf[db][i][j] = key0 + j < Tk ? vf[db][i][j] : 0.0f;
+            }
+          }
         }
       }
 #pragma unroll
