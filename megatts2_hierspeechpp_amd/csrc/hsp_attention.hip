@@ -8,74 +8,233 @@
 // scores for ALL keys are kept in LDS, soft-maxed by rows, then multiplied with V.  They serve every launch
 // whose score rows fit the CU's LDS (T <= a few hundred on the 50 Hz path); beyond that the key-streaming
 // kernels at the end of this file (online softmax over key blocks) take over, so no launch has a length ceiling.
-#include <atomic>
 #include "hsp_device.h"
 
 namespace {
 
-constexpr int QT = 16;       // queries per workgroup
+constexpr int QT = 16;       // queries per workgroup of the scalar kernels
+constexpr int MQT = 32;      // ... of the MFMA kernels
 constexpr int ATT_THREADS = 256;
+typedef float mha_f32x16 __attribute__((ext_vector_type(16)));
 
-__global__ __launch_bounds__(ATT_THREADS) void mha_kernel(const hsp_mha_args a, int n_qt, int dpad, int spad) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* Qs = lds;                       // [D][QT]
-  float* S = Qs + a.D * QT;              // [QT][spad]
-  float* Vs = S + QT * spad;             // [64][dpad]
+// ---------------------------------------------------------------------------------------
+// The steps the kernels share, each said once.
+
+// Where a workgroup works: its batch item and first query, the channel strides (the host fills the defaults) and the
+// four planes of its head.  Every kernel starts from mha_head_of<queries per workgroup>.
+struct mha_head {
+  int b, i0;
+  int64_t qcs, kcs, vcs, ocs;
+  const float *qh, *kh, *vh;
+  float* oh;
+};
+
+template <int QTILE>
+__device__ __forceinline__ mha_head mha_head_of(const hsp_mha_args& a, int n_qt) {
   int bid = blockIdx.x;
   const int qt = bid % n_qt;
   bid /= n_qt;
   const int h = bid % a.H;
   const int b = bid / a.H;
-  const int i0 = qt * QT;
+  mha_head t;
+  t.b = b;
+  t.i0 = qt * QTILE;
+  t.qcs = a.q_cs, t.kcs = a.k_cs, t.vcs = a.v_cs, t.ocs = a.o_cs;
+  t.qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * a.D * t.qcs;
+  t.kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * a.D * t.kcs;
+  t.vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * a.D * t.vcs;
+  t.oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * a.D * t.ocs;
+  return t;
+}
+
+// masked_fill(mask == 0, -1e4) of attentions.py:175, the one statement of it: a score whose mask value is 0 becomes
+// the VALUE -1e4.  mha_mask applies it to score s of query i < Tq and key j < Tk of batch item b, for the factor masks
+// (mask_q[i] * mask_k[j]; mk = mask_k[b][j] where the caller holds it already) and for the dense mask.
+__device__ __forceinline__ bool mha_masked(float m) { return m == 0.0f; }
+constexpr float MHA_MASKED = -1e4f;
+
+__device__ __forceinline__ void mha_mask(const hsp_mha_args& a, int b, int i, int j, float& s, float mk) {
+  if (a.mask_q && mha_masked(a.mask_q[(int64_t)b * a.Tq + i] * mk)) s = MHA_MASKED;
+  if (a.mask_dense && mha_masked(a.mask_dense[(int64_t)b * a.mask_dense_bs + (int64_t)i * a.Tk + j])) s = MHA_MASKED;
+}
+__device__ __forceinline__ void mha_mask(const hsp_mha_args& a, int b, int i, int j, float& s) {
+  mha_mask(a, b, i, j, s, a.mask_q ? a.mask_k[(int64_t)b * a.Tk + j] : 1.0f);
+}
+
+// The two exponentials of the online softmax: the scalar kernels keep libm's expf, the MFMA ones the hardware exp2
+struct mha_exp_libm { __device__ __forceinline__ float operator()(float x) const { return expf(x); } };
+struct mha_exp_hw { __device__ __forceinline__ float operator()(float x) const { return hsp_exp2e(x); } };
+
+// One online-softmax step of a wave on one query row over the 64 NCOL columns of a key block (columns beyond Tk hold
+// -3e38 and get weight 0): the row becomes exp(s - m_new), and lane 0 moves the row's running maximum *m and sum *l and
+// leaves exp(m_old - m_new), the factor the PV accumulators are rescaled by (0 on the first block), in *al.
+template <int NCOL, class Exp>
+__device__ __forceinline__ void mha_online_row(float* row, int lane, float* m, float* l, float* al, Exp ex) {
+  float sv[NCOL];
+  float mx = -3.0e38f;
+#pragma unroll
+  for (int q = 0; q < NCOL; ++q) { sv[q] = row[lane + 64 * q]; mx = fmaxf(mx, sv[q]); }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  const float mo = *m;
+  const float mn = fmaxf(mo, mx);
+  float sum = 0.0f;
+#pragma unroll
+  for (int q = 0; q < NCOL; ++q) {
+    const float e = sv[q] > -1.0e38f ? ex(sv[q] - mn) : 0.0f;
+    row[lane + 64 * q] = e;
+    sum += e;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (lane == 0) {
+    const float a_ = ex(mo - mn);
+    *al = a_;
+    *l = *l * a_ + sum;
+    *m = mn;
+  }
+}
+
+// O^T accumulator of head-dim block db (queries on the lanes) -> o[d][i0 + l32] = (acc [+ add]) * inv for the rows
+// d < D.  ADD: `add` is this lane's first element of a second partial sum laid out [16][64] (TOK's other key half).
+template <bool ADD = false>
+__device__ __forceinline__ void mha_store_o(const mha_head& t, int D, int db, int l32, int half, const mha_f32x16& acc, float inv,
+                                            const float* add = nullptr) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int d = db * 32 + HSP_ACC_ROW(r, half);
+    if (d < D) t.oh[(int64_t)d * t.ocs + t.i0 + l32] = (ADD ? acc[r] + add[r * 64] : acc[r]) * inv;
+  }
+}
+
+// ---- scalar family (mha_kernel, mha_stream_kernel): 16 queries per workgroup
+// LDS in floats: Qs [D][QT] at 0 | S [QT][sp] | Vs [64][dpad] | the streaming form's running max, sum, rescale [3][QT]
+template <class I> struct row_lds { I S, Vs, state, total; };
+template <class I>
+__host__ __device__ constexpr row_lds<I> row_layout(I D, I sp, I dpad, bool stream) {
+  row_lds<I> L{};
+  L.S = D * QT;
+  L.Vs = L.S + QT * sp;
+  L.state = L.Vs + 64 * dpad;
+  L.total = L.state + (stream ? 3 * QT : 0);
+  return L;
+}
+
+// Q tile, pre-scaled (attentions.py:164 divides the query; timm scales the product), zero beyond Tq
+__device__ __forceinline__ void row_stage_q(const hsp_mha_args& a, const mha_head& t, float* Qs, int tid) {
+  for (int e = tid; e < a.D * QT; e += ATT_THREADS) {
+    const int i = e % QT, d = e / QT;
+    Qs[e] = (t.i0 + i < a.Tq) ? t.qh[(int64_t)d * t.qcs + t.i0 + i] * a.qk_scale : 0.0f;
+  }
+}
+
+// sv[u] = score of query i0 + iq + u against key j < Tk: the dot over the head dim, the relative-key term of a key
+// inside the query's window, the mask
+__device__ __forceinline__ void row_score4(const hsp_mha_args& a, const mha_head& t, const float* Qs, int iq, int j, float sv[4]) {
+  const int D = a.D;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int d = 0; d < D; ++d) {
+    const float kv = t.kh[(int64_t)d * t.kcs + j];
+    const float4 qv = *reinterpret_cast<const float4*>(Qs + d * QT + iq);
+    s0 = fmaf(qv.x, kv, s0);
+    s1 = fmaf(qv.y, kv, s1);
+    s2 = fmaf(qv.z, kv, s2);
+    s3 = fmaf(qv.w, kv, s3);
+  }
+  sv[0] = s0; sv[1] = s1; sv[2] = s2; sv[3] = s3;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = t.i0 + iq + u;
+    float s = sv[u];
+    if (a.rel_k) {
+      const int r = j - i;
+      if (r >= -a.window && r <= a.window && i < a.Tq) {
+        const float* ek = a.rel_k + (int64_t)(r + a.window) * D;
+        float e = 0.0f;
+        for (int d = 0; d < D; ++d) e = fmaf(Qs[d * QT + iq + u], ek[d], e);
+        s += e;
+      }
+    }
+    if (i < a.Tq) mha_mask(a, t.b, i, j, s);
+    sv[u] = s;
+  }
+}
+
+// V slab: keys jb .. jb + 63 (zero from jend on) x head dims d0 .. d0 + 127 -> Vs [64][dpad]; wave w brings dims w, w + 4, ...
+__device__ __forceinline__ void row_stage_v(const mha_head& t, float* Vs, int D, int dpad, int d0, int jb, int jend, int lane, int wave) {
+  for (int dd = wave; dd < 128 && d0 + dd < D; dd += 4)
+    Vs[lane * dpad + dd] = (jb + lane < jend) ? t.vh[(int64_t)(d0 + dd) * t.vcs + jb + lane] : 0.0f;
+}
+
+// ---- MFMA family (mha_mfma_kernel, mha_mfma_stream_kernel): 32 queries per workgroup, DP = head dim padded to 32s
+// LDS in floats: Qs [DP][32] at 0 | S [32][sp] | Vs [DP][vp] | the streaming form's running max, sum, rescale [3][32]
+constexpr int SLAB_VP = 65;   // V pitch of the slab form (64 keys, odd)
+template <class I> struct mfma_lds { I S, Vs, state, total; };
+template <class I>
+__host__ __device__ constexpr mfma_lds<I> mfma_layout(I DP, I sp, I vp, bool stream) {
+  mfma_lds<I> L{};
+  L.S = DP * 32;
+  L.Vs = L.S + 32 * sp;
+  L.state = L.Vs + DP * vp;
+  L.total = L.state + (stream ? 3 * 32 : 0);
+  return L;
+}
+
+// Q tile [DP][32] = scale * q, zero rows beyond D and columns beyond Tq
+template <int DP>
+__device__ __forceinline__ void mfma_stage_q(const hsp_mha_args& a, const mha_head& t, float* Qs, int tid) {
+  const int D = a.D, Tq = a.Tq, i0 = t.i0;
+  const float* qh = t.qh;
+  const int64_t qcs = t.qcs;
+#pragma unroll
+  for (int u = 0; u < DP * 32 / 256; ++u) {
+    const int e = tid + 256 * u;
+    const int i = e & 31, d = e >> 5;
+    Qs[e] = (d < D && i0 + i < Tq) ? qh[(int64_t)d * qcs + i0 + i] * a.qk_scale : 0.0f;
+  }
+}
+
+// S[32 queries][32 keys] = (scale Q)^T K for the key block whose key j sits on this lane (zero beyond Tk): the block's K
+// fragments are fetched in one batch straight from the channel-major plane, the A fragments come from the Q tile
+template <int DP>
+__device__ __forceinline__ mha_f32x16 mfma_score_block(const hsp_mha_args& a, const mha_head& t, const float* Qs, int j, int l32, int half) {
+  const bool jok = j < a.Tk;
+  float kf[DP / 2];
+#pragma unroll
+  for (int kk = 0; kk < DP / 2; ++kk) {
+    const int d = 2 * kk + half;
+    kf[kk] = (jok && d < a.D) ? t.kh[(int64_t)d * t.kcs + j] : 0.0f;
+  }
+  mha_f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+  for (int kk = 0; kk < DP / 2; ++kk)
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Qs[(2 * kk + half) * 32 + l32], kf[kk], acc, 0, 0, 0);
+  return acc;
+}
+
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(ATT_THREADS) void mha_kernel(const hsp_mha_args a, int n_qt, int dpad, int spad) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const auto L = row_layout<int>(a.D, spad, dpad, false);
+  float* Qs = lds;
+  float* S = lds + L.S;
+  float* Vs = lds + L.Vs;
+  const mha_head t = mha_head_of<QT>(a, n_qt);
+  const int i0 = t.i0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = a.D, Tq = a.Tq, Tk = a.Tk;
-  const int64_t qcs = a.q_cs, kcs = a.k_cs, vcs = a.v_cs, ocs = a.o_cs;  // channel strides (host fills the defaults)
-  const float* qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * D * qcs;
-  const float* kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * D * kcs;
-  const float* vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * D * vcs;
-  float* oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * D * ocs;
 
-  // ---- Q tile, pre-scaled (attentions.py:164 divides the query; timm scales the product)
-  for (int e = tid; e < D * QT; e += ATT_THREADS) {
-    const int i = e % QT, d = e / QT;
-    Qs[e] = (i0 + i < Tq) ? qh[(int64_t)d * qcs + i0 + i] * a.qk_scale : 0.0f;
-  }
+  row_stage_q(a, t, Qs, tid);
   __syncthreads();
 
   // ---- scores: wave w owns queries 4w..4w+3, lanes run along keys
-  {
-    const int iq = wave * 4;
-    for (int j = lane; j < Tk; j += 64) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-      for (int d = 0; d < D; ++d) {
-        const float kv = kh[(int64_t)d * kcs + j];
-        const float4 qv = *reinterpret_cast<const float4*>(Qs + d * QT + iq);
-        s0 = fmaf(qv.x, kv, s0);
-        s1 = fmaf(qv.y, kv, s1);
-        s2 = fmaf(qv.z, kv, s2);
-        s3 = fmaf(qv.w, kv, s3);
-      }
-      float sv[4] = {s0, s1, s2, s3};
+  for (int j = lane; j < Tk; j += 64) {
+    float sv[4];
+    row_score4(a, t, Qs, wave * 4, j, sv);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + iq + u;
-        float s = sv[u];
-        if (a.rel_k) {
-          const int r = j - i;
-          if (r >= -a.window && r <= a.window && i < Tq) {
-            const float* ek = a.rel_k + (int64_t)(r + a.window) * D;
-            float t = 0.0f;
-            for (int d = 0; d < D; ++d) t = fmaf(Qs[d * QT + iq + u], ek[d], t);
-            s += t;
-          }
-        }
-        if (a.mask_q && i < Tq) {
-          if (a.mask_q[(int64_t)b * Tq + i] * a.mask_k[(int64_t)b * Tk + j] == 0.0f) s = -1e4f;
-        }
-        if (a.mask_dense && i < Tq && a.mask_dense[(int64_t)b * a.mask_dense_bs + (int64_t)i * Tk + j] == 0.0f) s = -1e4f;
-        S[(iq + u) * spad + j] = s;
-      }
-    }
+    for (int u = 0; u < 4; ++u) S[(wave * 4 + u) * spad + j] = sv[u];
   }
   __syncthreads();
 
@@ -101,15 +260,12 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_kernel(const hsp_mha_args a, 
   // ---- O = P V : thread = (head-dim d, query group of 8)
   const int d = tid & 127, ig = tid >> 7;
   float acc[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) acc[u] = 0.0f;
   for (int d0 = 0; d0 < D; d0 += 128) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc[u] = 0.0f;
     for (int j0 = 0; j0 < Tk; j0 += 64) {
       __syncthreads();  // softmax rows complete (first pass) / previous slab consumed
-      for (int dd = wave; dd < 128 && d0 + dd < D; dd += 4)
-        Vs[lane * dpad + dd] = (j0 + lane < Tk) ? vh[(int64_t)(d0 + dd) * vcs + j0 + lane] : 0.0f;
+      row_stage_v(t, Vs, D, dpad, d0, j0, Tk, lane, wave);
       __syncthreads();
       if (d0 + d < D) {
         const int jn = min(64, Tk - j0);
@@ -132,7 +288,7 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_kernel(const hsp_mha_args a, 
             if (j >= 0 && j < Tk) v = fmaf(S[(ig * 8 + u) * spad + j], a.rel_v[(int64_t)(r + a.window) * D + d0 + d], v);
           }
         }
-        oh[(int64_t)(d0 + d) * ocs + i] = v;
+        t.oh[(int64_t)(d0 + d) * t.ocs + i] = v;
       }
     }
   }
@@ -149,8 +305,6 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_kernel(const hsp_mha_args a, 
 //   O^T[D x 32] = V P^T with M = head dim, N = queries, k = keys: V is staged through LDS in
 //                    64-key slabs (odd pitch: the column reads of both operands are conflict
 //                    free) and the result lands with queries on the lanes -> coalesced stores.
-constexpr int MQT = 32;
-typedef float mha_f32x16 __attribute__((ext_vector_type(16)));
 
 // NDB = ceil(D / 32).  WHOLE_V: all of V (D x Tk) is staged in LDS once, next to the Q tile, so the kernel
 // has three global round trips in sequence (Q + V, the K fragments of this wave's key blocks, nothing else)
@@ -160,22 +314,16 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D = a.D, Tq = a.Tq, Tk = a.Tk;
   constexpr int DP = NDB * 32;
-  float* Qs = lds;                 // [DP][32]  scale * q, zero rows beyond D
-  float* S = Qs + DP * 32;         // [32][sp]
-  float* Vs = S + 32 * sp;         // WHOLE_V: [DP][vp] (vp odd, >= Tk rounded up to 64) ; else [DP][65]
-  int bid = blockIdx.x;
-  const int qt = bid % n_qt;
-  bid /= n_qt;
-  const int h = bid % a.H;
-  const int b = bid / a.H;
-  const int i0 = qt * MQT;
+  const auto L = mfma_layout<int>(DP, sp, WHOLE_V ? vp : SLAB_VP, false);   // WHOLE_V: vp odd, >= Tk rounded up to 64
+  float* Qs = lds;
+  float* S = lds + L.S;
+  float* Vs = lds + L.Vs;
+  const mha_head t = mha_head_of<MQT>(a, n_qt);
+  const int b = t.b, i0 = t.i0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l32 = lane & 31, half = lane >> 5;
-  const int64_t qcs = a.q_cs, kcs = a.k_cs, vcs = a.v_cs, ocs = a.o_cs;  // channel strides (host fills the defaults)
-  const float* qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * D * qcs;
-  const float* kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * D * kcs;
-  const float* vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * D * vcs;
-  float* oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * D * ocs;
+  const float* vh = t.vh;
+  const int64_t vcs = t.vcs;
 
   if constexpr (WHOLE_V) {
     // V rows straight into LDS (LDS-DMA, 4 B per lane, nothing waits here); padding is zeroed by hand
@@ -189,12 +337,7 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
           Vs[d * vp + j0 + lane] = 0.0f;
       }
   }
-#pragma unroll
-  for (int u = 0; u < DP * 32 / 256; ++u) {
-    const int e = tid + 256 * u;
-    const int i = e & 31, d = e >> 5;
-    Qs[e] = (d < D && i0 + i < Tq) ? qh[(int64_t)d * qcs + i0 + i] * a.qk_scale : 0.0f;
-  }
+  mfma_stage_q<DP>(a, t, Qs, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -204,21 +347,9 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
   const int nkb = (Tk + 31) >> 5;
   for (int jb = wave; jb < nkb; jb += 4) {
     const int j = jb * 32 + l32;
-    const bool jok = j < Tk;
-    float kf[DP / 2];
+    const mha_f32x16 acc = mfma_score_block<DP>(a, t, Qs, j, l32, half);
 #pragma unroll
-    for (int kk = 0; kk < DP / 2; ++kk) {
-      const int d = 2 * kk + half;
-      kf[kk] = (jok && d < D) ? kh[(int64_t)d * kcs + j] : 0.0f;
-    }
-    mha_f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-    for (int kk = 0; kk < DP / 2; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Qs[(2 * kk + half) * 32 + l32], kf[kk], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) S[((r & 3) + 8 * (r >> 2) + 4 * half) * sp + j] = acc[r];
+    for (int r = 0; r < 16; ++r) S[HSP_ACC_ROW(r, half) * sp + j] = acc[r];
   }
   __syncthreads();
 
@@ -234,8 +365,8 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
     float mx = -3.0e38f;
     for (int j = lane; j < Tk; j += 64) {
       float sv = row[j];
-      if (a.mask_q && mq * a.mask_k[(int64_t)b * Tk + j] == 0.0f) sv = -1e4f;
-      if (md && md[j] == 0.0f) sv = -1e4f;
+      if (a.mask_q && mha_masked(mq * a.mask_k[(int64_t)b * Tk + j])) sv = MHA_MASKED;
+      if (md && mha_masked(md[j])) sv = MHA_MASKED;
       row[j] = sv;
       mx = fmaxf(mx, sv);
     }
@@ -243,7 +374,7 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     float sum = 0.0f;
     for (int j = lane; j < nkb * 32 + 32 && j < sp; j += 64) {
-      const float e = j < Tk ? __builtin_amdgcn_exp2f((row[j] - mx) * 1.4426950408889634f) : 0.0f;
+      const float e = j < Tk ? hsp_exp2e(row[j] - mx) : 0.0f;
       row[j] = e;
       sum += e;
     }
@@ -269,10 +400,10 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
     for (int j0 = 0; j0 < Tk; j0 += 64) {
       __syncthreads();  // softmax complete (first slab) / previous slab consumed
       for (int d = wave; d < DP; d += 4)
-        Vs[d * 65 + lane] = (d < D && j0 + lane < Tk) ? vh[(int64_t)d * vcs + j0 + lane] : 0.0f;
+        Vs[d * SLAB_VP + lane] = (d < D && j0 + lane < Tk) ? vh[(int64_t)d * vcs + j0 + lane] : 0.0f;
       __syncthreads();
       if (wave < NDB) {
-        const float* va = Vs + (wave * 32 + l32) * 65 + half;
+        const float* va = Vs + (wave * 32 + l32) * SLAB_VP + half;
         const float* pb = S + l32 * sp + j0 + half;
 #pragma unroll 8
         for (int jj = 0; jj < 64; jj += 2)
@@ -280,39 +411,15 @@ __global__ __launch_bounds__(256) void mha_mfma_kernel(const hsp_mha_args a, int
       }
     }
   }
-  if (wave < NDB && i0 + l32 < Tq) {
-    const float inv = inv_s[l32];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (d < D) oh[(int64_t)d * ocs + i0 + l32] = acc[r] * inv;
-    }
-  }
+  if (wave < NDB && i0 + l32 < Tq) mha_store_o(t, D, wave, l32, half, acc, inv_s[l32]);
 }
 
 // What mha_decide (end of this file) settled for a launch: the kernel (HSP_MHA_*), its head-dim blocks, the launch
-// shape and the LDS pitches.  The launchers below only carry it out; hsp_mha_plan reports it.
+// shape and the LDS pitches.  hsp_mha_f32 only carries it out; hsp_mha_plan reports it.
 struct mha_choice {
   int kernel, ndb, n_qt, sp, vp, dpad;
   int64_t lds, blocks;
 };
-
-template <int NDB>
-int mha_mfma_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
-  if (c.kernel == HSP_MHA_MFMA_WHOLE) {
-    static hsp_lds_flags flags;
-    if (c.lds > 32 * 1024)
-      if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_kernel<NDB, true>), 160 * 1024, flags)) return e;
-    hipLaunchKernelGGL((mha_mfma_kernel<NDB, true>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt, c.sp, c.vp);
-  } else {
-    static hsp_lds_flags flags;
-    if (c.lds > 32 * 1024)
-      if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_kernel<NDB, false>), 160 * 1024, flags)) return e;
-    hipLaunchKernelGGL((mha_mfma_kernel<NDB, false>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt, c.sp, c.vp);
-  }
-  return (int)hipGetLastError();
-}
-
 
 // ---------------------------------------------------------------------------------------
 // Key-streaming variants (online softmax): no launch depends on Tk fitting LDS.  Used when the whole-row kernels
@@ -330,32 +437,21 @@ __global__ __launch_bounds__(256) void mha_mfma_stream_kernel(const hsp_mha_args
   const int D = a.D, Tq = a.Tq, Tk = a.Tk;
   constexpr int DP = NDB * 32;
   constexpr int SP = SKB + 1, VP = SKB + 1;
-  float* Qs = lds;                 // [DP][32]  scale * q, zero rows beyond D
-  float* S = Qs + DP * 32;         // [32][SP]
-  float* Vs = S + 32 * SP;         // [DP][VP]
-  float* mrow = Vs + DP * VP;      // [32] running maximum
+  constexpr auto L = mfma_layout<int>(DP, SP, VP, true);
+  float* Qs = lds;
+  float* S = lds + L.S;
+  float* Vs = lds + L.Vs;
+  float* mrow = lds + L.state;     // [32] running maximum
   float* lrow = mrow + 32;         // [32] running sum
   float* arow = lrow + 32;         // [32] rescale factor of the current block
-  int bid = blockIdx.x;
-  const int qt = bid % n_qt;
-  bid /= n_qt;
-  const int h = bid % a.H;
-  const int b = bid / a.H;
-  const int i0 = qt * MQT;
+  const mha_head t = mha_head_of<MQT>(a, n_qt);
+  const int b = t.b, i0 = t.i0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l32 = lane & 31, half = lane >> 5;
-  const int64_t qcs = a.q_cs, kcs = a.k_cs, vcs = a.v_cs, ocs = a.o_cs;
-  const float* qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * D * qcs;
-  const float* kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * D * kcs;
-  const float* vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * D * vcs;
-  float* oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * D * ocs;
+  const float* vh = t.vh;
+  const int64_t vcs = t.vcs;
 
-#pragma unroll
-  for (int u = 0; u < DP * 32 / 256; ++u) {
-    const int e = tid + 256 * u;
-    const int i = e & 31, d = e >> 5;
-    Qs[e] = (d < D && i0 + i < Tq) ? qh[(int64_t)d * qcs + i0 + i] * a.qk_scale : 0.0f;
-  }
+  mfma_stage_q<DP>(a, t, Qs, tid);
   if (tid < 32) { mrow[tid] = -3.0e38f; lrow[tid] = 0.0f; }
   mha_f32x16 oacc;
 #pragma unroll
@@ -371,28 +467,14 @@ __global__ __launch_bounds__(256) void mha_mfma_stream_kernel(const hsp_mha_args
     {
       const int j = j0 + wave * 32 + l32;
       const bool jok = j < Tk;
-      float kf[DP / 2];
-#pragma unroll
-      for (int kk = 0; kk < DP / 2; ++kk) {
-        const int d = 2 * kk + half;
-        kf[kk] = (jok && d < D) ? kh[(int64_t)d * kcs + j] : 0.0f;
-      }
-      mha_f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-      for (int kk = 0; kk < DP / 2; ++kk)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Qs[(2 * kk + half) * 32 + l32], kf[kk], acc, 0, 0, 0);
+      const mha_f32x16 acc = mfma_score_block<DP>(a, t, Qs, j, l32, half);
       const float mk = (a.mask_k && jok) ? a.mask_k[(int64_t)b * Tk + j] : 1.0f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row_i = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int row_i = HSP_ACC_ROW(r, half);
         const int i = i0 + row_i;
         float sv = acc[r];
-        if (i < Tq && jok) {
-          if (a.mask_q && a.mask_q[(int64_t)b * Tq + i] * mk == 0.0f) sv = -1e4f;
-          if (a.mask_dense && a.mask_dense[(int64_t)b * a.mask_dense_bs + (int64_t)i * Tk + j] == 0.0f) sv = -1e4f;
-        }
+        if (i < Tq && jok) mha_mask(a, b, i, j, sv, mk);
         S[row_i * SP + wave * 32 + l32] = jok ? sv : -3.0e38f;
       }
     }
@@ -400,26 +482,7 @@ __global__ __launch_bounds__(256) void mha_mfma_stream_kernel(const hsp_mha_args
     // online softmax of rows 8 wave .. 8 wave + 7 over the block's 128 columns (two per lane)
     for (int u = 0; u < 8; ++u) {
       const int row_i = wave * 8 + u;
-      float* row = S + row_i * SP;
-      const float s0 = row[lane], s1 = row[lane + 64];
-      float mx = fmaxf(s0, s1);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      const float mo = mrow[row_i];
-      const float mn = fmaxf(mo, mx);
-      const float e0 = s0 > -1.0e38f ? __builtin_amdgcn_exp2f((s0 - mn) * 1.4426950408889634f) : 0.0f;
-      const float e1 = s1 > -1.0e38f ? __builtin_amdgcn_exp2f((s1 - mn) * 1.4426950408889634f) : 0.0f;
-      row[lane] = e0;
-      row[lane + 64] = e1;
-      float sum = e0 + e1;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-      if (lane == 0) {
-        const float al = __builtin_amdgcn_exp2f((mo - mn) * 1.4426950408889634f);   // 0 on the first block
-        arow[row_i] = al;
-        lrow[row_i] = lrow[row_i] * al + sum;
-        mrow[row_i] = mn;
-      }
+      mha_online_row<SKB / 64>(S + row_i * SP, lane, mrow + row_i, lrow + row_i, arow + row_i, mha_exp_hw{});
     }
     __syncthreads();
     // O^T += V P^T on the rescaled accumulators: wave w owns head-dim block w, queries sit on the lanes
@@ -433,23 +496,7 @@ __global__ __launch_bounds__(256) void mha_mfma_stream_kernel(const hsp_mha_args
       for (int jj = 0; jj < SKB; jj += 2) oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[jj], pb[jj], oacc, 0, 0, 0);
     }
   }
-  if (wave < NDB && i0 + l32 < Tq) {
-    const float inv = 1.0f / lrow[l32];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (d < D) oh[(int64_t)d * ocs + i0 + l32] = oacc[r] * inv;
-    }
-  }
-}
-
-template <int NDB>
-int mha_mfma_stream_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
-  static hsp_lds_flags flags;
-  if (c.lds > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_mfma_stream_kernel<NDB>), (int)c.lds, flags)) return e;
-  hipLaunchKernelGGL((mha_mfma_stream_kernel<NDB>), dim3((unsigned)c.blocks), dim3(256), (size_t)c.lds, stream, a, c.n_qt);
-  return (int)hipGetLastError();
+  if (wave < NDB && i0 + l32 < Tq) mha_store_o(t, D, wave, l32, half, oacc, 1.0f / lrow[l32]);
 }
 
 // Window (relative-position) kernel, key-streaming form.  Same thread roles as mha_kernel: wave w scores
@@ -461,29 +508,20 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D = a.D, Tq = a.Tq, Tk = a.Tk;
   constexpr int SPW = WKB + 1;
-  float* Qs = lds;                       // [D][QT]
-  float* S = Qs + D * QT;                // [QT][SPW]
-  float* Vs = S + QT * SPW;              // [64][dpad]
-  float* mrow = Vs + 64 * dpad;          // [QT]
+  const auto L = row_layout<int>(D, SPW, dpad, true);
+  float* Qs = lds;
+  float* S = lds + L.S;
+  float* Vs = lds + L.Vs;
+  float* mrow = lds + L.state;           // [QT]
   float* lrow = mrow + QT;
   float* arow = lrow + QT;
-  int bid = blockIdx.x;
-  const int qt = bid % n_qt;
-  bid /= n_qt;
-  const int h = bid % a.H;
-  const int b = bid / a.H;
-  const int i0 = qt * QT;
+  const mha_head t = mha_head_of<QT>(a, n_qt);
+  const int i0 = t.i0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t qcs = a.q_cs, kcs = a.k_cs, vcs = a.v_cs, ocs = a.o_cs;
-  const float* qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * D * qcs;
-  const float* kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * D * kcs;
-  const float* vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * D * vcs;
-  float* oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * D * ocs;
+  float* oh = t.oh;
+  const int64_t ocs = t.ocs;
 
-  for (int e = tid; e < D * QT; e += ATT_THREADS) {
-    const int i = e % QT, d = e / QT;
-    Qs[e] = (i0 + i < Tq) ? qh[(int64_t)d * qcs + i0 + i] * a.qk_scale : 0.0f;
-  }
+  row_stage_q(a, t, Qs, tid);
   if (tid < QT) { mrow[tid] = -3.0e38f; lrow[tid] = 0.0f; }
   const int d = tid & 127, ig = tid >> 7;       // PV role: head dims d and d + 128, queries 8 ig .. 8 ig + 7
   float acc0[8], acc1[8];
@@ -493,73 +531,16 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
   for (int j0 = 0; j0 < Tk; j0 += WKB) {
     const int jn = min(WKB, Tk - j0);
     __syncthreads();   // Q / state ready; previous block's S consumed
-    {
-      const int iq = wave * 4;
-      for (int jj = lane; jj < WKB; jj += 64) {
-        const int j = j0 + jj;
-        float sv[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
-        if (jj < jn) {
-          float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-          for (int dd = 0; dd < D; ++dd) {
-            const float kv = kh[(int64_t)dd * kcs + j];
-            const float4 qv = *reinterpret_cast<const float4*>(Qs + dd * QT + iq);
-            s0 = fmaf(qv.x, kv, s0);
-            s1 = fmaf(qv.y, kv, s1);
-            s2 = fmaf(qv.z, kv, s2);
-            s3 = fmaf(qv.w, kv, s3);
-          }
-          sv[0] = s0; sv[1] = s1; sv[2] = s2; sv[3] = s3;
+    for (int jj = lane; jj < WKB; jj += 64) {
+      float sv[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+      if (jj < jn) row_score4(a, t, Qs, wave * 4, j0 + jj, sv);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int i = i0 + iq + u;
-            float s = sv[u];
-            if (a.rel_k) {
-              const int r = j - i;
-              if (r >= -a.window && r <= a.window && i < Tq) {
-                const float* ek = a.rel_k + (int64_t)(r + a.window) * D;
-                float t = 0.0f;
-                for (int dd = 0; dd < D; ++dd) t = fmaf(Qs[dd * QT + iq + u], ek[dd], t);
-                s += t;
-              }
-            }
-            if (i < Tq) {
-              if (a.mask_q && a.mask_q[(int64_t)b * Tq + i] * a.mask_k[(int64_t)b * Tk + j] == 0.0f) s = -1e4f;
-              if (a.mask_dense && a.mask_dense[(int64_t)b * a.mask_dense_bs + (int64_t)i * Tk + j] == 0.0f) s = -1e4f;
-            }
-            sv[u] = s;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) S[(iq + u) * SPW + jj] = sv[u];
-      }
+      for (int u = 0; u < 4; ++u) S[(wave * 4 + u) * SPW + jj] = sv[u];
     }
     __syncthreads();
     for (int u = 0; u < 4; ++u) {
       const int row_i = wave * 4 + u;
-      float* row = S + row_i * SPW;
-      float sv[WKB / 64];
-      float mx = -3.0e38f;
-#pragma unroll
-      for (int q = 0; q < WKB / 64; ++q) { sv[q] = row[lane + 64 * q]; mx = fmaxf(mx, sv[q]); }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      const float mo = mrow[row_i];
-      const float mn = fmaxf(mo, mx);
-      float sum = 0.0f;
-#pragma unroll
-      for (int q = 0; q < WKB / 64; ++q) {
-        const float e = sv[q] > -1.0e38f ? expf(sv[q] - mn) : 0.0f;
-        row[lane + 64 * q] = e;
-        sum += e;
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-      if (lane == 0) {
-        const float al = expf(mo - mn);
-        arow[row_i] = al;
-        lrow[row_i] = lrow[row_i] * al + sum;
-        mrow[row_i] = mn;
-      }
+      mha_online_row<WKB / 64>(S + row_i * SPW, lane, mrow + row_i, lrow + row_i, arow + row_i, mha_exp_libm{});
     }
     __syncthreads();
 #pragma unroll
@@ -567,8 +548,7 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
     for (int d0 = 0; d0 < D; d0 += 128) {
       for (int js = 0; js < jn; js += 64) {
         __syncthreads();
-        for (int dd = wave; dd < 128 && d0 + dd < D; dd += 4)
-          Vs[lane * dpad + dd] = (js + lane < jn) ? vh[(int64_t)(d0 + dd) * vcs + j0 + js + lane] : 0.0f;
+        row_stage_v(t, Vs, D, dpad, d0, j0 + js, j0 + jn, lane, wave);
         __syncthreads();
         if (d0 + d < D) {
           const int jm = min(64, jn - js);
@@ -589,12 +569,12 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
         for (int u = 0; u < 8; ++u) {
           const int i = i0 + ig * 8 + u;
           if (i >= Tq) continue;
-          float t = 0.0f;
+          float rv = 0.0f;
           for (int r = -a.window; r <= a.window; ++r) {
             const int j = i + r;
-            if (j >= j0 && j < j0 + jn) t = fmaf(S[(ig * 8 + u) * SPW + j - j0], a.rel_v[(int64_t)(r + a.window) * D + d0 + d], t);
+            if (j >= j0 && j < j0 + jn) rv = fmaf(S[(ig * 8 + u) * SPW + j - j0], a.rel_v[(int64_t)(r + a.window) * D + d0 + d], rv);
           }
-          if (d0 == 0) acc0[u] += t; else acc1[u] += t;
+          if (d0 == 0) acc0[u] += rv; else acc1[u] += rv;
         }
       }
     }
@@ -608,23 +588,6 @@ __global__ __launch_bounds__(ATT_THREADS) void mha_stream_kernel(const hsp_mha_a
     if (d + 128 < D) oh[(int64_t)(d + 128) * ocs + i] = acc1[u] * inv;
   }
 }
-
-int mha_stream_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
-  static hsp_lds_flags flags;
-  if (c.lds > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_stream_kernel), 160 * 1024, flags)) return e;   // once per device: the maximum
-  hipLaunchKernelGGL(mha_stream_kernel, dim3((unsigned)c.blocks), dim3(ATT_THREADS), (size_t)c.lds, stream, a, c.n_qt, c.dpad);
-  return (int)hipGetLastError();
-}
-
-int mha_row_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
-  static hsp_lds_flags flags;
-  if (c.lds > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_kernel), 160 * 1024, flags)) return e;
-  hipLaunchKernelGGL(mha_kernel, dim3((unsigned)c.blocks), dim3(ATT_THREADS), (size_t)c.lds, stream, a, c.n_qt, c.dpad, c.sp);
-  return (int)hipGetLastError();
-}
-
 
 // ---------------------------------------------------------------------------------------
 // Short-sequence attention without masks or window (the PLM loop's 4 x 69 heads over a growing prefix, timm
@@ -641,29 +604,39 @@ int mha_row_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t strea
 //     are added through LDS.
 // LDS = 32 x (Tk + pad) scores + the partial-sum buffer: 45 KB at Tk = 256 -> three workgroups per CU.
 constexpr int TQT = 32;
+constexpr int TOK_NW = 8;   // eight waves: one key block each, two key halves in the PV phase.  (A four-wave form, of which a
+                            // CU holds more, was measured on 448 / 896 workgroups: 38.7 / 53.5 us against 32.6 / 58.1 -- its
+                            // per-workgroup chain is twice as long -- and is not built.)
+
+// LDS in floats: S [32][sp] at 0 | red [NDB][16][64], the partial O of the second key half (two key halves only) | inv_s [32]
+constexpr int tok_kh(int nw, int ndb) { return nw / ndb >= 2 ? 2 : 1; }   // key halves in the PV phase (8 waves: 2, 4 waves: 1)
+constexpr int tok_sp(int Tk) { return ((((Tk + 31) >> 5) * 32 + 7) & ~7) + 1; }
+template <class I> struct tok_lds { I red, inv_s, total; };
+template <class I>
+__host__ __device__ constexpr tok_lds<I> tok_layout(I sp, int ndb, int nw) {
+  tok_lds<I> L{};
+  L.red = 32 * sp;
+  L.inv_s = L.red + (tok_kh(nw, ndb) == 2 ? ndb * 16 * 64 : 0);
+  L.total = L.inv_s + 32;
+  return L;
+}
 
 template <int NDB, int NW>
 __global__ __launch_bounds__(64 * NW) void mha_tok_kernel(const hsp_mha_args a, int n_qt, int sp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int KH = NW / NDB >= 2 ? 2 : 1;          // key halves in the PV phase (8 waves: 2, 4 waves: 1)
+  constexpr int KH = tok_kh(NW, NDB);
   const int D = a.D, Tq = a.Tq, Tk = a.Tk;
-  float* S = lds;                        // [32][sp]
-  float* red = S + 32 * sp;              // [NDB][16][64] partial O of the second key half (KH == 2)
-  float* inv_s = red + (KH == 2 ? NDB * 16 * 64 : 0);    // [32]
-  int bid = blockIdx.x;
-  const int qt = bid % n_qt;
-  bid /= n_qt;
-  const int h = bid % a.H;
-  const int b = bid / a.H;
-  const int i0 = qt * TQT;
+  const auto L = tok_layout<int>(sp, NDB, NW);
+  float* S = lds;
+  float* red = lds + L.red;
+  float* inv_s = lds + L.inv_s;
+  const mha_head t = mha_head_of<TQT>(a, n_qt);
+  const int i0 = t.i0;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, half = lane >> 5;
-  const int64_t qcs = a.q_cs, kcs = a.k_cs, vcs = a.v_cs, ocs = a.o_cs;
-  const float* qh = a.q + (int64_t)b * a.q_bs + (int64_t)h * D * qcs;
-  const float* kh = a.k + (int64_t)b * a.k_bs + (int64_t)h * D * kcs;
-  const float* vh = a.v + (int64_t)b * a.v_bs + (int64_t)h * D * vcs;
-  float* oh = a.o + (int64_t)b * a.o_bs + (int64_t)h * D * ocs;
+  const int64_t qcs = t.qcs, kcs = t.kcs, vcs = t.vcs;
+  const float *qh = t.qh, *kh = t.kh, *vh = t.vh;
   const int nkb = (Tk + 31) >> 5;
 #ifdef HSP_TUNING
   unsigned long long* stamps = (a.window == 1003 && blockIdx.x == 0 && tid == 0) ? (unsigned long long*)a.rel_v : nullptr;
@@ -708,7 +681,7 @@ __global__ __launch_bounds__(64 * NW) void mha_tok_kernel(const hsp_mha_args a, 
       }
       const bool jok = j < Tk;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) S[((r & 3) + 8 * (r >> 2) + 4 * half) * sp + j] = jok ? acc[r] : -3.0e38f;
+      for (int r = 0; r < 16; ++r) S[HSP_ACC_ROW(r, half) * sp + j] = jok ? acc[r] : -3.0e38f;
     }
   }
   MT_STAMP(1);
@@ -764,7 +737,7 @@ __global__ __launch_bounds__(64 * NW) void mha_tok_kernel(const hsp_mha_args a, 
 #pragma unroll
       for (int u = 0; u < NR; ++u) {
         const float sv = rows[u][j];
-        const float e = sv > -1.0e38f ? __builtin_amdgcn_exp2f((sv - mx[u]) * 1.4426950408889634f) : 0.0f;
+        const float e = sv > -1.0e38f ? hsp_exp2e(sv - mx[u]) : 0.0f;
         rows[u][j] = e;
         sum[u] += e;
       }
@@ -837,32 +810,11 @@ __global__ __launch_bounds__(64 * NW) void mha_tok_kernel(const hsp_mha_args a, 
   MT_STAMP(5);
   if (KH == 2) __syncthreads();
   MT_STAMP(6);
-  if (kh2 == 0 && i0 + l32 < Tq) {
-    const float inv = inv_s[l32];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (d < D) oh[(int64_t)d * ocs + i0 + l32] = (oacc[r] + (KH == 2 ? red[(db * 16 + r) * 64 + lane] : 0.0f)) * inv;
-    }
-  }
+  if (kh2 == 0 && i0 + l32 < Tq) mha_store_o<KH == 2>(t, D, db, l32, half, oacc, inv_s[l32], red + db * 16 * 64 + lane);
   MT_STAMP(7);
 #undef MT_STAMP
 }
 
-// eight waves: one key block each, two key halves in the PV phase.  (A four-wave form, of which a CU holds more,
-// was measured on 448 / 896 workgroups: 38.7 / 53.5 us against 32.6 / 58.1 -- its per-workgroup chain is twice as
-// long -- and is not built.)
-constexpr int TOK_NW = 8;
-
-template <int NDB>
-int mha_tok_launch(const hsp_mha_args& a, const mha_choice& c, hipStream_t stream) {
-  static hsp_lds_flags flags;   // raised ONCE per device, so to the kernel's maximum (Tk = 256), not to this launch's size
-  constexpr int kMaxLds = (32 * 265 + NDB * 16 * 64 + 32) * (int)sizeof(float);
-  if (c.lds > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_tok_kernel<NDB, TOK_NW>), kMaxLds, flags)) return e;
-  hipLaunchKernelGGL((mha_tok_kernel<NDB, TOK_NW>), dim3((unsigned)c.blocks), dim3(64 * TOK_NW), (size_t)c.lds, stream, a, c.n_qt, c.sp);
-  return (int)hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------
 // THE decision: validation, defaults, and which kernel with which launch shape serves the struct.  hsp_mha_f32 launches
@@ -887,17 +839,16 @@ int mha_decide(hsp_mha_args& a, mha_choice& c) {
     return c.blocks > 0 && c.blocks <= 0x7fffffff;
   };
   auto tok = [&]() {
-    constexpr int KH = TOK_NW / 3 >= 2 ? 2 : 1;   // NDB <= 3: two key halves x head-dim blocks = 6 of the 8 waves
-    const int nkb = (a.Tk + 31) >> 5;
     c.kernel = HSP_MHA_TOK;
     c.ndb = ndb32 < 3 ? ndb32 : 3;
-    c.sp = ((nkb * 32 + 7) & ~7) + 1;
-    c.lds = ((int64_t)32 * c.sp + (KH == 2 ? c.ndb * 16 * 64 : 0) + 32) * (int64_t)sizeof(float);
+    c.sp = tok_sp(a.Tk);
+    c.lds = tok_layout<int64_t>(c.sp, c.ndb, TOK_NW).total * (int64_t)sizeof(float);
     return grid(TQT) ? 0 : HSP_EINVAL;
   };
   c = mha_choice{};
 #ifdef HSP_TUNING
-  if (a.window == 1003 && a.rel_v && !a.rel_k) return tok();   // in-kernel phase stamps of workgroup 0 -> rel_v (8 x uint64): tools/mha_stamps.py
+  // in-kernel phase stamps of workgroup 0 -> rel_v (8 x uint64): tools/mha_stamps.py.  Inside TOK's own range only: its LDS limit is raised for Tk <= 256
+  if (a.window == 1003 && a.rel_v && !a.rel_k && a.Tk >= 4 && a.Tk <= 256 && a.D <= 96) return tok();
 #endif
   if ((a.rel_k || a.rel_v) && (a.window <= 0 || a.Tq != a.Tk)) return HSP_EINVAL;
   if (a.mask_dense && a.mask_dense_bs < (int64_t)a.Tq * a.Tk) return HSP_EINVAL;
@@ -912,15 +863,14 @@ int mha_decide(hsp_mha_args& a, mha_choice& c) {
     if (!force_stream) {
       c.sp = ((a.Tk + 31) & ~31) + 33;  // odd pitch, room for one zero slab column block
       const int vp = ((a.Tk + 63) & ~63) + 1;
-      const int64_t base = ((int64_t)DP * 32 + 32 * (int64_t)c.sp) * (int64_t)sizeof(float);
-      const int64_t lds_whole = base + (int64_t)DP * vp * (int64_t)sizeof(float);
-      const int64_t lds_slab = base + (int64_t)DP * 65 * (int64_t)sizeof(float);
+      const int64_t lds_whole = mfma_layout<int64_t>(DP, c.sp, vp, false).total * (int64_t)sizeof(float);
+      const int64_t lds_slab = mfma_layout<int64_t>(DP, c.sp, SLAB_VP, false).total * (int64_t)sizeof(float);
       // whole-V needs one round trip less per 64 keys but more LDS: with more workgroups than CUs prefer the
       // footprint that lets two of them share a CU (their latencies then overlap instead of queueing)
       const bool whole = lds_whole <= 160 * 1024 && (c.blocks <= 256 || lds_whole <= 80 * 1024 || lds_slab > 80 * 1024);
       if (whole || lds_slab <= 160 * 1024) {
         c.kernel = whole ? HSP_MHA_MFMA_WHOLE : HSP_MHA_MFMA_SLAB;
-        c.vp = whole ? vp : 65;
+        c.vp = whole ? vp : SLAB_VP;
         c.lds = whole ? lds_whole : lds_slab;
         return 0;
       }
@@ -928,7 +878,7 @@ int mha_decide(hsp_mha_args& a, mha_choice& c) {
     c.kernel = HSP_MHA_MFMA_STREAM;
     c.sp = SKB + 1;
     c.vp = SKB + 1;
-    c.lds = ((int64_t)DP * 32 + 32 * (SKB + 1) + (int64_t)DP * (SKB + 1) + 96) * (int64_t)sizeof(float);
+    c.lds = mfma_layout<int64_t>(DP, c.sp, c.vp, true).total * (int64_t)sizeof(float);
     return 0;
   }
   // scalar kernels: a relative-position window, or head dim 129 .. 256
@@ -936,14 +886,32 @@ int mha_decide(hsp_mha_args& a, mha_choice& c) {
   c.ndb = (a.D + 127) / 128;
   c.dpad = (a.D < 128 ? a.D : 128) | 1;
   c.sp = a.Tk + 1;
-  c.lds = ((int64_t)a.D * QT + (int64_t)QT * c.sp + 64 * c.dpad) * (int64_t)sizeof(float);
+  c.lds = row_layout<int64_t>(a.D, c.sp, c.dpad, false).total * (int64_t)sizeof(float);
   c.kernel = HSP_MHA_ROW;
   if (c.lds > 160 * 1024 || force_stream) {
     c.kernel = HSP_MHA_ROW_STREAM;
     c.sp = WKB + 1;
-    c.lds = ((int64_t)a.D * QT + (int64_t)QT * (WKB + 1) + 64 * (int64_t)c.dpad + 3 * QT) * (int64_t)sizeof(float);
+    c.lds = row_layout<int64_t>(a.D, c.sp, c.dpad, true).total * (int64_t)sizeof(float);
   }
   return 0;
+}
+
+// The kernels that are built per head-dim block count.  TOK is raised once per device, so to its maximum (Tk = 256),
+// not to this launch's size; the MFMA streaming kernel's size does not depend on the launch.
+template <int NDB>
+int mha_launch_ndb(const hsp_mha_args& a, const mha_choice& c, hipStream_t st) {
+  const int lds = (int)c.lds;
+  switch (c.kernel) {
+    case HSP_MHA_TOK:
+      if constexpr (NDB <= 3) {
+        constexpr int kMaxLds = tok_layout<int>(tok_sp(256), NDB, TOK_NW).total * (int)sizeof(float);
+        return hsp_launch<mha_tok_kernel<NDB, TOK_NW>>(c.blocks, 64 * TOK_NW, lds, kMaxLds, st, a, c.n_qt, c.sp);
+      }
+      return HSP_EINVAL;   // mha_decide gives TOK at most three blocks
+    case HSP_MHA_MFMA_WHOLE: return hsp_launch<mha_mfma_kernel<NDB, true>>(c.blocks, 256, lds, 160 * 1024, st, a, c.n_qt, c.sp, c.vp);
+    case HSP_MHA_MFMA_SLAB: return hsp_launch<mha_mfma_kernel<NDB, false>>(c.blocks, 256, lds, 160 * 1024, st, a, c.n_qt, c.sp, c.vp);
+    default: return hsp_launch<mha_mfma_stream_kernel<NDB>>(c.blocks, 256, lds, lds, st, a, c.n_qt);
+  }
 }
 
 }  // namespace
@@ -966,25 +934,13 @@ extern "C" int hsp_mha_f32(const hsp_mha_args* ap, void* stream) {
   mha_choice c;
   if (int e = mha_decide(a, c)) return e;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-#define MHA_NDB(launch)                                   \
-  switch (c.ndb) {                                        \
-    case 1: return launch<1>(a, c, st);                   \
-    case 2: return launch<2>(a, c, st);                   \
-    case 3: return launch<3>(a, c, st);                   \
-    default: return launch<4>(a, c, st);                  \
+  if (c.kernel == HSP_MHA_ROW) return hsp_launch<mha_kernel>(c.blocks, ATT_THREADS, (int)c.lds, 160 * 1024, st, a, c.n_qt, c.dpad, c.sp);
+  if (c.kernel == HSP_MHA_ROW_STREAM)
+    return hsp_launch<mha_stream_kernel>(c.blocks, ATT_THREADS, (int)c.lds, 160 * 1024, st, a, c.n_qt, c.dpad);
+  switch (c.ndb) {
+    case 1: return mha_launch_ndb<1>(a, c, st);
+    case 2: return mha_launch_ndb<2>(a, c, st);
+    case 3: return mha_launch_ndb<3>(a, c, st);
+    default: return mha_launch_ndb<4>(a, c, st);
   }
-  switch (c.kernel) {
-    case HSP_MHA_TOK:
-      switch (c.ndb) {
-        case 1: return mha_tok_launch<1>(a, c, st);
-        case 2: return mha_tok_launch<2>(a, c, st);
-        default: return mha_tok_launch<3>(a, c, st);
-      }
-    case HSP_MHA_MFMA_WHOLE:
-    case HSP_MHA_MFMA_SLAB: MHA_NDB(mha_mfma_launch)
-    case HSP_MHA_MFMA_STREAM: MHA_NDB(mha_mfma_stream_launch)
-    case HSP_MHA_ROW: return mha_row_launch(a, c, st);
-    default: return mha_stream_launch(a, c, st);
-  }
-#undef MHA_NDB
 }

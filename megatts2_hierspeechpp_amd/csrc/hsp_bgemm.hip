@@ -458,12 +458,9 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
 template <int TM, int TN, bool LN, bool EXT>
 int bg_launch(const hsp_conv1d_args& a, hipStream_t s, int n_mt, int n_nt, int total) {
   using C = BgCfg<TM, TN>;
-  static hsp_lds_flags flags;
-  if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(bgemm_kernel<TM, TN, LN, EXT>), C::LDS_BYTES, flags)) return e;
+  static_assert(C::LDS_BYTES > 32 * 1024, "every launch raises the LDS limit");
   const int per_xcd = (total + 7) / 8;
-  hipLaunchKernelGGL((bgemm_kernel<TM, TN, LN, EXT>), dim3((unsigned)(8 * per_xcd)), dim3(512), C::LDS_BYTES, s, a, n_mt, n_nt,
-                     per_xcd, total);
-  return (int)hipGetLastError();
+  return hsp_launch<bgemm_kernel<TM, TN, LN, EXT>>(8 * per_xcd, 512, C::LDS_BYTES, C::LDS_BYTES, s, a, n_mt, n_nt, per_xcd, total);
 }
 
 // does the launch need bg_epilogue_ext?

@@ -402,8 +402,7 @@ struct Prod {
 };
 
 // ------------------------------------------------------------------------ kernel
-// C/D map of the 32x32 MFMA forms: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
-#define HSP_ACC_ROW(r, half) (((r) & 3) + 8 * ((r) >> 2) + 4 * (half))
+// (HSP_ACC_ROW, the C/D map of the 32x32 MFMA forms, is hsp_device.h's)
 
 // The consumer role of one wave: a (TM x TN) grid of 32 x 32 MFMA blocks at rows m0 + wm * TM * 32, columns
 // t0 + wn * TN * 32 of the tile.  TM / TN are the shape's own (C::kTM, C::kTN) except in a narrow tail tile

@@ -342,11 +342,8 @@ extern "C" int hsp_cprod3_f32(const hsp_cprod3_args* ap, void* stream) {
   const int n_mt = a.C / CP_BM, n_nt = (a.Np + CP_BN - 1) / CP_BN;
   const int64_t blocks = (int64_t)a.bins * n_mt * n_nt;
   constexpr int lds_bytes = 2 * CP_BUF * (int)sizeof(float);
-  static hsp_lds_flags flags;
-  if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(cprod3_kernel), kMaxLdsBytes, flags)) return e;
-  hipLaunchKernelGGL(cprod3_kernel, dim3((unsigned)blocks), dim3(CP_THREADS), lds_bytes, static_cast<hipStream_t>(stream), a, n_mt,
-                     n_nt);
-  return (int)hipGetLastError();
+  static_assert(lds_bytes > 32 * 1024, "every launch raises the LDS limit");
+  return hsp_launch<cprod3_kernel>(blocks, CP_THREADS, lds_bytes, kMaxLdsBytes, static_cast<hipStream_t>(stream), a, n_mt, n_nt);
 }
 
 extern "C" int hsp_dftseg_weight_spectrum_f32(const float* w, int32_t k, int32_t C, int32_t w_ld, const double* tw, float* out,

@@ -23,7 +23,29 @@ inline int hsp_raise_lds_limit(const void* kernel, int bytes, hsp_lds_flags& fla
   return 0;
 }
 
+// THE launch of a kernel with dynamic LDS: raise its limit to `lds_max` (once per device, and only when this launch
+// needs more than the 32 KB every kernel may have), launch, report.  The flags are a static of this function: every
+// call site of a kernel that passes the same argument types shares one set, so there is none to declare and none to
+// share between two kernels by mistake (a site with other argument types gets its own set and raises once more, which
+// is harmless).  `lds_max` is the most the kernel is ever launched with, not this launch's size: the raise happens
+// once.  The caller has checked 0 < blocks <= 0x7fffffff.
+template <auto Kernel, class... Args>
+int hsp_launch(int64_t blocks, int threads, int lds_bytes, int lds_max, hipStream_t s, Args... args) {
+  static hsp_lds_flags flags;
+  if (lds_bytes > 32 * 1024)
+    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(Kernel), lds_max, flags)) return e;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3((unsigned)threads), (size_t)lds_bytes, s, args...);
+  return (int)hipGetLastError();
+}
+
+// C/D map of the 32x32 MFMA forms: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+#define HSP_ACC_ROW(r, half) (((r) & 3) + 8 * ((r) >> 2) + 4 * (half))
+
 __device__ __forceinline__ float hsp_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// exp(x) on the hardware exp2 (v_exp_f32): 2^(x log2 e)
+constexpr float HSP_LOG2E = 1.4426950408889634f;
+__device__ __forceinline__ float hsp_exp2e(float x) { return __builtin_amdgcn_exp2f(x * HSP_LOG2E); }
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1) on the hardware exp2 (v_exp_f32) and a true division: ~12 instructions
 // instead of ocml tanhf's ~100 (which dominated the GELU / WN-gate epilogues).  Absolute error < 2e-7

@@ -55,7 +55,6 @@ typedef float ds_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ds_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DS_N = 128, DS_H = 64;
 constexpr int DS_MEM = 256;                                     // threads of a workgroup
-#define DS_ACC_ROW(r, half) (((r) & 3) + 8 * ((r) >> 2) + 4 * (half))
 
 // An item = `cg` channel rows of one utterance over a CHUNK of S consecutive segments (of every phase): the input
 // samples those segments read -- padded-time range [d s0 hop, d ((s0 + S - 1) hop + 128)) -- are one contiguous stretch
@@ -324,7 +323,7 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   // Two waves share a 32-column block: wave half `wh` owns the bins 16 wh .. 16 wh + 15 of E and O (rows 32 wh + l32 of
   // the 64 x 64 table: Re of those bins in tile rows 0..15, Im in 16..31), i.e. the output bins k and 64 - k; the wave
   // pairs (0, 1) and (2, 3) work on alternate column blocks.  A fragments: taps 2 ks + half, fetched once per launch.
-  // Accumulator register r (and r + 8) holds bin 16 wh + DS_ACC_ROW(r, half); its twiddle W^k comes out of LDS.
+  // Accumulator register r (and r + 8) holds bin 16 wh + HSP_ACC_ROW(r, half); its twiddle W^k comes out of LDS.
   const int wh = wave & 1, pairw = wave >> 1;
   float fa[32];
   {
@@ -623,7 +622,7 @@ __device__ __forceinline__ void ds_inv_stash(float* dst, int kf0, const float (&
   }
 }
 // Scatter of a block's time samples into the LDS image of the output rows: accumulator register r of wave (eo, wh) is
-// sample i = 2 (32 wh + DS_ACC_ROW(r, half)) + eo of the column's segment; the first `hop` samples of a segment are
+// sample i = 2 (32 wh + HSP_ACC_ROW(r, half)) + eo of the column's segment; the first `hop` samples of a segment are
 // valid.  rp = the address of this lane's sample of register 0; no test against the tensor's end (see above).
 template <int D>
 __device__ __forceinline__ void ds_inv_scatter_d(float* rp, int d, int i0, int hop, int wh, const ds_f32x16& acc, const ds_f32x16& acc2) {
@@ -1121,24 +1120,10 @@ extern "C" int hsp_dftseg_fwd_f32(const hsp_dftseg_args* ap, void* stream) {
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
   if (a.act_len && !act) return HSP_EINVAL;                    // per-row lengths belong to the fused activation
-  if (a.act_len) {
-    static hsp_lds_flags flags_rag;
-    if (lds_bytes > 32 * 1024)
-      if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_fwd_kernel<true, true>), 160 * 1024, flags_rag))
-        return e;
-    hipLaunchKernelGGL((dftseg_fwd_kernel<true, true>), dim3((unsigned)blocks), dim3(DS_MEM), lds_bytes,
-                       static_cast<hipStream_t>(stream), a, G);
-    return (int)hipGetLastError();
-  }
-  static hsp_lds_flags flags[2];
-  const void* kern = act ? reinterpret_cast<const void*>(dftseg_fwd_kernel<true>) : reinterpret_cast<const void*>(dftseg_fwd_kernel<false>);
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(kern, 160 * 1024, flags[act])) return e;
-  if (act)
-    hipLaunchKernelGGL(dftseg_fwd_kernel<true>, dim3((unsigned)blocks), dim3(DS_MEM), lds_bytes, static_cast<hipStream_t>(stream), a, G);
-  else
-    hipLaunchKernelGGL(dftseg_fwd_kernel<false>, dim3((unsigned)blocks), dim3(DS_MEM), lds_bytes, static_cast<hipStream_t>(stream), a, G);
-  return (int)hipGetLastError();
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (a.act_len) return hsp_launch<dftseg_fwd_kernel<true, true>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
+  if (act) return hsp_launch<dftseg_fwd_kernel<true>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
+  return hsp_launch<dftseg_fwd_kernel<false>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
 }
 
 extern "C" int hsp_dftseg_inv_f32(const hsp_dftseg_args* ap, void* stream) {
@@ -1151,12 +1136,7 @@ extern "C" int hsp_dftseg_inv_f32(const hsp_dftseg_args* ap, void* stream) {
   const int64_t items = (int64_t)a.B * G.ngrp * G.nchunk;
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
-  static hsp_lds_flags flags;
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_inv_kernel), 160 * 1024, flags)) return e;
-  hipLaunchKernelGGL(dftseg_inv_kernel, dim3((unsigned)blocks), dim3(DS_MEM), lds_bytes, static_cast<hipStream_t>(stream), a, G,
-                     nbuf);
-  return (int)hipGetLastError();
+  return hsp_launch<dftseg_inv_kernel>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, static_cast<hipStream_t>(stream), a, G, nbuf);
 }
 
 extern "C" int hsp_dftseg_pair_supported(const hsp_dftseg_args* inv, const hsp_dftseg_args* fwd) {
@@ -1171,17 +1151,9 @@ extern "C" int hsp_dftseg_pair_f32(const hsp_dftseg_args* inv, const hsp_dftseg_
   const int64_t items = (int64_t)inv->B * G.ngrp;
   if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
   const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
-  if (fwd->act_len) {
-    static hsp_lds_flags flags_rag;
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_pair_kernel<true>), 160 * 1024, flags_rag)) return e;
-    hipLaunchKernelGGL(dftseg_pair_kernel<true>, dim3((unsigned)blocks), dim3(512), lds_bytes, static_cast<hipStream_t>(stream),
-                       *inv, *fwd, G);
-    return (int)hipGetLastError();
-  }
-  static hsp_lds_flags flags;
-  if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(dftseg_pair_kernel<false>), 160 * 1024, flags)) return e;
-  hipLaunchKernelGGL(dftseg_pair_kernel<false>, dim3((unsigned)blocks), dim3(512), lds_bytes, static_cast<hipStream_t>(stream), *inv,
-                     *fwd, G);
-  return (int)hipGetLastError();
+  // (offT holds at least the 2 x 128 x 32 floats in front of it, so every launch is above 32 KB and raises the limit)
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (fwd->act_len) return hsp_launch<dftseg_pair_kernel<true>>(blocks, 512, (int)lds_bytes, 160 * 1024, st, *inv, *fwd, G);
+  return hsp_launch<dftseg_pair_kernel<false>>(blocks, 512, (int)lds_bytes, 160 * 1024, st, *inv, *fwd, G);
 }
 

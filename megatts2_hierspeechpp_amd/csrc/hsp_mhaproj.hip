@@ -35,7 +35,6 @@ typedef float mp_f4u __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int MP_QT = 16;  // queries per workgroup
 constexpr int MP_NW = 8;   // waves
-constexpr float MP_LOG2E = 1.4426950408889634f;
 constexpr float MP_NEG = -3.0e38f;
 
 template <int H_, int D_>
@@ -217,7 +216,7 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
     mg = fmaxf(mg, __shfl_xor(mg, 16, 64));
     mg = fmaxf(mg, __shfl_xor(mg, 32, 64));
     const float m_new = fmaxf(m_run, mg);             // finite: every group holds at least one real key
-    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * MP_LOG2E);   // first group: 2^(-huge) = 0
+    const float alpha = hsp_exp2e(m_run - m_new);   // first group: 2^(-huge) = 0
     m_run = m_new;
     float ls = 0.0f;
 #pragma unroll
@@ -225,7 +224,7 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float sv = sacc[j][i];
-        const float e = sv > -1.0e38f ? __builtin_amdgcn_exp2f((sv - m_new) * MP_LOG2E) : 0.0f;
+        const float e = sv > -1.0e38f ? hsp_exp2e(sv - m_new) : 0.0f;
         sacc[j][i] = e;
         ls += e;
       }
@@ -326,7 +325,7 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
     float f[KS], lt = 0.0f;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      f[s] = __builtin_amdgcn_exp2f((Mpart[(h + Cfg::H * s) * MP_QT + x] - mt) * MP_LOG2E);   // a wave without keys: 2^(-huge) = 0
+      f[s] = hsp_exp2e(Mpart[(h + Cfg::H * s) * MP_QT + x] - mt);   // a wave without keys: 2^(-huge) = 0
       lt = fmaf(Lpart[(h + Cfg::H * s) * MP_QT + x], f[s], lt);
     }
     const float inv = 1.0f / lt;
@@ -399,11 +398,7 @@ int mp_launch(const hsp_mha_proj_args& a, hipStream_t s) {
   if (blocks <= 0 || blocks > 0x7fffffff) return HSP_EINVAL;
   constexpr int lds_bytes = Cfg::LDS_TOTAL * (int)sizeof(float);
   static_assert(lds_bytes <= 160 * 1024, "LDS");
-  static hsp_lds_flags flags;
-  if (lds_bytes > 32 * 1024)
-    if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(mha_proj_kernel<Cfg, KL>), lds_bytes, flags)) return e;
-  hipLaunchKernelGGL((mha_proj_kernel<Cfg, KL>), dim3((unsigned)blocks), dim3(64 * MP_NW), lds_bytes, s, a, n_qt);
-  return (int)hipGetLastError();
+  return hsp_launch<mha_proj_kernel<Cfg, KL>>(blocks, 64 * MP_NW, lds_bytes, lds_bytes, s, a, n_qt);
 }
 }  // namespace
 

@@ -98,22 +98,33 @@ def layernorm_mod(x, eps: float, mask=None, shift=None, scale=None, gamma=None, 
     return y
 
 
+def _mha_qkv(a, q, k, v, n_heads: int, qk_scale: float):
+    """What MhaArgs and MhaProjArgs share: q [B, H*D, Tq], k / v [B, H*D, Tk] with unit time stride, their batch and
+    channel strides, the sizes and the scale.  Returns (B, H*D, Tq, Tk)."""
+    B, HD, Tq = q.shape
+    Tk = k.shape[2]
+    for t_, T_ in ((q, Tq), (k, Tk), (v, Tk)):
+        assert (t_.stride(2) == 1 or T_ == 1), "attention operands need unit time stride"
+    a.q, a.k, a.v = L.fptr(q), L.fptr(k), L.fptr(v)
+    a.q_bs, a.k_bs, a.v_bs = q.stride(0), k.stride(0), v.stride(0)
+    a.q_cs, a.k_cs, a.v_cs = q.stride(1), k.stride(1), v.stride(1)
+    a.B, a.H, a.D, a.Tq, a.Tk = B, n_heads, HD // n_heads, Tq, Tk
+    a.qk_scale = float(qk_scale)
+    return B, HD, Tq, Tk
+
+
 def mha(q, k, v, n_heads: int, qk_scale: float, mask_q=None, mask_k=None, rel_k=None, rel_v=None, window=0,
         out=None, mask_dense=None, force_stream=False):
     """q [B, H*D, Tq], k/v [B, H*D, Tk] (any batch / channel strides, unit time stride) -> [B, H*D, Tq].
     Strided views let a batch live side by side on the column axis of one [C, B*T] matrix
     (``x.view(C, B, T).permute(1, 0, 2)``), the layout of the PLM loop."""
-    B, HD, Tq = q.shape
-    Tk = k.shape[2]
-    o = torch.empty(B, HD, Tq, dtype=torch.float32, device=q.device) if out is None else out
-    for t_, T_ in ((q, Tq), (k, Tk), (v, Tk), (o, Tq)):
-        assert (t_.stride(2) == 1 or T_ == 1) and t_.stride(1) >= T_, "attention operands need unit time stride"
     a = L.MhaArgs()
-    a.q, a.k, a.v, a.o = L.fptr(q), L.fptr(k), L.fptr(v), L.fptr(o)
-    a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    a.q_cs, a.k_cs, a.v_cs, a.o_cs = q.stride(1), k.stride(1), v.stride(1), o.stride(1)
-    a.B, a.H, a.D, a.Tq, a.Tk = B, n_heads, HD // n_heads, Tq, Tk
-    a.qk_scale = float(qk_scale)
+    B, HD, Tq, Tk = _mha_qkv(a, q, k, v, n_heads, qk_scale)
+    o = torch.empty(B, HD, Tq, dtype=torch.float32, device=q.device) if out is None else out
+    assert o.stride(2) == 1 or Tq == 1, "attention operands need unit time stride"
+    for t_, T_ in ((q, Tq), (k, Tk), (v, Tk), (o, Tq)):
+        assert t_.stride(1) >= T_, "attention operands need unit time stride"
+    a.o, a.o_bs, a.o_cs = L.fptr(o), o.stride(0), o.stride(1)
     if mask_q is not None:
         a.mask_q, a.mask_k = L.fptr(_c(mask_q)), L.fptr(_c(mask_k))
     if rel_k is not None:
@@ -146,18 +157,11 @@ def mha_proj(q, k, v, n_heads: int, qk_scale: float, wt, bias=None, mask=None, c
     stride (strided views as for ``mha``); ``wt`` [M, H*D] row-major (the nn.Linear weight as stored); ``res`` / ``out``
     [B, M, Tq] with ANY strides; ``mask`` [B, 1, Tq] or [B, Tq]; ``cscale`` [B, M]; ``key_len`` (device int64 [B]): the
     softmax of row b covers keys [0, key_len[b]) only."""
-    B, HD, Tq = q.shape
-    Tk = k.shape[2]
+    a = L.MhaProjArgs()
+    B, HD, Tq, Tk = _mha_qkv(a, q, k, v, n_heads, qk_scale)
     M = wt.shape[0]
     y = torch.empty(B, M, Tq, dtype=torch.float32, device=q.device) if out is None else out
     assert y.shape == (B, M, Tq) and wt.shape == (M, HD) and wt.stride(1) == 1
-    for t_, T_ in ((q, Tq), (k, Tk), (v, Tk)):
-        assert (t_.stride(2) == 1 or T_ == 1), "attention operands need unit time stride"
-    a = L.MhaProjArgs()
-    a.q, a.k, a.v = L.fptr(q), L.fptr(k), L.fptr(v)
-    a.q_bs, a.q_cs, a.k_bs, a.k_cs, a.v_bs, a.v_cs = q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1)
-    a.B, a.H, a.D, a.Tq, a.Tk = B, n_heads, HD // n_heads, Tq, Tk
-    a.qk_scale = float(qk_scale)
     a.wt, a.M, a.wt_ld = L.fptr(wt), M, wt.stride(0)
     if bias is not None:
         a.bias = L.fptr(bias)

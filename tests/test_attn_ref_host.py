@@ -230,6 +230,39 @@ def test_mha_case_takes_the_kernel_its_id_names(id, L):
     assert forced == ("natural" not in id and kern in (R.MSTR, R.RSTR)), id
 
 
+# out4 = (kernel, NDB, LDS bytes, workgroups) of one case per reachable (kernel, NDB) pair, written down as numbers from
+# the library as it stood before the LDS sizes of mha_decide moved into the kernels' layout functions: a change to those
+# functions, to a pitch or to a threshold shows here.
+PINNED_PLANS = {
+    "TOK1_d20_tq1_tk4_contig": (0, 1, 8448, 6),
+    "TOK2_d33_tq16_tk7_side1": (0, 2, 12544, 6),
+    "TOK3_d69_tq31_tk9_ocs": (0, 3, 16640, 6),
+    "WHOLE1_d20_tq17_tk1_contig_nomask": (1, 1, 20736, 6),
+    "WHOLE2_d33_tq15_tk2_side1_factor": (1, 2, 33152, 6),
+    "WHOLE3_d69_tq16_tk3_side4_nomask": (1, 3, 45568, 6),
+    "WHOLE4_d97_tq31_tk63_own_nomask": (1, 4, 62080, 6),
+    "SLAB1_d32_tq300_tk270_side1": (2, 1, 53504, 260),
+    "SLAB2_d64_tq300_tk270_contig": (2, 2, 65920, 260),
+    "SLAB3_d69_tq33_tk300_side4_causal": (2, 3, 82432, 8),
+    "SLAB4_d128_tq33_tk300_contig": (2, 4, 94848, 4),
+    "MSTR1_d20_tq17_tk127_contig_nomask": (3, 1, 37504, 4),
+    "MSTR2_d64_tq33_tk128_side1_factor": (3, 2, 58112, 8),
+    "MSTR3_d69_tq31_tk129_side4_causal": (3, 3, 78720, 4),
+    "MSTR4_d128_tq33_tk257_own_factor+irreg": (3, 4, 99328, 8),
+    "ROW1_d20_t17_w4_contig_factor": (4, 1, 7808, 8),
+    "ROW2_d129_t16_w2_side4_causal": (4, 2, 42368, 4),
+    "RSTR1_d20_t255_w4_contig_factor": (5, 1, 23296, 64),
+    "RSTR2_d160_t257_w3_side4_causal": (5, 2, 59904, 68),
+}
+
+
+def test_plan_is_pinned(L):
+    assert {R.named_kernel(id) for id in PINNED_PLANS} == {(p[0], p[1]) for p in PINNED_PLANS.values()} and len(PINNED_PLANS) == 19
+    for id, want in PINNED_PLANS.items():
+        rc, got = _plan(L, R.args(id))
+        assert rc == 0 and got == want, (id, rc, got, want)
+
+
 def _reachable(L):
     """Every (kernel, NDB) hsp_mha_plan returns over a sweep of the quantities the decision reads: head dim, key
     count, masks, window, the force-stream hook and the workgroup count."""
