@@ -520,6 +520,60 @@ int hsp_plm_embed_sample_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int3
  * the j - 1 entries just before out[b * out_bs] (out = &codes[0, j]).  One workgroup per row.  Same refusals. */
 int hsp_sample_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out, int64_t out_bs,
                    int32_t j, const hsp_sample_args* args, void* stream);
+
+/* ------------------------------------------------ causal PLM decoding (additive: HSP_VERSION unchanged)
+ * One pre-LN transformer layer of the prosody LM for ONE new position t of B rows, against a K/V cache
+ * (csrc/hsp_plm_decode.hip): the layer of ttv_v1/transformer_mega.py:118-132 under the causal mask the reference trains
+ * with (ttv_v1/utils_mega.py:21-39, t2w2v_transformer.py:691), where position t attends to positions 0 .. t only and
+ * so nothing computed for an older position ever changes.  Per row b, with Dh = D / H:
+ *   h       = LayerNorm(x[b]; g1, b1, eps)                               (biased variance, as torch.nn.LayerNorm)
+ *   q, k, v = Wq h + bq, Wk h + bk, Wv h + bv
+ *   k_cache[b, :, t] = k ;  v_cache[b, :, t] = v
+ *   a[h Dh + d] = sum_{j <= t} softmax_j(q_h . k_cache[b, h Dh + :, j] / sqrt(Dh)) v_cache[b, h Dh + d, j]
+ *   x1      = x[b] + Wo a + bo
+ *   y[b]    = x1 + W2 relu(W1 LayerNorm(x1; g2, b2, eps) + c1) + c2
+ * x / y: element (b, c) at base + b * bs + c * cs -- a [1, D, B] matrix is (1, B), column t of a [D, B, Tp] buffer is
+ * (Tp, B Tp); y may be x (a row is read whole before it is written).  k_cache / v_cache: element (b, c, j) at
+ * base + b * bs + c * cs + j, one pair of buffers per layer, written by the calls for t = 0, 1, ... in order; this call
+ * writes column t and reads columns 0 .. t - 1: columns > t are never read (they may hold anything, NaN included),
+ * columns < t are never written.  t travels by value, so a captured graph of a fixed-length loop replays.
+ * Weights: TRANSPOSED copies of the nn.Linear weights, packed once at finalize, each [in][out] row-major and 16-byte
+ * aligned: wqkv_t [D][3 D] = cat(w_q.weight, w_k.weight, w_v.weight)^T with bqkv [3 D] the three biases in that order,
+ * wo_t [D][D] = out_proj.0.weight^T, w1_t [D][F] = ff.0.weight^T, w2_t [F][D] = ff.3.weight^T; g1 / b1 / g2 / b2 [D]
+ * the two LayerNorms' weight and bias (NOT folded into the GEMMs), bo [D], c1 [F], c2 [D].
+ * Three launches on the stream (attention per (row, head); out-proj + feed-forward per (row, slice of F /
+ * HSP_PLM_DECODE_SPLIT hidden units); the sum of the slices' partial results), so that a row's weights stream through
+ * 4 and then 12 compute units instead of one; every sum of a row is taken in an order that does not depend on B, so row
+ * b of a batch equals the call on that row alone bit for bit.  No allocation, no host synchronisation, no global state.
+ * The attention launch needs more than 32 KB of LDS from about 3 000 keys on; the first such call on a device raises
+ * the kernel's limit (a function attribute, set once), which is not legal inside a stream capture: a graph that reaches
+ * such a t is captured after one eager call at a t that large (the loop of Megatts2PLM1.infer run once eagerly does).
+ * workspace: caller-provided device scratch, 16-byte aligned, at least the bytes hsp_plm_decode_workspace_bytes gives
+ * for (B, D) = 4 B D (1 + HSP_PLM_DECODE_SPLIT); it carries nothing between calls (the calls of one stream may share it).
+ * hsp_plm_decode_supported: 1 when kernels exist for the geometry: D a multiple of 4 up to 1024, H dividing D with
+ * 3 D / H <= 1024, F a multiple of 4 HSP_PLM_DECODE_SPLIT up to 12288 (the PLM's 276 / 4 / 1104 among them).
+ * HSP_EINVAL, nothing launched: a NULL operand (the workspace included); B <= 0 or > 65535; t < 0; t >= cs; a negative
+ * stride; an unsupported geometry; a workspace that is too small or not 16-byte aligned; a weight matrix that is not
+ * 16-byte aligned; a non-zero debug; t + 1 keys whose scores do not fit one compute unit's LDS (about 36 000 keys at
+ * the PLM geometry; its position table ends at 4 000). */
+#define HSP_PLM_DECODE_SPLIT 12
+typedef struct hsp_plm_decode_args {
+  const float* x;
+  int64_t x_bs, x_cs;
+  float* y;
+  int64_t y_bs, y_cs;
+  float *k_cache, *v_cache;
+  int64_t bs, cs; /* both caches: batch and channel strides; the time stride is 1 */
+  int32_t t, B, D, H, F;
+  float eps;
+  const float *g1, *b1, *wqkv_t, *bqkv, *wo_t, *bo, *g2, *b2, *w1_t, *c1, *w2_t, *c2;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t debug; /* must be 0 (as hsp_conv1d_args.debug) */
+} hsp_plm_decode_args;
+int hsp_plm_decode_supported(int32_t D, int32_t H, int32_t F);
+int64_t hsp_plm_decode_workspace_bytes(int32_t B, int32_t D);
+int hsp_plm_decode_layer_f32(const hsp_plm_decode_args* a, void* stream);
 /* y[b, c, t] (contiguous) = x[b * s_bs + c * s_cs + t * s_ts] : strided gather, e.g. the last
  * position of every utterance (`[:, -1:, :]`, ttv_v1/t2w2v_transformer.py:716) */
 int hsp_copy_strided_f32(const float* x, int64_t s_bs, int64_t s_cs, int64_t s_ts, float* y, int32_t B,

@@ -109,6 +109,19 @@ class SampleArgs(C.Structure):
     ]
 
 
+class PlmDecodeArgs(C.Structure):
+    """Mirror of ``hsp_plm_decode_args``."""
+    _fields_ = [
+        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64),
+        ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64),
+        ("k_cache", _fp), ("v_cache", _fp), ("bs", C.c_int64), ("cs", C.c_int64),
+        ("t", C.c_int32), ("B", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("F", C.c_int32), ("eps", C.c_float),
+        ("g1", _fp), ("b1", _fp), ("wqkv_t", _fp), ("bqkv", _fp), ("wo_t", _fp), ("bo", _fp), ("g2", _fp), ("b2", _fp),
+        ("w1_t", _fp), ("c1", _fp), ("w2_t", _fp), ("c2", _fp),
+        ("workspace", _fp), ("workspace_bytes", C.c_int64), ("debug", C.c_int32),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -159,6 +172,9 @@ SIGNATURES = {
                                            C.POINTER(SampleArgs), _fp]),
     "hsp_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, C.c_int32,
                                  C.POINTER(SampleArgs), _fp]),
+    "hsp_plm_decode_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "hsp_plm_decode_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "hsp_plm_decode_layer_f32": (C.c_int, [C.POINTER(PlmDecodeArgs), _fp]),
     "hsp_embedding_sum_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp,
                                         C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

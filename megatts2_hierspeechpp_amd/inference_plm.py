@@ -107,13 +107,20 @@ def write_wav(path, sample_rate: int, pcm):
         f.writeframes(a.astype("<i2").tobytes())
 
 
+def _check_scale_norm(scale_norm: str) -> None:
+    if scale_norm not in SCALE_NORMS:
+        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
+
+
 @torch.no_grad()
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
-        target_lufs: float = -23.0):
+        target_lufs: float = -23.0, plm_causal: bool = False):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
-    make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
+    make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.  ``plm_causal``: the
+    prosody LM decodes under the causal mask it is trained with, through a K/V cache (``infer(causal=True)``: other
+    codes than the reference's bidirectional loop gives); False: the reference's loop.
     ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
     peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
     length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
@@ -125,12 +132,24 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     their own length (times ``gain``: 0.999, or the prompt's peak for scale_norm='prompt').  B > 1 runs the utterances side by side; rows are independent up to the
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
-    if scale_norm not in SCALE_NORMS:
-        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
+    _check_scale_norm(scale_norm)
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
-    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds)
+    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal)
+    return tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
+                          denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
+                          gain=gain, scale_norm=scale_norm, target_lufs=target_lufs)
+
+
+@torch.no_grad()
+def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
+                   noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
+                   return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0):
+    """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
+    ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode."""
+    _check_scale_norm(scale_norm)
+    B = x_frame.shape[0]
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
     pitch = zero_below(pitch, math.log(55.0))                                  # :166 pitch clipping
     T2 = w2v_x.shape[2]
@@ -182,7 +201,7 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     noise_scale_vc: float = 0.333, output_sr: int = 16000, dur=None, noise=None,
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
-                    takes: int = 1, target_lufs: float = -23.0):
+                    takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -194,6 +213,7 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     ``return_float``).
 
     ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling): the prosody LM samples its codes with seed ``seed``.
+    ``plm_causal``: causal K/V-cached decoding of the prosody LM (see `tts`).
     ``takes`` = N > 1: one call synthesises N takes of the same text and prompt, take k with the PLM seed ``seed + k``
     (each take equals the solo call with that seed: the rows of a batch are independent and have one length, since the
     durations do not depend on the codes); returns int16 [N, n_out] and writes ``<stem>_take<k><ext>``.  An explicit
@@ -225,7 +245,7 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                      noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
                      noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
                      seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
-                     target_lufs=target_lufs)
+                     target_lufs=target_lufs, plm_causal=plm_causal)
     rate = output_sr if output_sr in (24000, 48000) else 16000
     if B == 1:
         wav = wav[0]
@@ -240,11 +260,12 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
 
 
 def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
-                         plm_sampling=None, seed: int = 0, takes: int = 1, **kwargs):
+                         plm_sampling=None, seed: int = 0, takes: int = 1, plm_causal: bool = False, **kwargs):
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
-    ``takes`` and ``kwargs`` go to `tts_from_prompt`."""
+    ``takes`` / ``plm_causal`` and ``kwargs`` go to `tts_from_prompt`."""
     from . import audio as A
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
-                           prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, **kwargs)
+                           prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
+                           **kwargs)

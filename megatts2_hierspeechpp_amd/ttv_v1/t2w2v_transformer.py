@@ -5,6 +5,7 @@ import ctypes
 import dataclasses
 import math
 import os
+import types
 from typing import Optional
 
 import torch
@@ -133,12 +134,18 @@ class Megatts2PLM1(nn.Module):
     """t2w2v_transformer.Megatts2PLM1 (:627-718): greedy prosody-code generation.
 
     ``infer`` follows the reference loop exactly -- at step t the whole prefix of t+1 positions is
-    re-encoded bidirectionally (no KV cache is possible) and the last position's logits pick the next
+    re-encoded bidirectionally (no KV cache is possible in that mode) and the last position's logits pick the next
     code -- but it takes a batch: the reference's go token is ``[1, 1]`` so it runs one utterance per
     call; utterances are independent, so B rows run the same loop side by side (rows shorter than
     the longest simply produce codes past their length that the caller drops).  The code buffer
     lives in device memory and every step is a fixed chain of launches, so the loop has no host
-    synchronisation and can be captured in a hipGraph."""
+    synchronisation and can be captured in a hipGraph.
+
+    ``infer(causal=True)`` (opt-in) decodes the way the model is TRAINED instead: the reference's ``forward`` runs the
+    encoder under a causal mask (:691), under which position j's activations never change after step j, so a step is one
+    new column per row through a K/V cache in all layers (hsp_plm_decode_layer_f32).  Its step-t logits are the
+    teacher-forced logits ``score(tc_latent, codes, lens)[:, t]`` of its own codes; they are not the logits of the
+    bidirectional loop, and the codes differ."""
 
     GO_ID = 1024
 
@@ -242,9 +249,61 @@ class Megatts2PLM1(nn.Module):
 
     @_entry
     @torch.no_grad()
+    def score(self, tc_latent: torch.Tensor, p_codes: torch.Tensor, lens) -> torch.Tensor:
+        """Teacher-forced logits [B, T, vq_bins] of the code sequences ``p_codes`` int64 [B, T] given ``tc_latent``
+        [B, 256, T]: the ``logits`` of the reference's ``forward`` (:685-692) -- the codes shifted right behind the go
+        token, the encoder under ``causal=True`` with ``lens`` (int [B], max == T as the reference asserts), the predict
+        layer.  Positions t >= lens[b] of a row hold what the reference computes there (nothing reads them); the loss and
+        the accuracy of ``forward`` are training and are not mirrored."""
+        if self.pos_emb._pe_t is None:
+            raise L.HspError("Megatts2PLM1 used before finalize()")
+        B, D, T = tc_latent.shape
+        assert D == self.tc_latent_dim and tc_latent.stride(2) == 1 and 1 <= T <= self.pos_emb.N_POS
+        assert p_codes.shape == (B, T) and p_codes.dtype == torch.int64
+        codes = torch.empty(B, T, dtype=torch.int64, device=tc_latent.device)       # pad_y_go: F.pad(y, (1, 0), go)[:, :-1]
+        codes[:, 0] = self.GO_ID
+        codes[:, 1:] = p_codes[:, :T - 1]
+        x = self.plm(self._embed(tc_latent, codes, T), x_lens=lens, causal=True, batch=(B, T))
+        lg = self.predict_layer(x)                                                   # [1, vq_bins, Np]
+        return lg[0][:, :B * T].reshape(self.vq_bins, B, T).permute(1, 2, 0)
+
+    def _infer_causal(self, tc_latent, return_logits, sampling, seeds):
+        """The K/V-cached loop: per step one embedded column per row (_embed_one, which also takes the previous step's
+        choice), ``num_layers`` calls of hsp_plm_decode_layer_f32 and the predict layer -- no host synchronisation."""
+        B, _, T = tc_latent.shape
+        dev, D = tc_latent.device, self.d_model
+        if not all(layer.decode_supported() for layer in self.plm.layers):
+            raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {D}, {self.plm.layers[0].n_heads} "
+                             f"heads, ff {self.plm.layers[0].ff_dim}")
+        codes = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
+        codes[:, 0] = self.GO_ID
+        all_logits = torch.empty(T, self.vq_bins, B, dtype=torch.float32, device=dev) if return_logits else None
+        Tp = (T + 3) & ~3
+        cache = types.SimpleNamespace(emb=torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
+        kv = [(torch.empty(D, B, Tp, dtype=torch.float32, device=dev), torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
+              for _ in self.plm.layers]
+        x = torch.empty(1, D, B, dtype=torch.float32, device=dev)
+        ws = self.plm.layers[0].decode_workspace(B, dev)
+        lg = None
+        for t in range(T):
+            sample = sampling.c_args(seeds) if sampling is not None and lg is not None else None
+            self._embed_one(tc_latent, codes, t, cache, lg, sample)
+            src = cache.emb[:, :, t]
+            for layer, (kc, vc) in zip(self.plm.layers, kv):
+                layer.decode_step(src, x[0], kc, vc, t, ws)
+                src = x[0]
+            # the encoder's final norm (None in the PLM) reads x and leaves it in place for the next step's layers
+            lg = self.predict_layer(x if self.plm.norm is None else self.plm.norm(x), out=all_logits[t:t + 1] if return_logits else None)
+        return codes, lg, all_logits
+
+    @_entry
+    @torch.no_grad()
     def infer(self, tc_latent: torch.Tensor, return_logits: bool = False, sampling: Optional[PlmSampling] = None,
-              seeds=None):
+              seeds=None, causal: bool = False):
         """tc_latent (B, D, T) -> int64 codes (B, T)  [+ fp32 logits (B, T, vq_bins)].
+
+        ``causal`` False: the reference's bidirectional loop.  True: K/V-cached decoding under the causal mask the model
+        is trained with (class docstring); ``sampling`` / ``seeds`` / ``return_logits`` mean the same in both modes.
 
         ``sampling`` None: greedy (the reference).  A PlmSampling: every code is drawn instead (include/hsp.h "sampled
         PLM decoding"); ``seeds`` an int (row b gets seed + b; None = 0) or an int64 [B] tensor (a device tensor is read
@@ -257,6 +316,9 @@ class Megatts2PLM1(nn.Module):
         B, D, T = tc_latent.shape
         seeds = plm_seeds(seeds, B, tc_latent.device) if sampling is not None else None
         assert D == self.tc_latent_dim and tc_latent.stride(2) == 1 and T <= self.pos_emb.N_POS
+        if causal:
+            codes, lg, all_logits = self._infer_causal(tc_latent, return_logits, sampling, seeds)
+            return self._last_choice(codes, lg, all_logits, sampling, seeds)
         codes = torch.empty(B, T + 1, dtype=torch.int64, device=tc_latent.device)
         codes[:, 0] = self.GO_ID
         all_logits = torch.empty(T, self.vq_bins, B, dtype=torch.float32, device=tc_latent.device) if return_logits \
@@ -265,7 +327,6 @@ class Megatts2PLM1(nn.Module):
         cache = None
         if PLM_CACHE_L0 and self.plm.num_layers > 1 and \
                 Fh.mha_proj_supported(self.plm.layers[0].attn.n_heads, self.plm.layers[0].attn.head_dim, self.d_model, T):
-            import types
             Tp = (T + 3) & ~3
             cache = types.SimpleNamespace(
                 emb=torch.empty(self.d_model, B, Tp, dtype=torch.float32, device=tc_latent.device),
@@ -274,13 +335,18 @@ class Megatts2PLM1(nn.Module):
             # the greedy choice of step t-1 is taken inside step t's embedding launch; only the last step's needs its own
             lg = self.step_logits(tc_latent, codes, t + 1, out=all_logits[t:t + 1] if return_logits else None,
                                   prev_logits=lg, cache=cache, sampling=sampling, seeds=seeds)
+        return self._last_choice(codes, lg, all_logits, sampling, seeds)
+
+    def _last_choice(self, codes, lg, all_logits, sampling, seeds):
+        """The choice of the last step (every earlier one is taken inside the next step's embedding launch)."""
+        B, T = codes.shape[0], codes.shape[1] - 1
         if sampling is None:
             L.check(L.lib().hsp_argmax_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0),
                                            L.stream_ptr()), "hsp_argmax_f32")
         else:
             L.check(L.lib().hsp_sample_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0), T,
                                            ctypes.byref(sampling.c_args(seeds)), L.stream_ptr()), "hsp_sample_f32")
-        return (codes[:, 1:], all_logits.permute(2, 0, 1)) if return_logits else codes[:, 1:]
+        return (codes[:, 1:], all_logits.permute(2, 0, 1)) if all_logits is not None else codes[:, 1:]
 
 
 # ======================================================================= front-end (SURVEY A17)

@@ -5,9 +5,14 @@ The reference works time-major ``[B, T, D]``; here a batch is ONE channel-major 
 attention where they are), so that every ``nn.Linear`` is a single GEMM over all B*T tokens on the
 MFMA conv kernel; the three q/k/v projections run as one stacked GEMM, attention is ``hsp_mha_f32``
 on strided views.  Inference only: dropout is the identity
-(transformer_mega.py:78 passes ``dropout_p = 0`` outside training)."""
+(transformer_mega.py:78 passes ``dropout_p = 0`` outside training).
+
+Two further forms serve the causal mode (Megatts2PLM1.score / infer(causal=True)): ``TransformerEncoder.forward`` with
+``x_lens`` / ``causal`` is the reference's masked full pass (hsp_mha_f32 with a dense mask, then the projection), and
+``TransformerEncoderLayer.decode_step`` is one new position against a K/V cache (hsp_plm_decode_layer_f32)."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -43,9 +48,44 @@ class LayerNorm(HipLayer):
         return Fh.layernorm_mod(x, self.eps, gamma=self._g, beta=self._b)
 
 
+class DecodeWeights(HipLayer):
+    """The weights of one encoder layer as hsp_plm_decode_layer_f32 reads them: every nn.Linear weight transposed to
+    [in][out] (q / k / v stacked), the biases, and the two LayerNorms un-folded.  Owns no parameters: the copies are
+    gathered from the layer's own modules at finalize, into the weight arena."""
+
+    def __init__(self, layer):
+        super().__init__()
+        self.__dict__["_layer"] = layer      # not registered as a sub-module (no cycle, no duplicate state_dict keys)
+        self._views = None
+
+    def _spec(self):
+        D, F = self._layer.dim, self._layer.ff_dim
+        return [("wqkv_t", D * 3 * D), ("bqkv", 3 * D), ("wo_t", D * D), ("bo", D), ("w1_t", D * F), ("c1", F),
+                ("w2_t", F * D), ("c2", D)]
+
+    def hsp_requests(self):
+        return self._spec()
+
+    def hsp_fill(self, arena, materialize):
+        v = {name: arena.view(self, name) for name, _ in self._spec()}
+        self._views = v
+        if materialize:
+            ly = self._layer
+            at, D, F = ly.attn, ly.dim, ly.ff_dim
+            parts = (at.w_q, at.w_k, at.w_v)
+            v["wqkv_t"].view(D, 3 * D).copy_(torch.cat([p.weight.data for p in parts], 0).t())
+            v["bqkv"].copy_(torch.cat([p.bias.data for p in parts], 0))
+            v["wo_t"].view(D, D).copy_(at.out_proj[0].weight.data.t())
+            v["bo"].copy_(at.out_proj[0].bias.data)
+            v["w1_t"].view(D, F).copy_(ly.ff["0"].weight.data.t())
+            v["c1"].copy_(ly.ff["0"].bias.data)
+            v["w2_t"].view(F, D).copy_(ly.ff["3"].weight.data.t())
+            v["c2"].copy_(ly.ff["3"].bias.data)
+
+
 class MultiHeadAttention(nn.Module):
-    """transformer_mega.MultiHeadAttention (:44-87), self-attention without a mask (the only form
-    Megatts2PLM1.infer uses: ``self.plm(x_pos)`` passes no lengths, t2w2v_transformer.py:715)."""
+    """transformer_mega.MultiHeadAttention (:44-87), self-attention; without a mask on the path Megatts2PLM1.infer uses
+    (``self.plm(x_pos)`` passes no lengths, t2w2v_transformer.py:715), with a dense one in the masked full pass."""
 
     def __init__(self, qkv_dim, n_heads=8, dropout=0., pre_norm=None):
         """``pre_norm``: the LayerNorm the encoder layer applies to this module's input; it is folded into
@@ -87,12 +127,14 @@ class MultiHeadAttention(nn.Module):
     def forward(self, x, kv=None, mask=None, res=None, batch=None, last_only=False):
         """x [1, D, B*T] -> out_proj(attention) [+ res]; ``last_only`` -> [1, D, B]: only the last
         position of every utterance (columns T-1, 2T-1, ...), ``res`` then being [1, D, B] already."""
-        if kv is not None or mask is not None:
-            raise NotImplementedError("cross-attention / masks are not on the PLM inference path")
+        if kv is not None:
+            raise NotImplementedError("cross-attention is not on the PLM inference path")
+        if mask is not None and (batch is None or last_only):
+            raise NotImplementedError("a mask goes with the side-by-side layout (batch=(B, T)), all positions")
         D = self.qkv_dim
         B, T = batch if batch is not None else (x.shape[0], x.shape[2])
         qkv = self.qkv(x)
-        if batch is not None and Fh.mha_proj_supported(self.n_heads, self.head_dim, D, T):
+        if mask is None and batch is not None and Fh.mha_proj_supported(self.n_heads, self.head_dim, D, T):
             # ONE launch: attention over all heads of a 16-query tile + out_proj + bias + residual (round 4)
             per = lambda m: m[:, :B * T].reshape(-1, B, T).permute(1, 0, 2)       # [B, C, T] view of a [C, Np] matrix
             q, k, v = (per(qkv[0, i * D:(i + 1) * D]) for i in range(3))
@@ -114,7 +156,10 @@ class MultiHeadAttention(nn.Module):
         per_utt = lambda m: m[:, :B * T].reshape(-1, B, T).permute(1, 0, 2) if batch is not None else m
         q, k, v = (per_utt(qkv[0, i * D:(i + 1) * D]) if batch is not None else qkv[:, i * D:(i + 1) * D]
                    for i in range(3))
-        Fh.mha(q, k, v, self.n_heads, 1.0 / math.sqrt(self.head_dim), out=per_utt(o[0]) if batch is not None else o)
+        # mask [B, T, T] (1 = attend): the fused kernel has no mask inside its softmax (hsp.h), so a masked pass is
+        # hsp_mha_f32 with mask_dense and the projection as two launches
+        Fh.mha(q, k, v, self.n_heads, 1.0 / math.sqrt(self.head_dim), out=per_utt(o[0]) if batch is not None else o,
+               mask_dense=mask)
         if last_only:
             o = o[0][:, :B * T].reshape(D, B, T)[:, :, T - 1].unsqueeze(0)  # [1, D, B] view, time stride T
         return self.out_proj[0](o, res=res)
@@ -135,6 +180,36 @@ class TransformerEncoderLayer(nn.Module):
         # nn.Sequential(Linear, ReLU, Dropout, Linear): keys "ff.0" and "ff.3"
         self.ff = nn.ModuleDict({"0": LinearCT(dim, ff_dim), "3": LinearCT(ff_dim, dim)})
         self.ff["0"].fuse_input_layernorm(self.norm2)
+        self.decode = DecodeWeights(self)
+
+    def decode_supported(self) -> bool:
+        return bool(L.lib().hsp_plm_decode_supported(self.dim, self.n_heads, self.ff_dim))
+
+    def decode_workspace(self, B: int, device) -> torch.Tensor:
+        """The scratch buffer decode_step needs for B rows (the layers and steps of one stream may share it)."""
+        n = L.lib().hsp_plm_decode_workspace_bytes(B, self.dim)
+        return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+    def decode_step(self, x, y, k_cache, v_cache, t: int, workspace):
+        """One new position t of every row against this layer's K/V cache (hsp_plm_decode_layer_f32): x, y [D, B] views
+        (any strides; y may be x), k_cache / v_cache [D, B, Tp], ``workspace`` from decode_workspace.  Writes column t
+        of both caches."""
+        w = self.decode._views
+        if w is None or self.norm1._g is None:
+            raise L.HspError("TransformerEncoderLayer used before finalize()")
+        D, B = x.shape
+        assert y.shape == (D, B) and k_cache.shape == v_cache.shape and k_cache.is_contiguous() and v_cache.is_contiguous()
+        assert k_cache.shape[:2] == (D, B) and 0 <= t < k_cache.shape[2]
+        a = L.PlmDecodeArgs()
+        a.x, a.x_bs, a.x_cs = L.fptr(x), x.stride(1), x.stride(0)
+        a.y, a.y_bs, a.y_cs = L.fptr(y), y.stride(1), y.stride(0)
+        a.k_cache, a.v_cache, a.bs, a.cs = L.fptr(k_cache), L.fptr(v_cache), k_cache.stride(1), k_cache.stride(0)
+        a.t, a.B, a.D, a.H, a.F, a.eps = t, B, D, self.n_heads, self.ff_dim, self.norm1.eps
+        a.g1, a.b1, a.g2, a.b2 = (L.fptr(v) for v in (self.norm1._g, self.norm1._b, self.norm2._g, self.norm2._b))
+        for name in ("wqkv_t", "bqkv", "wo_t", "bo", "w1_t", "c1", "w2_t", "c2"):
+            setattr(a, name, L.fptr(w[name]))
+        a.workspace, a.workspace_bytes = L.fptr(workspace), workspace.numel() * 4
+        L.check(L.lib().hsp_plm_decode_layer_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_decode_layer_f32")
 
     def forward(self, x, mask=None, batch=None, last_only=False, cache=None):
         """``last_only`` returns just the last position of every utterance ``[1, D, B]`` (all the
@@ -165,9 +240,33 @@ class TransformerEncoder(nn.Module):
                                            for _ in range(num_layers - 1)])
         self.num_layers, self.norm = num_layers, norm
 
+    @staticmethod
+    def attn_mask(x_lens, T: int, causal: bool, device) -> torch.Tensor:
+        """make_attn_mask (ttv_v1/utils_mega.py:21-39) as the [B, T, T] 0/1 matrix hsp_mha_f32 takes (1 = attend): key j of
+        row b is visible when j < x_lens[b], and, when ``causal``, j <= i.  The reference asserts that the longest row
+        fills the matrix when causal (:31); so does this.  Index comparisons only, no arithmetic on activations."""
+        lens = torch.as_tensor(x_lens).to(torch.int64).reshape(-1)
+        if causal and int(lens.max()) != T:
+            raise L.HspError("Causal mask requires all lengths to be equal to max_len")
+        if int(lens.max()) > T or int(lens.min()) < 1:
+            raise L.HspError(f"x_lens must lie in [1, {T}]")
+        j = torch.arange(T, device=device)
+        vis = (j[None, :] < lens.to(device)[:, None])[:, None, :].expand(-1, T, -1)
+        if causal:
+            vis = vis & (j[None, :] <= j[:, None])[None]
+        return vis.to(torch.float32).contiguous()
+
     def forward(self, x, x_lens=None, causal=False, batch=None, last_only=False, cache=None):
-        if x_lens is not None or causal:
-            raise NotImplementedError("length / causal masks belong to the training forward, not to infer()")
+        """Without ``x_lens`` (the reference builds no mask then, whatever ``causal`` says: :155-158) the unmasked pass
+        of the greedy loop.  With ``x_lens`` (int [B]; ``batch=(B, T)`` locates the rows in x [1, D, >= B*T]): every layer
+        under the reference's mask -- key padding, plus the triangle when ``causal``."""
+        if x_lens is not None:
+            if batch is None or last_only or cache is not None:
+                raise NotImplementedError("the masked pass is the full side-by-side form: batch=(B, T), all positions")
+            mask = self.attn_mask(x_lens, batch[1], causal, x.device)
+            for layer in self.layers:
+                x = layer(x, mask=mask, batch=batch)
+            return x if self.norm is None else self.norm(x)
         for i, layer in enumerate(self.layers):
             x = layer(x, batch=batch, last_only=last_only and i == self.num_layers - 1,
                       cache=cache if i == 0 and self.num_layers > 1 else None)
