@@ -574,6 +574,38 @@ typedef struct hsp_plm_decode_args {
 int hsp_plm_decode_supported(int32_t D, int32_t H, int32_t F);
 int64_t hsp_plm_decode_workspace_bytes(int32_t B, int32_t D);
 int hsp_plm_decode_layer_f32(const hsp_plm_decode_args* a, void* stream);
+/* Per-row positions (ragged request streams from one captured step; additive: HSP_VERSION unchanged).  The three entry
+ * points below take the position from device memory, pos int32 [B], read when the kernels run, so one captured graph of
+ * a single step serves rows of every length side by side.  Row b is ACTIVE when 0 <= pos[b] <= the call's largest
+ * position (a->t / max_pos) and IDLE for every other value (negative ones, INT32_MIN and values above the bound
+ * included): an idle row's workgroups return before they touch memory -- nothing of the row (x, y, cache, workspace,
+ * codes, pos) is read or written.  That bound check is part of the contract: it is what keeps a stale or wrong
+ * position from becoming a store out of range.  The branch is uniform over a workgroup.
+ *  - hsp_plm_decode_layer_pos_f32: the layer above with t = pos[b] per row.  a->t is the LARGEST position a row may
+ *    hold: it sizes the attention launch's LDS and is checked against cs as above.  An active row runs the device
+ *    functions of hsp_plm_decode_layer_f32 with t = pos[b] and equals that call on the row alone bit for bit (y and
+ *    column pos[b] of both caches; no other cache column is written).  Refusals as above, plus NULL pos.
+ *  - hsp_plm_embed_pos_f32: x[b * x_bs + c * x_cs] = cat(tc[b, :, t], emb[codes[b, t]])[c] + alpha[0] * pe_t[c, t] with
+ *    t = pos[b]: hsp_plm_embed_f32 in its one-position form, with UN-shifted tc (strides tc_bs, tc_cs, 1; more than
+ *    max_pos columns), codes (row stride codes_bs; clamped into [0, n_emb) as there) and pe_t [Dtc + Demb][P].
+ *    HSP_EINVAL: a NULL operand, B <= 0 or > 65535, Dtc / Demb / n_emb <= 0, a negative stride, max_pos < 0 or >= P.
+ *  - hsp_plm_choose_advance_f32, after the predict layer: for an active row at t = pos[b], codes[b, t + 1] = the
+ *    decision for column j = t + 1 from logits[b * l_bs + c * l_cs], c < N -- args NULL: the first maximal index, by the
+ *    device function of hsp_argmax_f32; else the sampled decision above, by the device function of hsp_sample_f32,
+ *    with seeds[b] and the row's previous codes (columns 1 .. t) -- and then pos[b] = t + 1 < len[b] ? t + 1 : -1
+ *    (len int32 [B], device): pos advances IN PLACE, which is what makes a replayed graph step, and a row that has
+ *    chosen column len[b] is finished and idle.  A codes row holds at least max_pos + 2 entries.  HSP_EINVAL: NULL
+ *    logits / codes / pos / len, B <= 0 or > 65535, N <= 0, l_cs <= 0, l_bs < 0, max_pos < 0, and with args the
+ *    refusals of hsp_sample_f32.
+ * All refusals are decided before any HIP call; nothing is launched on one. */
+int hsp_plm_decode_layer_pos_f32(const hsp_plm_decode_args* a, const int32_t* pos, void* stream);
+int hsp_plm_embed_pos_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t Dtc, const int64_t* codes,
+                          int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb, const float* pe_t, int32_t P,
+                          const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B, const int32_t* pos,
+                          int32_t max_pos, void* stream);
+int hsp_plm_choose_advance_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* codes,
+                               int64_t codes_bs, int32_t* pos, const int32_t* len, int32_t max_pos,
+                               const hsp_sample_args* args, void* stream);
 /* y[b, c, t] (contiguous) = x[b * s_bs + c * s_cs + t * s_ts] : strided gather, e.g. the last
  * position of every utterance (`[:, -1:, :]`, ttv_v1/t2w2v_transformer.py:716) */
 int hsp_copy_strided_f32(const float* x, int64_t s_bs, int64_t s_cs, int64_t s_ts, float* y, int32_t B,

@@ -175,6 +175,11 @@ SIGNATURES = {
     "hsp_plm_decode_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "hsp_plm_decode_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "hsp_plm_decode_layer_f32": (C.c_int, [C.POINTER(PlmDecodeArgs), _fp]),
+    "hsp_plm_decode_layer_pos_f32": (C.c_int, [C.POINTER(PlmDecodeArgs), _fp, _fp]),
+    "hsp_plm_embed_pos_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32, C.c_int32,
+                                        _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, _fp]),
+    "hsp_plm_choose_advance_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, _fp,
+                                             C.c_int32, C.POINTER(SampleArgs), _fp]),
     "hsp_embedding_sum_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp,
                                         C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

@@ -2,6 +2,8 @@
 // ttv_v1/t2w2v_transformer.py:702-718): the per-step input assembly and the greedy argmax
 // that feeds the next step.  Both read/write the code buffer in device memory so that the
 // whole T-step loop is a chain of launches without a host round trip (hipGraph-capturable).
+// The per-row-position forms at the end (hsp_plm_embed_pos_f32, hsp_plm_choose_advance_f32) also keep each row's position
+// in device memory, so that one captured step serves rows of every length.
 #include <cmath>
 
 #include "hsp_device.h"
@@ -43,6 +45,30 @@ __global__ __launch_bounds__(256) void plm_embed_kernel(const float* __restrict_
   }
 }
 
+// argmax_c row[c * l_cs] over c < N by one 256-thread workgroup: ties -> lowest index (torch.argmax on CPU returns the
+// first maximal element), 0 when nothing compares (all NaN).  The result is valid on thread 0 only.  Has a barrier.
+__device__ __forceinline__ int argmax_row(const float* __restrict__ row, int64_t l_cs, int N, float* smax, int* sidx) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = tid; c < N; c += 256) {
+    const float v = row[(int64_t)c * l_cs];
+    if (v > best || (v == best && c < bi)) best = v, bi = c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) best = ov, bi = oi;
+  }
+  if (lane == 0) smax[wave] = best, sidx[wave] = bi;
+  __syncthreads();
+  if (tid == 0)
+    for (int w = 1; w < 4; ++w)
+      if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) best = smax[w], bi = sidx[w];
+  return bi == 0x7fffffff ? 0 : bi;
+}
+
 // The same with the greedy choice of the PREVIOUS step folded in (one launch per step less): workgroup (b, 0) first
 // takes codes[b, n - 1] = argmax_c logits[b * l_bs + c * l_cs] (ties -> lowest index, as argmax_kernel), stores it and
 // then writes the code-embedding rows of utterance b; the workgroups (b, 1 ...) write the tc_latent rows, which do
@@ -58,29 +84,12 @@ __global__ __launch_bounds__(256) void plm_embed_step_kernel(const float* __rest
   __shared__ float smax[4];
   __shared__ int sidx[4];
   __shared__ int s_code;
-  const int b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
   const float al = alpha[0];
   const int D = Dtc + Demb;
   if (part == 0) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    const float* row = logits + (int64_t)b * l_bs;
-    for (int c = tid; c < n_logits; c += 256) {
-      const float v = row[(int64_t)c * l_cs];
-      if (v > best || (v == best && c < bi)) best = v, bi = c;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) best = ov, bi = oi;
-    }
-    if (lane == 0) smax[wave] = best, sidx[wave] = bi;
-    __syncthreads();
+    const int bi = argmax_row(logits + (int64_t)b * l_bs, l_cs, n_logits, smax, sidx);
     if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) best = smax[w], bi = sidx[w];
-      bi = bi == 0x7fffffff ? 0 : bi;
       codes[(int64_t)b * codes_bs + n - 1] = bi;
       s_code = bi;
     }
@@ -106,33 +115,14 @@ __global__ __launch_bounds__(256) void plm_embed_step_kernel(const float* __rest
   }
 }
 
-// out[b * out_bs] = argmax_c logits[b * l_bs + c * l_cs]; ties -> lowest index (torch.argmax on CPU returns the
-// first maximal element).  One workgroup per row.
+// out[b * out_bs] = argmax_c logits[b * l_bs + c * l_cs] (argmax_row).  One workgroup per row.
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int64_t l_bs, int64_t l_cs, int N,
                                                      int64_t* __restrict__ out, int64_t out_bs) {
   __shared__ float smax[4];
   __shared__ int sidx[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* row = logits + (int64_t)b * l_bs;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c = tid; c < N; c += 256) {
-    const float v = row[(int64_t)c * l_cs];
-    if (v > best || (v == best && c < bi)) best = v, bi = c;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) best = ov, bi = oi;
-  }
-  if (lane == 0) smax[wave] = best, sidx[wave] = bi;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) best = smax[w], bi = sidx[w];
-    out[(int64_t)b * out_bs] = bi == 0x7fffffff ? 0 : bi;
-  }
+  const int b = blockIdx.x;
+  const int bi = argmax_row(logits + (int64_t)b * l_bs, l_cs, N, smax, sidx);
+  if (threadIdx.x == 0) out[(int64_t)b * out_bs] = bi;
 }
 
 // y[b, c, t] (contiguous) = x[b * s_bs + c * s_cs + t * s_ts]
@@ -437,6 +427,55 @@ __global__ __launch_bounds__(256) void plm_embed_sample_kernel(const float* __re
   }
 }
 
+// ------------------------------------------------------------------------------------- per-row positions (hsp.h)
+// hsp_plm_embed_pos_f32: workgroup b embeds position pos[b] of row b -- plm_embed_kernel's expression for one column,
+// with the indexing done here.  An idle row (pos[b] outside [0, max_pos]) returns before it touches memory.
+__global__ __launch_bounds__(256) void plm_embed_pos_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
+                                                            int Dtc, const int64_t* __restrict__ codes, int64_t codes_bs,
+                                                            const float* __restrict__ emb, int Demb, int n_emb,
+                                                            const float* __restrict__ pe_t, int P,
+                                                            const float* __restrict__ alpha, float* __restrict__ x,
+                                                            int64_t x_bs, int64_t x_cs, const int32_t* __restrict__ pos,
+                                                            int max_pos) {
+  const int b = blockIdx.x, t = pos[b];
+  if (t < 0 || t > max_pos) return;
+  const float al = alpha[0];
+  for (int c = threadIdx.x; c < Dtc + Demb; c += 256) {
+    float v;
+    if (c < Dtc) {
+      v = tc[b * tc_bs + c * tc_cs + t];
+    } else {
+      int64_t id = codes[b * codes_bs + t];
+      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);  // a corrupted code must not fault the GPU
+      v = emb[id * Demb + (c - Dtc)];
+    }
+    x[b * x_bs + c * x_cs] = fmaf(al, pe_t[(int64_t)c * P + t], v);
+  }
+}
+
+// hsp_plm_choose_advance_f32: workgroup b takes codes[b, t + 1] for t = pos[b] -- argmax_row, or sample_decide for
+// column j = t + 1 with the row's codes 1 .. t -- and then moves pos[b] on, to -1 at the row's length.  Every thread
+// reads pos[b] before the barriers of the decision, thread 0 writes it after them.  Idle rows return at once.
+__global__ __launch_bounds__(256) void plm_choose_advance_kernel(const float* __restrict__ logits, int64_t l_bs,
+                                                                 int64_t l_cs, int N, int64_t* __restrict__ codes,
+                                                                 int64_t codes_bs, int32_t* pos,
+                                                                 const int32_t* __restrict__ len, int max_pos,
+                                                                 bool sampled, hsp_sample_args a) {
+  __shared__ SampleSmem s;
+  const int b = blockIdx.x, t = pos[b];
+  if (t < 0 || t > max_pos) return;
+  int64_t* row = codes + (int64_t)b * codes_bs;
+  int tok;
+  if (sampled)
+    tok = sample_decide(logits + (int64_t)b * l_bs, l_cs, N, row + 1, t, t + 1, a, a.probs, s);
+  else
+    tok = argmax_row(logits + (int64_t)b * l_bs, l_cs, N, s.redf, s.redi);
+  if (threadIdx.x == 0) {
+    row[t + 1] = tok;
+    pos[b] = t + 1 < len[b] ? t + 1 : -1;
+  }
+}
+
 }  // namespace
 
 #define HSP_STREAM static_cast<hipStream_t>(stream)
@@ -524,5 +563,28 @@ extern "C" int hsp_sample_f32(const float* logits, int64_t l_bs, int64_t l_cs, i
   if (!logits || !out || B <= 0 || B > 65535 || l_cs <= 0 || l_bs < 0 || !sample_args_ok(args, N, j)) return HSP_EINVAL;
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logits, l_bs, l_cs, N, out, out_bs, j,
                      *args);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_plm_embed_pos_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t Dtc, const int64_t* codes,
+                                     int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb, const float* pe_t,
+                                     int32_t P, const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B,
+                                     const int32_t* pos, int32_t max_pos, void* stream) {
+  if (!tc || !codes || !emb || !pe_t || !alpha || !x || !pos) return HSP_EINVAL;
+  if (B <= 0 || B > 65535 || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || max_pos < 0 || max_pos >= P) return HSP_EINVAL;
+  if (tc_bs < 0 || tc_cs < 0 || codes_bs < 0 || x_bs < 0 || x_cs < 0) return HSP_EINVAL;
+  hipLaunchKernelGGL(plm_embed_pos_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, tc, tc_bs, tc_cs, Dtc, codes,
+                     codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, pos, max_pos);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_plm_choose_advance_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N,
+                                          int64_t* codes, int64_t codes_bs, int32_t* pos, const int32_t* len,
+                                          int32_t max_pos, const hsp_sample_args* args, void* stream) {
+  if (!logits || !codes || !pos || !len) return HSP_EINVAL;
+  if (B <= 0 || B > 65535 || N <= 0 || l_cs <= 0 || l_bs < 0 || codes_bs < 0 || max_pos < 0) return HSP_EINVAL;
+  if (args && !sample_args_ok(args, N, 1)) return HSP_EINVAL;   // j = pos[b] + 1 >= 1 for every active row
+  hipLaunchKernelGGL(plm_choose_advance_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logits, l_bs, l_cs, N,
+                     codes, codes_bs, pos, len, max_pos, args != nullptr, args ? *args : hsp_sample_args{});
   return (int)hipGetLastError();
 }

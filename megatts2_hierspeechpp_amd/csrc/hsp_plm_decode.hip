@@ -19,6 +19,11 @@
 // output meet in LDS in a fixed order, and so do the P partial sums of launch 3: a row's result does not depend on the
 // batch around it.  Attention: one thread per key takes the dot product with lanes running along the cache's time axis
 // (unit stride), one wave does the softmax in LDS, then four channels per wave sum p V with lanes along time again.
+//
+// Two forms of every launch share one body per row (attn_row / ffn_row / sum_row): by value, every row at a.t
+// (hsp_plm_decode_layer_f32), and by position, row b at pos[b] read from device memory (hsp_plm_decode_layer_pos_f32;
+// hsp.h "per-row positions"), where a row outside [0, a.t] is idle and its workgroups return at once -- the form that lets
+// one captured step serve rows of every length (Megatts2PLM1.decode_session).
 #include <cmath>
 
 #include "hsp_device.h"
@@ -98,10 +103,9 @@ __device__ __forceinline__ float* ws_part(const hsp_plm_decode_args& a, int b, i
   return static_cast<float*>(a.workspace) + (int64_t)a.B * a.D + ((int64_t)b * kP + p) * a.D;
 }
 
-// launch 1, grid B * H: workgroup b * H + h
-__global__ __launch_bounds__(kThreads) void plm_decode_attn_kernel(hsp_plm_decode_args a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int D = a.D, t = a.t, n = a.t + 1, Dh = a.D / a.H;
+// launch 1 for row b, head h at position t (the by-value kernel passes a.t, the position form pos[b])
+__device__ __forceinline__ void attn_row(const hsp_plm_decode_args& a, int b, int h, int t, float* lds) {
+  const int D = a.D, n = t + 1, Dh = a.D / a.H;
   const int Dhp = (Dh + 3) & ~3;
   float* xs = lds;                 // [D]   x
   float* hs = xs + D;              // [D]   LayerNorm(x)
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void plm_decode_attn_kernel(hsp_plm_decod
   float* part = qkv + 3 * Dhp;     // [S][3 Dh] partial sums
   float* linv = part + kPartFloats;   // [4]
   float* sc = linv + 4;            // [n] scores, then exp(score - max)
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   const float* xb = a.x + (int64_t)b * a.x_bs;
   for (int c = tid; c < D; c += kThreads) xs[c] = xb[(int64_t)c * a.x_cs];
@@ -191,15 +195,14 @@ __global__ __launch_bounds__(kThreads) void plm_decode_attn_kernel(hsp_plm_decod
   }
 }
 
-// launch 2, grid B * kP: workgroup b * kP + p
-__global__ __launch_bounds__(kThreads) void plm_decode_ffn_kernel(hsp_plm_decode_args a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// launch 2 for row b, slice p of the hidden units
+__device__ __forceinline__ void ffn_row(const hsp_plm_decode_args& a, int b, int p, float* lds) {
   const int D = a.D, F = a.F, Fs = a.F / kP;
   float* xs = lds;                 // [D]  x, then x1
   float* hs = xs + D;              // [D]  attention output, then LayerNorm(x1)
   float* ff = hs + D;              // [Fs] relu(W1 h + c1), this workgroup's hidden units
   float* part = ff + Fs;           // [kPartFloats]
-  const int b = blockIdx.x / kP, p = blockIdx.x % kP, tid = threadIdx.x;
+  const int tid = threadIdx.x;
 
   const float* xb = a.x + (int64_t)b * a.x_bs;
   const float* at = ws_at(a, b);
@@ -223,15 +226,51 @@ __global__ __launch_bounds__(kThreads) void plm_decode_ffn_kernel(hsp_plm_decode
   }
 }
 
-// launch 3, grid (B): y = the kP partial sums in order
-__global__ __launch_bounds__(256) void plm_decode_sum_kernel(hsp_plm_decode_args a) {
-  const int b = blockIdx.x;
+// launch 3 for row b: y = the kP partial sums in order
+__device__ __forceinline__ void sum_row(const hsp_plm_decode_args& a, int b) {
   float* yb = a.y + (int64_t)b * a.y_bs;
   for (int m = threadIdx.x; m < a.D; m += 256) {
     float v = ws_part(a, b, 0)[m];
     for (int p = 1; p < kP; ++p) v += ws_part(a, b, p)[m];
     yb[(int64_t)m * a.y_cs] = v;
   }
+}
+
+// The kernels: grid B * H (workgroup b * H + h), B * kP (workgroup b * kP + p) and B.  By value, every row is at a.t.
+__global__ __launch_bounds__(kThreads) void plm_decode_attn_kernel(hsp_plm_decode_args a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  attn_row(a, blockIdx.x / a.H, blockIdx.x % a.H, a.t, lds);
+}
+__global__ __launch_bounds__(kThreads) void plm_decode_ffn_kernel(hsp_plm_decode_args a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  ffn_row(a, blockIdx.x / kP, blockIdx.x % kP, lds);
+}
+__global__ __launch_bounds__(256) void plm_decode_sum_kernel(hsp_plm_decode_args a) {
+  sum_row(a, blockIdx.x);
+}
+
+// Position form (hsp.h "per-row positions"): row b is at pos[b], read here.  A row whose position is not in [0, a.t] is
+// idle: its workgroups return before they touch memory -- the check is what bounds the cache column and the LDS scores
+// (sized for a.t + 1 keys by the host).  One row per workgroup, so the branch is uniform.
+__device__ __forceinline__ bool row_active(const hsp_plm_decode_args& a, const int32_t* __restrict__ pos, int b, int* t) {
+  *t = pos[b];
+  return *t >= 0 && *t <= a.t;
+}
+__global__ __launch_bounds__(kThreads) void plm_decode_attn_pos_kernel(hsp_plm_decode_args a,
+                                                                      const int32_t* __restrict__ pos) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int t;
+  if (row_active(a, pos, blockIdx.x / a.H, &t)) attn_row(a, blockIdx.x / a.H, blockIdx.x % a.H, t, lds);
+}
+__global__ __launch_bounds__(kThreads) void plm_decode_ffn_pos_kernel(hsp_plm_decode_args a,
+                                                                     const int32_t* __restrict__ pos) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int t;
+  if (row_active(a, pos, blockIdx.x / kP, &t)) ffn_row(a, blockIdx.x / kP, blockIdx.x % kP, lds);
+}
+__global__ __launch_bounds__(256) void plm_decode_sum_pos_kernel(hsp_plm_decode_args a, const int32_t* __restrict__ pos) {
+  int t;
+  if (row_active(a, pos, blockIdx.x, &t)) sum_row(a, blockIdx.x);
 }
 
 constexpr int kLdsMax = 160 * 1024;
@@ -258,22 +297,43 @@ extern "C" int64_t hsp_plm_decode_workspace_bytes(int32_t B, int32_t D) {
   return (int64_t)B * D * (1 + kP) * 4;
 }
 
-extern "C" int hsp_plm_decode_layer_f32(const hsp_plm_decode_args* a, void* stream) {
-  if (!a) return HSP_EINVAL;
-  if (!a->x || !a->y || !a->k_cache || !a->v_cache || !a->workspace) return HSP_EINVAL;
+namespace {
+
+// the refusals of both layer entry points (hsp.h); the attention launch's LDS bytes for a->t + 1 keys, or -1
+int64_t decode_args_lds(const hsp_plm_decode_args* a) {
+  if (!a) return -1;
+  if (!a->x || !a->y || !a->k_cache || !a->v_cache || !a->workspace) return -1;
   if (!a->g1 || !a->b1 || !a->wqkv_t || !a->bqkv || !a->wo_t || !a->bo || !a->g2 || !a->b2 || !a->w1_t || !a->c1 ||
       !a->w2_t || !a->c2)
-    return HSP_EINVAL;
-  if (a->debug != 0 || a->B <= 0 || a->B > 65535 || a->t < 0 || (int64_t)a->t >= a->cs || a->bs < 0) return HSP_EINVAL;
-  if (a->x_bs < 0 || a->x_cs < 0 || a->y_bs < 0 || a->y_cs < 0 || !(a->eps >= 0.0f)) return HSP_EINVAL;
-  if (!hsp_plm_decode_supported(a->D, a->H, a->F)) return HSP_EINVAL;
-  if (a->workspace_bytes < hsp_plm_decode_workspace_bytes(a->B, a->D) || !aligned16(a->workspace)) return HSP_EINVAL;
-  if (!aligned16(a->wqkv_t) || !aligned16(a->wo_t) || !aligned16(a->w1_t) || !aligned16(a->w2_t)) return HSP_EINVAL;
+    return -1;
+  if (a->debug != 0 || a->B <= 0 || a->B > 65535 || a->t < 0 || (int64_t)a->t >= a->cs || a->bs < 0) return -1;
+  if (a->x_bs < 0 || a->x_cs < 0 || a->y_bs < 0 || a->y_cs < 0 || !(a->eps >= 0.0f)) return -1;
+  if (!hsp_plm_decode_supported(a->D, a->H, a->F)) return -1;
+  if (a->workspace_bytes < hsp_plm_decode_workspace_bytes(a->B, a->D) || !aligned16(a->workspace)) return -1;
+  if (!aligned16(a->wqkv_t) || !aligned16(a->wo_t) || !aligned16(a->w1_t) || !aligned16(a->w2_t)) return -1;
   const int64_t lds = attn_lds_bytes(a->D, a->H, a->F, (int64_t)a->t + 1);
-  if (lds > kLdsMax) return HSP_EINVAL;   // more keys than one compute unit's LDS holds scores for
+  return lds > kLdsMax ? -1 : lds;   // more keys than one compute unit's LDS holds scores for
+}
+
+}  // namespace
+
+extern "C" int hsp_plm_decode_layer_f32(const hsp_plm_decode_args* a, void* stream) {
+  const int64_t lds = decode_args_lds(a);
+  if (lds < 0) return HSP_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int e = hsp_launch<plm_decode_attn_kernel>((int64_t)a->B * a->H, kThreads, (int)lds, kLdsMax, s, *a)) return e;
   const int lds2 = (2 * a->D + a->F / kP + kPartFloats) * 4;      // at most 28 KB (decode geometry check)
   if (int e = hsp_launch<plm_decode_ffn_kernel>((int64_t)a->B * kP, kThreads, lds2, lds2, s, *a)) return e;
   return hsp_launch<plm_decode_sum_kernel>(a->B, 256, 0, 0, s, *a);
+}
+
+extern "C" int hsp_plm_decode_layer_pos_f32(const hsp_plm_decode_args* a, const int32_t* pos, void* stream) {
+  const int64_t lds = decode_args_lds(a);
+  if (lds < 0 || !pos) return HSP_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int e = hsp_launch<plm_decode_attn_pos_kernel>((int64_t)a->B * a->H, kThreads, (int)lds, kLdsMax, s, *a, pos))
+    return e;
+  const int lds2 = (2 * a->D + a->F / kP + kPartFloats) * 4;
+  if (int e = hsp_launch<plm_decode_ffn_pos_kernel>((int64_t)a->B * kP, kThreads, lds2, lds2, s, *a, pos)) return e;
+  return hsp_launch<plm_decode_sum_pos_kernel>(a->B, 256, 0, 0, s, *a, pos);
 }

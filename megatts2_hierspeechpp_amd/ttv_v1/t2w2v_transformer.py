@@ -130,6 +130,166 @@ def plm_seeds(seeds, B: int, device) -> torch.Tensor:
     return torch.arange(s, s + B, dtype=torch.int64, device=device)
 
 
+def session_plan(lengths, slots: int):
+    """The schedule of a decode session, from the request lengths alone: requests are taken in order, each goes to the
+    lowest free slot at the earliest step that has one, and a slot is free on the step after its row's last (a row of
+    length n admitted at step s runs steps s .. s + n - 1).  Returns ``(admissions, steps)``: ``admissions[step]`` the
+    ``(request, slot)`` pairs admitted before that step runs, ``steps`` the number of steps until every row is done."""
+    lengths = [int(n) for n in lengths]
+    if int(slots) < 1:
+        raise L.HspError(f"a session needs at least one slot, got {slots}")
+    if any(n < 1 for n in lengths):
+        raise L.HspError(f"every request needs at least one frame, got lengths {lengths}")
+    free_at = [0] * int(slots)
+    admissions, step = {}, 0
+    for i, n in enumerate(lengths):
+        step = max(step, min(free_at))
+        slot = next(k for k, f in enumerate(free_at) if f <= step)
+        free_at[slot] = step + n
+        admissions.setdefault(step, []).append((i, slot))
+    return admissions, (max(free_at) if lengths else 0)
+
+
+class PlmDecodeSession:
+    """Causal decoding of ragged request streams from ONE step (Megatts2PLM1.decode_session): ``slots`` rows of fixed-shape
+    device state, each row at its own position ``pos[slot]`` in device memory (include/hsp.h "per-row positions"), so the
+    same chain of launches -- embed, one position-form layer call per layer, the predict layer over all slots, choose and
+    advance -- serves every length, rows of different lengths run side by side, and a slot whose row has finished
+    (pos = -1: idle, its workgroups return at once) takes the next request while the others keep going.  ``capture``
+    turns the step into one graph that ``step`` replays.  The host keeps no device state: which slots are busy follows
+    from the lengths it admitted and the steps it enqueued, so nothing here synchronises or reads back."""
+
+    def __init__(self, plm, slots: int, max_len: int, sampling=None):
+        if sampling is not None and not isinstance(sampling, PlmSampling):
+            raise L.HspError("sampling must be a PlmSampling or None")
+        if int(slots) < 1 or int(slots) > 65535:
+            raise L.HspError(f"a session needs 1 .. 65535 slots, got {slots}")
+        if int(max_len) < 1 or int(max_len) > plm.pos_emb.N_POS:
+            raise L.HspError(f"max_len must lie in [1, {plm.pos_emb.N_POS}] (the position table), got {max_len}")
+        if not all(layer.decode_supported() for layer in plm.plm.layers):
+            raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {plm.d_model}, "
+                             f"{plm.plm.layers[0].n_heads} heads, ff {plm.plm.layers[0].ff_dim}")
+        self.plm, self.slots, self.max_len, self.sampling = plm, int(slots), int(max_len), sampling
+        S, D, dev = self.slots, plm.d_model, plm.pos_emb._pe_t.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.tc = torch.zeros(S, plm.tc_latent_dim, self.max_len, **f32)
+        self.codes = torch.full((S, self.max_len + 1), plm.GO_ID, dtype=torch.int64, device=dev)
+        self.pos = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.len = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.seeds = torch.zeros(S, dtype=torch.int64, device=dev)
+        Tp = (self.max_len + 3) & ~3
+        self.kv = [(torch.empty(D, S, Tp, **f32), torch.empty(D, S, Tp, **f32)) for _ in plm.plm.layers]
+        self.x = torch.zeros(1, D, S, **f32)            # zero: the predict GEMM reads idle columns too; they stay finite
+        self.logits = torch.zeros(1, plm.vq_bins, S, **f32)
+        self.ws = plm.plm.layers[0].decode_workspace(S, dev)
+        self._sample = sampling.c_args(self.seeds) if sampling is not None else None
+        self._left = [0] * S                            # steps a slot's row still needs; 0 = free
+        self._len = [0] * S                             # the length last admitted to a slot
+        self._graph = None
+        self.steps = self.replays = self.captures = 0
+
+    def busy(self, slot: int) -> bool:
+        return self._left[slot] > 0
+
+    def admit(self, slot: int, tc_latent: torch.Tensor, seed: int = 0):
+        """Start a request in a free slot: ``tc_latent`` [256, T] with 1 <= T <= max_len.  Stream-ordered copies only (the
+        latent, the go token, len = T, pos = 0, the seed).  The slot's cache needs no clearing: columns above a row's
+        position are never read."""
+        if not 0 <= slot < self.slots:
+            raise L.HspError(f"slot {slot} is not one of the session's {self.slots}")
+        if tc_latent.dim() != 2 or tc_latent.shape[0] != self.plm.tc_latent_dim:
+            raise L.HspError(f"tc_latent must be [{self.plm.tc_latent_dim}, T], got {tuple(tc_latent.shape)}")
+        T = tc_latent.shape[1]
+        if T < 1 or T > self.max_len:
+            raise L.HspError(f"a request needs 1 .. max_len = {self.max_len} frames, got {T}")
+        if self.busy(slot):
+            raise L.HspError(f"slot {slot} is busy for {self._left[slot]} more steps")
+        self.tc[slot, :, :T].copy_(tc_latent, non_blocking=True)
+        self.codes[slot, :1].fill_(self.plm.GO_ID)
+        self.seeds[slot:slot + 1].fill_(int(seed))
+        self.len[slot:slot + 1].fill_(T)
+        self.pos[slot:slot + 1].fill_(0)
+        self._left[slot] = self._len[slot] = T
+
+    def enqueue_step(self):
+        """The launches of one step on the current stream, without the host's bookkeeping: what ``capture`` captures and
+        what an uncaptured ``step`` runs."""
+        m, S = self.plm, self.slots
+        top = self.max_len - 1                          # the largest position a row may hold
+        x = self.x[0]                                   # [D, S]: element (c, b) at c * S + b
+        L.check(L.lib().hsp_plm_embed_pos_f32(
+            L.fptr(self.tc), self.tc.stride(0), self.tc.stride(1), m.tc_latent_dim, L.ptr(self.codes),
+            self.codes.stride(0), L.fptr(m.pc_embedding._w), m.vq_dim, m.pc_embedding.num_embeddings,
+            L.fptr(m.pos_emb._pe_t), m.pos_emb.N_POS, L.fptr(m.pos_emb._alpha), L.fptr(x), x.stride(1), x.stride(0), S,
+            L.ptr(self.pos), top, L.stream_ptr()), "hsp_plm_embed_pos_f32")
+        for layer, (kc, vc) in zip(m.plm.layers, self.kv):
+            layer.decode_step(x, x, kc, vc, top, self.ws, pos=self.pos)
+        m.predict_layer(self.x if m.plm.norm is None else m.plm.norm(self.x), out=self.logits)
+        lg = self.logits
+        L.check(L.lib().hsp_plm_choose_advance_f32(
+            L.fptr(lg), 1, lg.stride(1), S, m.vq_bins, L.ptr(self.codes), self.codes.stride(0), L.ptr(self.pos),
+            L.ptr(self.len), top, ctypes.byref(self._sample) if self._sample is not None else None, L.stream_ptr()),
+            "hsp_plm_choose_advance_f32")
+
+    def step(self):
+        """One position of every busy slot: a replay of the captured graph, else the same launches eagerly.  No host
+        synchronisation, no allocation."""
+        if self._graph is not None:
+            self._graph.replay()
+            self.replays += 1
+        else:
+            self.enqueue_step()
+        self.steps += 1
+        self._left = [max(n - 1, 0) for n in self._left]
+
+    def capture(self):
+        """Capture the step as one graph (a single chain of launches); ``step`` replays it from then on.  Every slot must
+        be idle: one eager step runs first -- it changes nothing, and it is where the kernels' code objects are loaded and
+        the attention kernel's LDS limit is raised, which is not legal inside a capture."""
+        if self._graph is not None:
+            raise L.HspError("the session's step is captured already")
+        if any(self._left):
+            raise L.HspError("capture() needs every slot idle")
+        self.enqueue_step()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self.enqueue_step()
+        self._graph = graph
+        self.captures += 1
+
+    def run(self, tc_latents, seeds=None):
+        """Decode a sequence of requests ([256, T_i] each) through the session's slots -> a list of int64 [T_i] tensors.
+        The lengths are known here, so the whole schedule is computed up front (session_plan) and enqueued as admit /
+        step / copy-out of a finished row before its slot is admitted again: exactly the plan's number of steps, no
+        read-back, nothing that could wait on device state.  ``seeds``: an int s gives request i the seed s + i (None =
+        0), or one int per request.  Every slot must be idle."""
+        tc_latents = list(tc_latents)
+        n = len(tc_latents)
+        if isinstance(seeds, torch.Tensor):
+            seeds = seeds.tolist()
+        seeds = [int(seeds or 0) + i for i in range(n)] if seeds is None or isinstance(seeds, int) else [int(v) for v in seeds]
+        if len(seeds) != n:
+            raise L.HspError(f"{n} requests need {n} seeds, got {len(seeds)}")
+        if any(self._left):
+            raise L.HspError("run() needs every slot idle")
+        lengths = [t.shape[-1] for t in tc_latents]
+        plan, steps = session_plan(lengths, self.slots)
+        out = [torch.empty(T, dtype=torch.int64, device=self.codes.device) for T in lengths]
+        running = {}
+        for step in range(steps):
+            for req, slot in plan.get(step, ()):
+                self.admit(slot, tc_latents[req], seeds[req])
+                running[slot] = req
+            self.step()
+            for slot in [k for k in running if not self.busy(k)]:
+                out[running.pop(slot)].copy_(self.codes_of(slot))
+        return out
+
+    def codes_of(self, slot: int) -> torch.Tensor:
+        """The codes of the slot's current (or last) request: a view ``codes[slot, 1 : len + 1]``."""
+        return self.codes[slot, 1:self._len[slot] + 1]
+
+
 class Megatts2PLM1(nn.Module):
     """t2w2v_transformer.Megatts2PLM1 (:627-718): greedy prosody-code generation.
 
@@ -145,7 +305,8 @@ class Megatts2PLM1(nn.Module):
     encoder under a causal mask (:691), under which position j's activations never change after step j, so a step is one
     new column per row through a K/V cache in all layers (hsp_plm_decode_layer_f32).  Its step-t logits are the
     teacher-forced logits ``score(tc_latent, codes, lens)[:, t]`` of its own codes; they are not the logits of the
-    bidirectional loop, and the codes differ."""
+    bidirectional loop, and the codes differ.  ``infer_many`` / ``decode_session`` decode requests of different lengths
+    that way from one captured step, each row at its own position in device memory (PlmDecodeSession)."""
 
     GO_ID = 1024
 
@@ -336,6 +497,35 @@ class Megatts2PLM1(nn.Module):
             lg = self.step_logits(tc_latent, codes, t + 1, out=all_logits[t:t + 1] if return_logits else None,
                                   prev_logits=lg, cache=cache, sampling=sampling, seeds=seeds)
         return self._last_choice(codes, lg, all_logits, sampling, seeds)
+
+    @_entry
+    def decode_session(self, slots: int, max_len: int, sampling: Optional[PlmSampling] = None) -> PlmDecodeSession:
+        """Fixed-shape state for decoding up to ``slots`` requests of up to ``max_len`` frames side by side, each at its
+        own position (PlmDecodeSession): admit(slot, tc_latent [256, T], seed), step(), capture(), codes_of(slot)."""
+        if self.pos_emb._pe_t is None:
+            raise L.HspError("Megatts2PLM1 used before finalize()")
+        return PlmDecodeSession(self, slots, max_len, sampling)
+
+    @_entry
+    @torch.no_grad()
+    def infer_many(self, tc_latents, slots: int = 16, sampling: Optional[PlmSampling] = None, seeds=None,
+                   capture: bool = True):
+        """Causal decoding of many requests of different lengths: ``tc_latents`` a sequence of [256, T_i] tensors ->
+        a list of int64 [T_i] code tensors, request i's equal to ``infer(tc_i[None], causal=True, ...)[0]`` (with seed
+        ``seeds[i]``; an int s means s + i, as in ``infer``) whatever the other requests are: one session of ``slots``
+        rows, sized for the longest request, and PlmDecodeSession.run -- exactly session_plan's number of steps, no
+        read-back, no polling.  ``capture``: the step is one captured graph, replayed (else launched eagerly)."""
+        tc_latents = list(tc_latents)
+        if not tc_latents:
+            session_plan([], slots)
+            return []
+        if any(t.dim() != 2 for t in tc_latents):
+            raise L.HspError("every request is a [256, T] tensor")
+        session_plan([t.shape[1] for t in tc_latents], slots)          # refuse before any state is allocated
+        ses = self.decode_session(slots, max(t.shape[1] for t in tc_latents), sampling)
+        if capture:
+            ses.capture()
+        return ses.run(tc_latents, seeds)
 
     def _last_choice(self, codes, lg, all_logits, sampling, seeds):
         """The choice of the last step (every earlier one is taken inside the next step's embedding launch)."""

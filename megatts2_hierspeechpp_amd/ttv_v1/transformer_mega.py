@@ -9,7 +9,8 @@ on strided views.  Inference only: dropout is the identity
 
 Two further forms serve the causal mode (Megatts2PLM1.score / infer(causal=True)): ``TransformerEncoder.forward`` with
 ``x_lens`` / ``causal`` is the reference's masked full pass (hsp_mha_f32 with a dense mask, then the projection), and
-``TransformerEncoderLayer.decode_step`` is one new position against a K/V cache (hsp_plm_decode_layer_f32)."""
+``TransformerEncoderLayer.decode_step`` is one new position against a K/V cache (hsp_plm_decode_layer_f32; with a
+position tensor, one position PER ROW: hsp_plm_decode_layer_pos_f32)."""
 from __future__ import annotations
 
 import ctypes
@@ -190,10 +191,12 @@ class TransformerEncoderLayer(nn.Module):
         n = L.lib().hsp_plm_decode_workspace_bytes(B, self.dim)
         return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
 
-    def decode_step(self, x, y, k_cache, v_cache, t: int, workspace):
+    def decode_step(self, x, y, k_cache, v_cache, t: int, workspace, pos=None):
         """One new position t of every row against this layer's K/V cache (hsp_plm_decode_layer_f32): x, y [D, B] views
         (any strides; y may be x), k_cache / v_cache [D, B, Tp], ``workspace`` from decode_workspace.  Writes column t
-        of both caches."""
+        of both caches.  With ``pos`` (int32 [B] on the device, read when the kernels run) row b is at ``pos[b]`` and
+        ``t`` is the largest position a row may hold; a row whose position is outside [0, t] is idle and untouched
+        (hsp_plm_decode_layer_pos_f32)."""
         w = self.decode._views
         if w is None or self.norm1._g is None:
             raise L.HspError("TransformerEncoderLayer used before finalize()")
@@ -209,7 +212,13 @@ class TransformerEncoderLayer(nn.Module):
         for name in ("wqkv_t", "bqkv", "wo_t", "bo", "w1_t", "c1", "w2_t", "c2"):
             setattr(a, name, L.fptr(w[name]))
         a.workspace, a.workspace_bytes = L.fptr(workspace), workspace.numel() * 4
-        L.check(L.lib().hsp_plm_decode_layer_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_decode_layer_f32")
+        if pos is None:
+            L.check(L.lib().hsp_plm_decode_layer_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_decode_layer_f32")
+            return
+        if pos.dtype != torch.int32 or pos.shape != (B,) or pos.stride(0) != 1:
+            raise L.HspError("pos must be a contiguous int32 [B] tensor")
+        L.check(L.lib().hsp_plm_decode_layer_pos_f32(ctypes.byref(a), L.ptr(pos), L.stream_ptr()),
+                "hsp_plm_decode_layer_pos_f32")
 
     def forward(self, x, mask=None, batch=None, last_only=False, cache=None):
         """``last_only`` returns just the last position of every utterance ``[1, D, B]`` (all the
