@@ -606,6 +606,45 @@ int hsp_plm_embed_pos_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t
 int hsp_plm_choose_advance_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* codes,
                                int64_t codes_bs, int32_t* pos, const int32_t* len, int32_t max_pos,
                                const hsp_sample_args* args, void* stream);
+/* PLM prefill (continue from given codes; additive: HSP_VERSION unchanged).  csrc/hsp_plm_prefill.hip.  When the first n
+ * codes of a row are given, every position of that prefix is known at once: each projection of a layer is one GEMM over
+ * n columns, and what remains is this entry point.  For ONE row, given the stacked projection q | k | v of its first n
+ * positions, it fills the row's slice of the layer's decode caches
+ *   k_cache[c, j] = k[c, j] ;  v_cache[c, j] = v[c, j]                                     for j < n, c < D
+ * and computes the causal attention output, with Dh = D / H,
+ *   out[h Dh + d, i] = sum_{j <= i} softmax_{j <= i}(q[h Dh + :, i] . k[h Dh + :, j] / sqrt(Dh)) v[h Dh + d, j]   for i < n
+ * -- what hsp_plm_decode_layer_f32 computes as `a` at t = i, for every i < n at once -- so that a decode that starts at
+ * position n reads the caches as if it had stepped through the prefix.
+ * qkv: rows q | k | v of the stacked GEMM output, element (r, j) at qkv[r * q_rs + j], r < 3 D.  out: element (c, j) at
+ * out[c * o_rs + j]; it may be NULL: then only the caches are filled (the last layer's case: nothing reads the last
+ * layer's outputs at prefix positions), with the same bits as a call with out.  k_cache / v_cache: THIS ROW's slice,
+ * element (c, j) at base[c * cs + j]: row b of a [D, B, Tp] buffer is base + b * Tp with cs = B * Tp.
+ * Columns >= n of the caches, of out and of qkv are never read or written (they may hold NaN); every cache and out
+ * element with j < n is written exactly once; qkv is not written.  No dense mask: one workgroup per (tile of 16 queries,
+ * head) walks 64-key blocks up to its diagonal and no further, with a running maximum and sum per query; scores and
+ * probabilities never reach global memory.  No atomics and every sum in a fixed order: column i of out depends on
+ * columns 0 .. i of the head's q / k / v alone -- not on n, not on anything beside the row.  One launch, no allocation,
+ * no host synchronisation, no global state; heads of more than 87 channels need more than 32 KB of LDS, and the first
+ * such call on a device raises the kernel's limit, which is not legal inside a stream capture.
+ * hsp_plm_prefill_attn_supported(D, H): 1 when a kernel exists: H dividing D, D / H <= 128, D <= 8192 (the PLM's
+ * 276 / 4 and 64 / 8 among them).
+ * HSP_EINVAL, decided before any HIP call, nothing launched: NULL a, qkv, k_cache or v_cache; n < 1; n > q_rs; out given
+ * and n > o_rs; n > cs; a negative stride; D % H != 0 or a geometry without a kernel; a non-zero debug;
+ * n > HSP_PLM_PREFILL_MAX_N = 65 536 keys (the bound the 32-bit column indices and the grid are checked for; the PLM's
+ * position table ends at 4 000). */
+#define HSP_PLM_PREFILL_MAX_N 65536
+typedef struct hsp_plm_prefill_attn_args {
+  const float* qkv;
+  int64_t q_rs;
+  float* out; /* may be NULL */
+  int64_t o_rs;
+  float *k_cache, *v_cache;
+  int64_t cs; /* both caches: channel stride; the time stride is 1 */
+  int32_t n, D, H;
+  int32_t debug; /* must be 0 (as hsp_conv1d_args.debug) */
+} hsp_plm_prefill_attn_args;
+int hsp_plm_prefill_attn_supported(int32_t D, int32_t H);
+int hsp_plm_prefill_attn_f32(const hsp_plm_prefill_attn_args* a, void* stream);
 /* y[b, c, t] (contiguous) = x[b * s_bs + c * s_cs + t * s_ts] : strided gather, e.g. the last
  * position of every utterance (`[:, -1:, :]`, ttv_v1/t2w2v_transformer.py:716) */
 int hsp_copy_strided_f32(const float* x, int64_t s_bs, int64_t s_cs, int64_t s_ts, float* y, int32_t B,

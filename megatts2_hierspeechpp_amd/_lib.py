@@ -122,6 +122,15 @@ class PlmDecodeArgs(C.Structure):
     ]
 
 
+class PlmPrefillAttnArgs(C.Structure):
+    """Mirror of ``hsp_plm_prefill_attn_args``."""
+    _fields_ = [
+        ("qkv", _fp), ("q_rs", C.c_int64), ("out", _fp), ("o_rs", C.c_int64),
+        ("k_cache", _fp), ("v_cache", _fp), ("cs", C.c_int64),
+        ("n", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("debug", C.c_int32),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -180,6 +189,8 @@ SIGNATURES = {
                                         _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, _fp]),
     "hsp_plm_choose_advance_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, _fp,
                                              C.c_int32, C.POINTER(SampleArgs), _fp]),
+    "hsp_plm_prefill_attn_supported": (C.c_int, [C.c_int32, C.c_int32]),
+    "hsp_plm_prefill_attn_f32": (C.c_int, [C.POINTER(PlmPrefillAttnArgs), _fp]),
     "hsp_embedding_sum_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp,
                                         C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,

@@ -116,11 +116,15 @@ def _check_scale_norm(scale_norm: str) -> None:
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
-        target_lufs: float = -23.0, plm_causal: bool = False):
+        target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
     make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.  ``plm_causal``: the
     prosody LM decodes under the causal mask it is trained with, through a K/V cache (``infer(causal=True)``: other
     codes than the reference's bidirectional loop gives); False: the reference's loop.
+    ``plm_prefix`` (int64 [B, P], needs ``plm_causal``): the first P prosody codes of every row are given and only the
+    rest is decoded (``infer(prefix_codes=)``) -- durations do not depend on the codes, so the kept beginning of an
+    earlier take of the same text and prompt fits frame for frame.  ``return_codes``: the PLM codes int64 [B, T] are
+    appended to the result (the codes a later ``plm_prefix`` is cut from).
     ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
     peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
     length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
@@ -133,13 +137,18 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
     _check_scale_norm(scale_norm)
+    if plm_prefix is not None and not plm_causal:
+        raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
-    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal)
-    return tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
-                          denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
-                          gain=gain, scale_norm=scale_norm, target_lufs=target_lufs)
+    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal, prefix_codes=plm_prefix)
+    out = tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
+                         denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
+                         gain=gain, scale_norm=scale_norm, target_lufs=target_lufs)
+    if not return_codes:
+        return out
+    return (*out, codes) if return_float else (out, codes)
 
 
 @torch.no_grad()
@@ -201,7 +210,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     noise_scale_vc: float = 0.333, output_sr: int = 16000, dur=None, noise=None,
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
-                    takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False):
+                    takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
+                    return_codes: bool = False):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -217,12 +227,22 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     ``takes`` = N > 1: one call synthesises N takes of the same text and prompt, take k with the PLM seed ``seed + k``
     (each take equals the solo call with that seed: the rows of a batch are independent and have one length, since the
     durations do not depend on the codes); returns int16 [N, n_out] and writes ``<stem>_take<k><ext>``.  An explicit
-    ``noise`` with one row is used by every take; None: every take draws its own."""
+    ``noise`` with one row is used by every take; None: every take draws its own.
+    ``plm_prefix`` (int64 [P] or [1, P], needs ``plm_causal``): the first P prosody codes are given (see `tts`); with
+    ``takes`` = N the one prefix is shared by all N takes: N different endings of one beginning.  ``return_codes``
+    appends the PLM codes (int64 [T], or [N, T] with takes) to the result."""
     takes = int(takes)
     if takes < 1:
         raise L.HspError(f"takes must be >= 1, got {takes}")
     if takes > 1 and plm_sampling is None:
         raise L.HspError("takes > 1 needs plm_sampling: greedy decoding gives the same take every time")
+    if plm_prefix is not None:
+        if not plm_causal:
+            raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
+        if not isinstance(plm_prefix, torch.Tensor) or plm_prefix.dim() not in (1, 2) or \
+                (plm_prefix.dim() == 2 and plm_prefix.shape[0] != 1):
+            raise L.HspError("plm_prefix must be an int64 [P] or [1, P] tensor: one prefix, shared by every take")
+        plm_prefix = plm_prefix.reshape(1, -1).expand(takes, -1).contiguous()
     if denoise_ratio != 0 and denoiser is None:
         raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as inference_plm.py:144-147")
     if int(prompt_sr) != 16000:
@@ -241,14 +261,14 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
-    wav, audio = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
-                     noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
-                     noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
-                     seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
-                     target_lufs=target_lufs, plm_causal=plm_causal)
+    wav, audio, codes = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
+                            noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
+                            noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
+                            seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
+                            target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True)
     rate = output_sr if output_sr in (24000, 48000) else 16000
     if B == 1:
-        wav = wav[0]
+        wav, codes = wav[0], codes[0]
         if output_path is not None:
             write_wav(output_path, rate, wav)
     elif output_path is not None:
@@ -256,16 +276,20 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
         stem, ext = os.path.splitext(str(output_path))
         for k in range(B):
             write_wav(f"{stem}_take{k}{ext}", rate, wav[k])
-    return (wav, audio) if return_float else wav
+    out = (wav, audio) if return_float else (wav,)
+    if return_codes:
+        out = (*out, codes)
+    return out if len(out) > 1 else out[0]
 
 
 def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
-                         plm_sampling=None, seed: int = 0, takes: int = 1, plm_causal: bool = False, **kwargs):
+                         plm_sampling=None, seed: int = 0, takes: int = 1, plm_causal: bool = False, plm_prefix=None,
+                         return_codes: bool = False, **kwargs):
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
-    ``takes`` / ``plm_causal`` and ``kwargs`` go to `tts_from_prompt`."""
+    ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` and ``kwargs`` go to `tts_from_prompt`."""
     from . import audio as A
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
-                           **kwargs)
+                           plm_prefix=plm_prefix, return_codes=return_codes, **kwargs)

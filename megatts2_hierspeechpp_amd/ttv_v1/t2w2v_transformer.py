@@ -150,6 +150,25 @@ def session_plan(lengths, slots: int):
     return admissions, (max(free_at) if lengths else 0)
 
 
+def check_prefix(prefix, T: int, vq_bins: int, dims: int = 1) -> int:
+    """The argument checks of a given code prefix (``infer(prefix_codes=)``, ``PlmDecodeSession.admit(prefix_codes=)``),
+    as a pure function of the tensor: int64, ``dims``-dimensional ([P], or [B, P] with ``dims`` = 2), 1 <= P < T -- at
+    least one position is left to decode -- and every code in [0, vq_bins) (the go and pad ids are not codes).  Returns P.
+    Reading the values of a device tensor is one read-back: callers run this outside any capture."""
+    if not isinstance(prefix, torch.Tensor) or prefix.dtype != torch.int64:
+        raise L.HspError(f"prefix codes must be an int64 tensor, got {getattr(prefix, 'dtype', type(prefix).__name__)}")
+    if prefix.dim() != dims:
+        raise L.HspError(f"prefix codes must be {'[P]' if dims == 1 else '[B, P]'}, got shape {tuple(prefix.shape)}")
+    P = int(prefix.shape[-1])
+    if not 1 <= P < int(T):
+        raise L.HspError(f"a prefix needs 1 <= P < T = {int(T)} codes (one position at least is decoded), got P = {P}")
+    if prefix.numel():
+        lo, hi = int(prefix.min()), int(prefix.max())
+        if lo < 0 or hi >= int(vq_bins):
+            raise L.HspError(f"prefix codes must lie in [0, {int(vq_bins)}), got {lo} .. {hi}")
+    return P
+
+
 class PlmDecodeSession:
     """Causal decoding of ragged request streams from ONE step (Megatts2PLM1.decode_session): ``slots`` rows of fixed-shape
     device state, each row at its own position ``pos[slot]`` in device memory (include/hsp.h "per-row positions"), so the
@@ -191,10 +210,16 @@ class PlmDecodeSession:
     def busy(self, slot: int) -> bool:
         return self._left[slot] > 0
 
-    def admit(self, slot: int, tc_latent: torch.Tensor, seed: int = 0):
+    def admit(self, slot: int, tc_latent: torch.Tensor, seed: int = 0, prefix_codes=None):
         """Start a request in a free slot: ``tc_latent`` [256, T] with 1 <= T <= max_len.  Stream-ordered copies only (the
         latent, the go token, len = T, pos = 0, the seed).  The slot's cache needs no clearing: columns above a row's
-        position are never read."""
+        position are never read.
+
+        ``prefix_codes`` (int64 [P], 1 <= P < T; `check_prefix`, which reads a device tensor's values back once): the
+        row's first P codes are given.  They are written to ``codes[slot, 1 : P + 1]``, the slot's K / V caches are
+        prefilled for positions 0 .. P - 1 in one pass (Megatts2PLM1.prefill: eager launches on the current stream --
+        admit stays outside any capture, so they are legal between replays), and the row starts at pos = P: it takes
+        T - P steps, and ``codes_of`` returns all T codes, the prefix in front."""
         if not 0 <= slot < self.slots:
             raise L.HspError(f"slot {slot} is not one of the session's {self.slots}")
         if tc_latent.dim() != 2 or tc_latent.shape[0] != self.plm.tc_latent_dim:
@@ -204,12 +229,16 @@ class PlmDecodeSession:
             raise L.HspError(f"a request needs 1 .. max_len = {self.max_len} frames, got {T}")
         if self.busy(slot):
             raise L.HspError(f"slot {slot} is busy for {self._left[slot]} more steps")
+        P = 0 if prefix_codes is None else check_prefix(prefix_codes, T, self.plm.vq_bins)
         self.tc[slot, :, :T].copy_(tc_latent, non_blocking=True)
         self.codes[slot, :1].fill_(self.plm.GO_ID)
         self.seeds[slot:slot + 1].fill_(int(seed))
         self.len[slot:slot + 1].fill_(T)
-        self.pos[slot:slot + 1].fill_(0)
-        self._left[slot] = self._len[slot] = T
+        if P:
+            self.codes[slot, 1:P + 1].copy_(prefix_codes, non_blocking=True)
+            self.plm.prefill(self.tc[slot], self.codes[slot, 1:P + 1], [(kc[:, slot], vc[:, slot]) for kc, vc in self.kv])
+        self.pos[slot:slot + 1].fill_(P)
+        self._left[slot], self._len[slot] = T - P, T
 
     def enqueue_step(self):
         """The launches of one step on the current stream, without the host's bookkeeping: what ``capture`` captures and
@@ -257,8 +286,11 @@ class PlmDecodeSession:
         self._graph = graph
         self.captures += 1
 
-    def run(self, tc_latents, seeds=None):
+    def run(self, tc_latents, seeds=None, prefixes=None):
         """Decode a sequence of requests ([256, T_i] each) through the session's slots -> a list of int64 [T_i] tensors.
+        ``prefixes``: None, or one entry per request, each None or the request's first P_i codes (int64 [P_i], see
+        ``admit``): such a request takes T_i - P_i steps -- the schedule is ``session_plan([T_i - P_i], slots)`` -- and its
+        result holds all T_i codes.
         The lengths are known here, so the whole schedule is computed up front (session_plan) and enqueued as admit /
         step / copy-out of a finished row before its slot is admitted again: exactly the plan's number of steps, no
         read-back, nothing that could wait on device state.  ``seeds``: an int s gives request i the seed s + i (None =
@@ -273,12 +305,16 @@ class PlmDecodeSession:
         if any(self._left):
             raise L.HspError("run() needs every slot idle")
         lengths = [t.shape[-1] for t in tc_latents]
-        plan, steps = session_plan(lengths, self.slots)
+        prefixes = [None] * n if prefixes is None else list(prefixes)
+        if len(prefixes) != n:
+            raise L.HspError(f"{n} requests need {n} prefixes (None for a request without one), got {len(prefixes)}")
+        given = [0 if p is None else check_prefix(p, T, self.plm.vq_bins) for p, T in zip(prefixes, lengths)]
+        plan, steps = session_plan([T - P for T, P in zip(lengths, given)], self.slots)
         out = [torch.empty(T, dtype=torch.int64, device=self.codes.device) for T in lengths]
         running = {}
         for step in range(steps):
             for req, slot in plan.get(step, ()):
-                self.admit(slot, tc_latents[req], seeds[req])
+                self.admit(slot, tc_latents[req], seeds[req], prefixes[req])
                 running[slot] = req
             self.step()
             for slot in [k for k in running if not self.busy(k)]:
@@ -306,7 +342,9 @@ class Megatts2PLM1(nn.Module):
     new column per row through a K/V cache in all layers (hsp_plm_decode_layer_f32).  Its step-t logits are the
     teacher-forced logits ``score(tc_latent, codes, lens)[:, t]`` of its own codes; they are not the logits of the
     bidirectional loop, and the codes differ.  ``infer_many`` / ``decode_session`` decode requests of different lengths
-    that way from one captured step, each row at its own position in device memory (PlmDecodeSession)."""
+    that way from one captured step, each row at its own position in device memory (PlmDecodeSession).  In the causal
+    mode a row may start behind given codes (``prefix_codes`` / ``prefixes``): ``prefill`` leaves the K / V of the prefix in
+    the caches in one full pass and the loop decodes the rest."""
 
     GO_ID = 1024
 
@@ -428,25 +466,62 @@ class Megatts2PLM1(nn.Module):
         lg = self.predict_layer(x)                                                   # [1, vq_bins, Np]
         return lg[0][:, :B * T].reshape(self.vq_bins, B, T).permute(1, 2, 0)
 
-    def _infer_causal(self, tc_latent, return_logits, sampling, seeds):
+    @_entry
+    @torch.no_grad()
+    def prefill(self, tc_latent: torch.Tensor, prefix_codes: torch.Tensor, kv_rows):
+        """K / V of positions 0 .. P - 1 of ONE row into its cache slices, in one full pass instead of P decode steps:
+        ``tc_latent`` [256, >= P] (unit time stride), ``prefix_codes`` int64 [P] on the device (checked by the caller:
+        `check_prefix`), ``kv_rows`` one (k_row, v_row) pair of [D, >= P] slices per layer (``kv[l][*][:, b]`` of a
+        [D, B, Tp] cache).  The inputs of positions 0 .. P - 1 are the go token followed by ``prefix_codes[:P - 1]``: the
+        full-form embedding, then TransformerEncoder.prefill -- per layer the fused-LayerNorm q/k/v GEMM over the P
+        columns, hsp_plm_prefill_attn_f32, and (but for the last layer) out_proj and the feed-forward on the token GEMMs.
+
+        Prefill is always issued per row (B = 1, over that row's own P columns): a GEMM's kernel choice depends on its
+        column count, so a row prefilled beside others could differ from the row alone.  Issued per row, a request's
+        result does not depend on its neighbours -- the property the decode path has -- and a session admits rows one at a
+        time anyway.  The price: a batch of B prefixes costs B x about 20 small launches."""
+        if self.pos_emb._pe_t is None:
+            raise L.HspError("Megatts2PLM1 used before finalize()")
+        P = int(prefix_codes.shape[0])
+        if tc_latent.dim() != 2 or tc_latent.shape[0] != self.tc_latent_dim or tc_latent.stride(1) != 1:
+            raise L.HspError(f"tc_latent must be [{self.tc_latent_dim}, >= P] with unit time stride, got "
+                             f"{tuple(tc_latent.shape)}")
+        if not 1 <= P <= min(tc_latent.shape[1], self.pos_emb.N_POS):
+            raise L.HspError(f"a prefix of {P} codes needs 1 <= P <= {min(tc_latent.shape[1], self.pos_emb.N_POS)}")
+        if not all(layer.prefill_supported() for layer in self.plm.layers):
+            raise L.HspError(f"hsp_plm_prefill_attn_f32 has no kernel for d_model {self.d_model}, "
+                             f"{self.plm.layers[0].n_heads} heads")
+        codes_in = torch.empty(1, P, dtype=torch.int64, device=tc_latent.device)
+        codes_in[:, :1].fill_(self.GO_ID)
+        codes_in[0, 1:].copy_(prefix_codes[:P - 1])
+        self.plm.prefill(self._embed(tc_latent.unsqueeze(0), codes_in, P), P, kv_rows)
+
+    def _infer_causal(self, tc_latent, return_logits, sampling, seeds, prefix=None):
         """The K/V-cached loop: per step one embedded column per row (_embed_one, which also takes the previous step's
-        choice), ``num_layers`` calls of hsp_plm_decode_layer_f32 and the predict layer -- no host synchronisation."""
+        choice), ``num_layers`` calls of hsp_plm_decode_layer_f32 and the predict layer -- no host synchronisation.
+        ``prefix`` int64 [B, P] on the device: the first P codes of every row are given; the caches are prefilled row by
+        row (``prefill``) and the loop runs t = P .. T - 1, its first step reading the given ``codes[:, P]``."""
         B, _, T = tc_latent.shape
+        P = 0 if prefix is None else prefix.shape[1]
         dev, D = tc_latent.device, self.d_model
         if not all(layer.decode_supported() for layer in self.plm.layers):
             raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {D}, {self.plm.layers[0].n_heads} "
                              f"heads, ff {self.plm.layers[0].ff_dim}")
         codes = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
         codes[:, 0] = self.GO_ID
-        all_logits = torch.empty(T, self.vq_bins, B, dtype=torch.float32, device=dev) if return_logits else None
+        all_logits = torch.empty(T - P, self.vq_bins, B, dtype=torch.float32, device=dev) if return_logits else None
         Tp = (T + 3) & ~3
         cache = types.SimpleNamespace(emb=torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
         kv = [(torch.empty(D, B, Tp, dtype=torch.float32, device=dev), torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
               for _ in self.plm.layers]
         x = torch.empty(1, D, B, dtype=torch.float32, device=dev)
         ws = self.plm.layers[0].decode_workspace(B, dev)
+        if P:
+            codes[:, 1:P + 1] = prefix
+            for b in range(B):
+                self.prefill(tc_latent[b], codes[b, 1:P + 1], [(kc[:, b], vc[:, b]) for kc, vc in kv])
         lg = None
-        for t in range(T):
+        for t in range(P, T):
             sample = sampling.c_args(seeds) if sampling is not None and lg is not None else None
             self._embed_one(tc_latent, codes, t, cache, lg, sample)
             src = cache.emb[:, :, t]
@@ -454,13 +529,14 @@ class Megatts2PLM1(nn.Module):
                 layer.decode_step(src, x[0], kc, vc, t, ws)
                 src = x[0]
             # the encoder's final norm (None in the PLM) reads x and leaves it in place for the next step's layers
-            lg = self.predict_layer(x if self.plm.norm is None else self.plm.norm(x), out=all_logits[t:t + 1] if return_logits else None)
+            lg = self.predict_layer(x if self.plm.norm is None else self.plm.norm(x),
+                                    out=all_logits[t - P:t - P + 1] if return_logits else None)
         return codes, lg, all_logits
 
     @_entry
     @torch.no_grad()
     def infer(self, tc_latent: torch.Tensor, return_logits: bool = False, sampling: Optional[PlmSampling] = None,
-              seeds=None, causal: bool = False):
+              seeds=None, causal: bool = False, prefix_codes: Optional[torch.Tensor] = None):
         """tc_latent (B, D, T) -> int64 codes (B, T)  [+ fp32 logits (B, T, vq_bins)].
 
         ``causal`` False: the reference's bidirectional loop.  True: K/V-cached decoding under the causal mask the model
@@ -469,16 +545,32 @@ class Megatts2PLM1(nn.Module):
         ``sampling`` None: greedy (the reference).  A PlmSampling: every code is drawn instead (include/hsp.h "sampled
         PLM decoding"); ``seeds`` an int (row b gets seed + b; None = 0) or an int64 [B] tensor (a device tensor is read
         in place when the kernels run, so a captured loop replays with new seeds after ``seeds.copy_()``).  Row b
-        depends on its own seed only, not on the rest of the batch."""
+        depends on its own seed only, not on the rest of the batch.
+
+        ``prefix_codes`` (``causal=True`` only; int64 [B, P], 1 <= P < T, codes in [0, vq_bins): `check_prefix`): the
+        first P codes of every row are given -- the kept beginning of an earlier take, a row to resume, the codes of
+        preceding speech -- and only positions P .. T - 1 are decoded, behind K / V caches prefilled in one pass per row
+        (``prefill``).  The codes come back [B, T] with the prefix in front; ``return_logits`` gives [B, T - P, vq_bins],
+        entry i belonging to position P + i.  The repetition penalty sees the prefix codes and draws stay keyed by
+        (seed, column), so a tail drawn behind a prefix equals the tail of a full run that happened to draw that prefix.
+        None is exactly the loop without a prefix (a tensor of P = 0 columns is refused, like every P outside 1 .. T - 1)."""
         if self.pos_emb._pe_t is None:
             raise L.HspError("Megatts2PLM1 used before finalize()")
         if sampling is not None and not isinstance(sampling, PlmSampling):
             raise L.HspError("sampling must be a PlmSampling or None")
         B, D, T = tc_latent.shape
+        if prefix_codes is not None and not causal:
+            raise L.HspError("prefix_codes needs causal=True: the bidirectional loop re-encodes every position at every "
+                             "step, so nothing of a prefix can be kept")
+        if prefix_codes is not None:
+            check_prefix(prefix_codes, T, self.vq_bins, dims=2)
+            if prefix_codes.shape[0] != B:
+                raise L.HspError(f"prefix_codes must have one row per utterance ({B}), got {prefix_codes.shape[0]}")
+            prefix_codes = prefix_codes.to(tc_latent.device)
         seeds = plm_seeds(seeds, B, tc_latent.device) if sampling is not None else None
         assert D == self.tc_latent_dim and tc_latent.stride(2) == 1 and T <= self.pos_emb.N_POS
         if causal:
-            codes, lg, all_logits = self._infer_causal(tc_latent, return_logits, sampling, seeds)
+            codes, lg, all_logits = self._infer_causal(tc_latent, return_logits, sampling, seeds, prefix_codes)
             return self._last_choice(codes, lg, all_logits, sampling, seeds)
         codes = torch.empty(B, T + 1, dtype=torch.int64, device=tc_latent.device)
         codes[:, 0] = self.GO_ID
@@ -509,12 +601,15 @@ class Megatts2PLM1(nn.Module):
     @_entry
     @torch.no_grad()
     def infer_many(self, tc_latents, slots: int = 16, sampling: Optional[PlmSampling] = None, seeds=None,
-                   capture: bool = True):
+                   capture: bool = True, prefixes=None):
         """Causal decoding of many requests of different lengths: ``tc_latents`` a sequence of [256, T_i] tensors ->
         a list of int64 [T_i] code tensors, request i's equal to ``infer(tc_i[None], causal=True, ...)[0]`` (with seed
         ``seeds[i]``; an int s means s + i, as in ``infer``) whatever the other requests are: one session of ``slots``
         rows, sized for the longest request, and PlmDecodeSession.run -- exactly session_plan's number of steps, no
-        read-back, no polling.  ``capture``: the step is one captured graph, replayed (else launched eagerly)."""
+        read-back, no polling.  ``capture``: the step is one captured graph, replayed (else launched eagerly).
+        ``prefixes``: None, or per request None or its first P_i codes (int64 [P_i], 1 <= P_i < T_i): request i then equals
+        ``infer(tc_i[None], causal=True, prefix_codes=prefixes[i][None], ...)[0]``, takes T_i - P_i steps, and comes back
+        whole (PlmDecodeSession.run)."""
         tc_latents = list(tc_latents)
         if not tc_latents:
             session_plan([], slots)
@@ -525,7 +620,7 @@ class Megatts2PLM1(nn.Module):
         ses = self.decode_session(slots, max(t.shape[1] for t in tc_latents), sampling)
         if capture:
             ses.capture()
-        return ses.run(tc_latents, seeds)
+        return ses.run(tc_latents, seeds, prefixes)
 
     def _last_choice(self, codes, lg, all_logits, sampling, seeds):
         """The choice of the last step (every earlier one is taken inside the next step's embedding launch)."""

@@ -10,7 +10,8 @@ on strided views.  Inference only: dropout is the identity
 Two further forms serve the causal mode (Megatts2PLM1.score / infer(causal=True)): ``TransformerEncoder.forward`` with
 ``x_lens`` / ``causal`` is the reference's masked full pass (hsp_mha_f32 with a dense mask, then the projection), and
 ``TransformerEncoderLayer.decode_step`` is one new position against a K/V cache (hsp_plm_decode_layer_f32; with a
-position tensor, one position PER ROW: hsp_plm_decode_layer_pos_f32)."""
+position tensor, one position PER ROW: hsp_plm_decode_layer_pos_f32); ``prefill`` is ONE row's first n positions in a single
+full pass that leaves K and V in those caches (hsp_plm_prefill_attn_f32), so that a decode can start behind given codes."""
 from __future__ import annotations
 
 import ctypes
@@ -220,6 +221,38 @@ class TransformerEncoderLayer(nn.Module):
         L.check(L.lib().hsp_plm_decode_layer_pos_f32(ctypes.byref(a), L.ptr(pos), L.stream_ptr()),
                 "hsp_plm_decode_layer_pos_f32")
 
+    def prefill_supported(self) -> bool:
+        return bool(L.lib().hsp_plm_prefill_attn_supported(self.dim, self.n_heads))
+
+    def prefill(self, x, n: int, k_row, v_row, last: bool = False):
+        """The first ``n`` positions of ONE row in a single pass: x [1, D, Np] (Np >= n, padding columns zero) ->
+        this layer's output [1, D, Np] under the causal mask, with K / V of positions 0 .. n - 1 written to ``k_row`` /
+        ``v_row`` -- the row's [D, >= n] slices of the layer's decode caches (unit time stride, one channel stride), where
+        ``decode_step`` reads them from position n on.  The fused-LayerNorm stacked q/k/v GEMM over the Np columns, then
+        hsp_plm_prefill_attn_f32 (no dense mask), then out_proj (+ residual), ff.0 (ReLU), ff.3 (+ residual) as in
+        ``forward``.  ``last``: stop after K / V and return None -- nothing reads the last layer's outputs at prefix
+        positions."""
+        if self.norm1._g is None:
+            raise L.HspError("TransformerEncoderLayer used before finalize()")
+        D = self.dim
+        assert x.dim() == 3 and x.shape[0] == 1 and x.shape[1] == D and 1 <= n <= x.shape[2]
+        assert k_row.shape[0] == D and v_row.shape[0] == D and k_row.stride(1) == 1 and v_row.stride(1) == 1
+        assert k_row.stride(0) == v_row.stride(0) and k_row.shape[1] >= n and v_row.shape[1] >= n
+        qkv = self.attn.qkv(x)                                                    # norm1 fused: [1, 3 D, Np]
+        # padding columns (n not a multiple of 4) must stay finite: they flow through the following GEMMs
+        o = None if last else (torch.empty_like(x) if x.shape[2] == n else torch.zeros_like(x))
+        a = L.PlmPrefillAttnArgs()
+        a.qkv, a.q_rs = L.fptr(qkv), qkv.stride(1)
+        a.out, a.o_rs = (L.fptr(o), o.stride(1)) if o is not None else (None, 0)
+        a.k_cache, a.v_cache, a.cs = L.fptr(k_row), L.fptr(v_row), k_row.stride(0)
+        a.n, a.D, a.H, a.debug = n, D, self.n_heads, 0
+        L.check(L.lib().hsp_plm_prefill_attn_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_prefill_attn_f32")
+        if last:
+            return None
+        x = self.attn.out_proj[0](o, res=x)
+        h = self.ff["0"](x, act=L.ACT_RELU)                                       # norm2 fused into ff.0
+        return self.ff["3"](h, res=x)
+
     def forward(self, x, mask=None, batch=None, last_only=False, cache=None):
         """``last_only`` returns just the last position of every utterance ``[1, D, B]`` (all the
         greedy loop reads from the final layer); attention still sees the whole prefix.  ``cache`` (layer 0 of the greedy
@@ -264,6 +297,13 @@ class TransformerEncoder(nn.Module):
         if causal:
             vis = vis & (j[None, :] <= j[:, None])[None]
         return vis.to(torch.float32).contiguous()
+
+    def prefill(self, x, n: int, kv_rows):
+        """ONE row's first ``n`` positions through every layer (TransformerEncoderLayer.prefill): x [1, D, Np],
+        ``kv_rows`` one (k_row, v_row) pair of [D, >= n] cache slices per layer.  The last layer stops after its K / V."""
+        assert len(kv_rows) == self.num_layers
+        for i, (layer, (k_row, v_row)) in enumerate(zip(self.layers, kv_rows)):
+            x = layer.prefill(x, n, k_row, v_row, last=i == self.num_layers - 1)
 
     def forward(self, x, x_lens=None, causal=False, batch=None, last_only=False, cache=None):
         """Without ``x_lens`` (the reference builds no mask then, whatever ``causal`` says: :155-158) the unmasked pass
