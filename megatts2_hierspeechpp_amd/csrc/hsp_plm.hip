@@ -10,51 +10,79 @@
 
 namespace {
 
-// x[b, c, j] = (c < Dtc ? tc[b, c, j] : emb[codes[b, j], c - Dtc]) + alpha * pe_t[c, j],  j < n
+// The read-only operands every embed kernel shares (hsp.h "Mega-TTS2 PLM loop").  pe_t is the sinusoid table transposed
+// to [D][P] so that lanes (running along j) read it coalesced.  A kernel does NOT take this struct: its parameters are
+// the pointers themselves, each `const ... __restrict__` (PLM_EMBED_PARAMS), because that is where the compiler honours
+// the qualifier on a pointer.  The kernel builds the struct from its parameters (PLM_EMBED_OPS), which costs nothing
+// once the helpers below are inlined; the speed of the fused kernels was measured in this form.
+struct EmbedOps {
+  const float* tc;
+  int64_t tc_bs, tc_cs;
+  int Dtc;
+  const int64_t* codes;
+  int64_t codes_bs;
+  const float* emb;
+  int Demb, n_emb;
+  const float* pe_t;
+  int P;
+  const float* alpha;
+};
+// `codes_q`: const in the kernels that only read the codes
+#define PLM_EMBED_PARAMS(codes_q)                                                                                   \
+  const float *__restrict__ tc, int64_t tc_bs, int64_t tc_cs, int Dtc, codes_q int64_t *__restrict__ codes,         \
+      int64_t codes_bs, const float *__restrict__ emb, int Demb, int n_emb, const float *__restrict__ pe_t, int P,  \
+      const float *__restrict__ alpha
+#define PLM_EMBED_OPS EmbedOps{tc, tc_bs, tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha}
+#define PLM_EMBED_ARGS(o) o.tc, o.tc_bs, o.tc_cs, o.Dtc, o.codes, o.codes_bs, o.emb, o.Demb, o.n_emb, o.pe_t, o.P, o.alpha
+
+// x[b, c, j] = (c < Dtc ? tc[b, c, j] : emb[codes[b, j], c - Dtc]) + alpha * pe_t[c, j]
 // (torch.cat([tc_latent[:, :t+1], pc_embedding(p_code)], -1) then SinePositionalEmbedding.forward,
-//  t2w2v_transformer.py:711-713,510-514; x_scale = 1).  pe_t is the sinusoid table transposed
-// to [D][P] so that lanes (running along j) read it coalesced.
-__global__ __launch_bounds__(256) void plm_embed_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
-                                                        int Dtc, const int64_t* __restrict__ codes, int64_t codes_bs,
-                                                        const float* __restrict__ emb, int Demb, int n_emb,
-                                                        const float* __restrict__ pe_t, int P,
-                                                        const float* __restrict__ alpha, float* __restrict__ x,
-                                                        int64_t x_bs, int64_t x_cs, int B, int n) {
-  const int D = Dtc + Demb;
+//  t2w2v_transformer.py:711-713,510-514; x_scale = 1).  A fused kernel holds the code of its newest column in a
+// register before its store is visible: column `newest_j` embeds `newest` instead of codes[b, newest_j] (-1: no such
+// column, every code comes from memory).
+__device__ __forceinline__ float embed_value(const EmbedOps& o, float al, int b, int c, int j, int newest_j = -1,
+                                             int64_t newest = 0) {
+  float v;
+  if (c < o.Dtc) {
+    v = o.tc[b * o.tc_bs + c * o.tc_cs + j];
+  } else {
+    int64_t id = j == newest_j ? newest : o.codes[b * o.codes_bs + j];
+    id = id < 0 ? 0 : (id >= o.n_emb ? o.n_emb - 1 : id);  // a corrupted code must not fault the GPU
+    v = o.emb[id * o.Demb + (c - o.Dtc)];
+  }
+  return fmaf(al, o.pe_t[(int64_t)c * o.P + j], v);
+}
+
+// side-by-side layout (x_bs == n) with the row padded to x_cs > B*n columns: zero the padding.  The calling threads
+// share the work: each passes its index `first` among them and their number `stride` (unsigned, as gridDim.x * 256 is).
+__device__ __forceinline__ void embed_zero_padding(float* __restrict__ x, int64_t x_bs, int64_t x_cs, int D, int B, int n,
+                                                   int first, unsigned stride) {
+  if (x_bs != n || x_cs <= (int64_t)B * n) return;
+  const int padc = (int)(x_cs - (int64_t)B * n);
+  for (int e = first; e < D * padc; e += stride) x[(int64_t)(e / padc) * x_cs + (int64_t)B * n + e % padc] = 0.0f;
+}
+
+// embed_value for every (b, c, j < n), grid-stride
+__global__ __launch_bounds__(256) void plm_embed_kernel(PLM_EMBED_PARAMS(const), float* __restrict__ x, int64_t x_bs,
+                                                        int64_t x_cs, int B, int n) {
+  const EmbedOps o = PLM_EMBED_OPS;
+  const int D = o.Dtc + o.Demb;
   const int64_t total = (int64_t)B * D * n;
-  const float al = alpha[0];
+  const float al = o.alpha[0];
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int j = (int)(e % n);
     const int64_t bc = e / n;
     const int c = (int)(bc % D), b = (int)(bc / D);
-    float v;
-    if (c < Dtc) {
-      v = tc[b * tc_bs + c * tc_cs + j];
-    } else {
-      int64_t id = codes[b * codes_bs + j];
-      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);  // a corrupted code must not fault the GPU
-      v = emb[id * Demb + (c - Dtc)];
-    }
-    x[b * x_bs + c * x_cs + j] = fmaf(al, pe_t[(int64_t)c * P + j], v);
+    x[b * x_bs + c * x_cs + j] = embed_value(o, al, b, c, j);
   }
-  // side-by-side layout (x_bs == n) with the row padded to x_cs > B*n columns: zero the padding
-  if (x_bs == n && x_cs > (int64_t)B * n) {
-    const int padc = (int)(x_cs - (int64_t)B * n);
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < D * padc; e += gridDim.x * 256)
-      x[(int64_t)(e / padc) * x_cs + (int64_t)B * n + e % padc] = 0.0f;
-  }
+  embed_zero_padding(x, x_bs, x_cs, D, B, n, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
-// argmax_c row[c * l_cs] over c < N by one 256-thread workgroup: ties -> lowest index (torch.argmax on CPU returns the
-// first maximal element), 0 when nothing compares (all NaN).  The result is valid on thread 0 only.  Has a barrier.
-__device__ __forceinline__ int argmax_row(const float* __restrict__ row, int64_t l_cs, int N, float* smax, int* sidx) {
+// The maximum of the 256 threads' (value, index) pairs: the larger value wins, the LOWER index on equal values, and an
+// index of 0x7fffffff (a thread that saw nothing comparable) becomes 0.  A wave64 butterfly, then the four waves' pairs
+// through smax / sidx on thread 0: the result is valid on thread 0 only.  Has a barrier.
+__device__ __forceinline__ int block_argmax(float best, int bi, float* smax, int* sidx) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c = tid; c < N; c += 256) {
-    const float v = row[(int64_t)c * l_cs];
-    if (v > best || (v == best && c < bi)) best = v, bi = c;
-  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
@@ -69,50 +97,16 @@ __device__ __forceinline__ int argmax_row(const float* __restrict__ row, int64_t
   return bi == 0x7fffffff ? 0 : bi;
 }
 
-// The same with the greedy choice of the PREVIOUS step folded in (one launch per step less): workgroup (b, 0) first
-// takes codes[b, n - 1] = argmax_c logits[b * l_bs + c * l_cs] (ties -> lowest index, as argmax_kernel), stores it and
-// then writes the code-embedding rows of utterance b; the workgroups (b, 1 ...) write the tc_latent rows, which do
-// not depend on any code.  Grid (B, 1 + ceil(Dtc * n / 1024)).
-__global__ __launch_bounds__(256) void plm_embed_step_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
-                                                             int Dtc, int64_t* __restrict__ codes, int64_t codes_bs,
-                                                             const float* __restrict__ emb, int Demb, int n_emb,
-                                                             const float* __restrict__ pe_t, int P,
-                                                             const float* __restrict__ alpha, float* __restrict__ x,
-                                                             int64_t x_bs, int64_t x_cs, int B, int n,
-                                                             const float* __restrict__ logits, int64_t l_bs, int64_t l_cs,
-                                                             int n_logits) {
-  __shared__ float smax[4];
-  __shared__ int sidx[4];
-  __shared__ int s_code;
-  const int b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-  const float al = alpha[0];
-  const int D = Dtc + Demb;
-  if (part == 0) {
-    const int bi = argmax_row(logits + (int64_t)b * l_bs, l_cs, n_logits, smax, sidx);
-    if (tid == 0) {
-      codes[(int64_t)b * codes_bs + n - 1] = bi;
-      s_code = bi;
-    }
-    __syncthreads();
-    const int newest = s_code;
-    for (int e = tid; e < Demb * n; e += 256) {
-      const int j = e % n, c = Dtc + e / n;
-      int64_t id = j == n - 1 ? (int64_t)newest : codes[(int64_t)b * codes_bs + j];
-      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);   // a corrupted code must not fault the GPU
-      x[b * x_bs + (int64_t)c * x_cs + j] = fmaf(al, pe_t[(int64_t)c * P + j], emb[id * Demb + (c - Dtc)]);
-    }
-    // side-by-side layout (x_bs == n) with the row padded to x_cs > B*n columns: zero the padding
-    if (b == 0 && x_bs == n && x_cs > (int64_t)B * n) {
-      const int padc = (int)(x_cs - (int64_t)B * n);
-      for (int e = tid; e < D * padc; e += 256) x[(int64_t)(e / padc) * x_cs + (int64_t)B * n + e % padc] = 0.0f;
-    }
-  } else {
-    const int total = Dtc * n;
-    for (int e = (part - 1) * 1024 + tid; e < min(total, part * 1024); e += 256) {
-      const int j = e % n, c = e / n;
-      x[b * x_bs + (int64_t)c * x_cs + j] = fmaf(al, pe_t[(int64_t)c * P + j], tc[b * tc_bs + c * tc_cs + j]);
-    }
+// argmax_c row[c * l_cs] over c < N by one 256-thread workgroup: ties -> lowest index (torch.argmax on CPU returns the
+// first maximal element), 0 when nothing compares (all NaN).  The result is valid on thread 0 only.  Has a barrier.
+__device__ __forceinline__ int argmax_row(const float* __restrict__ row, int64_t l_cs, int N, float* smax, int* sidx) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = threadIdx.x; c < N; c += 256) {
+    const float v = row[(int64_t)c * l_cs];
+    if (v > best || (v == best && c < bi)) best = v, bi = c;
   }
+  return block_argmax(best, bi, smax, sidx);
 }
 
 // out[b * out_bs] = argmax_c logits[b * l_bs + c * l_cs] (argmax_row).  One workgroup per row.
@@ -352,19 +346,8 @@ __device__ int sample_decide(const float* __restrict__ row, int64_t l_cs, int N,
     const float score = (l[r] - mt) - (float)log(-log(u));
     if (score > best) best = score, bi = 4 * tid + r;   // ascending i within the thread: first wins ties
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) best = ov, bi = oi;
-  }
-  if ((tid & 63) == 0) s.redf[tid >> 6] = best, s.redi[tid >> 6] = bi;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (s.redf[w] > best || (s.redf[w] == best && s.redi[w] < bi)) best = s.redf[w], bi = s.redi[w];
-    s.token = bi == 0x7fffffff ? 0 : bi;
-  }
+  const int winner = block_argmax(best, bi, s.redf, s.redi);
+  if (tid == 0) s.token = winner;
   __syncthreads();
   const int token = s.token;
   if (probs) {
@@ -390,67 +373,80 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
   if (threadIdx.x == 0) *slot = tok;
 }
 
-// plm_embed_step_kernel with the sampled decision in place of the argmax (same grid, same writes)
-__global__ __launch_bounds__(256) void plm_embed_sample_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
-                                                               int Dtc, int64_t* __restrict__ codes, int64_t codes_bs,
-                                                               const float* __restrict__ emb, int Demb, int n_emb,
-                                                               const float* __restrict__ pe_t, int P,
-                                                               const float* __restrict__ alpha, float* __restrict__ x,
+// ------------------------------------------------------------------------------------- the fused embedding launch
+// How a fused launch takes its newest code.  A choice brings the LDS it needs (`Smem`: the greedy one stays at 36 bytes)
+// and is called by the whole workgroup, barriers inside, with the row's logits and the slot codes[b, n - 1] the code
+// goes to; every thread gets the code back.
+struct GreedyChoice {   // codes[b, n - 1] = argmax_c logits[b * l_bs + c * l_cs] (ties -> lowest index, as argmax_kernel)
+  struct Smem {
+    float smax[4];
+    int sidx[4];
+    int code;
+  };
+  __device__ int operator()(const float* __restrict__ row, int64_t l_cs, int N, const int64_t*, Smem& s) const {
+    const int bi = argmax_row(row, l_cs, N, s.smax, s.sidx);
+    if (threadIdx.x == 0) s.code = bi;
+    __syncthreads();
+    return s.code;
+  }
+};
+
+// the sampled decision for column j; the row's previous codes are the j - 1 entries before the slot.  a.probs is
+// ignored here (the fused launch writes no distribution): sample_decide gets a null probs and never reads a.probs_bs
+struct SampledChoice {
+  using Smem = SampleSmem;
+  int j;
+  hsp_sample_args a;
+  __device__ int operator()(const float* __restrict__ row, int64_t l_cs, int N, const int64_t* slot, Smem& s) const {
+    return sample_decide(row, l_cs, N, slot - (j - 1), j - 1, j, a, nullptr, s);
+  }
+};
+
+// plm_embed_kernel with the choice of the PREVIOUS step folded in (one launch per step less): workgroup (b, 0) first
+// takes codes[b, n - 1] = choose(logits of row b), stores it and then writes the code-embedding rows of utterance b;
+// the workgroups (b, 1 ...) write the tc_latent rows, which do not depend on any code.
+// Grid (B, 1 + ceil(Dtc * n / 1024)).  hsp_plm_embed_step_f32 is the GreedyChoice instantiation,
+// hsp_plm_embed_sample_f32 the SampledChoice one (same grid, same writes).
+template <class Choice>
+__global__ __launch_bounds__(256) void plm_embed_choose_kernel(PLM_EMBED_PARAMS(), float* __restrict__ x,
                                                                int64_t x_bs, int64_t x_cs, int B, int n,
                                                                const float* __restrict__ logits, int64_t l_bs,
-                                                               int64_t l_cs, int n_logits, int j, hsp_sample_args a) {
-  __shared__ SampleSmem s;
+                                                               int64_t l_cs, int n_logits, Choice choose) {
+  __shared__ typename Choice::Smem s;
+  const EmbedOps o = PLM_EMBED_OPS;
   const int b = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-  const float al = alpha[0];
-  const int D = Dtc + Demb;
+  const float al = o.alpha[0];
   if (part == 0) {
-    int64_t* slot = codes + (int64_t)b * codes_bs + n - 1;
-    const int newest = sample_decide(logits + (int64_t)b * l_bs, l_cs, n_logits, slot - (j - 1), j - 1, j, a,
-                                     nullptr, s);
+    int64_t* slot = codes + (int64_t)b * o.codes_bs + n - 1;
+    const int newest = choose(logits + (int64_t)b * l_bs, l_cs, n_logits, slot, s);
     if (tid == 0) *slot = newest;
-    for (int e = tid; e < Demb * n; e += 256) {
-      const int jj = e % n, c = Dtc + e / n;
-      int64_t id = jj == n - 1 ? (int64_t)newest : codes[(int64_t)b * codes_bs + jj];
-      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);   // a corrupted code must not fault the GPU
-      x[b * x_bs + (int64_t)c * x_cs + jj] = fmaf(al, pe_t[(int64_t)c * P + jj], emb[id * Demb + (c - Dtc)]);
+    for (int e = tid; e < o.Demb * n; e += 256) {
+      const int j = e % n, c = o.Dtc + e / n;
+      __builtin_assume(c >= o.Dtc);   // e >= 0: code channels only, so embed_value's tc branch folds away here
+      x[b * x_bs + (int64_t)c * x_cs + j] = embed_value(o, al, b, c, j, n - 1, newest);
     }
-    if (b == 0 && x_bs == n && x_cs > (int64_t)B * n) {
-      const int padc = (int)(x_cs - (int64_t)B * n);
-      for (int e = tid; e < D * padc; e += 256) x[(int64_t)(e / padc) * x_cs + (int64_t)B * n + e % padc] = 0.0f;
-    }
+    if (b == 0) embed_zero_padding(x, x_bs, x_cs, o.Dtc + o.Demb, B, n, tid, 256);
   } else {
-    const int total = Dtc * n;
+    const int total = o.Dtc * n;
     for (int e = (part - 1) * 1024 + tid; e < min(total, part * 1024); e += 256) {
-      const int jj = e % n, c = e / n;
-      x[b * x_bs + (int64_t)c * x_cs + jj] = fmaf(al, pe_t[(int64_t)c * P + jj], tc[b * tc_bs + c * tc_cs + jj]);
+      const int j = e % n, c = e / n;
+      __builtin_assume(c < o.Dtc);    // e < Dtc * n: tc channels only; without the hint the loop keeps a branch per
+                                      // element and is not unrolled, which measured 0.5 - 1 us per launch at B = 1
+      x[b * x_bs + (int64_t)c * x_cs + j] = embed_value(o, al, b, c, j);
     }
   }
 }
 
 // ------------------------------------------------------------------------------------- per-row positions (hsp.h)
-// hsp_plm_embed_pos_f32: workgroup b embeds position pos[b] of row b -- plm_embed_kernel's expression for one column,
-// with the indexing done here.  An idle row (pos[b] outside [0, max_pos]) returns before it touches memory.
-__global__ __launch_bounds__(256) void plm_embed_pos_kernel(const float* __restrict__ tc, int64_t tc_bs, int64_t tc_cs,
-                                                            int Dtc, const int64_t* __restrict__ codes, int64_t codes_bs,
-                                                            const float* __restrict__ emb, int Demb, int n_emb,
-                                                            const float* __restrict__ pe_t, int P,
-                                                            const float* __restrict__ alpha, float* __restrict__ x,
-                                                            int64_t x_bs, int64_t x_cs, const int32_t* __restrict__ pos,
-                                                            int max_pos) {
+// hsp_plm_embed_pos_f32: workgroup b embeds position pos[b] of row b -- embed_value for one column of un-shifted
+// operands.  An idle row (pos[b] outside [0, max_pos]) returns before it touches memory.
+__global__ __launch_bounds__(256) void plm_embed_pos_kernel(PLM_EMBED_PARAMS(const), float* __restrict__ x, int64_t x_bs,
+                                                            int64_t x_cs, const int32_t* __restrict__ pos, int max_pos) {
+  const EmbedOps o = PLM_EMBED_OPS;
   const int b = blockIdx.x, t = pos[b];
   if (t < 0 || t > max_pos) return;
-  const float al = alpha[0];
-  for (int c = threadIdx.x; c < Dtc + Demb; c += 256) {
-    float v;
-    if (c < Dtc) {
-      v = tc[b * tc_bs + c * tc_cs + t];
-    } else {
-      int64_t id = codes[b * codes_bs + t];
-      id = id < 0 ? 0 : (id >= n_emb ? n_emb - 1 : id);  // a corrupted code must not fault the GPU
-      v = emb[id * Demb + (c - Dtc)];
-    }
-    x[b * x_bs + c * x_cs] = fmaf(al, pe_t[(int64_t)c * P + t], v);
-  }
+  const float al = o.alpha[0];
+  for (int c = threadIdx.x; c < o.Dtc + o.Demb; c += 256) x[b * x_bs + c * x_cs] = embed_value(o, al, b, c, t);
 }
 
 // hsp_plm_choose_advance_f32: workgroup b takes codes[b, t + 1] for t = pos[b] -- argmax_row, or sample_decide for
@@ -480,17 +476,44 @@ __global__ __launch_bounds__(256) void plm_choose_advance_kernel(const float* __
 
 #define HSP_STREAM static_cast<hipStream_t>(stream)
 
+// What every hsp_plm_embed* entry point refuses: a NULL operand; B, Dtc, Demb or n_emb <= 0; a negative stride; fewer
+// than 1 or more than P reachable positions (`n`: the full forms' n, max_pos + 1 of the per-row-position form).  Negative
+// tc / codes strides used to be refused by the position form alone; no caller passes one, so all forms refuse them.
+// Two differences remain, each at its entry point: the full forms also need x_cs >= n (a row's n columns lie below the
+// channel stride; the position form writes one column per channel), and the forms whose grid has one workgroup row per
+// utterance need B <= 65535 (hsp_plm_embed_f32 strides a capped grid over any B).
+static bool embed_ok(const EmbedOps& o, const float* x, int64_t x_bs, int64_t x_cs, int32_t B, int64_t n) {
+  if (!o.tc || !o.codes || !o.emb || !o.pe_t || !o.alpha || !x) return false;
+  if (B <= 0 || o.Dtc <= 0 || o.Demb <= 0 || o.n_emb <= 0 || n < 1 || n > o.P) return false;
+  return o.tc_bs >= 0 && o.tc_cs >= 0 && o.codes_bs >= 0 && x_bs >= 0 && x_cs >= 0;
+}
+
 extern "C" int hsp_plm_embed_f32(const float* tc, int64_t tc_bs, int64_t tc_cs, int32_t Dtc, const int64_t* codes,
                                  int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb, const float* pe_t,
                                  int32_t P, const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B,
                                  int32_t n, void* stream) {
-  if (!tc || !codes || !emb || !pe_t || !alpha || !x) return HSP_EINVAL;
-  if (B <= 0 || n <= 0 || n > P || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || x_bs < 0 || x_cs < n) return HSP_EINVAL;
+  const EmbedOps o{tc, tc_bs, tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha};
+  if (!embed_ok(o, x, x_bs, x_cs, B, n) || x_cs < n) return HSP_EINVAL;
   const int64_t total = (int64_t)B * (Dtc + Demb) * n;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(plm_embed_kernel, dim3((unsigned)blocks), dim3(256), 0, HSP_STREAM, tc, tc_bs, tc_cs, Dtc, codes,
-                     codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, B, n);
+  hipLaunchKernelGGL(plm_embed_kernel, dim3((unsigned)blocks), dim3(256), 0, HSP_STREAM, PLM_EMBED_ARGS(o), x,
+                     x_bs, x_cs, B, n);
+  return (int)hipGetLastError();
+}
+
+// The fused pair behind what each refuses of its own: the shared operand check (n == 1 is the one-position form of
+// hsp.h), the logits operands, the grid (B, parts), the launch.
+template <class Choice>
+static int embed_choose(const EmbedOps& o, int64_t* codes, float* x, int64_t x_bs, int64_t x_cs, int32_t B, int32_t n,
+                        const float* logits, int64_t l_bs, int64_t l_cs, int32_t n_logits, Choice choose, void* stream) {
+  if (!embed_ok(o, x, x_bs, x_cs, B, n) || x_cs < n) return HSP_EINVAL;
+  if (!logits || n_logits <= 0 || l_cs <= 0 || l_bs < 0) return HSP_EINVAL;
+  const int64_t parts = 1 + ((int64_t)o.Dtc * n + 1023) / 1024;
+  if (B > 65535 || parts > 65535) return HSP_EINVAL;
+  hipLaunchKernelGGL(plm_embed_choose_kernel<Choice>, dim3((unsigned)B, (unsigned)parts), dim3(256), 0, HSP_STREAM, o.tc,
+                     o.tc_bs, o.tc_cs, o.Dtc, codes, o.codes_bs, o.emb, o.Demb, o.n_emb, o.pe_t, o.P, o.alpha, x, x_bs,
+                     x_cs, B, n, logits, l_bs, l_cs, n_logits, choose);
   return (int)hipGetLastError();
 }
 
@@ -499,15 +522,8 @@ extern "C" int hsp_plm_embed_step_f32(const float* tc, int64_t tc_bs, int64_t tc
                                       int32_t P, const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B,
                                       int32_t n, const float* logits, int64_t l_bs, int64_t l_cs, int32_t n_logits,
                                       void* stream) {
-  if (!tc || !codes || !emb || !pe_t || !alpha || !x || !logits) return HSP_EINVAL;
-  if (B <= 0 || n < 1 || n > P || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || x_bs < 0 || x_cs < n) return HSP_EINVAL;   // n == 1: hsp.h
-  if (n_logits <= 0 || l_cs <= 0 || l_bs < 0) return HSP_EINVAL;
-  const int parts = 1 + (int)(((int64_t)Dtc * n + 1023) / 1024);
-  if (B > 65535 || parts > 65535) return HSP_EINVAL;
-  hipLaunchKernelGGL(plm_embed_step_kernel, dim3((unsigned)B, (unsigned)parts), dim3(256), 0, HSP_STREAM, tc, tc_bs, tc_cs,
-                     Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, B, n, logits, l_bs, l_cs,
-                     n_logits);
-  return (int)hipGetLastError();
+  const EmbedOps o{tc, tc_bs, tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha};
+  return embed_choose(o, codes, x, x_bs, x_cs, B, n, logits, l_bs, l_cs, n_logits, GreedyChoice{}, stream);
 }
 
 extern "C" int hsp_argmax_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out,
@@ -544,18 +560,10 @@ extern "C" int hsp_plm_embed_sample_f32(const float* tc, int64_t tc_bs, int64_t 
                                         int64_t x_cs, int32_t B, int32_t n, const float* logits, int64_t l_bs,
                                         int64_t l_cs, int32_t n_logits, int32_t j, const hsp_sample_args* args,
                                         void* stream) {
-  if (!tc || !codes || !emb || !pe_t || !alpha || !x || !logits) return HSP_EINVAL;
-  if (B <= 0 || n < 1 || n > P || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || x_bs < 0 || x_cs < n) return HSP_EINVAL;
-  if (l_cs <= 0 || l_bs < 0 || !sample_args_ok(args, n_logits, j)) return HSP_EINVAL;
+  if (!sample_args_ok(args, n_logits, j)) return HSP_EINVAL;
   if (n > 1 && j != n - 1) return HSP_EINVAL;   // the full form chooses column n - 1
-  const int parts = 1 + (int)(((int64_t)Dtc * n + 1023) / 1024);
-  if (B > 65535 || parts > 65535) return HSP_EINVAL;
-  hsp_sample_args a = *args;
-  a.probs = nullptr;
-  hipLaunchKernelGGL(plm_embed_sample_kernel, dim3((unsigned)B, (unsigned)parts), dim3(256), 0, HSP_STREAM, tc, tc_bs,
-                     tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, B, n, logits, l_bs,
-                     l_cs, n_logits, j, a);
-  return (int)hipGetLastError();
+  const EmbedOps o{tc, tc_bs, tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha};
+  return embed_choose(o, codes, x, x_bs, x_cs, B, n, logits, l_bs, l_cs, n_logits, SampledChoice{j, *args}, stream);
 }
 
 extern "C" int hsp_sample_f32(const float* logits, int64_t l_bs, int64_t l_cs, int32_t B, int32_t N, int64_t* out,
@@ -570,11 +578,10 @@ extern "C" int hsp_plm_embed_pos_f32(const float* tc, int64_t tc_bs, int64_t tc_
                                      int64_t codes_bs, const float* emb, int32_t Demb, int32_t n_emb, const float* pe_t,
                                      int32_t P, const float* alpha, float* x, int64_t x_bs, int64_t x_cs, int32_t B,
                                      const int32_t* pos, int32_t max_pos, void* stream) {
-  if (!tc || !codes || !emb || !pe_t || !alpha || !x || !pos) return HSP_EINVAL;
-  if (B <= 0 || B > 65535 || Dtc <= 0 || Demb <= 0 || n_emb <= 0 || max_pos < 0 || max_pos >= P) return HSP_EINVAL;
-  if (tc_bs < 0 || tc_cs < 0 || codes_bs < 0 || x_bs < 0 || x_cs < 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(plm_embed_pos_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, tc, tc_bs, tc_cs, Dtc, codes,
-                     codes_bs, emb, Demb, n_emb, pe_t, P, alpha, x, x_bs, x_cs, pos, max_pos);
+  const EmbedOps o{tc, tc_bs, tc_cs, Dtc, codes, codes_bs, emb, Demb, n_emb, pe_t, P, alpha};
+  if (!embed_ok(o, x, x_bs, x_cs, B, (int64_t)max_pos + 1) || !pos || B > 65535) return HSP_EINVAL;
+  hipLaunchKernelGGL(plm_embed_pos_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, PLM_EMBED_ARGS(o), x, x_bs,
+                     x_cs, pos, max_pos);
   return (int)hipGetLastError();
 }
 

@@ -185,22 +185,17 @@ class PlmDecodeSession:
             raise L.HspError(f"a session needs 1 .. 65535 slots, got {slots}")
         if int(max_len) < 1 or int(max_len) > plm.pos_emb.N_POS:
             raise L.HspError(f"max_len must lie in [1, {plm.pos_emb.N_POS}] (the position table), got {max_len}")
-        if not all(layer.decode_supported() for layer in plm.plm.layers):
-            raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {plm.d_model}, "
-                             f"{plm.plm.layers[0].n_heads} heads, ff {plm.plm.layers[0].ff_dim}")
         self.plm, self.slots, self.max_len, self.sampling = plm, int(slots), int(max_len), sampling
         S, D, dev = self.slots, plm.d_model, plm.pos_emb._pe_t.device
+        self.kv, self.ws = plm.plm.decode_state(S, self.max_len, dev)
         f32 = dict(dtype=torch.float32, device=dev)
         self.tc = torch.zeros(S, plm.tc_latent_dim, self.max_len, **f32)
         self.codes = torch.full((S, self.max_len + 1), plm.GO_ID, dtype=torch.int64, device=dev)
         self.pos = torch.full((S,), -1, dtype=torch.int32, device=dev)
         self.len = torch.zeros(S, dtype=torch.int32, device=dev)
         self.seeds = torch.zeros(S, dtype=torch.int64, device=dev)
-        Tp = (self.max_len + 3) & ~3
-        self.kv = [(torch.empty(D, S, Tp, **f32), torch.empty(D, S, Tp, **f32)) for _ in plm.plm.layers]
         self.x = torch.zeros(1, D, S, **f32)            # zero: the predict GEMM reads idle columns too; they stay finite
         self.logits = torch.zeros(1, plm.vq_bins, S, **f32)
-        self.ws = plm.plm.layers[0].decode_workspace(S, dev)
         self._sample = sampling.c_args(self.seeds) if sampling is not None else None
         self._left = [0] * S                            # steps a slot's row still needs; 0 = free
         self._len = [0] * S                             # the length last admitted to a slot
@@ -236,7 +231,7 @@ class PlmDecodeSession:
         self.len[slot:slot + 1].fill_(T)
         if P:
             self.codes[slot, 1:P + 1].copy_(prefix_codes, non_blocking=True)
-            self.plm.prefill(self.tc[slot], self.codes[slot, 1:P + 1], [(kc[:, slot], vc[:, slot]) for kc, vc in self.kv])
+            self.plm.prefill(self.tc[slot], self.codes[slot, 1:P + 1], self.plm.plm.kv_rows(self.kv, slot))
         self.pos[slot:slot + 1].fill_(P)
         self._left[slot], self._len[slot] = T - P, T
 
@@ -364,6 +359,31 @@ class Megatts2PLM1(nn.Module):
         self.arena = _finalize(self, device, materialize)
         return self
 
+    def _ready(self):
+        if self.pos_emb._pe_t is None:
+            raise L.HspError("Megatts2PLM1 used before finalize()")
+
+    def _launch_embed(self, tc, codes, pe_t, x, x_bs, x_cs, B, n, prev_logits, sample, j):
+        """THE embedding launch of positions 0 .. n - 1 of the operand views: ``tc`` [B, 256, >= n], ``codes`` [B, >= n],
+        ``pe_t`` the flat [D][N_POS] table from the views' first position on, ``x`` with strides (x_bs, x_cs, 1).  Without
+        ``prev_logits`` hsp_plm_embed_f32; with them ([1, vq_bins, B], the scores of the step before) the launch first
+        takes ``codes[:, n - 1]`` -- code column ``j`` of the row -- as their argmax (hsp_plm_embed_step_f32) or, with
+        ``sample`` (a SampleArgs), as the sampled choice (hsp_plm_embed_sample_f32)."""
+        head = (L.fptr(tc), tc.stride(0), tc.stride(1), self.tc_latent_dim, L.ptr(codes), codes.stride(0),
+                L.fptr(self.pc_embedding._w), self.vq_dim, self.pc_embedding.num_embeddings, L.fptr(pe_t),
+                self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x), x_bs, x_cs, B, n)
+        if prev_logits is None:
+            L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
+            return
+        lg = prev_logits
+        assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
+        head += (L.fptr(lg), 1, lg.stride(1), self.vq_bins)
+        if sample is None:
+            L.check(L.lib().hsp_plm_embed_step_f32(*head, L.stream_ptr()), "hsp_plm_embed_step_f32")
+        else:
+            L.check(L.lib().hsp_plm_embed_sample_f32(*head, j, ctypes.byref(sample), L.stream_ptr()),
+                    "hsp_plm_embed_sample_f32")
+
     def _embed(self, tc, codes, n, prev_logits=None, sample=None):
         """[1, d_model, Np]: utterance b occupies columns b*n .. b*n+n-1; Np = B*n rounded up to a multiple
         of 4 (16-B rows for the token GEMM's DMA), padding columns are zero.  ``prev_logits`` [1, vq_bins, B]: the
@@ -371,47 +391,17 @@ class Megatts2PLM1(nn.Module):
         stores to ``codes[:, n-1]``) before it embeds."""
         B = tc.shape[0]
         x = torch.empty(1, self.d_model, (B * n + 3) & ~3, dtype=torch.float32, device=tc.device)
-        head = (L.fptr(tc), tc.stride(0), tc.stride(1), self.tc_latent_dim, L.ptr(codes), codes.stride(0),
-                L.fptr(self.pc_embedding._w), self.vq_dim, self.pc_embedding.num_embeddings, L.fptr(self.pos_emb._pe_t),
-                self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x), n, x.shape[2], B, n)
-        if prev_logits is None:
-            L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
-        elif sample is None:
-            lg = prev_logits
-            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
-            L.check(L.lib().hsp_plm_embed_step_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, L.stream_ptr()),
-                    "hsp_plm_embed_step_f32")
-        else:
-            lg = prev_logits
-            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
-            L.check(L.lib().hsp_plm_embed_sample_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, n - 1,
-                                                     ctypes.byref(sample), L.stream_ptr()), "hsp_plm_embed_sample_f32")
+        self._launch_embed(tc, codes, self.pos_emb._pe_t, x, n, x.shape[2], B, n, prev_logits, sample, n - 1)
         return x
 
     def _embed_one(self, tc, codes, t, cache, prev_logits, sample=None):
         """Position t of every utterance into ``cache.emb[:, :, t]`` ([D, B, Tp]: fixed pitch) -- the same launch as _embed
         with every per-position operand shifted to column t and n = 1 (the kernel then takes codes[:, t] = argmax of
         ``prev_logits`` first, as in the full form)."""
-        B = tc.shape[0]
-        emb = cache.emb
-        x_t = emb[:, :, t]                                           # [D, B] view: element (c, b) at c * B Tp + b Tp
-        tc_t, codes_t = tc[:, :, t], codes[:, t]
+        emb = cache.emb                                              # column t: element (c, b) at c * B Tp + b Tp
         pe_t = self.pos_emb._pe_t[t:]                                # flat [D][N_POS] table: row c, position t at c * N_POS + t
-        head = (L.fptr(tc_t), tc.stride(0), tc.stride(1), self.tc_latent_dim, L.ptr(codes_t), codes.stride(0),
-                L.fptr(self.pc_embedding._w), self.vq_dim, self.pc_embedding.num_embeddings, L.fptr(pe_t),
-                self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x_t), emb.stride(1), emb.stride(0), B, 1)
-        if prev_logits is None:
-            L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
-        elif sample is None:
-            lg = prev_logits
-            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
-            L.check(L.lib().hsp_plm_embed_step_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, L.stream_ptr()),
-                    "hsp_plm_embed_step_f32")
-        else:
-            lg = prev_logits
-            assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
-            L.check(L.lib().hsp_plm_embed_sample_f32(*head, L.fptr(lg), 1, lg.stride(1), self.vq_bins, t,
-                                                     ctypes.byref(sample), L.stream_ptr()), "hsp_plm_embed_sample_f32")
+        self._launch_embed(tc[:, :, t:], codes[:, t:], pe_t, emb[:, :, t], emb.stride(1), emb.stride(0), tc.shape[0], 1,
+                           prev_logits, sample, t)
 
     @_entry
     def step_logits(self, tc_latent, codes, n, out=None, prev_logits=None, cache=None, sampling=None, seeds=None):
@@ -434,13 +424,12 @@ class Megatts2PLM1(nn.Module):
             self._embed_one(tc_latent, codes, n - 1, cache, prev_logits, sample)
         if cache is not None and Fh.mha_proj_supported(att.n_heads, att.head_dim, self.d_model, n):
             x = self.plm(None, batch=(B, n), last_only=last_only, cache=cache)
-        elif cache is not None:
-            # the first three steps (fewer than four keys: no fused attention kernel): the new column still enters the cache,
-            # the step itself runs in the full form (its embedding launch takes the same argmax -- or the same draw, which
-            # depends on (seed, column, token) only -- again: idempotent)
-            att.qkv(cache.emb[:, :, n - 1:n].permute(1, 0, 2), out=cache.qkv[:, :, n - 1:n].permute(1, 0, 2))
-            x = self.plm(self._embed(tc_latent, codes, n, prev_logits, sample), batch=(B, n), last_only=last_only)
         else:
+            if cache is not None:
+                # the first three steps (fewer than four keys: no fused attention kernel): the new column still enters the
+                # cache, the step itself runs in the full form (its embedding launch takes the same argmax -- or the same
+                # draw, which depends on (seed, column, token) only -- again: idempotent)
+                att.qkv(cache.emb[:, :, n - 1:n].permute(1, 0, 2), out=cache.qkv[:, :, n - 1:n].permute(1, 0, 2))
             x = self.plm(self._embed(tc_latent, codes, n, prev_logits, sample), batch=(B, n), last_only=last_only)
         if not last_only:
             x = Fh.copy_strided(x[0][:, :B * n].reshape(self.d_model, B, n)[:, :, n - 1].unsqueeze(0))
@@ -454,8 +443,7 @@ class Megatts2PLM1(nn.Module):
         token, the encoder under ``causal=True`` with ``lens`` (int [B], max == T as the reference asserts), the predict
         layer.  Positions t >= lens[b] of a row hold what the reference computes there (nothing reads them); the loss and
         the accuracy of ``forward`` are training and are not mirrored."""
-        if self.pos_emb._pe_t is None:
-            raise L.HspError("Megatts2PLM1 used before finalize()")
+        self._ready()
         B, D, T = tc_latent.shape
         assert D == self.tc_latent_dim and tc_latent.stride(2) == 1 and 1 <= T <= self.pos_emb.N_POS
         assert p_codes.shape == (B, T) and p_codes.dtype == torch.int64
@@ -480,8 +468,7 @@ class Megatts2PLM1(nn.Module):
         column count, so a row prefilled beside others could differ from the row alone.  Issued per row, a request's
         result does not depend on its neighbours -- the property the decode path has -- and a session admits rows one at a
         time anyway.  The price: a batch of B prefixes costs B x about 20 small launches."""
-        if self.pos_emb._pe_t is None:
-            raise L.HspError("Megatts2PLM1 used before finalize()")
+        self._ready()
         P = int(prefix_codes.shape[0])
         if tc_latent.dim() != 2 or tc_latent.shape[0] != self.tc_latent_dim or tc_latent.stride(1) != 1:
             raise L.HspError(f"tc_latent must be [{self.tc_latent_dim}, >= P] with unit time stride, got "
@@ -504,22 +491,16 @@ class Megatts2PLM1(nn.Module):
         B, _, T = tc_latent.shape
         P = 0 if prefix is None else prefix.shape[1]
         dev, D = tc_latent.device, self.d_model
-        if not all(layer.decode_supported() for layer in self.plm.layers):
-            raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {D}, {self.plm.layers[0].n_heads} "
-                             f"heads, ff {self.plm.layers[0].ff_dim}")
+        kv, ws = self.plm.decode_state(B, T, dev)
         codes = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
         codes[:, 0] = self.GO_ID
         all_logits = torch.empty(T - P, self.vq_bins, B, dtype=torch.float32, device=dev) if return_logits else None
-        Tp = (T + 3) & ~3
-        cache = types.SimpleNamespace(emb=torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
-        kv = [(torch.empty(D, B, Tp, dtype=torch.float32, device=dev), torch.empty(D, B, Tp, dtype=torch.float32, device=dev))
-              for _ in self.plm.layers]
+        cache = types.SimpleNamespace(emb=torch.empty_like(kv[0][0]))                # [D, B, Tp], the caches' pitch
         x = torch.empty(1, D, B, dtype=torch.float32, device=dev)
-        ws = self.plm.layers[0].decode_workspace(B, dev)
         if P:
             codes[:, 1:P + 1] = prefix
             for b in range(B):
-                self.prefill(tc_latent[b], codes[b, 1:P + 1], [(kc[:, b], vc[:, b]) for kc, vc in kv])
+                self.prefill(tc_latent[b], codes[b, 1:P + 1], self.plm.kv_rows(kv, b))
         lg = None
         for t in range(P, T):
             sample = sampling.c_args(seeds) if sampling is not None and lg is not None else None
@@ -554,8 +535,7 @@ class Megatts2PLM1(nn.Module):
         entry i belonging to position P + i.  The repetition penalty sees the prefix codes and draws stay keyed by
         (seed, column), so a tail drawn behind a prefix equals the tail of a full run that happened to draw that prefix.
         None is exactly the loop without a prefix (a tensor of P = 0 columns is refused, like every P outside 1 .. T - 1)."""
-        if self.pos_emb._pe_t is None:
-            raise L.HspError("Megatts2PLM1 used before finalize()")
+        self._ready()
         if sampling is not None and not isinstance(sampling, PlmSampling):
             raise L.HspError("sampling must be a PlmSampling or None")
         B, D, T = tc_latent.shape
@@ -594,8 +574,7 @@ class Megatts2PLM1(nn.Module):
     def decode_session(self, slots: int, max_len: int, sampling: Optional[PlmSampling] = None) -> PlmDecodeSession:
         """Fixed-shape state for decoding up to ``slots`` requests of up to ``max_len`` frames side by side, each at its
         own position (PlmDecodeSession): admit(slot, tc_latent [256, T], seed), step(), capture(), codes_of(slot)."""
-        if self.pos_emb._pe_t is None:
-            raise L.HspError("Megatts2PLM1 used before finalize()")
+        self._ready()
         return PlmDecodeSession(self, slots, max_len, sampling)
 
     @_entry

@@ -298,6 +298,22 @@ class TransformerEncoder(nn.Module):
             vis = vis & (j[None, :] <= j[:, None])[None]
         return vis.to(torch.float32).contiguous()
 
+    def decode_state(self, B: int, T: int, device):
+        """The device state of a K/V-cached decode of B rows of up to T positions -> ``(kv, workspace)``: per layer a
+        (k_cache, v_cache) pair of [D, B, Tp] buffers, Tp = T rounded up to 4 columns (16-byte rows), and the workspace
+        the layers' decode_step calls share.  Refuses a geometry hsp_plm_decode_layer_f32 has no kernel for."""
+        e = self.layers[0]
+        if not all(layer.decode_supported() for layer in self.layers):
+            raise L.HspError(f"hsp_plm_decode_layer_f32 has no kernel for d_model {e.dim}, {e.n_heads} heads, ff {e.ff_dim}")
+        new = lambda: torch.empty(e.dim, B, (T + 3) & ~3, dtype=torch.float32, device=device)
+        kv = [(new(), new()) for _ in self.layers]
+        return kv, e.decode_workspace(B, device)
+
+    @staticmethod
+    def kv_rows(kv, b: int):
+        """Row b's [D, Tp] slices of every layer's caches: what ``prefill`` fills for that row."""
+        return [(kc[:, b], vc[:, b]) for kc, vc in kv]
+
     def prefill(self, x, n: int, kv_rows):
         """ONE row's first ``n`` positions through every layer (TransformerEncoderLayer.prefill): x [1, D, Np],
         ``kv_rows`` one (k_row, v_row) pair of [D, >= n] cache slices per layer.  The last layer stops after its K / V."""
