@@ -191,6 +191,16 @@ typedef struct hsp_conv1d_args {
    * hsp_dftseg_*_f32 below), where the batch index is the frequency BIN and every bin has its own [Cin][M] matrix.
    * The implicit-GEMM conv kernel only (the token GEMMs refuse it). */
   int64_t w_bs;
+  /* Folded columns (0 = off, 1 = on; additive: HSP_VERSION unchanged).  The column tiles of the launch are cut from the
+   * B * ncols virtual columns v = b * ncols + t instead of from every utterance on its own: ceil(B ncols / BN) column
+   * tiles where the per-utterance form has B ceil(ncols / BN), i.e. no padded tile at the end of every utterance.
+   * Tensors, strides and the order of the sum behind every output element are unchanged: with the same tile shape the
+   * result is bit-identical to the launch with 0.  Only the kernels that implement the form take the field -- the block
+   * token GEMM (hsp_conv1d_mfma_plan: KC = -2) and the short-sequence conv tiles 64 x 64 / gated 64 x 128 at the 64-
+   * column window slack (plan: BM = 64, KC > 0, LDS pitch BN + 64); any other kernel refuses 1 with HSP_EINVAL.  A
+   * kernel that implements it falls back to the per-utterance tiling, silently, where the geometry does not fit
+   * (ncols % 4 != 0, a window of seams wider than the tile's LDS pitch, ...). */
+  int32_t fold_cols;
 } hsp_conv1d_args;
 
 /* MFMA (v_mfma_f32_32x32x2_f32, exact fp32) path; stride must be 1, M % 4 == 0.  Behind this entry point: the

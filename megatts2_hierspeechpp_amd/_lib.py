@@ -46,6 +46,7 @@ class Conv1dArgs(C.Structure):
         ("ln_c1", _fp), ("ln_eps", C.c_float),
         ("split_row", C.c_int32), ("accumulate2", C.c_int32), ("mask_mode2", C.c_int32), ("y2", _fp),
         ("y2_bs", C.c_int64), ("y2_cs", C.c_int64), ("res_ts", C.c_int64), ("w_bs", C.c_int64),
+        ("fold_cols", C.c_int32),
     ]
 
 

@@ -28,6 +28,13 @@
 // rows; out-of-range 16-B lane groups read the zero buffer.  Epilogues (bg_epilogue, bg_epilogue_ext): the operation
 // order of the other token-GEMM kernels (bias + conditioning bias, LayerNorm correction, pointwise function, masks,
 // per-(b, c) scale, scale, residual, accumulate, post_scale), with a compile-time pointwise function.
+//
+// Folded columns (hsp_conv1d_args.fold_cols, 64 x 64 tiles): the column tiles are cut from the B * ncols virtual
+// columns v = b * ncols + t, so no utterance ends in a padded tile (200 frames: 256 staged and multiplied columns per
+// utterance otherwise).  ncols % 4 == 0 keeps every 16-B group inside one utterance: a producer lane takes the source
+// address of its group from the group's own (b, t) and the LDS image is what it was; a consumer lane takes (b, t) of its
+// column once per tile and every per-utterance operand of the epilogue is read at that b.  K order per output element
+// is unchanged, so the result is bit-identical to the per-utterance tiling.
 #include "hsp_device.h"
 
 #ifdef HSP_TUNING
@@ -63,6 +70,18 @@ __device__ __forceinline__ void bg_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+
+// Folded columns: virtual column v = b T + t -> (b, t), starting from the utterance b0 of the tile's first column (the
+// tile's one division) and stepping over the seams by compares.  A column past the last one, B T, comes out as
+// (B - 1, t >= T): every `t < ncols` test then refuses it.
+__device__ __forceinline__ void bg_fold(int v, int b0, int T, int B, int& b, int& t) {
+  b = b0;
+  t = v - b0 * T;
+  while (t >= T && b + 1 < B) {
+    t -= T;
+    ++b;
+  }
 }
 
 // Fragments of group G (k-steps GS G .. GS G + GS - 1 of the stage): A[step * TM + tm], B[step * TN + tn].
@@ -126,10 +145,14 @@ __device__ __forceinline__ void bg_stage(bg_f32x16 (&acc)[TM * TN], float (&A0)[
 // wave-uniform base + 32-bit lane offset, and bounds are checked per group of four rows.  Only the plain epilogue
 // exists here (bias, LayerNorm correction, NONE / RELU / GELU_TANH, residual): launches that ask for masks, a
 // per-channel scale, a running sum or non-unit scales stay with the other token-GEMM kernels (hsp_bgemm_try).
-template <int TM, int TN, bool LN, int ACT>
+// FOLD: `b` and `nw` are this LANE's utterance and column (TN == 1; l32 is already inside nw), bvl holds the bias alone
+// and the conditioning bias, a per-(b, row) operand, is read per element like the residual.
+template <int TM, int TN, bool LN, int ACT, bool FOLD>
 __device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f32x16 (&acc)[TM * TN], int b, int mw, int nw,
                                             int l32, int half, float bvl, float c1l, const float (&mean)[TN],
                                             const float (&rstd)[TN]) {
+  const int lc = FOLD ? 0 : l32;
+  const float* cbl = (FOLD && a.cbias) ? a.cbias + (int64_t)b * a.cbias_bs + 4 * half : nullptr;
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     // row operands by cross-lane read, with every lane of the wave still active
@@ -142,18 +165,20 @@ __device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f
     }
     {
       // lane offsets in bytes from the (uniform) address of row mu = mw + 32 tm + (r & 3) + 8 (r >> 2), column nw
-      const unsigned yo = 4u * (unsigned)(l32 + 4 * half * a.y_cs), ro = 4u * (unsigned)(l32 + 4 * half * a.res_cs);
+      const unsigned yo = 4u * (unsigned)(lc + 4 * half * a.y_cs), ro = 4u * (unsigned)(lc + 4 * half * a.res_cs);
       const char* ybase = reinterpret_cast<const char*>(a.y + (int64_t)b * a.y_bs + nw);
       const char* rbase = a.res ? reinterpret_cast<const char*>(a.res + (int64_t)b * a.res_bs + nw) : nullptr;
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn) {
-        if (nw + tn * 32 + l32 < a.ncols) {
+        if (nw + tn * 32 + lc < a.ncols) {
           // the block's residual operands in one batch (rows clamped: always a legal address)
           float rv[16];
+          [[maybe_unused]] float cb[16];
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int mc = min(mw + tm * 32 + (r & 3) + 8 * (r >> 2), a.Cout - 1 - 4 * half);
             rv[r] = rbase ? *reinterpret_cast<const float*>(rbase + (int64_t)mc * a.res_cs * 4 + tn * 128 + ro) : 0.0f;
+            if constexpr (FOLD) cb[r] = a.cbias ? cbl[mc] : 0.0f;
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -163,8 +188,10 @@ __device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f
               for (int i = 0; i < 4; ++i) {
                 const int r = 4 * q + i;
                 const float fin = acc[tm * TN + tn][r];
-                float v = fin + bvr[r];
-                if constexpr (LN) v = fmaf(rstd[tn], fmaf(-mean[tn], c1r[r], fin), bvr[r]);
+                float bv = bvr[r];
+                if constexpr (FOLD) bv = a.cbias ? bv + cb[r] : bv;
+                float v = fin + bv;
+                if constexpr (LN) v = fmaf(rstd[tn], fmaf(-mean[tn], c1r[r], fin), bv);
                 if constexpr (ACT == HSP_ACT_RELU) v = fmaxf(v, 0.0f);
                 else if constexpr (ACT == HSP_ACT_GELU_TANH) v = hsp_apply_act(v, HSP_ACT_GELU_TANH);
                 v += rv[r];
@@ -182,7 +209,8 @@ __device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f
 // 50 Hz part): mask before / after the residual, per-(b, c) scale, scale, running sum, post_scale and the second output
 // of hsp_conv1d_args.split_row (whole 64-row tiles at or beyond split_row write y2 with their own parameter set).
 // Same operation order as hsp_epilogue_store; a factor that is not asked for is an exact multiplication by 1.
-template <int TM, int TN, int ACT>
+// FOLD: as in bg_epilogue; the per-(b, row) scale is read per element as well.
+template <int TM, int TN, int ACT, bool FOLD>
 __device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const bg_f32x16 (&acc)[TM * TN], int b, int m0, int mw,
                                                 int nw, int l32, int half, float bvl) {
   const bool second = a.split_row > 0 && m0 >= a.split_row;
@@ -192,8 +220,12 @@ __device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const 
   const int64_t ycs = second ? a.y2_cs : a.y_cs;
   const char* ybase = reinterpret_cast<const char*>((second ? a.y2 + (int64_t)b * a.y2_bs : a.y + (int64_t)b * a.y_bs) + nw);
   const char* rbase = (a.res && !second) ? reinterpret_cast<const char*>(a.res + (int64_t)b * a.res_bs + nw) : nullptr;
-  const unsigned yo = 4u * (unsigned)(l32 + 4 * half * (int)ycs), ro = 4u * (unsigned)(l32 + 4 * half * a.res_cs);
-  const float csl = a.cscale ? a.cscale[(int64_t)b * a.cscale_bs + min(mw + l32 + 32 * half, a.Cout - 1)] : 1.0f;
+  const int lc = FOLD ? 0 : l32;
+  const unsigned yo = 4u * (unsigned)(lc + 4 * half * (int)ycs), ro = 4u * (unsigned)(lc + 4 * half * a.res_cs);
+  const float csl = (!FOLD && a.cscale) ? a.cscale[(int64_t)b * a.cscale_bs + min(mw + l32 + 32 * half, a.Cout - 1)] : 1.0f;
+  // FOLD: this lane's rows of the two per-(b, row) operands, indexed by the row of the whole launch
+  const float* cbl = (FOLD && a.cbias) ? a.cbias + (int64_t)b * a.cbias_bs + mo + 4 * half : nullptr;
+  const float* csp = (FOLD && a.cscale) ? a.cscale + (int64_t)b * a.cscale_bs + mo + 4 * half : nullptr;
   const float sc = a.scale, ps = a.post_scale;
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -206,16 +238,21 @@ __device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const 
     }
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
-      const int n = nw + tn * 32 + l32;
+      const int n = nw + tn * 32 + lc;
       if (n < a.ncols) {
         const float mk = mmode != HSP_MASK_NONE ? a.mask[(int64_t)b * a.mask_bs + n] : 1.0f;
         const float mk_pre = (mmode & HSP_MASK_PRE) ? mk : 1.0f, mk_post = (mmode & HSP_MASK_POST) ? mk : 1.0f;
         float rv[16], yv[16];
+        [[maybe_unused]] float cb[16], cs[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int mc = min(mw + tm * 32 + (r & 3) + 8 * (r >> 2), a.Cout - 1 - 4 * half) - mo;
           rv[r] = rbase ? *reinterpret_cast<const float*>(rbase + (int64_t)mc * a.res_cs * 4 + tn * 128 + ro) : 0.0f;
           yv[r] = accum ? *reinterpret_cast<const float*>(ybase + (int64_t)mc * ycs * 4 + tn * 128 + yo) : 0.0f;
+          if constexpr (FOLD) {
+            cb[r] = a.cbias ? cbl[mc] : 0.0f;
+            cs[r] = a.cscale ? csp[mc] : 1.0f;
+          }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -224,11 +261,13 @@ __device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int r = 4 * q + i;
-              float v = acc[tm * TN + tn][r] + bvr[r];
+              float bv = bvr[r];
+              if constexpr (FOLD) bv = a.cbias ? bv + cb[r] : bv;
+              float v = acc[tm * TN + tn][r] + bv;
               if constexpr (ACT == HSP_ACT_RELU) v = fmaxf(v, 0.0f);
               else if constexpr (ACT == HSP_ACT_GELU_TANH) v = hsp_apply_act(v, HSP_ACT_GELU_TANH);
               v *= mk_pre;
-              v *= csr[r];
+              v *= FOLD ? cs[r] : csr[r];
               v *= sc;
               v += rv[r];
               v *= mk_post;
@@ -245,7 +284,7 @@ __device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const 
 template <int N>
 __device__ __forceinline__ void bg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <int TM, int TN, bool LN, bool EXT>
+template <int TM, int TN, bool LN, bool EXT, bool FOLD>
 __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, int n_mt, int n_nt, int per_xcd,
                                                        int total) {
   using C = BgCfg<TM, TN>;
@@ -257,8 +296,11 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   const int mt = id % n_mt;
   id /= n_mt;
   const int nt = id % n_nt;
-  const int b = id / n_nt;
   const int m0 = mt * C::BM, n0 = nt * C::BN;
+  // FOLD: n_nt tiles over the B * ncols virtual columns, n0 the tile's first one; b = the utterance that column lies in
+  static_assert(!FOLD || TN == 1, "a lane of the folded form owns one column");
+  const int b = FOLD ? n0 / a.ncols : id / n_nt;
+  const int ncv = FOLD ? a.B * a.ncols : a.ncols;           // columns of the tiled axis
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int K = a.Cin;
   const int nstage = (K + BG_KS - 1) / BG_KS;
@@ -279,20 +321,22 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
     constexpr int LPRX = C::BN / 4, RPIX = 64 / LPRX;
     const int rw = lane / LPRW, cw = (lane % LPRW) * 4;
     const int rx = lane / LPRX, cx = (lane % LPRX) * 4;
-    const bool mok = m0 + cw < a.M, nok = n0 + cx < a.ncols;
+    int bx = b, tx = n0 + cx;                              // utterance and column of this lane's 16-B group
+    if constexpr (FOLD) bg_fold(n0 + cx, b, a.ncols, a.B, bx, tx);
+    const bool mok = m0 + cw < a.M, nok = tx < a.ncols;
     const float* wsrc = a.w + m0 + cw;
-    const float* xsrc = a.x + (int64_t)b * a.x_bs + n0 + cx;
+    const float* xsrc = a.x + (int64_t)bx * a.x_bs + tx;
     // Fast staging (the conv kernel's dma_w_fast idea): the fp32 MFMAs of the consumer wave on this SIMD run on the
     // VALU's own lanes, so every vector instruction of the address arithmetic (a 64-bit multiply-add, compares,
     // selects: ~45 cycles per DMA instruction in the general form below, a fifth of a stage's matrix time) is paid in
     // matrix time.  For a tile that lies inside the matrix and a stage that lies inside K -- all but the edge tiles
     // and the last stage -- a lane's byte offset is computed ONCE and each instruction adds it to a wave-uniform
     // base that the scalar unit walks: one vector instruction per DMA.
-    const bool wfast = m0 + C::BM <= a.M, xfast = n0 + C::BN <= a.ncols && a.x_cs < (1 << 26);
+    const bool wfast = m0 + C::BM <= a.M, xfast = n0 + C::BN <= ncv && a.x_cs < (1 << 26);
     // this lane's source inside the tile's first staged rows; hsp_conv1d_mfma_f32's validation bounds the element
     // offsets of the weight matrix and of one utterance to 31 bits
     const float* wlane = a.w + m0 + rw * a.w_ld + cw;
-    const float* xlane = a.x + (int64_t)b * a.x_bs + n0 + (xfast ? rx * (int)a.x_cs : 0) + cx;
+    const float* xlane = a.x + (int64_t)bx * a.x_bs + tx + (xfast ? rx * (int)a.x_cs : 0);
     const int wld = a.w_ld, xcs = (int)a.x_cs;
     auto issue = [&](int s) __attribute__((always_inline)) {
       float* Ws = lds + (s % C::NST) * C::STAGE;
@@ -356,6 +400,9 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   const int l32 = lane & 31, half = lane >> 5;
   const int wm = wave & 1, wn = wave >> 1;
   const int mw = m0 + wm * (32 * TM), nw = n0 + wn * (32 * TN);   // first row / column of this wave's blocks
+  // what the epilogue takes as utterance and first column: the wave's, or (FOLD) those of this lane's own column
+  int be = b, ne = nw;
+  if constexpr (FOLD) bg_fold(nw + l32, b, a.ncols, a.B, be, ne);
   bg_f32x16 acc[TM * TN];
 #pragma unroll
   for (int t = 0; t < TM * TN; ++t)
@@ -367,7 +414,7 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   {
     const int mc = min(mw + lane, a.Cout - 1);
     bvl = a.bias ? a.bias[mc] : 0.0f;
-    if (a.cbias) bvl += a.cbias[(int64_t)b * a.cbias_bs + mc];
+    if (!FOLD && a.cbias) bvl += a.cbias[(int64_t)b * a.cbias_bs + mc];
     if constexpr (LN) c1l = a.ln_c1[mc];
   }
   constexpr int GS = bg_gs(TM, TN);
@@ -443,24 +490,24 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   // ---- epilogue (hsp_bgemm_try admits these three pointwise functions only)
   if constexpr (EXT) {
     static_assert(!LN, "the extended epilogue is not built with the fused LayerNorm");
-    if (a.act == HSP_ACT_RELU) bg_epilogue_ext<TM, TN, HSP_ACT_RELU>(a, acc, b, m0, mw, nw, l32, half, bvl);
-    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue_ext<TM, TN, HSP_ACT_GELU_TANH>(a, acc, b, m0, mw, nw, l32, half, bvl);
-    else bg_epilogue_ext<TM, TN, HSP_ACT_NONE>(a, acc, b, m0, mw, nw, l32, half, bvl);
+    if (a.act == HSP_ACT_RELU) bg_epilogue_ext<TM, TN, HSP_ACT_RELU, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
+    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue_ext<TM, TN, HSP_ACT_GELU_TANH, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
+    else bg_epilogue_ext<TM, TN, HSP_ACT_NONE, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
   } else {
-    if (a.act == HSP_ACT_RELU) bg_epilogue<TM, TN, LN, HSP_ACT_RELU>(a, acc, b, mw, nw, l32, half, bvl, c1l, mean, rstd);
-    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue<TM, TN, LN, HSP_ACT_GELU_TANH>(a, acc, b, mw, nw, l32, half, bvl, c1l, mean, rstd);
-    else bg_epilogue<TM, TN, LN, HSP_ACT_NONE>(a, acc, b, mw, nw, l32, half, bvl, c1l, mean, rstd);
+    if (a.act == HSP_ACT_RELU) bg_epilogue<TM, TN, LN, HSP_ACT_RELU, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
+    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue<TM, TN, LN, HSP_ACT_GELU_TANH, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
+    else bg_epilogue<TM, TN, LN, HSP_ACT_NONE, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
   }
   BG_STAMP(3);
 #undef BG_STAMP
 }
 
-template <int TM, int TN, bool LN, bool EXT>
+template <int TM, int TN, bool LN, bool EXT, bool FOLD>
 int bg_launch(const hsp_conv1d_args& a, hipStream_t s, int n_mt, int n_nt, int total) {
   using C = BgCfg<TM, TN>;
   static_assert(C::LDS_BYTES > 32 * 1024, "every launch raises the LDS limit");
   const int per_xcd = (total + 7) / 8;
-  return hsp_launch<bgemm_kernel<TM, TN, LN, EXT>>(8 * per_xcd, 512, C::LDS_BYTES, C::LDS_BYTES, s, a, n_mt, n_nt, per_xcd, total);
+  return hsp_launch<bgemm_kernel<TM, TN, LN, EXT, FOLD>>(8 * per_xcd, 512, C::LDS_BYTES, C::LDS_BYTES, s, a, n_mt, n_nt, per_xcd, total);
 }
 
 // does the launch need bg_epilogue_ext?
@@ -478,9 +525,21 @@ int bg_go(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
     plan_out[0] = C::BM; plan_out[1] = C::BN; plan_out[2] = -2; plan_out[3] = C::LDS_BYTES;
     return 0;
   }
-  if (bg_extended(a)) return bg_launch<TM, TN, false, true>(a, s, n_mt, n_nt, (int)total);   // never with ln_c1 (hsp_bgemm_try)
-  return a.ln_c1 ? bg_launch<TM, TN, true, false>(a, s, n_mt, n_nt, (int)total)
-                 : bg_launch<TM, TN, false, false>(a, s, n_mt, n_nt, (int)total);
+  if constexpr (TM == 1 && TN == 1) {
+    // folded columns (hsp_bgemm_try has checked ncols % 4 == 0): the 64 x 64 shape only, and only where it changes the
+    // tiling; the launch was admitted and its shape chosen by the per-utterance tile counts above, so the field never
+    // moves a launch to another kernel
+    const int64_t vcols = (int64_t)a.B * a.ncols;
+    if (a.fold_cols && a.B > 1 && (a.ncols % C::BN) != 0 && vcols <= 0x3fffffff) {
+      const int n_vt = (int)((vcols + C::BN - 1) / C::BN), tot = n_mt * n_vt;
+      if (bg_extended(a)) return bg_launch<1, 1, false, true, true>(a, s, n_mt, n_vt, tot);
+      return a.ln_c1 ? bg_launch<1, 1, true, false, true>(a, s, n_mt, n_vt, tot)
+                     : bg_launch<1, 1, false, false, true>(a, s, n_mt, n_vt, tot);
+    }
+  }
+  if (bg_extended(a)) return bg_launch<TM, TN, false, true, false>(a, s, n_mt, n_nt, (int)total);   // never with ln_c1 (hsp_bgemm_try)
+  return a.ln_c1 ? bg_launch<TM, TN, true, false, false>(a, s, n_mt, n_nt, (int)total)
+                 : bg_launch<TM, TN, false, false, false>(a, s, n_mt, n_nt, (int)total);
 }
 
 }  // namespace

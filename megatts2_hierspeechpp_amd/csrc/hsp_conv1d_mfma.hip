@@ -31,6 +31,7 @@ int validate(const hsp_conv1d_args& a) {
   if (!a.zeros || (reinterpret_cast<uintptr_t>(a.zeros) & 15) != 0) return HSP_EINVAL;
   if (a.prologue != HSP_PRO_NONE && a.prologue != HSP_PRO_LRELU && a.prologue != HSP_PRO_ACT1D) return HSP_EINVAL;
   if (a.mask_mode != HSP_MASK_NONE && !a.mask) return HSP_EINVAL;
+  if (a.fold_cols != 0 && a.fold_cols != 1) return HSP_EINVAL;
   if (a.rows == HSP_ROWS_GATE_WN || a.rows == HSP_ROWS_GATE_GLU) {
     if (a.gate_half <= 0 || (a.gate_half & 31) || a.M != 2 * a.gate_half || a.Cout != a.gate_half) return HSP_EINVAL;
     if (a.prologue == HSP_PRO_ACT1D) return HSP_EINVAL;
@@ -54,6 +55,7 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   const bool short_seq = (int64_t)((a.M + 127) / 128) * ((a.ncols + 127) / 128) * a.B <= 128;
   // a residual read at a column stride: the register-path token GEMM or nothing
   if (a.res && a.res_ts > 1) {
+    if (a.fold_cols) return HSP_EINVAL;
     const int e = hsp_rgemm_try(a, s, plan_out);
     return e >= 0 ? e : HSP_EINVAL;
   }
@@ -63,8 +65,16 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
     const int e = hsp_bgemm_try(a, s, plan_out);
     if (e >= 0) return e;
   }
+  // Folded columns (hsp_conv1d_args.fold_cols): the block token GEMM above and the conv tiles S64 / S64G implement the
+  // form, every other kernel refuses the field -- launch_one does for the conv tiles.  Where a refusal would make way for
+  // the next kernel in line (register-path GEMM, K-split gated tile), that kernel is asked first, WITHOUT the field,
+  // whether it takes the launch: the field never moves a launch to another kernel.
+  hsp_conv1d_args plain = a;
+  plain.fold_cols = 0;
+  int32_t probe[4];
   // (tuning bit 1 << 24: try the register-path token GEMM whatever the launch size -- tools/gemm_sweep.py)
   if ((short_seq || a.ln_c1 || a.split_row || HSP_DBG(a, 1 << 24)) && !a.w_bs && !HSP_DBG(a, 128)) {
+    if (a.fold_cols && hsp_rgemm_try(plain, nullptr, probe) >= 0) return HSP_EINVAL;
     // 1x1 GEMMs over a few thousand token columns: the register-path kernel (hsp_rgemm.hip).  (The LDS-DMA token GEMM
     // of rounds 1-3, hsp_tokgemm.hip, was retired in round 4: tools/gemm_sweep.py found no (shape, B, T) cell of
     // profiles/r04_gemm_dispatch_table.txt where it beat the block GEMM or the register path by more than 2 %.)
@@ -97,6 +107,7 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
       // 512 tiles.
       const int64_t t128 = (int64_t)((a.M + 63) / 64) * ((a.ncols + 127) / 128) * a.B;
       if ((t128 <= 48 || (HSP_DBG(a, 1 << 28) && t128 <= 512)) && !HSP_DBG(a, 1 << 27)) {
+        if (a.fold_cols && hsp_conv_tile_S64G2(plain, epi, act, nullptr, probe) != HSP_EINVAL) return HSP_EINVAL;
         const int e = hsp_conv_tile_S64G2(a, epi, act, s, plan_out);
         if (e != HSP_EINVAL) return e;
       }

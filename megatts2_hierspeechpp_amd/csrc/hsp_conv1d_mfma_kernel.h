@@ -61,8 +61,11 @@ enum {
 
 namespace hspconv {
 
-template <int WM, int WN, int TM, int TN, int NPW_, int MINW_, int XSLACK_ = 64, int KS_ = 1>
+template <int WM, int WN, int TM, int TN, int NPW_, int MINW_, int XSLACK_ = 64, int KS_ = 1, bool FOLD_ = false>
 struct Cfg {
+  // FOLD_: the shape also carries the folded-columns form of its kernels (hsp_conv1d_args.fold_cols; "folded columns"
+  // below).  The short-sequence shapes of the 50 Hz part only: every other shape compiles to what it was.
+  static constexpr bool kFOLD = FOLD_;
   // KS_ > 1 (round 5): the K range of every chunk is split between KS_ groups of WM x WN consumer waves; their partial
   // sums meet in LDS behind the loop and group 0 runs the epilogue.  A short-sequence launch with fewer tiles than the chip
   // has CUs is bound by ONE tile's MFMA chain per SIMD; halving the tile and splitting its K range puts the same four SIMDs
@@ -183,6 +186,27 @@ __device__ __forceinline__ void wait_frags(float (&fa)[NA], float (&fb)[NB]) {
 // compiler may not move memory accesses across this point
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// ------------------------------------------------------------------- folded columns
+// hsp_conv1d_args.fold_cols: the column tiles of a launch are cut from the B * T virtual columns v = b T + t (T = ncols
+// = Lin, a "same" conv), so a tile of BN columns starting at v0 = b0 T + ts0 may run over the seams between utterances
+// b0, b0 + 1, ...  Its LDS window is the concatenation of those utterances' pieces, each with a halo of 4 floats on
+// either side (pad <= 4 and (K - 1) dil - pad <= 4): window index e holds position q - 4 of utterance b0 + i, where
+// q = e + ts0 - i (T + 8) in [0, T + 8); positions outside [0, T) -- the conv's own zero padding -- and utterances past
+// the last one are zeros.  T % 4 == 0 and ts0 % 4 == 0, so every 16-B group of the window is wholly one utterance's
+// data or wholly zeros (the zero buffer is its DMA source), and column `col` of the tile, in piece i, reads tap j at
+// col + 8 i + 4 - pad + j dil: the tap offsets stay what they are, the B-fragment base moves by 8 floats per seam.
+// K order per output element is unchanged: bit-identical to the per-utterance tiling.
+//
+// column `col` of the tile -> the piece i it lies in and its time t there
+__device__ __forceinline__ void fold_col(int col, int ts0, int T, int& i, int& t) {
+  i = 0;
+  t = ts0 + col;
+  while (t >= T) {
+    t -= T;
+    ++i;
+  }
+}
+
 // ------------------------------------------------------------------- producer side
 // Only the fields the producers touch, held by value (a reference to the by-value kernel
 // argument inside an aggregate makes the compiler spill the whole struct to scratch).
@@ -257,6 +281,17 @@ struct Prod {
           const float* src = (ci < a.Cin && p >= 0 && p < a.Lin) ? xc + p : a.zeros;
           dma16(src, Xa + kc * P.xwp + 4 * g0);
         }
+      }
+    }
+  }
+  // ---- folded columns: one 16-B group per lane (`on`: the lane has one), `xl` = its source in channel 0 and `xs` its
+  // channel stride -- the zero buffer and 0 for a group of zeros
+  static __device__ __forceinline__ void dma_x_fold(const float* xl, int xs, const float* zeros, int Cin, const LdsPlan& P,
+                                                    float* Xa, int c0, int pw, bool on) {
+    if (on) {
+      for (int kc = pw; kc < P.kc; kc += C::NPW) {
+        const int ci = c0 + kc;
+        dma16(ci < Cin ? xl + (int64_t)ci * xs : zeros, Xa + kc * P.xwp);
       }
     }
   }
@@ -408,11 +443,13 @@ struct Prod {
 // t0 + wn * TN * 32 of the tile.  TM / TN are the shape's own (C::kTM, C::kTN) except in a narrow tail tile
 // (has_tail_path): the slab and window layouts in LDS belong to the SHAPE (C::BM, C::XWP), only the part of the
 // tile a wave multiplies changes.
-template <class C, int EPI, bool ACT, int TM, int TN>
+// FOLD (folded columns): t0 is the tile's first VIRTUAL column, in utterance b at time ts0; every lane takes the utterance
+// and time of its own column (TN == 1), and the epilogues read each per-utterance operand there.
+template <class C, int EPI, bool ACT, int TM, int TN, bool FOLD = false>
 __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const LdsPlan& P, float* const lds, const int b,
                                              const int m0, const int t0, const int p0, const int wm, const int wn,
                                              const int lane, const int nchunks, const int lkc, const int xvec,
-                                             const int ks = 0) {
+                                             const int ks = 0, const int ts0 = 0) {
   constexpr int BM = C::BM;
   const int KC = P.kc;
   // validate() refuses Cin < 1.  Said to the compiler as well: without it the "no chunk at all" exit it generates runs the
@@ -422,7 +459,20 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
   const int wave = wm * C::kWN + wn;               // only the VEC epilogue's staging slot uses it (full tiles)
   const int l32 = lane & 31, half = lane >> 5;
   const int mw = m0 + wm * (TM * 32);               // first packed row of this wave
-  const int tw = t0 + wn * (TN * 32) + l32;         // this lane's column in block n = 0
+  int tw = t0 + wn * (TN * 32) + l32;               // this lane's column in block n = 0
+  int bl = b;                                       // ... and its utterance
+  int xfold = 0;                                    // FOLD: where the lane's column sits in the window, less the column
+  if constexpr (FOLD) {
+    static_assert(TN == 1 && C::kKS == 1 && EPI != HSP_EPI_SHUF && !ACT, "folded columns: one column per lane, plain kernels");
+    int i;
+    fold_col(wn * 32 + l32, ts0, a.ncols, i, tw);
+    xfold = 8 * i + 4 - a.pad;
+    bl = b + i;
+    if (bl >= a.B) {                                // past the last virtual column: a legal address, never a store
+      bl = a.B - 1;
+      tw = a.ncols;
+    }
+  }
   f32x16 acc[TM][TN];
 
   // (a plain-row tile with a K split -- 64 x 64, two groups of four waves -- was built and measured in round 5: single
@@ -472,7 +522,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
           for (int r = 0; r < 16; ++r) add[i][r] = 0.0f;
       }
       if (a.res) {
-        const float* const rb = a.res + (int64_t)b * a.res_bs;
+        const float* const rb = a.res + (int64_t)bl * a.res_bs;
         static_for<TM>([&](auto ii) __attribute__((always_inline)) {
           constexpr int i = decltype(ii)::value;
           static_for<16>([&](auto rr) __attribute__((always_inline)) {
@@ -502,7 +552,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
         });
       });
       if (a.cbias) {
-        const float* const cb = a.cbias + (int64_t)b * a.cbias_bs;
+        const float* const cb = a.cbias + (int64_t)bl * a.cbias_bs;
         static_for<TM>([&](auto ii) __attribute__((always_inline)) {
           constexpr int i = decltype(ii)::value;
           static_for<16>([&](auto rr) __attribute__((always_inline)) {
@@ -517,7 +567,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
       }
       if (a.accumulate) {
         // one 32 x 32 block at a time: its 16 loads issue together into temporaries, then one wait
-        const float* const yb = a.y + (int64_t)b * a.y_bs;
+        const float* const yb = a.y + (int64_t)bl * a.y_bs;
         static_for<TM>([&](auto ii) __attribute__((always_inline)) {
           constexpr int i = decltype(ii)::value;
           static_for<TN>([&](auto nn) __attribute__((always_inline)) {
@@ -559,7 +609,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
   }
 
   const int wlane = half * BM + wm * (TM * 32) + l32;
-  const int xlane = half * P.xwp + wn * (TN * 32) + l32 + (xvec ? (p0 & 3) : 0);
+  const int xlane = half * P.xwp + wn * (TN * 32) + l32 + (FOLD ? xfold : (xvec ? (p0 & 3) : 0));
   // steps of a chunk (even: KC >= 4, so a tap has an even number of channel pairs); with a K split this group's share,
   // [ks * nsteps, (ks + 1) * nsteps) of them (pick_lkc: the share is even, so a trip never straddles a tap)
   const int nsteps = ((a.K * KC) >> 1) / C::kKS;
@@ -715,9 +765,10 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
   if (HSP_DBG(a, 16)) return;
   if constexpr (EPI == HSP_EPI_INIT) {
     // stores only, straight from the accumulator layout: one instruction = two rows x 128 B
-    float* const yb = a.y + (int64_t)b * a.y_bs;
+    float* const yb = a.y + (int64_t)bl * a.y_bs;
     const int ycs = (int)a.y_cs;
-    const bool full = mw + TM * 32 <= a.Cout && t0 + wn * (TN * 32) + TN * 32 <= a.ncols;  // wave-uniform
+    const bool full = mw + TM * 32 <= a.Cout &&
+                      t0 + wn * (TN * 32) + TN * 32 <= (FOLD ? a.B * a.ncols : a.ncols);  // wave-uniform
     const float ps = a.post_scale;
     if (full) {
       const int lrow = mw + 4 * half;
@@ -760,6 +811,17 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
     float* const stage = lds + wave * (32 * ESTR);
     const int er = lane >> 3, ec = (lane & 7) * 4;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // utterance and time of this lane's four columns (FOLD: ncols % 4 == 0, a group of four never straddles a seam)
+    int bv = b, tv = t0 + wn * (TN * 32) + ec;
+    if constexpr (FOLD) {
+      int i;
+      fold_col(wn * 32 + ec, ts0, a.ncols, i, tv);
+      bv = b + i;
+      if (bv >= a.B) {
+        bv = a.B - 1;
+        tv = a.ncols;
+      }
+    }
     static_for<TM>([&](auto ii) __attribute__((always_inline)) {
       constexpr int i = decltype(ii)::value;
       float add[4], cs[4];
@@ -770,13 +832,13 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
         cs[q] = a.scale;
         if (co < a.Cout) {
           if (a.bias) add[q] = a.bias[co];
-          if (a.cbias) add[q] += a.cbias[(int64_t)b * a.cbias_bs + co];
-          if (a.cscale) cs[q] *= a.cscale[(int64_t)b * a.cscale_bs + co];
+          if (a.cbias) add[q] += a.cbias[(int64_t)bv * a.cbias_bs + co];
+          if (a.cscale) cs[q] *= a.cscale[(int64_t)bv * a.cscale_bs + co];
         }
       }
       static_for<TN>([&](auto nn) __attribute__((always_inline)) {
         constexpr int n = decltype(nn)::value;
-        const int t = t0 + wn * (TN * 32) + n * 32 + ec;
+        const int t = tv + n * 32;
         const bool tok = t < a.ncols;
         float4 rs[4], yo[4];
 #pragma unroll
@@ -785,11 +847,11 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
           const bool ok = tok && co < a.Cout;
           rs[q] = z4;
           yo[q] = z4;
-          if (ok && a.res) rs[q] = *reinterpret_cast<const float4*>(a.res + (int64_t)b * a.res_bs + (int64_t)co * a.res_cs + t);
-          if (ok && a.accumulate) yo[q] = *reinterpret_cast<const float4*>(a.y + (int64_t)b * a.y_bs + (int64_t)co * a.y_cs + t);
+          if (ok && a.res) rs[q] = *reinterpret_cast<const float4*>(a.res + (int64_t)bv * a.res_bs + (int64_t)co * a.res_cs + t);
+          if (ok && a.accumulate) yo[q] = *reinterpret_cast<const float4*>(a.y + (int64_t)bv * a.y_bs + (int64_t)co * a.y_cs + t);
         }
         float4 mk = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (a.mask_mode != HSP_MASK_NONE && tok) mk = *reinterpret_cast<const float4*>(a.mask + (int64_t)b * a.mask_bs + t);
+        if (a.mask_mode != HSP_MASK_NONE && tok) mk = *reinterpret_cast<const float4*>(a.mask + (int64_t)bv * a.mask_bs + t);
         static_for<16>([&](auto rr) __attribute__((always_inline)) {
           constexpr int r = decltype(rr)::value;
           stage[HSP_ACC_ROW(r, half) * ESTR + l32] = acc[i][n][r];
@@ -812,7 +874,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
               if (a.mask_mode & HSP_MASK_POST) x *= m4[u];
               e[u] = (x + y4[u]) * a.post_scale;
             }
-            *reinterpret_cast<float4*>(a.y + (int64_t)b * a.y_bs + (int64_t)co * a.y_cs + t) =
+            *reinterpret_cast<float4*>(a.y + (int64_t)bv * a.y_bs + (int64_t)co * a.y_cs + t) =
                 make_float4(e[0], e[1], e[2], e[3]);
           }
         }
@@ -836,11 +898,11 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
               float va = acc[i][n][r], vb = acc[i + 1][n][r];
               if (a.bias) { va += a.bias[co]; vb += a.bias[H + co]; }
               if (a.cbias) {
-                va += a.cbias[(int64_t)b * a.cbias_bs + co];
-                vb += a.cbias[(int64_t)b * a.cbias_bs + H + co];
+                va += a.cbias[(int64_t)bl * a.cbias_bs + co];
+                vb += a.cbias[(int64_t)bl * a.cbias_bs + H + co];
               }
               const float v = (a.rows == HSP_ROWS_GATE_WN ? hsp_tanh(va) : va) * hsp_sigmoid(vb);
-              hsp_epilogue_store(a, b, co, t, v);
+              hsp_epilogue_store(a, bl, co, t, v);
             }
           });
         }
@@ -967,9 +1029,9 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
             if (ok) {
               float v = acc[i][n][r];
               if (a.bias) v += a.bias[co];
-              if (a.cbias) v += a.cbias[(int64_t)b * a.cbias_bs + co];
+              if (a.cbias) v += a.cbias[(int64_t)bl * a.cbias_bs + co];
               v = hsp_apply_act(v, a.act);
-              hsp_epilogue_store(a, b, co, to, v);
+              hsp_epilogue_store(a, bl, co, to, v);
             }
           });
         }
@@ -995,7 +1057,8 @@ constexpr bool has_tail_path() {
 //          fetched from HBM / Infinity Cache once per XCD group instead of once per row tile.
 //   tail:  the last column tile of every utterance holds <= 32 valid columns; those tiles are enumerated LAST
 //          (short jobs at the end of the grid) and take the narrow consumer.
-template <class C, int EPI, bool ACT>
+// FOLD (folded columns, launch_one decides): n_nt column tiles over the B * ncols virtual columns; sched == 0.
+template <class C, int EPI, bool ACT, bool FOLD = false>
 __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const hsp_conv1d_args a, const int n_mt,
                                                                           const int n_nt, const int lkc,
                                                                           const int xvec, const int sched) {
@@ -1021,7 +1084,10 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
   }
   int nt, b;
   bool tail_tile = false;
-  if (sched >> 8) {
+  if constexpr (FOLD) {
+    nt = ct;
+    b = (nt * BN) / a.ncols;   // the utterance of the tile's first column: the workgroup's one division
+  } else if (sched >> 8) {
     const int n_main = (n_nt - 1) * a.B;
     if (ct < n_main) {
       nt = ct % (n_nt - 1);
@@ -1037,6 +1103,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
   }
   const int m0 = mt * BM, t0 = nt * BN;
   const int p0 = t0 - a.pad;  // first activated-input position of the window
+  const int ts0 = FOLD ? t0 - b * a.ncols : 0;   // FOLD: t0 is a virtual column, at time ts0 of utterance b
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -1052,7 +1119,36 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
     using PR = Prod<C>;
     float* const Ws0 = lds;
     float* const Xa0 = lds + P.xa_off;
-    if constexpr (!ACT) {
+    if constexpr (FOLD) {
+      // folded columns: lane g stages 16-B group g of every window row ("folded columns" above)
+      const int T = a.ncols;
+      const int ngrp = (BN + 8 * ((BN + T - 1) / T + 1)) >> 2;   // <= 64 (launch_one: the window fits the pitch)
+      int q = 4 * lane + ts0, piece = 0;
+      while (q >= T + 8) {
+        q -= T + 8;
+        ++piece;
+      }
+      const bool inside = b + piece < a.B && q >= 4 && q < T + 4;
+      const float* const xl = inside ? a.x + (int64_t)(b + piece) * a.x_bs + (q - 4) : a.zeros;
+      const int xs = inside ? (int)a.x_cs : 0;
+      const bool wfast = m0 + BM <= a.M && (a.Cin & (KC - 1)) == 0;   // wave-uniform (dma_w_fast's preconditions)
+      const float* const wtile = wb + m0;
+      const unsigned wofs = 4u * (unsigned)((lane / PR::CPR) * a.w_ld + (lane % PR::CPR) * 4);
+      auto stage = [&](int c0, float* Ws, float* Xa) __attribute__((always_inline)) {
+        if (wfast) PR::dma_w_fast(wtile, a.w_ld, a.Cin, a.K, P, Ws, c0, pw, wofs);
+        else PR::dma_w(pa, P, Ws, c0, m0, pw, lane);
+        PR::dma_x_fold(xl, xs, a.zeros, a.Cin, P, Xa, c0, pw, lane < ngrp);
+        wait_vm0();
+        if (a.prologue == HSP_PRO_LRELU) PR::lrelu_x(pa, P, Xa, pw, lane);
+      };
+      stage(0, Ws0, Xa0);
+      HSP_BARRIER(a);
+      for (int c = 0; c < nchunks; ++c) {
+        const int nb = (c + 1) & 1;
+        if (c + 1 < nchunks && !HSP_DBG(a, 1)) stage((c + 1) << lkc, Ws0 + nb * P.ws_sz, Xa0 + nb * P.xa_sz);
+        HSP_BARRIER(a);
+      }
+    } else if constexpr (!ACT) {
       const int p0a = p0 & ~3;
       const bool fast = xvec && m0 + BM <= a.M && (a.Cin & (KC - 1)) == 0 && !HSP_DBG(a, 512);  // wave-uniform
       if (fast) {
@@ -1127,7 +1223,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
       return;
     }
   }
-  if constexpr (C::kKS > 1) {
+  if constexpr (FOLD) {
+    conv_consume<C, EPI, ACT, TM, TN, true>(a, P, lds, b, m0, t0, p0, wave / C::kWN, wave % C::kWN, lane, nchunks, lkc, xvec, 0, ts0);
+  } else if constexpr (C::kKS > 1) {
     const int ks = wave / (C::kWM * C::kWN), w2 = wave % (C::kWM * C::kWN);
     conv_consume<C, EPI, ACT, TM, TN>(a, P, lds, b, m0, t0, p0, w2 / C::kWN, w2 % C::kWN, lane, nchunks, lkc, xvec, ks);
   } else {
@@ -1157,9 +1255,26 @@ int pick_lkc(const hsp_conv1d_args& a, int lds_limit) {
   return -1;
 }
 
+// does this instantiation carry the folded-columns form?
+template <class C, int EPI, bool ACT>
+constexpr bool has_fold_path() {
+  return C::kFOLD && !ACT && EPI != HSP_EPI_SHUF;
+}
+
+// folded columns: does the launch's geometry fit the form ("folded columns" above)?  Otherwise the per-utterance tiling.
+template <class C>
+bool fold_fits(const hsp_conv1d_args& a, bool xvec) {
+  const int T = a.ncols;
+  if (!a.fold_cols || a.B < 2 || !xvec || (T & 3) || (T % C::BN) == 0 || a.w_bs) return false;
+  if (a.Lin != T || a.Lout != T || a.pad > 4 || (a.K - 1) * a.dil - a.pad > 4) return false;   // a "same" conv, halo within the rounding
+  if (C::BN + 8 * ((C::BN + T - 1) / T + 1) > C::XWP) return false;   // the window with its worst-case seam count
+  return (int64_t)a.B * T <= 0x3fffffff;
+}
+
 // Launch one instantiation.  EPI / ACT must already match the arguments (select_epilogue()).
 template <class C, int EPI, bool ACT>
 int launch_one(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
+  if (a.fold_cols && !has_fold_path<C, EPI, ACT>()) return HSP_EINVAL;   // this kernel does not implement the form
   // a shape whose register budget admits two workgroups per CU keeps its LDS under half the
   // CU's; the others take the deepest chunk the whole 160 KB can stage (fewer barriers, and the
   // DMA of a chunk gets a longer MFMA phase to land under)
@@ -1217,6 +1332,19 @@ int launch_one(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool xvec = !ACT && a.x_ts == 1 && (a.Lin & 3) == 0 && (a.x_cs & 3) == 0 && (a.x_bs & 3) == 0 && al16(a.x) &&
                     !HSP_DBG(a, 64);
+  if constexpr (has_fold_path<C, EPI, ACT>()) {
+    // the chunk depth above came from the per-utterance tile count: the folded launch keeps the tile configuration, and
+    // with it the order of every output element's sum
+    if (fold_fits<C>(a, xvec)) {
+      auto kfold = conv1d_mfma_kernel<C, EPI, ACT, true>;
+      static hsp_lds_flags fflags;
+      if (lds_bytes > 32 * 1024)
+        if (int e = hsp_raise_lds_limit(reinterpret_cast<const void*>(kfold), kMaxLdsBytes, fflags)) return e;
+      const int n_vt = (int)(((int64_t)a.B * a.ncols + C::BN - 1) / C::BN);
+      hipLaunchKernelGGL(kfold, dim3((unsigned)(n_mt * n_vt)), dim3(C::THREADS), lds_bytes, s, a, n_mt, n_vt, lkc, 1, 0);
+      return (int)hipGetLastError();
+    }
+  }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::THREADS), lds_bytes, s, a, n_mt, n_nt, lkc, xvec ? 1 : 0, sched);
   return (int)hipGetLastError();
 }
@@ -1241,8 +1369,8 @@ using M64 = Cfg<1, 4, 2, 2, 8, 3>;     //  64 x 256, eight producer waves (fused
 using M32 = Cfg<1, 4, 1, 4, 8, 3>;     //  32 x 512, likewise
 using M64P = Cfg<1, 4, 2, 2, 4, 4>;    //  64 x 256, plain prologue: four producer waves, two workgroups per CU
 using M32P = Cfg<1, 4, 1, 4, 4, 4>;    //  32 x 512, likewise
-using S64 = Cfg<2, 2, 1, 1, 4, 2>;     //  64 x 64   short sequences: many small, deep-chunk tiles
-using S64G = Cfg<1, 4, 2, 1, 4, 2>;    //  64 x 128  short sequences, gated rows (needs TM even)
+using S64 = Cfg<2, 2, 1, 1, 4, 2, 64, 1, true>;    //  64 x 64   short sequences: many small, deep-chunk tiles; folded columns
+using S64G = Cfg<1, 4, 2, 1, 4, 2, 64, 1, true>;   //  64 x 128  short sequences, gated rows (needs TM even); folded columns
 using S32 = Cfg<1, 4, 1, 1, 4, 2>;     //  32 x 128
 using S64W = Cfg<2, 2, 1, 1, 4, 2, 128>;   //  64 x 64 with a 192-float window pitch: halos of 62 ... 125 columns
 using S64GW = Cfg<1, 4, 2, 1, 4, 2, 128>;  //  64 x 128 gated rows with a 256-float pitch (WN with dilation_rate > 1)

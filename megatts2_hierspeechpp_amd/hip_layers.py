@@ -36,6 +36,10 @@ LAUNCH_HOOK = None
 # hsp_conv1d_args.debug of every conv launch.  Always 0 in the product: the release libhsp.so refuses anything
 # else.  tools/ set it programmatically together with HSP_LIB=.../libhsp_tune.so (kernel decomposition runs).
 DEBUG_FLAGS = 0
+# Folded columns (hsp_conv1d_args.fold_cols): Conv1d.forward sets the field on the B > 1 launches whose kernel implements
+# it (fold_cols_wanted).  Results are bit-identical either way; HSP_FOLD_COLS is the switch of a same-box A/B
+# (tools/env_ab.py): "1" on, "0" off, "gemm" / "conv" the block token GEMM / the conv tiles alone.
+FOLD_COLS = os.environ.get("HSP_FOLD_COLS", "1")
 
 
 _ZEROS = {}
@@ -233,6 +237,41 @@ def _launch(kind: str, fn, a, flops: int, nbytes: int, soft: bool = False, keep=
     if SURVEY_ABI:
         fn = L.lib().hsp_convtr1d_f32 if a.rows == L.ROWS_SHUFFLE else L.lib().hsp_conv1d_f32
     return _bracket(kind, lambda: fn(C.byref(a), L.stream_ptr()), flops, nbytes, a, soft=soft)[0]
+
+
+def _set_fold_cols(a) -> None:
+    """hsp_conv1d_args.fold_cols of a filled MFMA-path struct: asks the library which kernel the launch takes."""
+    a.fold_cols = 0
+    if FOLD_COLS != "0" and a.B > 1 and a.ncols % 4 == 0:
+        a.debug = DEBUG_FLAGS
+        plan = (C.c_int32 * 4)()
+        gated = a.rows in (L.ROWS_GATE_WN, L.ROWS_GATE_GLU)
+        if L.lib().hsp_conv1d_mfma_plan(C.byref(a), C.byref(plan)) == 0 and \
+                FOLD_COLS in ("1", "gemm" if plan[2] == -2 else "conv") and \
+                fold_cols_wanted(plan, a.B, a.ncols, gated=gated, halo=(a.K - 1) * a.dil, act1d=a.prologue == L.PRO_ACT1D):
+            a.fold_cols = 1
+
+
+def fold_cols_kernel(plan, gated: bool = False, halo: int = 0, act1d: bool = False) -> bool:
+    """Does the kernel of a launch implement hsp_conv1d_args.fold_cols (any other refuses the field)?  ``plan``: the four
+    numbers of hsp_conv1d_mfma_plan for the launch, (BM, BN, KC, LDS bytes); ``halo`` = (K - 1) dilation.  The block token
+    GEMM (KC = -2; its 128 x 128 shape takes the field and keeps the per-utterance tiling) and the short-sequence conv
+    tiles with the 64-column window slack, 64 x 64 on plain rows and 64 x 128 on gated rows (KC > 0; the same tile sizes
+    with a halo beyond 61 columns, or 64 x 64 on gated rows, are other kernels), without the activation prologue."""
+    bm, bn, kc = int(plan[0]), int(plan[1]), int(plan[2])
+    if kc == -2:
+        return True
+    return kc > 0 and not act1d and halo + 3 <= 64 and (bm, bn) == ((64, 128) if gated else (64, 64))
+
+
+def fold_cols_wanted(plan, B: int, ncols: int, gated: bool = False, halo: int = 0, act1d: bool = False) -> bool:
+    """Does a launch of B utterances x ncols columns set the field?  Where its kernel implements the form and the form
+    changes the tiling: more than one utterance, 16-B groups that never straddle two of them (ncols % 4 == 0), a padded
+    last tile per utterance.  What else the conv tiles need (a "same" conv with a halo of at most 8, a window that fits
+    the LDS pitch) the library checks itself: it keeps the per-utterance tiling, silently, where that does not hold."""
+    if B < 2 or ncols % 4 != 0 or ncols % int(plan[1]) == 0 or (int(plan[2]) == -2 and int(plan[0]) != 64):
+        return False
+    return fold_cols_kernel(plan, gated, halo, act1d)
 
 
 # ------------------------------------------------------------------ index maps (host logic)
@@ -811,8 +850,11 @@ class Conv1d(_ConvBase):
             a.y2, a.y2_bs, a.y2_cs = L.fptr(out2), out2.stride(0), out2.stride(1)
             flops = 2 * B * self.cout * Cin * Lout
             nbytes += 4 * B * (self.cout - split_row) * Lout * (1 + bool(acc2))
+            _set_fold_cols(a)
             rc = _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, soft=True, keep=keep)
             return None if rc else (out, out2)
+        if not direct:
+            _set_fold_cols(a)
         if self._pre_norm is not None:
             # fused input LayerNorm: token-GEMM shapes only (16-B addressable columns), and not inside deferred() (the
             # fused entry points take plain GEMMs).  Anything else runs the normalisation as its own launch -- WITHOUT the
@@ -824,6 +866,8 @@ class Conv1d(_ConvBase):
             _set_in(a, xn)
             a.ln_c1 = None
             keep += (xn,)
+            if not direct:
+                _set_fold_cols(a)
         _launch(kind, fn, a, flops, nbytes, keep=keep)
         return out
 
