@@ -789,7 +789,8 @@ int hsp_power_mel_log_f32(const float* spec, int64_t s_bs, int32_t s_ld, const f
  *   hsp_dftseg_fwd_f32   x [B][C][L] -> xf [64 bins][2 C][Np]: row part * C + c of bin j holds Re (part 0) / Im (part 1)
  *                        of bin j of channel c (bin 0: DC in part 0, Nyquist in part 1); column n = (b * d + p) * nseg + s
  *                        is segment s of phase p (the samples xpad[p + d i]) of utterance b;
- *                        nseg = ceil(ceil(L / d) / (129 - k)), Np >= B d nseg (a multiple of 4)
+ *                        nseg = ceil(ceil(L / d) / (129 - k)), Np >= B d nseg (a multiple of 4); the transforms write (read) the columns
+ *                        [0, B d nseg) only: the padding columns up to Np and a bin plane beyond 2 C Np keep their contents
  *   the channel product  ONE launch over the 64 bins, either of
  *     hsp_cprod3_f32       (round 5, below; the forward transform then runs with prod3 = 1) three real C x C products per bin, or
  *     hsp_conv1d_mfma_f32  B = 64 (the bins), Cin = M = 2 C, K = 1, Lin = Np, w_bs = 4 C^2 -- per bin the real block matrix

@@ -55,6 +55,8 @@ typedef float ds_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ds_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DS_N = 128, DS_H = 64;
 constexpr int DS_MEM = 256;                                     // threads of a workgroup
+constexpr int DS_OPERAND = 128 * 32;                            // floats of one operand buffer of the inverse: [E^ | O^][64 slots][32 columns]
+constexpr size_t DS_LDS_MAX = 160 * 1024;                       // LDS of a CU: no launch asks for more
 
 // An item = `cg` channel rows of one utterance over a CHUNK of S consecutive segments (of every phase): the input
 // samples those segments read -- padded-time range [d s0 hop, d ((s0 + S - 1) hop + 128)) -- are one contiguous stretch
@@ -65,17 +67,6 @@ struct DsCol {
   int ch, p, s;
   bool ok;
 };
-__device__ __forceinline__ DsCol ds_col(int col, int ncols, int d, int S) {
-  DsCol c;
-  c.ok = col < ncols;
-  const int cc = c.ok ? col : ncols - 1;
-  const int per = d * S;
-  c.ch = cc / per;
-  const int rem = cc - c.ch * per;
-  c.p = rem / S;
-  c.s = rem - c.p * S;
-  return c;
-}
 
 struct DsGeom {
   int cg, S, pitch, ngrp, nchunk, bufsz;                   // bufsz: floats of one stretch ([cg][pitch], 16-B multiple)
@@ -117,6 +108,30 @@ __device__ __forceinline__ void ds_wait(float (&r)[8]) {
   for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(r[i]));
 }
 
+// Table loads, once per launch.  A fragments of a wave: row 32 wh + l32 of the 64 x 64 table, taps 2 ks + half.
+__device__ __forceinline__ void ds_load_afrag(float (&fa)[32], const float* dft, int wh, int l32, int half) {
+  const float* frow = dft + (32 * wh + l32) * DS_H + half;
+#pragma unroll
+  for (int ks = 0; ks < 32; ++ks) fa[ks] = frow[2 * ks];
+}
+// W^k of the bins kf0 .. kf0 + 3 an inverse staging thread recombines
+__device__ __forceinline__ void ds_load_twiddles(float (&twc)[4], float (&tws)[4], const float* dft, int kf0) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    twc[u] = dft[DS_H * DS_H + kf0 + u];
+    tws[u] = dft[DS_H * DS_H + 32 + kf0 + u];
+  }
+}
+// (cos | sin)(2 pi k / 128), k < 32, of the forward recombination into LDS: thread t < 64 one value
+__device__ __forceinline__ void ds_load_twl(float* twl, const float* dft, int t) {
+  if (t < 64) twl[t] = dft[DS_H * DS_H + t];
+}
+// the 24 activation taps into LDS as da_segment reads them -- hu[i] = 2 (filt[10 - 2 i], filt[11 - 2 i]): upsampling, x2
+// gain folded in, reversed; hd[i] = (filt[12 + 2 i], filt[13 + 2 i]): downsampling -- thread 0 <= t < 24 one value
+__device__ __forceinline__ void da_load_taps(float* flt, const float* filt, int t) {
+  if (t >= 0 && t < 24) flt[t] = t < 12 ? 2.0f * filt[10 - 2 * (t >> 1) + (t & 1)] : filt[t];
+}
+
 // ---------------------------------------------------------------------------------------------------------- forward
 // Staging of an item: row[j + sh] = xpad[t0 + j], xpad = the conv's zero-padded input, as a flat list of 16-B input
 // groups -- element e = ch * ng + gi is group g_lo + gi of row ch -- sixteen per thread and batch.
@@ -154,6 +169,19 @@ __device__ __forceinline__ DsCol ds_col_f(int col, int ncols, int d, int S, floa
   c.p = d == 1 ? 0 : ds_div(rem, S, inv_S);
   c.s = rem - c.p * S;
   return c;
+}
+// byte offset of column q of item I inside a spectrum row: n = (b d + p) nseg + s of row c (below 4 GB: ds_check)
+__device__ __forceinline__ unsigned ds_col_bytes(const hsp_dftseg_args& a, const DsItem& I, const DsCol& q) {
+  return 4u * (unsigned)((I.c0 + q.ch) * a.Np + (I.b * a.dil + q.p) * a.nseg + I.s0 + q.s);
+}
+// The conv's zero padding of the stretch rows on either side: in front of input sample 0 and from sample `end` (the
+// row's length) on
+__device__ __forceinline__ void ds_zero_pad(float* buf, int pitch, int ncg, const DsStage& s, int end, int tid, int nthreads) {
+  for (int ch = 0; ch < ncg; ++ch) {
+    float* row = buf + ch * pitch + s.sh;
+    for (int j = tid; j < min(-s.t0, s.len); j += nthreads) row[j] = 0.0f;
+    for (int j = max(end - s.t0, 0) + tid; j < s.len; j += nthreads) row[j] = 0.0f;
+  }
 }
 
 __device__ __forceinline__ void ds_stage_load(const hsp_dftseg_args& a, const DsItem& I, const DsStage& s, int e0, int t,
@@ -214,15 +242,22 @@ __device__ __forceinline__ ds_f32x4 da_load(const hsp_dftseg_args& a, const DsIt
   const float* xr = a.x + (int64_t)I.b * a.x_bs + (int64_t)(I.c0 + ch) * a.x_cs;
   return *reinterpret_cast<const ds_f32x4*>(xr + hsp_clampi(p0 - 8 + 4 * lane, 0, a.L - 4));
 }
+// Where the rows of a segment's raw window come from: `add` joins every raw sample (the pair kernel: the first conv's
+// bias); RAG: the rows are valid over [0, lb) and `last` points at row 0's last valid input x[lb - 1] (global memory or
+// LDS, rows `last_cs` floats apart), replicated from lb on.  The default: the plain forward transform's rows.
+struct DaRow {
+  float add = 0.0f;
+  int lb = 0;
+  const float* last = nullptr;
+  int64_t last_cs = 0;
+};
 // one segment: raw window in registers -> act -> the stretch (row[j + sh] = act(x)[t0 + j] for t0 + j in [pa, pb))
-// RAG: `last` points at the row's last valid input x[lb - 1] (global memory or LDS), replicated from lb on
 template <bool RAG = false>
 __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeom& G, const DsItem& I, const DsStage& s,
                                            const DaItem& A, int sI, int lane, ds_f32x4 rv, float* slice, float* buf,
-                                           const float* flt, float add = 0.0f, int lb = 0, const float* last = nullptr,
-                                           int64_t last_cs = 0) {
+                                           const float* flt, const DaRow& src = DaRow()) {
   const int ch = sI / A.nsg, p0 = A.pa4 + DA_SEG * (sI - ch * A.nsg);
-  const int L = RAG ? lb : a.L;
+  const int L = RAG ? src.lb : a.L;
   const int n_out = min(DA_SEG, L - p0);                        // a multiple of 4 (RAG: any count >= 1)
   const int c = I.c0 + ch;
   const float kf = a.act_alpha_exp[c] * 0.318309886183790672f, kb = 0.5f * a.act_beta_inv[c];
@@ -238,11 +273,11 @@ __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeo
   // ---- phase A: registers -> LDS (replicate padding: the clamped address was 0 or L - 4)
   {
     const int idx = p0 - 8 + 4 * lane;
-    ds_f32x4 t = rv + add;                                      // (the pair kernel: the first conv's bias)
+    ds_f32x4 t = rv + src.add;
     t = idx < 0 ? ds_f32x4{t.x, t.x, t.x, t.x} : t;
     t = idx >= a.L ? ds_f32x4{t.w, t.w, t.w, t.w} : t;
     if constexpr (RAG) {
-      const float rl = last[ch * last_cs] + add;
+      const float rl = src.last[ch * src.last_cs] + src.add;
       t.x = idx >= L ? rl : t.x;
       t.y = idx + 1 >= L ? rl : t.y;
       t.z = idx + 2 >= L ? rl : t.z;
@@ -311,6 +346,24 @@ __device__ __forceinline__ void da_segment(const hsp_dftseg_args& a, const DsGeo
   da_fence();                                                   // raw / a2 are rewritten by the next segment
 }
 
+// Forward recombination of one accumulator pair: E, O = bin kb of the 64-point transforms of a segment's even / odd
+// samples, (wc, ws) = W^kb  ->  X[kb] = E + W^kb O and X[64 - kb] = conj(E - W^kb O).  z: bin 0's lane, which holds
+// (E[0], E[32]) and (O[0], O[32]), all real: DC = E0 + O0 and Nyquist = E0 - O0 share bin slot 0 -- (-E0, -O0) there for
+// the three-product form, hsp.h prod3 -- and X[32] = E[32] - i O[32] goes where the other lanes put bin 64 - kb.
+struct DsBins {
+  float kr, ki, mr, mi;                                         // X[kb] Re, Im, X[64 - kb] Re, Im
+};
+__device__ __forceinline__ DsBins ds_fwd_recombine(float er, float ei, float orr, float oi, float wc, float ws, bool z, int prod3) {
+  const float tr = wc * orr + ws * oi, ti = wc * oi - ws * orr;
+  const bool z3 = z && prod3;
+  DsBins X;
+  X.kr = z3 ? -er : er + tr;
+  X.ki = z ? (prod3 ? -tr : er - tr) : ei + ti;
+  X.mr = z ? ei : er - tr;
+  X.mi = z ? -oi : ti - ei;
+  return X;
+}
+
 // RAG (ACT only): per-row lengths hsp_dftseg_args.act_len -- the ragged activation (see da_item)
 template <bool ACT, bool RAG = false>
 __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) void dftseg_fwd_kernel(const hsp_dftseg_args a, const DsGeom G) {
@@ -326,13 +379,9 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   // Accumulator register r (and r + 8) holds bin 16 wh + HSP_ACC_ROW(r, half); its twiddle W^k comes out of LDS.
   const int wh = wave & 1, pairw = wave >> 1;
   float fa[32];
-  {
-    const float* frow = a.dft + (32 * wh + l32) * DS_H + half;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) fa[ks] = frow[2 * ks];
-  }
+  ds_load_afrag(fa, a.dft, wh, l32, half);
   float* const twl = lds + G.bufsz;                             // (cos | sin)(2 pi k / 128), k < 32, behind the stretch
-  if (tid < 64) twl[tid] = a.dft[DS_H * DS_H + tid];
+  ds_load_twl(twl, a.dft, tid);
   // the previous column block's outputs of this lane (bin register r: X[kb] Re, Im, X[64 - kb] Re, Im) and where they go:
   // 32-bit byte offsets into the spectrum (ds_check bounds it below 4 GB), lane part in two registers -- bins
   // kb = lanek + c_r count up from lb1, bins 64 - kb down from lb2 -- and the register's part c_r xf_bs uniform (the
@@ -356,13 +405,12 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   // Generator's shapes) are loaded into registers before this item's MFMAs and written to LDS behind them: the HBM round
   // trip of the staging is off the critical path.
   constexpr bool act = ACT;                                     // (the host asks for it on 16-B addressable rows only)
-  float* const flt = lds + G.bufsz + 64;                        // upsampling taps (x2 gain folded in, reversed) | downsampling taps
+  float* const flt = lds + G.bufsz + 64;                        // the activation's taps (da_load_taps)
   float* const slice = flt + 32 + wave * DA_SLICE;              // this wave's activation scratch
-  if (act && tid < 24) {
-    const int i = tid >> 1;                                     // hu[i] = 2 (filt[10 - 2 i], filt[11 - 2 i]), hd[i] = (filt[12 + 2 i], filt[13 + 2 i])
-    flt[tid] = tid < 12 ? 2.0f * a.act_filt[10 - 2 * i + (tid & 1)] : a.act_filt[tid];
+  if (act) {
+    da_load_taps(flt, a.act_filt, tid);
+    __syncthreads();                                            // the first item's staging reads the taps
   }
-  if (act) __syncthreads();                                     // the first item's staging reads the taps
   DsItem I = ds_item(blockIdx.x, a, G);
   DsStage sg = ds_stage_of(a, I);
   auto row_len = [&](const DsItem& It) __attribute__((always_inline)) {
@@ -384,18 +432,13 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (it) ds_barrier();                                       // the previous item's stretch has been read
     // ---- finish the staging of item `it`
     if (act) {
-      const float* last = RAG ? a.x + (int64_t)I.b * a.x_bs + (int64_t)I.c0 * a.x_cs + (lb - 1) : nullptr;
+      const DaRow src = RAG ? DaRow{0.0f, lb, a.x + (int64_t)I.b * a.x_bs + (int64_t)I.c0 * a.x_cs + (lb - 1), a.x_cs} : DaRow();
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (wave + 4 * i < da.nsegs)
-          da_segment<RAG>(a, G, I, sg, da, wave + 4 * i, lane, pv[i], slice, lds, flt, 0.0f, lb, last, a.x_cs);
+        if (wave + 4 * i < da.nsegs) da_segment<RAG>(a, G, I, sg, da, wave + 4 * i, lane, pv[i], slice, lds, flt, src);
       for (int sI = wave + 64; sI < da.nsegs; sI += 4)          // beyond the prefetch depth
-        da_segment<RAG>(a, G, I, sg, da, sI, lane, da_load<RAG>(a, I, da, sI, lane), slice, lds, flt, 0.0f, lb, last, a.x_cs);
-      for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
-        float* row = lds + ch * pitch + sg.sh;
-        for (int j = tid; j < min(-sg.t0, sg.len); j += DS_MEM) row[j] = 0.0f;
-        for (int j = max((RAG ? lb : a.L) - sg.t0, 0) + tid; j < sg.len; j += DS_MEM) row[j] = 0.0f;
-      }
+        da_segment<RAG>(a, G, I, sg, da, sI, lane, da_load<RAG>(a, I, da, sI, lane), slice, lds, flt, src);
+      ds_zero_pad(lds, pitch, I.ncg, sg, lb, tid, DS_MEM);
     } else if (vec) {
       ds_stage_write(G, sg, 0, tid, lds, pv);
       for (int e0 = DS_MEM * 16; e0 < sg.tot; e0 += DS_MEM * 16) {
@@ -403,11 +446,7 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         ds_stage_load(a, I, sg, e0, tid, v);
         ds_stage_write(G, sg, e0, tid, lds, v);
       }
-      for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
-        float* row = lds + ch * pitch + sg.sh;
-        for (int j = tid; j < min(-sg.t0, sg.len); j += DS_MEM) row[j] = 0.0f;
-        for (int j = max(a.L - sg.t0, 0) + tid; j < sg.len; j += DS_MEM) row[j] = 0.0f;
-      }
+      ds_zero_pad(lds, pitch, I.ncg, sg, a.L, tid, DS_MEM);
     } else {
       for (int ch = 0; ch < I.ncg; ++ch) {
         const float* xr = a.x + (int64_t)I.b * a.x_bs + (int64_t)(I.c0 + ch) * a.x_cs;
@@ -470,25 +509,17 @@ __global__ __launch_bounds__(DS_MEM) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           put(4 * g + j);                                       // one of the previous block's 32 stores
         }
       }
-      // X[kb] = E + W^kb O, X[64 - kb] = conj(E - W^kb O) for the eight bins of this lane; bin 0's lane holds (E[0],
-      // E[32]) and (O[0], O[32]), all real: DC = E0 + O0 and Nyquist = E0 - O0 share bin slot 0, and X[32] = E[32] -
-      // i O[32] goes where the other lanes put bin 64 - kb.  The values wait in registers: their stores are issued one
+      // The eight bins of this lane (ds_fwd_recombine).  The values wait in registers: their stores are issued one
       // per k-step under the NEXT block's MFMAs (as a burst behind the loop they cost 2500 cycles per block -- every
       // CU bursts at the same time, and a wave that cannot issue its stores cannot issue its MFMAs either).
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const float er = ae[r], ei = ae[r + 8], orr = ao[r], oi = ao[r + 8];
-        const float wc = twl[lanek + (r & 3) + 8 * (r >> 2)], ws = twl[32 + lanek + (r & 3) + 8 * (r >> 2)];
-        const float tr = wc * orr + ws * oi, ti = wc * oi - ws * orr;
-        const bool z = r == 0 && wh == 0 && half == 0;
-        const bool z3 = z && a.prod3;                           // slot 0 for the three-product form: (-E0, -O0), hsp.h prod3
-        ov[4 * r + 0] = z3 ? -er : er + tr;
-        ov[4 * r + 1] = z ? (a.prod3 ? -tr : er - tr) : ei + ti;
-        ov[4 * r + 2] = z ? ei : er - tr;
-        ov[4 * r + 3] = z ? -oi : ti - ei;
+        const int kr = lanek + (r & 3) + 8 * (r >> 2);
+        const DsBins X = ds_fwd_recombine(ae[r], ae[r + 8], ao[r], ao[r + 8], twl[kr], twl[32 + kr], r == 0 && lanek == 0, a.prod3);
+        ov[4 * r + 0] = X.kr, ov[4 * r + 1] = X.ki, ov[4 * r + 2] = X.mr, ov[4 * r + 3] = X.mi;
       }
       {
-        const unsigned colb = 4u * (unsigned)((Ic.c0 + q.ch) * a.Np + (Ic.b * d + q.p) * a.nseg + Ic.s0 + q.s);
+        const unsigned colb = ds_col_bytes(a, Ic, q);
         pok = q.ok;
         lb1 = colb + (unsigned)lanek * rowb;
         lb2 = colb + (unsigned)(64 - lanek) * rowb;
@@ -617,8 +648,10 @@ __device__ __forceinline__ void ds_inv_stash(float* dst, int kf0, const float (&
     const bool z = u == 0 && kf == 0;                           // (DC, Nyquist, Re X[32], Im X[32]): E^0 E^32 O^0 O^32 real
     dst[kf * 32] = z ? xr + xi : xr + yr;                       // Re E^[k]
     dst[(32 + kf) * 32] = z ? 2.0f * yr : xi - yi;              // Im E^[k]             (slot 32: E^[32] = 2 Re X[32])
-    dst[(64 + kf) * 32] = z ? xr - xi : dr * twc[u] - di * tws[u];       // Re O^[k]
-    dst[(96 + kf) * 32] = z ? -2.0f * yi : dr * tws[u] + di * twc[u];    // Im O^[k]  (slot 32: O^[32] = -2 Im X[32])
+    // (the fused multiply-adds spelled out: left to the compiler, which of the two products joins the fma follows the
+    // order of unrelated code around the call, and with it the last bit of every output)
+    dst[(64 + kf) * 32] = z ? xr - xi : __builtin_fmaf(dr, twc[u], -(di * tws[u]));      // Re O^[k]
+    dst[(96 + kf) * 32] = z ? -2.0f * yi : __builtin_fmaf(di, twc[u], dr * tws[u]);      // Im O^[k]  (slot 32: O^[32] = -2 Im X[32])
   }
 }
 // Scatter of a block's time samples into the LDS image of the output rows: accumulator register r of wave (eo, wh) is
@@ -643,93 +676,114 @@ __device__ __forceinline__ void ds_inv_scatter(float* rp, int d, int i0, int hop
   else ds_inv_scatter_d<0>(rp, d, i0, hop, wh, acc, acc2);
 }
 
+// The roles of a thread among the four waves (eo, wh) that work on ONE 32-column block of the inverse.  As an MFMA wave it
+// produces the even (eo = 0) or odd time samples 2 (32 wh + row) + eo of the block's segments from E^ (O^); A fragments:
+// rows 32 wh + l32 of the 64 x 64 inverse table (time j x packed spectrum slot: slot t < 32 = Re of bin t, slot 32 = bin
+// 32 (real), slot 32 + t = Im of bin t).  As a staging thread it recombines the bins kf0 + u, u < 4, of column l32.
+struct DsInvRole {
+  int l32, half, wh, eo, kf0, i0;                               // i0: sample (inside its segment) of accumulator register 0
+};
+__device__ __forceinline__ DsInvRole ds_inv_role(int w4, int lane) {
+  const int half = lane >> 5, wh = w4 & 1, eo = w4 >> 1;
+  return {lane & 31, half, wh, eo, 8 * w4 + 4 * half, 2 * (32 * wh + 4 * half) + eo};
+}
+// The fetch stream of such a group of four waves: the position (item, block) its next fetch reads -- the blocks start,
+// start + stride, ... of every item the workgroup walks (dftseg_inv_kernel: 0, 1, 2, ...; a group of the pair kernel: grp,
+// grp + 2, ...; a block behind the item's last column has no valid one: clamped addresses, nothing scattered).  The
+// fetches run TWO blocks ahead of the MFMAs, across item boundaries: a block is 32 MFMAs per wave, 1 us, less than one
+// HBM round trip.
+struct DsFetch {
+  int start, stride, nmine;
+  int it, blk, ncols;
+  DsItem I;
+  float ipc, isc;                                               // 1 / (d S), 1 / S of the item: ds_col_f
+  bool more;
+  __device__ __forceinline__ void begin(const hsp_dftseg_args& a, const DsGeom& G, int nmine_, int start_, int stride_) {
+    start = start_, stride = stride_, nmine = nmine_, it = 0, more = true;
+    enter(a, G);
+  }
+  __device__ __forceinline__ void enter(const hsp_dftseg_args& a, const DsGeom& G) {
+    I = ds_item(blockIdx.x + it * gridDim.x, a, G);
+    blk = start;
+    ncols = I.ncg * a.dil * I.S;
+    ipc = 1.0f / (float)(a.dil * I.S);
+    isc = 1.0f / (float)I.S;
+  }
+  // (behind the last block of the last item the position stays: two harmless repeats)
+  __device__ __forceinline__ void advance(const hsp_dftseg_args& a, const DsGeom& G) {
+    if (32 * (blk - start + stride) < ncols) {
+      blk += stride;
+    } else if (more && it + 1 < nmine) {
+      ++it;
+      enter(a, G);
+    } else {
+      more = false;
+    }
+  }
+};
+// fetch the stream's next block into v; q = its column decode (handed to the scatter two steps later)
+__device__ __forceinline__ void ds_fetch_next(DsFetch& F, const DsInvSrc& src, const hsp_dftseg_args& a, const DsGeom& G, int l32,
+                                              float (&v)[16], DsCol& q) {
+  q = ds_col_f(32 * F.blk + l32, F.ncols, a.dil, F.I.S, F.ipc, F.isc);
+  ds_inv_fetch(src, ds_col_bytes(a, F.I, q), v);
+  F.advance(a, G);
+}
+// One step = one column block: stage its operand (fetched two steps ago) in `ob`, refill the same registers with the
+// block two steps ahead (in flight under this block's and the next one's MFMAs), multiply in two chains (even / odd
+// k-steps), scatter into the stretch rows at `stretch`, G.pitch floats apart.  Called alternately with two register
+// sets, so no set is ever copied (a copy would wait for the loads it copies).  No load stands between the refill and the
+// scatter: it would wait for the fetches just issued (vmcnt(0)).
+__device__ __forceinline__ void ds_inv_block(const hsp_dftseg_args& a, const DsGeom& G, const DsInvRole& R, const DsInvSrc& src,
+                                             const float (&fa)[32], const float (&twc)[4], const float (&tws)[4], DsFetch& F,
+                                             float* ob, float* stretch, float (&v)[16], DsCol& qv) {
+  const int hop = DS_N - (a.k - 1), d = a.dil;
+  ds_inv_stash(ob + R.l32, R.kf0, v, twc, tws);
+  const DsCol q = qv;                                           // this block's decode, before the refill overwrites it
+  ds_barrier();
+  ds_fetch_next(F, src, a, G, R.l32, v, qv);
+  const float* bp = ob + R.eo * (64 * 32) + R.half * 32 + R.l32;
+  ds_f32x16 acc, acc2;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.0f;
+#pragma unroll
+  for (int ks = 0; ks < 32; ks += 2) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ks], bp[ks * 64], acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ks + 1], bp[ks * 64 + 64], acc2, 0, 0, 0);
+  }
+  if (q.ok) ds_inv_scatter(stretch + q.ch * G.pitch + q.p + d * (q.s * hop + R.i0), d, R.i0, hop, R.wh, acc, acc2);
+}
+
 __global__ __launch_bounds__(DS_MEM) void dftseg_inv_kernel(const hsp_dftseg_args a, const DsGeom G, int nbuf) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // [cg][pitch] output stretch of every row | B buffers
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l32 = lane & 31, half = lane >> 5;
-  const int hop = DS_N - (a.k - 1), d = a.dil, pitch = G.pitch;
+  const int hop = DS_N - (a.k - 1), d = a.dil;
   const int nitems = a.B * G.ngrp * G.nchunk;                   // persistent workgroups, as the forward kernel
-  // All four waves work on ONE 32-column block: wave (eo, wh) produces the even (eo = 0) or odd time samples
-  // 2 (32 wh + row) + eo of its segments from E^ (O^).  A fragments: rows 32 wh + l32 of the 64 x 64 inverse table
-  // (time j x packed spectrum slot: slot t < 32 = Re of bin t, slot 32 = bin 32 (real), slot 32 + t = Im of bin t).
-  const int wh = wave & 1, eo = wave >> 1;
+  const DsInvRole R = ds_inv_role(wave, lane);                  // all four waves work on ONE 32-column block
   float fa[32], twc[4], tws[4];
-  {
-    const float* frow = a.dft + (32 * wh + l32) * DS_H + half;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) fa[ks] = frow[2 * ks];
-    // staging: this thread recombines the bins kf(u) = 8 wave + 4 half + u, u < 4, of column l32
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      twc[u] = a.dft[DS_H * DS_H + 8 * wave + 4 * half + u];
-      tws[u] = a.dft[DS_H * DS_H + 32 + 8 * wave + 4 * half + u];
-    }
-  }
+  ds_load_afrag(fa, a.dft, R.wh, R.l32, R.half);
+  ds_load_twiddles(twc, tws, a.dft, R.kf0);
   float* const bbuf = lds + G.bufsz;                            // [nbuf][E^ | O^][64 slots][32 columns]
-  const DsInvSrc src = ds_inv_src(a.xf, a.xf_bs, a.C, a.Np, wave, half);
-  const int kf0 = 8 * wave + 4 * half;
+  const DsInvSrc src = ds_inv_src(a.xf, a.xf_bs, a.C, a.Np, wave, R.half);
   // the epilogue runs in the scalar form unless every row it touches is 16-B addressable (workgroup-uniform)
   const bool vec0 = ((a.L | (int)a.y_bs | (int)a.y_cs | (int)a.res_bs | (int)a.res_cs) & 3) == 0 &&
                     ((reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0;
   // B operand of a column block: [E^ | O^][64 slots][32 columns], the same for all four waves, so it is staged through
   // LDS once.  A thread fetches X[k] and X[64 - k] (bin 0's thread: DC | Nyquist and X[32]) of four bins of one column
-  // -- every load instruction two 128-B runs -- and stores E^, O^ (ds_inv_stash).  The fetches run TWO column blocks
-  // ahead of the MFMAs, across item boundaries (the first block of the next row is in flight under this row's epilogue):
-  // a block is 32 MFMAs per wave, 1 us, less than one HBM round trip.
+  // -- every load instruction two 128-B runs -- and stores E^, O^ (ds_inv_stash); the first block of the next row is
+  // in flight under this row's epilogue (DsFetch).
   const int nmine = (nitems - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  auto item_of = [&](int it) __attribute__((always_inline)) { return ds_item(blockIdx.x + it * gridDim.x, a, G); };
-  int it_f = 0, blk_f = 0;                                      // the position the next fetch reads
-  DsItem If = item_of(0);
-  int ncols_f = If.ncg * d * If.S;
-  float ipf = 1.0f / (float)(d * If.S), isf = 1.0f / (float)If.S;
-  bool more_f = true;
-  // fetch the next block of the fetch stream into v; q = its column decode (handed to the scatter two steps later)
-  auto fetch_next = [&](float (&v)[16], DsCol& q) __attribute__((always_inline)) {
-    q = ds_col_f(32 * blk_f + l32, ncols_f, d, If.S, ipf, isf);
-    ds_inv_fetch(src, 4u * (unsigned)((If.c0 + q.ch) * a.Np + (If.b * d + q.p) * a.nseg + If.s0 + q.s), v);
-    // advance (behind the last block of the last item the position stays: two harmless repeats)
-    if (32 * (blk_f + 1) < ncols_f) {
-      ++blk_f;
-    } else if (more_f && it_f + 1 < nmine) {
-      ++it_f;
-      blk_f = 0;
-      If = item_of(it_f);
-      ncols_f = If.ncg * d * If.S;
-      ipf = 1.0f / (float)(d * If.S);
-      isf = 1.0f / (float)If.S;
-    } else {
-      more_f = false;
-    }
-  };
+  DsFetch F;
+  F.begin(a, G, nmine, 0, 1);
   // the position the MFMAs are at
   int it_c = 0, blk_c = 0, buf = 0;
-  DsItem I = item_of(0);
+  DsItem I = ds_item(blockIdx.x, a, G);
   int ncols = I.ncg * d * I.S;
   bool done = false;
-  const int i0 = 2 * (32 * wh + 4 * half) + eo;                 // sample (inside its segment) of accumulator register 0
-  // One step = one column block: stage its operand (fetched two steps ago), refill the same registers with the block
-  // two steps ahead, multiply, scatter; behind the last block of an item, its epilogue.  Called alternately with the
-  // two register sets, so no set is ever copied (a copy would wait for the loads it copies).
+  // ds_inv_block of the next block; behind the last block of an item, its epilogue
   auto step = [&](float (&v)[16], DsCol& qv) __attribute__((always_inline)) {
     const int nblk = (ncols + 31) >> 5;
     // (the barrier behind the first stash of an item also says: everyone has left the previous item's epilogue)
-    float* const ob = bbuf + buf * (128 * 32);
-    ds_inv_stash(ob + l32, kf0, v, twc, tws);
-    const DsCol q = qv;                                         // this block's decode, before the refill overwrites it
-    ds_barrier();
-    fetch_next(v, qv);                                          // in flight under this block's and the next one's MFMAs
-    {
-      const float* bp = ob + eo * (64 * 32) + half * 32 + l32;
-      ds_f32x16 acc, acc2;                                      // two chains: even / odd k-steps
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < 32; ks += 2) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ks], bp[ks * 64], acc, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[ks + 1], bp[ks * 64 + 64], acc2, 0, 0, 0);
-      }
-      if (q.ok) ds_inv_scatter(lds + q.ch * pitch + q.p + d * (q.s * hop + i0), d, i0, hop, wh, acc, acc2);
-    }
+    ds_inv_block(a, G, R, src, fa, twc, tws, F, bbuf + buf * DS_OPERAND, lds, v, qv);
     const bool last = blk_c + 1 == nblk;
     if (nbuf == 1 || last) ds_barrier();                        // the buffer is free again / the item is scattered
     buf = nbuf == 1 ? 0 : buf ^ 1;
@@ -743,7 +797,7 @@ __global__ __launch_bounds__(DS_MEM) void dftseg_inv_kernel(const hsp_dftseg_arg
     else ds_inv_epilogue<1, 4>(a, G, I, lds, wave, 4, lane, tb, tl);
     if (++it_c < nmine) {
       blk_c = 0;
-      I = item_of(it_c);
+      I = ds_item(blockIdx.x + it_c * gridDim.x, a, G);
       ncols = I.ncg * d * I.S;
     } else {
       done = true;
@@ -751,8 +805,8 @@ __global__ __launch_bounds__(DS_MEM) void dftseg_inv_kernel(const hsp_dftseg_arg
   };
   float v1[16], v2[16];
   DsCol q1, q2;
-  fetch_next(v1, q1);
-  fetch_next(v2, q2);
+  ds_fetch_next(F, src, a, G, R.l32, v1, q1);
+  ds_fetch_next(F, src, a, G, R.l32, v2, q2);
   while (true) {
     step(v1, q1);
     if (done) break;
@@ -767,8 +821,8 @@ __global__ __launch_bounds__(DS_MEM) void dftseg_inv_kernel(const hsp_dftseg_arg
 // forward transform of c2's input in ONE launch -- xt is never in HBM (a write and a read of the tensor, the staging
 // of the forward kernel and the epilogue of the inverse one go away).  One persistent 8-wave workgroup per CU, an item =
 // `cg` whole channel rows of one utterance (both convs unchunked), three phases separated by workgroup barriers:
-//   1. inverse of c1 into stretch A: the waves form two groups of four, each group one column block per step (fetches
-//      two steps ahead, across items, as in dftseg_inv_kernel);
+//   1. inverse of c1 into stretch A: the waves form two groups of four, each group one column block per step
+//      (ds_inv_block, its fetch stream two steps ahead, across items, as in dftseg_inv_kernel);
 //   2. activation A -> stretch B (the forward stretch of c2: zero padding, 16-B shift): a wave per 240-sample segment,
 //      its raw window a 16-B LDS load of A instead of a global one, then exactly da_segment;
 //   3. forward of c2 out of B: four wave pairs on alternate column blocks.
@@ -784,131 +838,61 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, half = lane >> 5;
-  const int hop1 = DS_N - (ai.k - 1), d1 = ai.dil, hop2 = DS_N - (af.k - 1), d2 = af.dil;
+  const int hop2 = DS_N - (af.k - 1), d2 = af.dil;
   float* const sA = lds;
   float* const sB = lds + G.offB;
   float* const twl = lds + G.offT;                              // forward twiddles (cos | sin)(2 pi k / 128)
-  float* const flt = twl + 64;                                  // activation taps as da_segment wants them
+  float* const flt = twl + 64;                                  // the activation's taps (da_load_taps)
   // phase-1 role: group grp of four waves, wave (eo, wh) of it; phase-3 role: pair pw, bin half wh3
-  const int grp = wave >> 2, w4 = wave & 3, wh1 = w4 & 1, eo = w4 >> 1;
+  const int grp = wave >> 2;
+  const DsInvRole R = ds_inv_role(wave & 3, lane);
   const int pw = wave >> 1, wh3 = wave & 1;
-  float* const bbuf = lds + G.offX + grp * (128 * 32);
+  float* const bbuf = lds + G.offX + grp * DS_OPERAND;
   float* const slice = lds + G.offX + wave * DA_SLICE;
   float fa1[32], fa3[32], twc[4], tws[4];
-  {
-    const float* frow = ai.dft + (32 * wh1 + l32) * DS_H + half;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) fa1[ks] = frow[2 * ks];
-    const float* grow = af.dft + (32 * wh3 + l32) * DS_H + half;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) fa3[ks] = grow[2 * ks];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      twc[u] = ai.dft[DS_H * DS_H + 8 * w4 + 4 * half + u];
-      tws[u] = ai.dft[DS_H * DS_H + 32 + 8 * w4 + 4 * half + u];
-    }
-  }
-  if (tid < 64) twl[tid] = af.dft[DS_H * DS_H + tid];
-  if (tid >= 64 && tid < 88) {
-    const int j = tid - 64, i = j >> 1;
-    flt[j] = j < 12 ? 2.0f * af.act_filt[10 - 2 * i + (j & 1)] : af.act_filt[j];
-  }
+  ds_load_afrag(fa1, ai.dft, R.wh, l32, half);
+  ds_load_afrag(fa3, af.dft, wh3, l32, half);
+  ds_load_twiddles(twc, tws, ai.dft, R.kf0);
+  ds_load_twl(twl, af.dft, tid);
+  da_load_taps(flt, af.act_filt, tid - 64);
+  // the two transforms' item geometry as the shared steps read it: whole rows, one chunk
+  const DsGeom Gi = {G.cg, G.S1, G.pitchA, G.ngrp, 1, 0}, Gf = {G.cg, G.S2, G.pitchB, G.ngrp, 1, 0};
   const int nitems = ai.B * G.ngrp;
   const int nmine = (nitems - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  auto item_of = [&](int it) __attribute__((always_inline)) {
-    DsItem I;
-    const int id = blockIdx.x + it * gridDim.x;
-    I.b = id / G.ngrp;
-    I.c0 = (id - I.b * G.ngrp) * G.cg;
-    I.ncg = min(G.cg, ai.C - I.c0);
-    I.s0 = 0;
-    I.S = G.S1;
-    return I;
-  };
-  // ---- phase-1 fetch stream of this group: blocks grp, grp + 2, ... of every item (a block behind the item's last one
-  // has no valid column: clamped addresses, nothing scattered), two steps ahead
-  int it_f = 0, st_f = 0;
-  DsItem If = item_of(0);
-  int ncols_f = If.ncg * d1 * G.S1;
-  bool more_f = true;
-  const float ip1 = 1.0f / (float)(d1 * G.S1), is1 = 1.0f / (float)G.S1;
-  const DsInvSrc src = ds_inv_src(ai.xf, ai.xf_bs, ai.C, ai.Np, w4, half);
-  const int kf0 = 8 * w4 + 4 * half;
-  const int i0 = 2 * (32 * wh1 + 4 * half) + eo;                // sample (inside its segment) of accumulator register 0
-  // (round 6: addresses, column decode and scatter as in dftseg_inv_kernel -- four uniform bases + 32-bit offsets, float-
-  // reciprocal decode handed from the fetch to the scatter, no per-sample bounds test)
-  auto fetch_next = [&](float (&v)[16], DsCol& q) __attribute__((always_inline)) {
-    q = ds_col_f(32 * (2 * st_f + grp) + l32, ncols_f, d1, G.S1, ip1, is1);
-    ds_inv_fetch(src, 4u * (unsigned)((If.c0 + q.ch) * ai.Np + (If.b * d1 + q.p) * ai.nseg + q.s), v);
-    if (64 * (st_f + 1) < ncols_f) {
-      ++st_f;
-    } else if (more_f && it_f + 1 < nmine) {
-      ++it_f;
-      st_f = 0;
-      If = item_of(it_f);
-      ncols_f = If.ncg * d1 * G.S1;
-    } else {
-      more_f = false;
-    }
-  };
-  const DsGeom Gf = {G.cg, G.S2, G.pitchB, G.ngrp, 1, 0};        // what da_segment reads of the forward geometry: pitch
+  DsFetch F;
+  F.begin(ai, Gi, nmine, grp, 2);                               // phase 1 of this group: blocks grp, grp + 2, ...
+  const DsInvSrc src = ds_inv_src(ai.xf, ai.xf_bs, ai.C, ai.Np, wave & 3, half);
   float v1[16], v2[16];
   DsCol q1, q2;
-  fetch_next(v1, q1);
-  fetch_next(v2, q2);
+  ds_fetch_next(F, src, ai, Gi, l32, v1, q1);
+  ds_fetch_next(F, src, ai, Gi, l32, v2, q2);
   __syncthreads();                                              // tables in LDS
   bool odd = false;                                             // which register set the next step stages
   for (int it = 0; it < nmine; ++it) {
-    const DsItem I = item_of(it);
-    const int ncols1 = I.ncg * d1 * G.S1, nst = (ncols1 + 63) >> 6;
-    // ---------------- phase 1
-    auto step1 = [&](float (&v)[16], DsCol& qv) __attribute__((always_inline)) {
-      ds_inv_stash(bbuf + l32, kf0, v, twc, tws);
-      const DsCol q = qv;
-      ds_barrier();
-      fetch_next(v, qv);
-      const float* bp = bbuf + eo * (64 * 32) + half * 32 + l32;
-      ds_f32x16 acc, acc2;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.0f;
-#pragma unroll
-      for (int ks = 0; ks < 32; ks += 2) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[ks], bp[ks * 64], acc, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa1[ks + 1], bp[ks * 64 + 64], acc2, 0, 0, 0);
-      }
-      // (c1's bias joins in phase 2: a load in this branch would wait for the fetches just issued -- vmcnt(0).  A block
-      // behind the item's last one has no valid column.  pitchA >= d1 S1 hop1: every index the scatter forms is inside
-      // its row, and phases 2 / 3 read [0, L) only.)
-      if (q.ok) ds_inv_scatter(sA + q.ch * G.pitchA + q.p + d1 * (q.s * hop1 + i0), d1, i0, hop1, wh1, acc, acc2);
-      ds_barrier();                                             // the operand buffer is free / A is complete
-    };
+    const DsItem I = ds_item(blockIdx.x + it * gridDim.x, ai, Gi);
+    const int nst = (I.ncg * ai.dil * G.S1 + 63) >> 6;
+    // ---------------- phase 1 (c1's bias joins in phase 2.  pitchA >= d1 S1 hop1: every index the scatter forms is
+    // inside its row, and phases 2 / 3 read [0, L) only.)
     for (int st = 0; st < nst; ++st) {
-      if (odd) step1(v2, q2);
-      else step1(v1, q1);
+      if (odd) ds_inv_block(ai, Gi, R, src, fa1, twc, tws, F, bbuf, sA, v2, q2);
+      else ds_inv_block(ai, Gi, R, src, fa1, twc, tws, F, bbuf, sA, v1, q1);
+      ds_barrier();                                             // the operand buffer is free / A is complete
       odd = !odd;
     }
     // ---------------- phase 2: A -> act -> B
     {
-      DsStage sg;
-      sg.t0 = -af.pad;
-      sg.len = d2 * ((G.S2 - 1) * hop2 + DS_N);
-      sg.sh = 4 + (sg.t0 & 3);
-      sg.g_lo = 0;
-      sg.ng = 0;
-      sg.tot = 0;
+      DsItem I2 = I;                                            // the same rows as an item of c2's forward transform
+      I2.S = G.S2;
+      const DsStage sg = ds_stage_of(af, I2);
       const int lb = RAG ? (int)min(max(af.act_len[I.b], (int64_t)1), (int64_t)af.L) : af.L;
-      const DaItem da = da_item<RAG>(af, I, sg, lb);
+      const DaItem da = da_item<RAG>(af, I2, sg, lb);
       for (int sI = wave; sI < da.nsegs; sI += 8) {
         const int ch = sI / da.nsg, p0 = da.pa4 + DA_SEG * (sI - ch * da.nsg);
         const ds_f32x4 rv = *reinterpret_cast<const ds_f32x4*>(sA + ch * G.pitchA + hsp_clampi(p0 - 8 + 4 * lane, 0, af.L - 4));
-        da_segment<RAG>(af, Gf, I, sg, da, sI, lane, rv, slice, sB, flt, ai.bias ? ai.bias[I.c0 + ch] : 0.0f,
-                        lb, sA + (lb - 1), G.pitchA);
+        da_segment<RAG>(af, Gf, I2, sg, da, sI, lane, rv, slice, sB, flt,
+                        DaRow{ai.bias ? ai.bias[I.c0 + ch] : 0.0f, lb, sA + (lb - 1), G.pitchA});
       }
-      for (int ch = 0; ch < I.ncg; ++ch) {                      // the conv's zero padding on either side
-        float* row = sB + ch * G.pitchB + sg.sh;
-        for (int j = tid; j < min(-sg.t0, sg.len); j += 512) row[j] = 0.0f;
-        for (int j = max(lb - sg.t0, 0) + tid; j < sg.len; j += 512) row[j] = 0.0f;
-      }
+      ds_zero_pad(sB, G.pitchB, I.ncg, sg, lb, tid, 512);
       ds_barrier();
       // ---------------- phase 3: forward of c2 out of B
       const int ncols2 = I.ncg * d2 * G.S2;
@@ -928,23 +912,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           ae = __builtin_amdgcn_mfma_f32_32x32x2f32(fa3[ks], bp[ks * step], ae, 0, 0, 0);
           ao = __builtin_amdgcn_mfma_f32_32x32x2f32(fa3[ks], bp[ks * step + d2], ao, 0, 0, 0);
         }
-        if (q.ok) {
-          const unsigned colb = 4u * (unsigned)((I.c0 + q.ch) * af.Np + (I.b * d2 + q.p) * af.nseg + q.s);
+        if (q.ok) {                                             // (stored at once: dftseg_fwd_kernel defers them)
+          const unsigned colb = ds_col_bytes(af, I2, q);
           char* const base = reinterpret_cast<char*>(af.xf);
 #pragma unroll
           for (int r = 0; r < 8; ++r) {
             const int kr = (r & 3) + 8 * (r >> 2);
-            const float er = ae[r], ei = ae[r + 8], orr = ao[r], oi = ao[r + 8];
-            const float wc = twl[lanek + kr], ws = twl[32 + lanek + kr];
-            const float tr = wc * orr + ws * oi, ti = wc * oi - ws * orr;
             const bool z = r == 0 && lanek == 0;
-            const bool z3 = z && af.prod3;                      // (-E0, -O0) in slot 0: hsp.h prod3
+            const DsBins X = ds_fwd_recombine(ae[r], ae[r + 8], ao[r], ao[r + 8], twl[lanek + kr], twl[32 + lanek + kr], z, af.prod3);
             const unsigned o1 = colb + (unsigned)(lanek + kr) * rowb;
             const unsigned o2 = colb + (z ? 32u : (unsigned)(64 - lanek - kr)) * rowb;
-            *reinterpret_cast<float*>(base + o1) = z3 ? -er : er + tr;
-            *reinterpret_cast<float*>(base + o1 + imb) = z ? (af.prod3 ? -tr : er - tr) : ei + ti;
-            *reinterpret_cast<float*>(base + o2) = z ? ei : er - tr;
-            *reinterpret_cast<float*>(base + o2 + imb) = z ? -oi : ti - ei;
+            *reinterpret_cast<float*>(base + o1) = X.kr;
+            *reinterpret_cast<float*>(base + o1 + imb) = X.ki;
+            *reinterpret_cast<float*>(base + o2) = X.mr;
+            *reinterpret_cast<float*>(base + o2 + imb) = X.mi;
           }
         }
       }
@@ -972,15 +953,36 @@ int64_t ds_resident(size_t lds_bytes) {
       n = 256;
     cus = n;
   }
-  const int per = (int)std::min<size_t>(2, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
+  const int per = (int)std::min<size_t>(2, std::max<size_t>(1, DS_LDS_MAX / std::max<size_t>(lds_bytes, 1)));
   return (int64_t)cus * per;
+}
+// LDS bytes of a forward launch (stretch | twiddles [| taps | four activation slices]) and of an inverse one (stretch |
+// nbuf operand buffers); `stretch` = floats of the item's rows
+size_t ds_fwd_lds(size_t stretch, bool act) { return (stretch + 64 + (act ? 32 + 4 * DA_SLICE : 0)) * sizeof(float); }
+size_t ds_inv_lds(size_t stretch, int nbuf) { return (stretch + (size_t)nbuf * DS_OPERAND) * sizeof(float); }
+
+// Rows per item: the count in [(cmax + 1) / 2, cmax] with the best score = column fill x round balance.  fill(cg) = the
+// used share of the MFMA column blocks of an item of cg rows (112 columns of 16 rows x 7 segments leave an eighth of the
+// fourth block empty, 18 rows fill it); balance = items / whole ROUNDS of the persistent grid of resident(cg) workgroups
+// (round 6: 512 channels x 800 samples with 19 rows per item are 864 items on 512 resident workgroups -- a third of them
+// walks one item while the others walk two, 84 % of two rounds; 16 rows per item are 1 024 = two rounds exactly).
+template <class Fill, class Resident>
+int ds_rows_per_item(int cmax, int64_t B, int C, int nchunk, Fill fill, Resident resident) {
+  int best = cmax;
+  double best_score = 0.0;
+  for (int cg = cmax; cg >= (cmax + 1) / 2; --cg) {
+    const int64_t res = resident(cg), items = B * ((C + cg - 1) / cg) * nchunk;
+    const double balance = (double)items / (double)(((items + res - 1) / res) * res);
+    const double score = fill(cg) * balance;
+    if (score > best_score + 1e-9) best_score = score, best = cg;
+  }
+  return best;
 }
 
 // Chunk geometry: the LARGEST even segment count whose stretch fits the LDS budget (the whole row at the Generator's
 // lengths: one staging per row -- smaller chunks were measured 1.1-2 x slower), then as many channel rows as still fit,
-// preferring a count that fills the last MFMA column block (112 columns of 16 rows x 7 segments leave an eighth of
-// the fourth block empty, 18 rows fill it).  Budget: 68 KB of input stretch (forward) / 64 KB of output stretch
-// (inverse, next to one or two 16-KB B buffers): two workgroups per CU either way.
+// by ds_rows_per_item.  Budget: 68 KB of input stretch (forward) / 64 KB of output stretch (inverse, next to one or two
+// 16-KB B buffers): two workgroups per CU either way.
 DsGeom ds_geom(const hsp_dftseg_args& a, bool inverse) {
   const int hop = DS_N - (a.k - 1), d = a.dil;
   const int budget = inverse ? 16384 : 17408;
@@ -997,32 +999,21 @@ DsGeom ds_geom(const hsp_dftseg_args& a, bool inverse) {
   DsGeom G;
   G.S = S;
   G.pitch = row_of(S);
+  G.nchunk = (a.nseg + S - 1) / S;
   int cmax = budget / G.pitch;
   cmax = cmax < 1 ? 1 : (cmax > 32 ? 32 : cmax);
   cmax = cmax > a.C ? a.C : cmax;
   const int quantum = inverse ? 32 : 64;                        // columns of one round of the MFMA waves
-  // (round 6) ... and a count whose items come out in whole ROUNDS of the persistent grid: 512 channels x 800 samples
-  // with 19 rows per item are 864 items on 512 resident workgroups -- a third of them walks one item while the others
-  // walk two (84 % of two rounds); 16 rows per item are 1 024 = two rounds exactly, for an eighth of the last column
-  // block left empty.  Score = column fill x round balance.
-  const int nchunk = (a.nseg + S - 1) / S;
-  int best = cmax;
-  double best_score = 0.0;
-  for (int cg = cmax; cg >= (cmax + 1) / 2; --cg) {
-    const int ncols = cg * d * S;
-    const double fill = (double)ncols / (quantum * ((ncols + quantum - 1) / quantum));
-    const size_t lds = inverse ? ((size_t)cg * G.pitch + 128 * 32) * sizeof(float) : ((size_t)cg * G.pitch + 64 + 32 + 4 * DA_SLICE) * sizeof(float);
-    const int64_t res = ds_resident(lds), items = (int64_t)a.B * ((a.C + cg - 1) / cg) * nchunk;
-    const double balance = (double)items / (double)(((items + res - 1) / res) * res);
-    const double score = fill * balance;
-    if (score > best_score + 1e-9) best_score = score, best = cg;
-  }
-  G.cg = best;
+  G.cg = ds_rows_per_item(
+      cmax, a.B, a.C, G.nchunk,
+      [&](int cg) { return (double)(cg * d * S) / (quantum * ((cg * d * S + quantum - 1) / quantum)); },
+      [&](int cg) { return ds_resident(inverse ? ds_inv_lds((size_t)cg * G.pitch, 1) : ds_fwd_lds((size_t)cg * G.pitch, true)); });
   G.bufsz = (G.cg * G.pitch + 3) & ~3;
-  G.nchunk = (a.nseg + S - 1) / S;
   G.ngrp = (a.C + G.cg - 1) / G.cg;
   return G;
 }
+// one operand buffer per workgroup, or two while two workgroups per CU still fit
+int ds_inv_nbuf(const DsGeom& G) { return ds_inv_lds(G.bufsz, 2) <= DS_LDS_MAX / 2 ? 2 : 1; }
 
 // The pair kernel's geometry; cg == 0: the pair cannot be fused (the caller runs the two launches)
 DpGeom dp_geom(const hsp_dftseg_args& ai, const hsp_dftseg_args& af) {
@@ -1035,41 +1026,43 @@ DpGeom dp_geom(const hsp_dftseg_args& ai, const hsp_dftseg_args& af) {
   G.S2 = af.nseg;
   G.pitchA = (ai.dil * G.S1 * hop1 + 3) & ~3;
   G.pitchB = (af.dil * ((G.S2 - 1) * hop2 + DS_N) + 12 + 3) & ~3;
-  const int avail = 160 * 1024 / 4 - 2 * 128 * 32 - 96;        // floats left for the two stretches
+  const int avail = (int)(DS_LDS_MAX / 4) - 2 * DS_OPERAND - 96;   // floats left for the two stretches
   int cg = avail / (G.pitchA + G.pitchB);
   cg = cg > 32 ? 32 : cg;
   cg = cg > ai.C ? ai.C : cg;
   if (cg < 1) return G;
-  {
-    // (round 6) whole rounds of the one-workgroup-per-CU grid, as in ds_geom: 864 items of 19 rows on 256 workgroups are
-    // four rounds at 84 %, 1 024 items of 16 rows four rounds exactly
-    const int64_t res = ds_resident(160 * 1024);
-    int best = cg;
-    double best_score = 0.0;
-    for (int c = cg; c >= (cg + 1) / 2; --c) {
-      const int n1 = c * ai.dil * G.S1, n2 = c * af.dil * G.S2;
-      const double fill = 0.5 * ((double)n1 / (64 * ((n1 + 63) / 64)) + (double)n2 / (128 * ((n2 + 127) / 128)));
-      const int64_t items = (int64_t)ai.B * ((ai.C + c - 1) / c);
-      const double score = fill * (double)items / (double)(((items + res - 1) / res) * res);
-      if (score > best_score + 1e-9) best_score = score, best = c;
-    }
-    cg = best;
-  }
+  // (round 6) whole rounds of the one-workgroup-per-CU grid, as in ds_geom: 864 items of 19 rows on 256 workgroups are
+  // four rounds at 84 %, 1 024 items of 16 rows four rounds exactly; fill: the mean of phase 1's (two groups of 32 columns)
+  // and phase 3's (four pairs)
+  cg = ds_rows_per_item(
+      cg, ai.B, ai.C, 1,
+      [&](int c) {
+        const int n1 = c * ai.dil * G.S1, n2 = c * af.dil * G.S2;
+        return 0.5 * ((double)n1 / (64 * ((n1 + 63) / 64)) + (double)n2 / (128 * ((n2 + 127) / 128)));
+      },
+      [](int) { return ds_resident(DS_LDS_MAX); });
   G.cg = cg;
   G.ngrp = (ai.C + cg - 1) / cg;
   G.offB = cg * G.pitchA;
   G.offX = G.offB + cg * G.pitchB;
-  G.offT = G.offX + 2 * 128 * 32;
+  G.offT = G.offX + 2 * DS_OPERAND;
   return G;
 }
 // what hsp_dftseg_fwd_f32 / hsp_dftseg_inv_f32 refuse beyond ds_check, from the geometry alone (hsp_dftseg_supported)
+bool ds_fits(int64_t items, size_t lds_bytes) { return lds_bytes <= DS_LDS_MAX && items <= 0x7fffffff; }
 int ds_limits(const hsp_dftseg_args& a, bool act) {
   const DsGeom Gf = ds_geom(a, false), Gi = ds_geom(a, true);
-  const size_t lds_f = ((size_t)Gf.bufsz + 64 + (act ? 32 + 4 * DA_SLICE : 0)) * sizeof(float);
-  const size_t lds_i = ((size_t)Gi.bufsz + 128 * 32) * sizeof(float);
-  if (lds_f > 160 * 1024 || lds_i > 160 * 1024) return HSP_EINVAL;
-  if ((int64_t)a.B * Gf.ngrp * Gf.nchunk > 0x7fffffff || (int64_t)a.B * Gi.ngrp * Gi.nchunk > 0x7fffffff) return HSP_EINVAL;
-  return 0;
+  const bool ok = ds_fits((int64_t)a.B * Gf.ngrp * Gf.nchunk, ds_fwd_lds(Gf.bufsz, act)) &&
+                  ds_fits((int64_t)a.B * Gi.ngrp * Gi.nchunk, ds_inv_lds(Gi.bufsz, 1));
+  return ok ? 0 : HSP_EINVAL;
+}
+// The launch tail of every entry point: `items` over the persistent grid -- the workgroups the device keeps resident at
+// this footprint, or fewer
+template <auto Kernel, class... Args>
+int ds_launch(int64_t items, int threads, size_t lds_bytes, void* stream, Args... args) {
+  if (!ds_fits(items, lds_bytes)) return HSP_EINVAL;
+  const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
+  return hsp_launch<Kernel>(blocks, threads, (int)lds_bytes, (int)DS_LDS_MAX, static_cast<hipStream_t>(stream), args...);
 }
 }  // namespace
 
@@ -1115,15 +1108,12 @@ extern "C" int hsp_dftseg_fwd_f32(const hsp_dftseg_args* ap, void* stream) {
   const bool act = a.act_alpha_exp != nullptr;
   if (act && (!a.act_beta_inv || !a.act_filt || ((a.L | (int)a.x_bs | (int)a.x_cs) & 3) || (reinterpret_cast<uintptr_t>(a.x) & 15)))
     return HSP_EINVAL;                                          // the fused activation wants 16-B addressable rows
-  const size_t lds_bytes = ((size_t)G.bufsz + 64 + (act ? 32 + 4 * DA_SLICE : 0)) * sizeof(float);
-  const int64_t items = (int64_t)a.B * G.ngrp * G.nchunk;
-  if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
-  const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
   if (a.act_len && !act) return HSP_EINVAL;                    // per-row lengths belong to the fused activation
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (a.act_len) return hsp_launch<dftseg_fwd_kernel<true, true>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
-  if (act) return hsp_launch<dftseg_fwd_kernel<true>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
-  return hsp_launch<dftseg_fwd_kernel<false>>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, st, a, G);
+  const int64_t items = (int64_t)a.B * G.ngrp * G.nchunk;
+  const size_t lds_bytes = ds_fwd_lds(G.bufsz, act);
+  if (a.act_len) return ds_launch<dftseg_fwd_kernel<true, true>>(items, DS_MEM, lds_bytes, stream, a, G);
+  if (act) return ds_launch<dftseg_fwd_kernel<true>>(items, DS_MEM, lds_bytes, stream, a, G);
+  return ds_launch<dftseg_fwd_kernel<false>>(items, DS_MEM, lds_bytes, stream, a, G);
 }
 
 extern "C" int hsp_dftseg_inv_f32(const hsp_dftseg_args* ap, void* stream) {
@@ -1131,12 +1121,8 @@ extern "C" int hsp_dftseg_inv_f32(const hsp_dftseg_args* ap, void* stream) {
   const hsp_dftseg_args& a = *ap;
   if (int e = ds_check(a)) return e;
   const DsGeom G = ds_geom(a, true);
-  const int nbuf = ((size_t)G.bufsz + 2 * 128 * 32) * sizeof(float) <= 80 * 1024 ? 2 : 1;   // two workgroups per CU
-  const size_t lds_bytes = ((size_t)G.bufsz + nbuf * 128 * 32) * sizeof(float);
-  const int64_t items = (int64_t)a.B * G.ngrp * G.nchunk;
-  if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
-  const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
-  return hsp_launch<dftseg_inv_kernel>(blocks, DS_MEM, (int)lds_bytes, 160 * 1024, static_cast<hipStream_t>(stream), a, G, nbuf);
+  const int nbuf = ds_inv_nbuf(G);
+  return ds_launch<dftseg_inv_kernel>((int64_t)a.B * G.ngrp * G.nchunk, DS_MEM, ds_inv_lds(G.bufsz, nbuf), stream, a, G, nbuf);
 }
 
 extern "C" int hsp_dftseg_pair_supported(const hsp_dftseg_args* inv, const hsp_dftseg_args* fwd) {
@@ -1147,13 +1133,9 @@ extern "C" int hsp_dftseg_pair_f32(const hsp_dftseg_args* inv, const hsp_dftseg_
   if (!inv || !fwd) return HSP_EINVAL;
   const DpGeom G = dp_geom(*inv, *fwd);
   if (G.cg < 1) return HSP_EINVAL;
+  // (offT holds at least the two operand buffers in front of it, so every launch is above 32 KB and raises the limit)
   const size_t lds_bytes = (size_t)(G.offT + 96) * sizeof(float);
   const int64_t items = (int64_t)inv->B * G.ngrp;
-  if (lds_bytes > 160 * 1024 || items > 0x7fffffff) return HSP_EINVAL;
-  const int64_t blocks = std::min<int64_t>(items, ds_resident(lds_bytes));
-  // (offT holds at least the 2 x 128 x 32 floats in front of it, so every launch is above 32 KB and raises the limit)
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  if (fwd->act_len) return hsp_launch<dftseg_pair_kernel<true>>(blocks, 512, (int)lds_bytes, 160 * 1024, st, *inv, *fwd, G);
-  return hsp_launch<dftseg_pair_kernel<false>>(blocks, 512, (int)lds_bytes, 160 * 1024, st, *inv, *fwd, G);
+  if (fwd->act_len) return ds_launch<dftseg_pair_kernel<true>>(items, 512, lds_bytes, stream, *inv, *fwd, G);
+  return ds_launch<dftseg_pair_kernel<false>>(items, 512, lds_bytes, stream, *inv, *fwd, G);
 }
-

@@ -625,14 +625,22 @@ class Conv1d(_ConvBase):
         da.prod3 = int(self.fft_form() == "three")
         return da
 
+    @staticmethod
+    def _fft_point(da, xf, table):
+        """Point hsp_dftseg_args at a spectrum buffer [64][2 C][Np] and a transform table."""
+        da.xf, da.xf_bs, da.dft = L.fptr(xf), xf.stride(0), L.fptr(table)
+
+    def _fft_probe(self, B, Lx, dummy=None):
+        """What a *_supported predicate is asked with: geometry, a dense plane stride, ``dummy`` pointers (none is read)."""
+        da = self._fft_args(B, Lx)
+        da.xf_bs = 2 * self.cin * da.Np
+        da.xf = da.dft = da.act_alpha_exp = da.act_beta_inv = da.act_filt = dummy
+        return da
+
     def fft_supported(self, B, Lx) -> bool:
         """Do the transform kernels take this geometry (hsp_dftseg_supported: dilation <= 8, a spectrum below 4 GiB per
         launch, item counts within int)?  fft_wins asks before choosing the form; beyond it the direct conv runs."""
-        if not self._fft:
-            return False
-        da = self._fft_args(B, Lx)
-        da.xf_bs = 2 * self.cin * da.Np
-        return bool(L.lib().hsp_dftseg_supported(C.byref(da)))
+        return self._fft and bool(L.lib().hsp_dftseg_supported(C.byref(self._fft_probe(B, Lx))))
 
     @staticmethod
     def _fft_set_act(da, x_like, act1d):
@@ -650,7 +658,7 @@ class Conv1d(_ConvBase):
         da = self._fft_args(B, Lx)
         xf = _spectrum(Cc, da.Np, x.device)
         da.x, da.x_bs, da.x_cs = L.fptr(x), x.stride(0), x.stride(1)
-        da.xf, da.xf_bs, da.dft = L.fptr(xf), xf.stride(0), L.fptr(_dft_tables(x.device)[0])
+        self._fft_point(da, xf, _dft_tables(x.device)[0])
         if act1d is not None:
             if not fft_act_fusable(x):
                 raise L.HspError("forward_fft(act1d=...) needs 16-B addressable rows")
@@ -684,7 +692,7 @@ class Conv1d(_ConvBase):
 
     def _fft_inverse_args(self, yf, B, Lx):
         da = self._fft_args(B, Lx)
-        da.xf, da.xf_bs, da.dft = L.fptr(yf), yf.stride(0), L.fptr(_dft_tables(yf.device)[1])
+        self._fft_point(da, yf, _dft_tables(yf.device)[1])
         da.bias = L.fptr(self._b) if self._b is not None else None
         return da
 
@@ -739,10 +747,8 @@ class Conv1d(_ConvBase):
         if not self._fft or not second._fft or second.cin != self.cin or x.shape[2] % 4:
             return False
         B, _, Lx = x.shape
-        ia, fa = self._fft_args(B, Lx), second._fft_args(B, Lx)
-        dummy = L.fptr(_zeros(x.device))                          # the predicate reads geometry only; pointers must be non-null
-        ia.xf = ia.dft = fa.xf = fa.dft = fa.act_alpha_exp = fa.act_beta_inv = fa.act_filt = dummy
-        ia.xf_bs, fa.xf_bs = 2 * self.cin * ia.Np, 2 * self.cin * fa.Np
+        dummy = L.fptr(_zeros(x.device))
+        ia, fa = self._fft_probe(B, Lx, dummy), second._fft_probe(B, Lx, dummy)
         return bool(L.lib().hsp_dftseg_pair_supported(C.byref(ia), C.byref(fa)))
 
     def _fft_pair_launch(self, second, yf, B, Lx, act_second, like):
@@ -752,7 +758,7 @@ class Conv1d(_ConvBase):
         ia = self._fft_inverse_args(yf, B, Lx)
         fa = second._fft_args(B, Lx)
         xf2 = _spectrum(Cc, fa.Np, yf.device)
-        fa.xf, fa.xf_bs, fa.dft = L.fptr(xf2), xf2.stride(0), L.fptr(_dft_tables(yf.device)[0])
+        self._fft_point(fa, xf2, _dft_tables(yf.device)[0])
         self._fft_set_act(fa, like, act_second)
         _bracket("hsp_dftseg_pair_f32", lambda: L.lib().hsp_dftseg_pair_f32(C.byref(ia), C.byref(fa), L.stream_ptr()),
                  2 * 2 * 64 * 64 * B * Cc * (ia.dil * ia.nseg + fa.dil * fa.nseg), 4 * 128 * Cc * (ia.Np + fa.Np), None)
