@@ -205,16 +205,16 @@ typedef struct hsp_conv1d_args {
 
 /* MFMA (v_mfma_f32_32x32x2_f32, exact fp32) path; stride must be 1, M % 4 == 0.  Behind this entry point: the
  * implicit-GEMM conv kernel (any K / dilation / prologue / row mode) and, for 1x1 convs over token columns (or with
- * ln_c1 / split_row), three token GEMMs -- the register-path and the LDS-DMA kernel (latency-oriented, up to a few
- * hundred thousand outputs) and the block token GEMM (64 x 64 / 128 x 128 tiles, from ~96 tiles of 64 x 64 upward);
+ * ln_c1 / split_row), two token GEMMs -- the register-path kernel (latency-oriented, up to about 1.4 M outputs) and
+ * the block token GEMM (64 x 64 / 128 x 128 tiles, from ~96 tiles of 64 x 64 upward, or any size with split_row);
  * hsp_conv1d_mfma_plan tells which one a launch takes. */
 int hsp_conv1d_mfma_f32(const hsp_conv1d_args* a, void* stream);
 /* VALU path: any shape (Cin = 1, Cout = 1, stride > 1, L = 1 "Linear" cases);
  * rows must be PLAIN; prologue NONE/LRELU/SILU. */
 int hsp_conv1d_direct_f32(const hsp_conv1d_args* a, void* stream);
 /* which kernel / tile configuration hsp_conv1d_mfma_f32 would pick: writes BM, BN, KC, LDS bytes
- * (KC > 0: the conv kernel's chunk depth; KC = 0: the LDS-DMA token GEMM; KC = -1: the register-path token GEMM;
- * KC = -2: the block token GEMM of hsp_bgemm.hip, 64 x 64 or 128 x 128 tiles) */
+ * (KC > 0: the conv kernel's chunk depth; KC = -1: the register-path token GEMM of hsp_rgemm.hip, 32 x 32 or 64 x 32
+ * tiles; KC = -2: the block token GEMM of hsp_bgemm.hip, 64 x 64 or 128 x 128 tiles) */
 int hsp_conv1d_mfma_plan(const hsp_conv1d_args* a, int32_t out4[4]);
 
 /* --------------------------------------- feature producer of inference_vc.py */

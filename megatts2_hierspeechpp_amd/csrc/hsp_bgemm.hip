@@ -4,10 +4,11 @@
 // ttv_v1/transformer_mega.py:63-73 (w_q / w_k / w_v, out_proj), :121-126 (ff.0, ff.3); the DiT qkv / proj / fc2 and WN
 // res_skip 1x1s of a front group of the vocoder, modules.py:166-174,357-411).
 //
-// Why a third token-GEMM kernel.  hsp_rgemm.hip (no staging, 32 x 32 / 64 x 32 tiles, K split over the waves) and
-// hsp_tokgemm.hip (LDS-DMA, 64 x 64 tiles) are built around the latency of ONE small launch; at 1 600-3 200 columns they
-// sat at 35-40 TFLOP/s, and their fused input LayerNorm took its statistics on the producers' critical path (+14 us at
-// 3 200 columns).  Two tile shapes here (hsp_bgemm_try picks; tools/gemm_bench.py, profiles/r03_bgemm_bench.txt):
+// Why a second token-GEMM kernel.  hsp_rgemm.hip (no staging, 32 x 32 / 64 x 32 tiles, K split over the waves) is built
+// around the latency of ONE small launch, as was the LDS-DMA token GEMM of rounds 1-3 (retired in round 4); at
+// 1 600-3 200 columns they sat at 35-40 TFLOP/s, and the retired kernel's fused input LayerNorm took its statistics on
+// the producers' critical path (+14 us at 3 200 columns).  Two tile shapes here (hsp_bgemm_try picks;
+// tools/gemm_bench.py, profiles/r03_bgemm_bench.txt):
 //   64 x 64   three 48-channel stages = 72 KB of LDS -> TWO workgroups per CU: the second resident tile covers the
 //             first one's start (1.2 us to the first stage) and its epilogue; the default;
 //   128 x 128 one workgroup per CU, half the L2 traffic per flop; from ~850 small tiles (1104 x 3 200).
@@ -16,18 +17,16 @@
 //   waves 0-3  consumers (2 x 2 over the tile, TM x TN blocks of 32 x 32 each): A / B fragments by plain LDS loads one
 //              group of k-steps ahead of the MFMAs that use them (the compiler counts them and places the waits; a
 //              scheduling barrier per group keeps the order); with a fused input LayerNorm they also form the column
-//              statistics from the B fragments passing through their registers (pivot-shifted sums, as in the other two
-//              kernels) -- no extra pass over the staged tile and no work on the producers' critical path;
+//              statistics from the B fragments passing through their registers (pivot-shifted sums, as in the register
+//              path) -- no extra pass over the staged tile and no work on the producers' critical path;
 //   waves 4-7  producers: LDS-DMA only, three (four: 128 x 64) stages in flight; one vector instruction per DMA on
 //              interior tiles (lane offset once per tile, the row walked by the scalar unit).
 //
 // Workgroup order is XCD-aware: the row tiles of one column tile get consecutive logical ids and an XCD takes a
 // contiguous range of ids, so a column tile's activations are fetched into ONE L2 and reused there by its row tiles.
 //
-// Operands as in hsp_tokgemm.hip: W packed [K][w_ld], X channel-major with unit column stride and 16-B addressable
-// rows; out-of-range 16-B lane groups read the zero buffer.  Epilogues (bg_epilogue, bg_epilogue_ext): the operation
-// order of the other token-GEMM kernels (bias + conditioning bias, LayerNorm correction, pointwise function, masks,
-// per-(b, c) scale, scale, residual, accumulate, post_scale), with a compile-time pointwise function.
+// Operand layout and epilogue order: hsp_token_gemm.h (X with unit column stride and 16-B addressable rows; out-of-
+// range 16-B lane groups read the zero buffer).  The epilogue (bg_epilogue) has a compile-time pointwise function.
 //
 // Folded columns (hsp_conv1d_args.fold_cols, 64 x 64 tiles): the column tiles are cut from the B * ncols virtual
 // columns v = b * ncols + t, so no utterance ends in a padded tile (200 frames: 256 staged and multiplied columns per
@@ -35,13 +34,9 @@
 // address of its group from the group's own (b, t) and the LDS image is what it was; a consumer lane takes (b, t) of its
 // column once per tile and every per-utterance operand of the epilogue is read at that b.  K order per output element
 // is unchanged, so the result is bit-identical to the per-utterance tiling.
-#include "hsp_device.h"
+#include "hsp_token_gemm.h"
 
-#ifdef HSP_TUNING
-#define BG_DBG(a, bit) (((a).debug & (bit)) != 0)
-#else
-#define BG_DBG(a, bit) false
-#endif
+#include <type_traits>
 
 namespace {
 
@@ -86,7 +81,7 @@ __device__ __forceinline__ void bg_fold(int v, int b0, int T, int B, int& b, int
 
 // Fragments of group G (k-steps GS G .. GS G + GS - 1 of the stage): A[step * TM + tm], B[step * TN + tn].
 // Plain LDS loads: the compiler counts them (LDS returns in order) and places s_waitcnt lgkmcnt(n) itself.  A first
-// version issued them from inline asm with hand-placed waits, as hsp_tokgemm.hip does; there the compiler is free to
+// version issued them from inline asm with hand-placed waits; there the compiler is free to
 // COPY an asm output register before the wait that makes it valid (it did, in the peeled first stage of the
 // LayerNorm variants: stale fragments in some waves), so the hand-counted form is not used here.
 typedef const __attribute__((address_space(3))) float* bg_lptr;
@@ -142,137 +137,92 @@ __device__ __forceinline__ void bg_stage(bg_f32x16 (&acc)[TM * TN], float (&A0)[
 // 45 000 cycles against 42 000): hsp_apply_act's run-time switch inlined 16 TM TN times (330 KB of libm branches to
 // fetch), and a 64-bit row-stride multiply + per-element bounds branch in front of every store (quarter-rate VALU
 // ops, ~35 instructions per element).  So: ACT is a compile-time pointwise function, a row is addressed as
-// wave-uniform base + 32-bit lane offset, and bounds are checked per group of four rows.  Only the plain epilogue
-// exists here (bias, LayerNorm correction, NONE / RELU / GELU_TANH, residual): launches that ask for masks, a
-// per-channel scale, a running sum or non-unit scales stay with the other token-GEMM kernels (hsp_bgemm_try).
+// wave-uniform base + 32-bit lane offset, and bounds are checked per group of four rows.
+// Two forms of one body.  Plain (!EXT): bias, LayerNorm correction, NONE / RELU / GELU_TANH, residual -- the PLM loop;
+// kept free of every operand it does not use.  EXT: everything hsp_conv1d_args can ask of a plain-row epilogue (the
+// DiT / WN token GEMMs of the vocoder's 50 Hz part) in the order of hsp_token_gemm.h, and the second output of
+// hsp_conv1d_args.split_row (whole 64-row tiles at or beyond split_row write y2 with their own parameter set).
 // FOLD: `b` and `nw` are this LANE's utterance and column (TN == 1; l32 is already inside nw), bvl holds the bias alone
-// and the conditioning bias, a per-(b, row) operand, is read per element like the residual.
-template <int TM, int TN, bool LN, int ACT, bool FOLD>
-__device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f32x16 (&acc)[TM * TN], int b, int mw, int nw,
-                                            int l32, int half, float bvl, float c1l, const float (&mean)[TN],
+// and the per-(b, row) operands, conditioning bias and scale, are read per element like the residual.
+template <int TM, int TN, bool LN, bool EXT, int ACT, bool FOLD>
+__device__ __forceinline__ void bg_epilogue(const hsp_conv1d_args& a, const bg_f32x16 (&acc)[TM * TN], int b, int m0, int mw,
+                                            int nw, int l32, int half, float bvl, float c1l, const float (&mean)[TN],
                                             const float (&rstd)[TN]) {
+  static_assert(!(LN && EXT), "the extended epilogue is not built with the fused LayerNorm");
+  const bool second = EXT && a.split_row > 0 && m0 >= a.split_row;     // this tile writes y2; its row 0 is row split_row
+  const int mo = second ? a.split_row : 0;
+  [[maybe_unused]] const int mmode = !EXT ? HSP_MASK_NONE : second ? a.mask_mode2 : a.mask_mode;
+  [[maybe_unused]] const bool accum = EXT && (second ? a.accumulate2 : a.accumulate) != 0;
+  const int64_t ycs = second ? a.y2_cs : a.y_cs;
   const int lc = FOLD ? 0 : l32;
-  const float* cbl = (FOLD && a.cbias) ? a.cbias + (int64_t)b * a.cbias_bs + 4 * half : nullptr;
+  [[maybe_unused]] const float csl =
+      (EXT && !FOLD && a.cscale) ? a.cscale[(int64_t)b * a.cscale_bs + min(mw + l32 + 32 * half, a.Cout - 1)] : 1.0f;
+  // FOLD: this lane's rows of the two per-(b, row) operands, indexed by the row of the whole launch
+  const float* cbl = (FOLD && a.cbias) ? a.cbias + (int64_t)b * a.cbias_bs + mo + 4 * half : nullptr;
+  [[maybe_unused]] const float* csp = (EXT && FOLD && a.cscale) ? a.cscale + (int64_t)b * a.cscale_bs + mo + 4 * half : nullptr;
+  [[maybe_unused]] const float sc = EXT ? a.scale : 1.0f, ps = EXT ? a.post_scale : 1.0f;
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     // row operands by cross-lane read, with every lane of the wave still active
-    float bvr[16], c1r[16];
+    float bvr[16];
+    [[maybe_unused]] float c1r[16], csr[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int src = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;     // the lane that holds this row's operands
+      const int src = tm * 32 + HSP_ACC_ROW(r, half);                  // the lane that holds this row's operands
       bvr[r] = __shfl(bvl, src, 64);
-      c1r[r] = LN ? __shfl(c1l, src, 64) : 0.0f;
+      if constexpr (LN) c1r[r] = __shfl(c1l, src, 64);
+      if constexpr (EXT) csr[r] = __shfl(csl, src, 64);
     }
-    {
-      // lane offsets in bytes from the (uniform) address of row mu = mw + 32 tm + (r & 3) + 8 (r >> 2), column nw
-      const unsigned yo = 4u * (unsigned)(lc + 4 * half * a.y_cs), ro = 4u * (unsigned)(lc + 4 * half * a.res_cs);
-      const char* ybase = reinterpret_cast<const char*>(a.y + (int64_t)b * a.y_bs + nw);
-      const char* rbase = a.res ? reinterpret_cast<const char*>(a.res + (int64_t)b * a.res_bs + nw) : nullptr;
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        if (nw + tn * 32 + lc < a.ncols) {
-          // the block's residual operands in one batch (rows clamped: always a legal address)
-          float rv[16];
-          [[maybe_unused]] float cb[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int mc = min(mw + tm * 32 + (r & 3) + 8 * (r >> 2), a.Cout - 1 - 4 * half);
-            rv[r] = rbase ? *reinterpret_cast<const float*>(rbase + (int64_t)mc * a.res_cs * 4 + tn * 128 + ro) : 0.0f;
-            if constexpr (FOLD) cb[r] = a.cbias ? cbl[mc] : 0.0f;
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int mu = mw + tm * 32 + 8 * q;                      // uniform; this lane's rows: mu + 4 half + (0..3)
-            if (mu + 4 * half < a.Cout) {                             // Cout % 4 == 0: the four rows stand or fall together
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                const int r = 4 * q + i;
-                const float fin = acc[tm * TN + tn][r];
-                float bv = bvr[r];
-                if constexpr (FOLD) bv = a.cbias ? bv + cb[r] : bv;
-                float v = fin + bv;
-                if constexpr (LN) v = fmaf(rstd[tn], fmaf(-mean[tn], c1r[r], fin), bv);
-                if constexpr (ACT == HSP_ACT_RELU) v = fmaxf(v, 0.0f);
-                else if constexpr (ACT == HSP_ACT_GELU_TANH) v = hsp_apply_act(v, HSP_ACT_GELU_TANH);
-                v += rv[r];
-                *reinterpret_cast<float*>(const_cast<char*>(ybase) + (int64_t)(mu + i) * a.y_cs * 4 + tn * 128 + yo) = v;
-              }
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// The same with everything hsp_conv1d_args can ask of a plain-row epilogue (the DiT / WN token GEMMs of the vocoder's
-// 50 Hz part): mask before / after the residual, per-(b, c) scale, scale, running sum, post_scale and the second output
-// of hsp_conv1d_args.split_row (whole 64-row tiles at or beyond split_row write y2 with their own parameter set).
-// Same operation order as hsp_epilogue_store; a factor that is not asked for is an exact multiplication by 1.
-// FOLD: as in bg_epilogue; the per-(b, row) scale is read per element as well.
-template <int TM, int TN, int ACT, bool FOLD>
-__device__ __forceinline__ void bg_epilogue_ext(const hsp_conv1d_args& a, const bg_f32x16 (&acc)[TM * TN], int b, int m0, int mw,
-                                                int nw, int l32, int half, float bvl) {
-  const bool second = a.split_row > 0 && m0 >= a.split_row;
-  const int mo = second ? a.split_row : 0;
-  const int mmode = second ? a.mask_mode2 : a.mask_mode;
-  const bool accum = (second ? a.accumulate2 : a.accumulate) != 0;
-  const int64_t ycs = second ? a.y2_cs : a.y_cs;
-  const char* ybase = reinterpret_cast<const char*>((second ? a.y2 + (int64_t)b * a.y2_bs : a.y + (int64_t)b * a.y_bs) + nw);
-  const char* rbase = (a.res && !second) ? reinterpret_cast<const char*>(a.res + (int64_t)b * a.res_bs + nw) : nullptr;
-  const int lc = FOLD ? 0 : l32;
-  const unsigned yo = 4u * (unsigned)(lc + 4 * half * (int)ycs), ro = 4u * (unsigned)(lc + 4 * half * a.res_cs);
-  const float csl = (!FOLD && a.cscale) ? a.cscale[(int64_t)b * a.cscale_bs + min(mw + l32 + 32 * half, a.Cout - 1)] : 1.0f;
-  // FOLD: this lane's rows of the two per-(b, row) operands, indexed by the row of the whole launch
-  const float* cbl = (FOLD && a.cbias) ? a.cbias + (int64_t)b * a.cbias_bs + mo + 4 * half : nullptr;
-  const float* csp = (FOLD && a.cscale) ? a.cscale + (int64_t)b * a.cscale_bs + mo + 4 * half : nullptr;
-  const float sc = a.scale, ps = a.post_scale;
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm) {
-    float bvr[16], csr[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int src = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      bvr[r] = __shfl(bvl, src, 64);
-      csr[r] = __shfl(csl, src, 64);
-    }
+    // a row = wave-uniform base of (row, column nw) + this lane's offset in bytes.  None of the four depends on tm: they
+    // are loop-invariant and stand inside the loop, after the cross-lane reads, ON PURPOSE.  Stated ahead of the loop the
+    // compiler scheduled the plain form 1-2 % slower at 32 x 200 columns (profiles/README.md, refactor of the token
+    // GEMMs); the effect is the scheduler's, so re-measure both placements after a compiler update before moving them.
+    const char* ybase = reinterpret_cast<const char*>((second ? a.y2 + (int64_t)b * a.y2_bs : a.y + (int64_t)b * a.y_bs) + nw);
+    const char* rbase = (a.res && !second) ? reinterpret_cast<const char*>(a.res + (int64_t)b * a.res_bs + nw) : nullptr;
+    const unsigned yo = 4u * (unsigned)(lc + 4 * half * ycs), ro = 4u * (unsigned)(lc + 4 * half * a.res_cs);
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
       const int n = nw + tn * 32 + lc;
       if (n < a.ncols) {
-        const float mk = mmode != HSP_MASK_NONE ? a.mask[(int64_t)b * a.mask_bs + n] : 1.0f;
-        const float mk_pre = (mmode & HSP_MASK_PRE) ? mk : 1.0f, mk_post = (mmode & HSP_MASK_POST) ? mk : 1.0f;
-        float rv[16], yv[16];
-        [[maybe_unused]] float cb[16], cs[16];
+        [[maybe_unused]] float mk_pre = 1.0f, mk_post = 1.0f;
+        if constexpr (EXT) {
+          const float mk = mmode != HSP_MASK_NONE ? a.mask[(int64_t)b * a.mask_bs + n] : 1.0f;
+          mk_pre = (mmode & HSP_MASK_PRE) ? mk : 1.0f;
+          mk_post = (mmode & HSP_MASK_POST) ? mk : 1.0f;
+        }
+        // the block's per-element operands in one batch (rows clamped: always a legal address)
+        float rv[16];
+        [[maybe_unused]] float yv[16], cb[16], cs[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int mc = min(mw + tm * 32 + (r & 3) + 8 * (r >> 2), a.Cout - 1 - 4 * half) - mo;
+          const int mc = min(mw + tm * 32 + HSP_ACC_ROW(r, 0), a.Cout - 1 - 4 * half) - mo;
           rv[r] = rbase ? *reinterpret_cast<const float*>(rbase + (int64_t)mc * a.res_cs * 4 + tn * 128 + ro) : 0.0f;
-          yv[r] = accum ? *reinterpret_cast<const float*>(ybase + (int64_t)mc * ycs * 4 + tn * 128 + yo) : 0.0f;
-          if constexpr (FOLD) {
-            cb[r] = a.cbias ? cbl[mc] : 0.0f;
-            cs[r] = a.cscale ? csp[mc] : 1.0f;
-          }
+          if constexpr (EXT) yv[r] = accum ? *reinterpret_cast<const float*>(ybase + (int64_t)mc * ycs * 4 + tn * 128 + yo) : 0.0f;
+          if constexpr (FOLD) cb[r] = a.cbias ? cbl[mc] : 0.0f;
+          if constexpr (FOLD && EXT) cs[r] = a.cscale ? csp[mc] : 1.0f;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int mu = mw + tm * 32 + 8 * q;
-          if (mu + 4 * half < a.Cout) {
+          const int mu = mw + tm * 32 + 8 * q;                        // uniform; this lane's rows: mu + 4 half + (0..3)
+          if (mu + 4 * half < a.Cout) {                               // Cout % 4 == 0: the four rows stand or fall together
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int r = 4 * q + i;
+              const float fin = acc[tm * TN + tn][r];
               float bv = bvr[r];
               if constexpr (FOLD) bv = a.cbias ? bv + cb[r] : bv;
-              float v = acc[tm * TN + tn][r] + bv;
+              float v = fin + bv;
+              if constexpr (LN) v = hsp_tg_ln_apply(rstd[tn], mean[tn], c1r[r], fin, bv);
               if constexpr (ACT == HSP_ACT_RELU) v = fmaxf(v, 0.0f);
               else if constexpr (ACT == HSP_ACT_GELU_TANH) v = hsp_apply_act(v, HSP_ACT_GELU_TANH);
-              v *= mk_pre;
-              v *= FOLD ? cs[r] : csr[r];
-              v *= sc;
+              if constexpr (EXT) {                // a factor that is not asked for is an exact multiplication by 1
+                v *= mk_pre;
+                v *= FOLD ? cs[r] : csr[r];
+                v *= sc;
+              }
               v += rv[r];
-              v *= mk_post;
-              v += yv[r];
-              *reinterpret_cast<float*>(const_cast<char*>(ybase) + (int64_t)(mu + i - mo) * ycs * 4 + tn * 128 + yo) = v * ps;
+              if constexpr (EXT) v = (v * mk_post + yv[r]) * ps;
+              *reinterpret_cast<float*>(const_cast<char*>(ybase) + (int64_t)(mu + i - mo) * ycs * 4 + tn * 128 + yo) = v;
             }
           }
         }
@@ -305,8 +255,8 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   const int K = a.Cin;
   const int nstage = (K + BG_KS - 1) / BG_KS;
 #ifdef HSP_TUNING
-  // tuning bit 1 << 20: cycle-counter stamps of workgroup 0 (consumer wave 0: 0-3, producer wave 4: 4-6) -> a.filt
-  unsigned long long* stamps = ((a.debug & (1 << 20)) && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 4))
+  // cycle-counter stamps of workgroup 0 (consumer wave 0: 0-3, producer wave 4: 4-6) -> a.filt
+  unsigned long long* stamps = ((a.debug & HSP_TG_STAMPS) && blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 4))
                                    ? (unsigned long long*)a.filt : nullptr;
 #define BG_STAMP(i) do { if (stamps) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -390,7 +340,7 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
       bg_barrier();                                       // A_s: stage s is in LDS
       if (s + C::NST < nstage) {
         bg_barrier();                                     // B_s: the consumers are done with this slot
-        if (!BG_DBG(a, 1)) issue(s + C::NST);
+        if (!HSP_TG_DBG(a, HSP_TG_NO_DMA)) issue(s + C::NST);
       }
     }
     return;
@@ -433,11 +383,11 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
     rows = rows > BG_KS ? BG_KS : rows;
     const bg_lptr wa = (bg_lptr)(Ws + half * C::BM + wm * (32 * TM) + l32);
     const bg_lptr xa = (bg_lptr)(Xs + half * C::BN + wn * (32 * TN) + l32);
-    if (!BG_DBG(a, 2)) {
+    if (!HSP_TG_DBG(a, HSP_TG_NO_MFMA)) {
       bg_read<TM, TN, 0>(A0, B0, wa, xa);
       if constexpr (!LN) {
         bg_stage<TM, TN, false, 0, false>(acc, A0, B0, A1, B1, wa, xa, s1, s2, pivot, 0);
-      } else if (BG_DBG(a, 1 << 25)) {   // tuning: the LayerNorm variant WITHOUT its statistics (wrong results): what are they worth?
+      } else if (HSP_TG_DBG(a, HSP_TG_BG_LN_NO_STATS)) {   // what are the statistics worth?
         bg_stage<TM, TN, false, 0, false>(acc, A0, B0, A1, B1, wa, xa, s1, s2, pivot, 0);
         s2 = 1.0f;
       } else if (rows == BG_KS) {
@@ -462,10 +412,8 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
   if constexpr (LN) {
     const float t1 = s1 + __shfl_xor(s1, 32, 64);
     const float t2 = s2 + __shfl_xor(s2, 32, 64);
-    const float dm = t1 / (float)K;
-    const float mu = pivot + dm;
-    const float var = fmaxf(t2 / (float)K - dm * dm, 0.0f);
-    const float rs = 1.0f / sqrtf(var + a.ln_eps);
+    float mu, rs;
+    hsp_tg_ln_finish(t1, t2, K, pivot, a.ln_eps, mu, rs);
     if constexpr (TN == 1) {
       mean[0] = mu;
       rstd[0] = rs;
@@ -487,17 +435,13 @@ __global__ __launch_bounds__(512, 1) void bgemm_kernel(const hsp_conv1d_args a, 
     }
   }
 
-  // ---- epilogue (hsp_bgemm_try admits these three pointwise functions only)
-  if constexpr (EXT) {
-    static_assert(!LN, "the extended epilogue is not built with the fused LayerNorm");
-    if (a.act == HSP_ACT_RELU) bg_epilogue_ext<TM, TN, HSP_ACT_RELU, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
-    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue_ext<TM, TN, HSP_ACT_GELU_TANH, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
-    else bg_epilogue_ext<TM, TN, HSP_ACT_NONE, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl);
-  } else {
-    if (a.act == HSP_ACT_RELU) bg_epilogue<TM, TN, LN, HSP_ACT_RELU, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
-    else if (a.act == HSP_ACT_GELU_TANH) bg_epilogue<TM, TN, LN, HSP_ACT_GELU_TANH, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
-    else bg_epilogue<TM, TN, LN, HSP_ACT_NONE, FOLD>(a, acc, be, mw, ne, l32, half, bvl, c1l, mean, rstd);
-  }
+  // ---- epilogue: the compile-time pointwise function is chosen here (hsp_bgemm_try admits these three only)
+  auto epilogue = [&](auto act) __attribute__((always_inline)) {
+    bg_epilogue<TM, TN, LN, EXT, decltype(act)::value, FOLD>(a, acc, be, m0, mw, ne, l32, half, bvl, c1l, mean, rstd);
+  };
+  if (a.act == HSP_ACT_RELU) epilogue(std::integral_constant<int, HSP_ACT_RELU>{});
+  else if (a.act == HSP_ACT_GELU_TANH) epilogue(std::integral_constant<int, HSP_ACT_GELU_TANH>{});
+  else epilogue(std::integral_constant<int, HSP_ACT_NONE>{});
   BG_STAMP(3);
 #undef BG_STAMP
 }
@@ -510,7 +454,7 @@ int bg_launch(const hsp_conv1d_args& a, hipStream_t s, int n_mt, int n_nt, int t
   return hsp_launch<bgemm_kernel<TM, TN, LN, EXT, FOLD>>(8 * per_xcd, 512, C::LDS_BYTES, C::LDS_BYTES, s, a, n_mt, n_nt, per_xcd, total);
 }
 
-// does the launch need bg_epilogue_ext?
+// does the launch need the extended form of bg_epilogue?
 inline bool bg_extended(const hsp_conv1d_args& a) {
   return a.mask_mode != HSP_MASK_NONE || a.cscale || a.accumulate || a.scale != 1.0f || a.post_scale != 1.0f || a.split_row > 0;
 }
@@ -544,17 +488,14 @@ int bg_go(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
 
 }  // namespace
 
-// Host side: eligibility + tile choice + launch; called by the conv dispatcher ahead of the two latency-oriented
-// token GEMMs.  Returns -1 when the shape is not one this kernel takes.
+// Host side: eligibility + tile choice + launch; called by the conv dispatcher ahead of the latency-oriented
+// register path.  Returns -1 when the shape is not one this kernel takes.
 int hsp_bgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (BG_DBG(a, 1 << 22)) return -1;
-  if (a.K != 1 || a.stride != 1 || a.pad != 0 || a.prologue != HSP_PRO_NONE || a.rows != HSP_ROWS_PLAIN) return -1;
-  if (a.x_ts != 1 || a.Lin != a.ncols || a.Lout != a.ncols) return -1;
+  if (HSP_TG_DBG(a, HSP_TG_BG_OFF)) return -1;
+  if (!hsp_tg_eligible(a) || a.x_ts != 1) return -1;
   if ((a.Cin & 3) || (a.ncols & 3) || (a.x_bs & 3) || (a.x_cs & 3) || !al16(a.x) || !al16(a.w) || (a.w_ld & 3)) return -1;
   if (a.Cin < 96 || a.Cin > 8192) return -1;
-  if (a.ln_c1 && !(a.ln_eps > 0.0f)) return -1;
-  if (a.mask_mode != HSP_MASK_NONE && !a.mask) return -1;
   if (a.act != HSP_ACT_NONE && a.act != HSP_ACT_RELU && a.act != HSP_ACT_GELU_TANH) return -1;
   // the epilogues address a row as uniform base + 32-bit lane offset and test bounds per group of four rows
   if (a.y_cs >= (1 << 24) || a.res_cs >= (1 << 24) || (a.Cout & 3)) return -1;
@@ -566,20 +507,19 @@ int hsp_bgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   }
 #ifdef HSP_TUNING
   if (!a.split_row) {
-    if (a.debug & (1 << 18)) return bg_go<2, 2>(a, s, plan_out);
-    if (a.debug & (1 << 19)) return bg_go<2, 1>(a, s, plan_out);
-    if (a.debug & (1 << 21)) return bg_go<1, 2>(a, s, plan_out);
+    if (a.debug & HSP_TG_BG_128x128) return bg_go<2, 2>(a, s, plan_out);
+    if (a.debug & HSP_TG_BG_128x64) return bg_go<2, 1>(a, s, plan_out);
+    if (a.debug & HSP_TG_BG_64x128) return bg_go<1, 2>(a, s, plan_out);
   }
-  if (a.debug & (1 << 23)) return bg_go<1, 1>(a, s, plan_out);
+  if (a.debug & HSP_TG_BG_64x64) return bg_go<1, 1>(a, s, plan_out);
 #endif
   // Tile choice (tools/gemm_bench.py, profiles/r03_bgemm_bench.txt).  64 x 64 tiles at two workgroups per CU are the
   // default: a second resident tile covers the first one's 1.8-us start and its epilogue, which a lone 128 x 128
   // tile per CU leaves exposed, and up to 3 200 columns that outweighs the doubled L2 traffic.  Below ~96 tiles the
   // latency-oriented kernels win (7-11 us floors against 9.5-11.5 here); from ~850 tiles (1104 x 3 200) the
   // 128 x 128 shape is ahead (33 against 35 us).
-  auto tiles = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.ncols + bn - 1) / bn) * a.B; };
   auto waste_ok = [&](int bm) { return 4 * (int64_t)(((a.M + bm - 1) / bm) * bm - a.M) <= a.M; };
-  const int64_t t64 = tiles(64, 64);
+  const int64_t t64 = hsp_tile_count(a, 64, 64);
   if (t64 < 96 && !a.split_row) return -1;   // (a second-output launch has no other kernel: better one launch here than two)
   // (round 4, tools/gemm_sweep.py over B in {1..64} x T in {50, 200, 1000}: profiles/r04_gemm_dispatch_table.txt)  The
   // 128 x 128 shape runs one workgroup per CU, so what it costs is ROUNDS of 256 tiles: it wins only for many rows
@@ -590,7 +530,7 @@ int hsp_bgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   // tiles at two per CU are ahead (WN res_skip at 64 x 1 000 frames: 95 against 117 us)
   if (t64 >= 5000 && a.Cin <= 256 && !a.ln_c1 && !a.split_row && !bg_extended(a)) return -1;
   if (t64 >= 700 && a.M >= 768 && waste_ok(128) && a.ncols >= 512 && !a.split_row) {
-    const int64_t t128 = tiles(128, 128);
+    const int64_t t128 = hsp_tile_count(a, 128, 128);
     const int64_t rounds = (t128 + 255) / 256;
     if (100 * rounds * 256 <= 115 * t128) return bg_go<2, 2>(a, s, plan_out);
   }

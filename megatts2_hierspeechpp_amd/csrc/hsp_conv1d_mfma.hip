@@ -1,12 +1,10 @@
 // hsp_conv1d_mfma_f32: argument validation and the choice of kernel, tile shape and epilogue kind.
 // The kernel itself is the template in hsp_conv1d_mfma_kernel.h, instantiated per tile shape by
-// hsp_conv1d_tile.hip; 1x1 convs over short column axes go to the token GEMM (hsp_tokgemm.hip).
+// hsp_conv1d_tile.hip; 1x1 convs over token columns go to one of the two token GEMMs (hsp_token_gemm.h).
 //
 // Reference call sites: see include/hsp.h (hsp_conv1d_args).
 #include "hsp_conv1d_mfma_kernel.h"
-
-int hsp_rgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out);    // hsp_rgemm.hip; likewise
-int hsp_bgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out);    // hsp_bgemm.hip; likewise
+#include "hsp_token_gemm.h"
 
 namespace {
 using namespace hspconv;
@@ -52,7 +50,7 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   // chunks so that more CUs get work.  A lone 64 x 64 tile takes half as long as a lone 128 x 128 one (measured:
   // 36 us against 67 us at C = 128, k = 7) for a quarter of the work, so the small shape wins up to 64 big tiles,
   // ties up to 128 and loses 2x beyond (tools/conv_sweep.py, profiles/r02_tile_threshold.txt).
-  const bool short_seq = (int64_t)((a.M + 127) / 128) * ((a.ncols + 127) / 128) * a.B <= 128;
+  const bool short_seq = hsp_tile_count(a, 128, 128) <= 128;
   // a residual read at a column stride: the register-path token GEMM or nothing
   if (a.res && a.res_ts > 1) {
     if (a.fold_cols) return HSP_EINVAL;
@@ -61,7 +59,7 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   }
   // 1x1 GEMMs with enough outputs for about one 128 x 128 / 128 x 64 tile per CU (the PLM loop beyond ~60 prefix
   // positions): the throughput-oriented token GEMM (hsp_bgemm.hip)
-  if (a.K == 1 && !a.w_bs && !HSP_DBG(a, 128)) {
+  if (a.K == 1 && !a.w_bs && !HSP_TG_DBG(a, HSP_TG_OFF)) {
     const int e = hsp_bgemm_try(a, s, plan_out);
     if (e >= 0) return e;
   }
@@ -72,11 +70,11 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   hsp_conv1d_args plain = a;
   plain.fold_cols = 0;
   int32_t probe[4];
-  // (tuning bit 1 << 24: try the register-path token GEMM whatever the launch size -- tools/gemm_sweep.py)
-  if ((short_seq || a.ln_c1 || a.split_row || HSP_DBG(a, 1 << 24)) && !a.w_bs && !HSP_DBG(a, 128)) {
+  // (HSP_TG_RG_ANY_SIZE: try the register-path token GEMM whatever the launch size -- tools/gemm_sweep.py)
+  if ((short_seq || a.ln_c1 || a.split_row || HSP_TG_DBG(a, HSP_TG_RG_ANY_SIZE)) && !a.w_bs && !HSP_TG_DBG(a, HSP_TG_OFF)) {
     if (a.fold_cols && hsp_rgemm_try(plain, nullptr, probe) >= 0) return HSP_EINVAL;
     // 1x1 GEMMs over a few thousand token columns: the register-path kernel (hsp_rgemm.hip).  (The LDS-DMA token GEMM
-    // of rounds 1-3, hsp_tokgemm.hip, was retired in round 4: tools/gemm_sweep.py found no (shape, B, T) cell of
+    // of rounds 1-3 was retired in round 4: tools/gemm_sweep.py found no (shape, B, T) cell of
     // profiles/r04_gemm_dispatch_table.txt where it beat the block GEMM or the register path by more than 2 %.)
     const int e = hsp_rgemm_try(a, s, plan_out);
     if (e >= 0) return e;
@@ -105,7 +103,7 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
       // CUs with each other's launches -- there the wider footprint LOSES (same box: 57.5-57.6 -> 57.8 ms per step with
       // the split tile on the 96-tile in-layers, profiles/r05_ab_s64g2*.json).  Tuning bits: 1 << 27 never, 1 << 28 up to
       // 512 tiles.
-      const int64_t t128 = (int64_t)((a.M + 63) / 64) * ((a.ncols + 127) / 128) * a.B;
+      const int64_t t128 = hsp_tile_count(a, 64, 128);
       if ((t128 <= 48 || (HSP_DBG(a, 1 << 28) && t128 <= 512)) && !HSP_DBG(a, 1 << 27)) {
         if (a.fold_cols && hsp_conv_tile_S64G2(plain, epi, act, nullptr, probe) != HSP_EINVAL) return HSP_EINVAL;
         const int e = hsp_conv_tile_S64G2(a, epi, act, s, plan_out);

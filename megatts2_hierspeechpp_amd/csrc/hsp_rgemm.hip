@@ -1,12 +1,12 @@
 // Register-path fp32-MFMA GEMM for the token matrices of the 50 Hz part (the PLM loop above all):
 //   Y[M x N] = epilogue(W[M x K] X[K x N]),  K = 192 .. 1104, N = 16 .. a few thousand columns.
 //
-// Why a second token-GEMM kernel.  hsp_tokgemm.hip stages both operands through LDS with LDS-DMA; measured
-// (round 3, tools/conv_sweep.py on the PLM shapes, libhsp_tune.so): a launch with the DMA and the MFMAs switched
-// off still takes 12.5 us, because every tile first pulls three stages (147 KB) through a path that sustains
-// ~20 GB/s per CU -- 7 us before the first MFMA -- and a K = 1104 tile needs 565 KB = 28 us however few tiles the
-// launch has.  LDS-DMA is the right tool where a staged byte is reused 64-128 times (the conv kernel needs ~10 GB/s
-// per CU); a 64 x 64 GEMM tile reuses it 32 times and starves.
+// Why no staging.  A kernel that stages both operands through LDS with LDS-DMA (the token GEMM of rounds 1-3, since
+// retired) was measured in round 3 (tools/conv_sweep.py on the PLM shapes, libhsp_tune.so): a launch with the DMA and
+// the MFMAs switched off still took 12.5 us, because every tile first pulled three stages (147 KB) through a path that
+// sustains ~20 GB/s per CU -- 7 us before the first MFMA -- and a K = 1104 tile needed 565 KB = 28 us however few tiles
+// the launch had.  LDS-DMA is the right tool where a staged byte is reused 64-128 times (the conv kernel needs
+// ~10 GB/s per CU); a 64 x 64 GEMM tile reuses it 32 times and starves.
 //
 // Here nothing is staged.  The packed weight is [K][M] (rows fastest) and the activations are channel-major
 // [K][N], so BOTH MFMA fragments of v_mfma_f32_32x32x2_f32 are plain coalesced dword loads: lane (l32, half) reads
@@ -17,16 +17,9 @@
 // instead of a few pipelined ones: 4 of them share a CU, so one wave's load latency is another's MFMA time, and a
 // launch is one L2 round trip + a short MFMA chain + one LDS exchange.
 //
-// Epilogue = hsp_tokgemm.hip's (bias, conditioning bias, fused input LayerNorm, pointwise function, masks,
-// per-(b, c) scale, residual, accumulate), same operation order.  The LayerNorm statistics come from the B
-// fragments the waves load anyway (pivot-shifted sums, as in the LDS kernel).
-#include "hsp_device.h"
-
-#ifdef HSP_TUNING
-#define RG_DBG(a, bit) (((a).debug & (bit)) != 0)
-#else
-#define RG_DBG(a, bit) false
-#endif
+// Operand layout and epilogue order: hsp_token_gemm.h (any hsp_apply_act function, a residual at any column stride).
+// The LayerNorm statistics come from the B fragments the waves load anyway (pivot-shifted sums).
+#include "hsp_token_gemm.h"
 
 namespace {
 
@@ -61,8 +54,8 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rgemm_kernel(const hsp_conv1d_a
   const int kk0 = ks * per, kk1 = min(kk0 + per, ksteps);
 
 #ifdef HSP_TUNING
-  // tuning bit 1 << 20: cycle-counter stamps of workgroup (gridDim.x / 2), wave 0, lane 0 -> a.filt (6 x uint64)
-  unsigned long long* stamps = ((a.debug & (1 << 20)) && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
+  // cycle-counter stamps of workgroup (gridDim.x / 2), wave 0, lane 0 -> a.filt (6 x uint64)
+  unsigned long long* stamps = ((a.debug & HSP_TG_STAMPS) && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
                                    ? (unsigned long long*)a.filt : nullptr;
 #define RG_STAMP(i) do { if (stamps) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -120,7 +113,7 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rgemm_kernel(const hsp_conv1d_a
       B[u] = xp[(int64_t)k * xst];
     }
   };
-  if (!RG_DBG(a, 2)) {
+  if (!HSP_TG_DBG(a, HSP_TG_NO_MFMA)) {
 #pragma unroll 1
     for (int kk = kk0; kk < kk1; kk += RG_U) {
       load(kk, fa, fb);
@@ -158,10 +151,7 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rgemm_kernel(const hsp_conv1d_a
       t1 += stat[blk + q * nblk][0][l32];
       t2 += stat[blk + q * nblk][1][l32];
     }
-    const float dm = t1 / (float)K;
-    mean = pivot + dm;
-    const float var = fmaxf(t2 / (float)K - dm * dm, 0.0f);
-    rstd = 1.0f / sqrtf(var + a.ln_eps);
+    hsp_tg_ln_finish(t1, t2, K, pivot, a.ln_eps, mean, rstd);
   }
   if (ncol >= a.ncols) return;
 #pragma unroll
@@ -172,8 +162,8 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rgemm_kernel(const hsp_conv1d_a
     if (mr >= a.Cout) continue;
     float fin = 0.0f;
     for (int q = 0; q < ksplit; ++q) fin += part[blk + q * nblk][r][lane];   // fixed order: deterministic
-    float v = a.ln_c1 ? fmaf(rstd, fmaf(-mean, c1[i], fin), bv[i]) : fin + bv[i];
-    v = hsp_apply_act(v, a.act);                // then the order of hsp_epilogue_store
+    float v = a.ln_c1 ? hsp_tg_ln_apply(rstd, mean, c1[i], fin, bv[i]) : fin + bv[i];
+    v = hsp_apply_act(v, a.act);                // then the order of hsp_token_gemm.h
     if (a.mask_mode & HSP_MASK_PRE) v *= mk;
     v *= cs[i];
     v *= a.scale;
@@ -188,38 +178,32 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rgemm_kernel(const hsp_conv1d_a
 
 }  // namespace
 
-// Host side: eligibility + launch; called by the conv dispatcher ahead of the LDS-DMA token GEMM.
+// Host side: eligibility + launch; called by the conv dispatcher after the block GEMM has declined.
 // Returns -1 when the shape is not one this kernel takes.
 int hsp_rgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
-  if (a.K != 1 || a.stride != 1 || a.pad != 0 || a.prologue != HSP_PRO_NONE || a.rows != HSP_ROWS_PLAIN) return -1;
-  if (a.x_ts < 1 || a.Lin != a.ncols || a.Lout != a.ncols || a.split_row) return -1;   // any column stride of x
+  if (!hsp_tg_eligible(a) || a.split_row) return -1;      // any column stride of x
   if (a.Cin < 32 || a.Cin > 8192) return -1;
-  if (a.ln_c1 && !(a.ln_eps > 0.0f)) return -1;
-  if (a.mask_mode != HSP_MASK_NONE && !a.mask) return -1;
   // Where it wins (tools/gemm_bench.py, hipGraph replay, profiles/r03_gemm_bench.txt): up to ~1.4 M outputs per
-  // launch -- 7-8 us against 12-15 us for the LDS-DMA kernel at a few hundred columns (its floor is the three-stage
-  // prologue), 14 against 29 us at K = 1104 -- and a tie around 1 600 x 828; beyond that the LDS kernel's operand
-  // reuse wins (3 200 columns: 34-49 us against 43-52), so larger launches stay there.
-  auto tiles = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.ncols + bn - 1) / bn) * a.B; };
-  const bool forced = RG_DBG(a, 8 | 16) || (a.res && a.res_ts > 1);   // a strided residual has no other kernel
+  // launch -- 7-8 us against 12-15 us for an LDS-staged kernel at a few hundred columns (its floor is the three-stage
+  // prologue), 14 against 29 us at K = 1104 -- and a tie around 1 600 x 828; beyond that operand reuse through LDS
+  // wins (3 200 columns: 34-49 us against 43-52), so larger launches go to the block GEMM or the conv tiles.
+  const bool forced = HSP_TG_DBG(a, HSP_TG_RG_64x32 | HSP_TG_RG_32x32) || (a.res && a.res_ts > 1);   // a strided residual has no other kernel
   const int64_t outs = (int64_t)a.M * a.ncols * a.B;
   if (!forced && a.x_ts == 1 && (outs > 1400000 || outs * a.Cin > 500000000)) return -1;
   // many short utterances ([B, C, T <= 64]: every utterance is two ragged 32-column tiles): beyond ~400 such tiles the
   // conv kernel's tiles win by 1.4-1.6 x, below the register path does by up to 1.8 x (profiles/r04_gemm_dispatch_table.txt)
   // (a fused input LayerNorm that the block GEMM did not take has no other kernel: e.g. the ONE new column per utterance of
   // the PLM loop's cached layer 0 -- B utterances x 1 column, 26 x 16 tiles -- round 6)
-  if (!forced && !a.ln_c1 && a.ncols <= 64 && tiles(32, 32) > 400) return -1;
+  if (!forced && !a.ln_c1 && a.ncols <= 64 && hsp_tile_count(a, 32, 32) > 400) return -1;
   // tile: 64 x 32 where that still fills the chip, else 32 x 32 (a 64 x 64 / K-split-2 form was measured and lost)
   int nbm = 1, nbn = 1;
-  if (tiles(64, 32) >= 200) { nbm = 2; nbn = 1; }
-#ifdef HSP_TUNING
-  if (a.debug & 8) { nbm = 2; nbn = 1; }
-  if (a.debug & 16) { nbm = 1; nbn = 1; }
-#endif
+  if (hsp_tile_count(a, 64, 32) >= 200) { nbm = 2; nbn = 1; }
+  if (HSP_TG_DBG(a, HSP_TG_RG_64x32)) { nbm = 2; nbn = 1; }
+  if (HSP_TG_DBG(a, HSP_TG_RG_32x32)) { nbm = 1; nbn = 1; }
   const int n_mt = (a.M + 32 * nbm - 1) / (32 * nbm), n_nt = (a.ncols + 32 * nbn - 1) / (32 * nbn);
   const int64_t blocks = (int64_t)n_mt * n_nt * a.B;
   if (blocks <= 0 || blocks > 0x7fffffff) return -1;
-  if (plan_out) {  // {BM, BN, -1 = "register-path token GEMM" (0 = the LDS-DMA one, > 0 = the conv kernel's chunk depth), LDS bytes}
+  if (plan_out) {  // {BM, BN, -1 = "register-path token GEMM" (> 0 = the conv kernel's chunk depth), LDS bytes}
     plan_out[0] = 32 * nbm; plan_out[1] = 32 * nbn; plan_out[2] = -1; plan_out[3] = (int32_t)(sizeof(float) * (RG_WAVES * 16 * 64 + RG_WAVES * 64));
     return 0;
   }

@@ -8,6 +8,9 @@ strides differ from the dense ones and from one another.  test_conv_ref_host.py 
 CPU conv1d / conv_transpose1d in float64 through the packing maps of hip_layers, and checks for every case that the
 library's own plan is the tile shape the case id names.
 
+`_evaluate` also states the two fields only the 1x1 token GEMMs take, `ln_c1` (fused input LayerNorm) and `res_ts`
+(column stride of the residual); their case table and the two-output form are in tests/tokgemm_ref.py.
+
 Activation1d (HSP_PRO_ACT1D) is the index statement of oracle.hsp_oracle.act1d_closed_form, vectorised and taking the
 operands the kernel takes (exp(alpha), 1 / (exp(beta) + 1e-9), the 12 + 12 taps); the host test pins one against the
 other.
@@ -130,7 +133,16 @@ def _evaluate(a, absolute=False):
     acc = np.zeros((B, M, ncols), F64)
     for j in range(K):
         xs = xp[:, :, j * dil: j * dil + (ncols - 1) * stride + 1: stride]
-        acc += np.einsum("bcm,bct->bmt", w[:, j], xs)
+        acc += np.matmul(w[:, j].transpose(0, 2, 1), xs)
+    if a.get("ln_c1") is not None:
+        # fused input LayerNorm of the 1x1 token GEMMs, as the header writes it: column mean and biased variance over the
+        # Cin inputs, rstd = 1 / sqrt(var + ln_eps), acc <- rstd (acc - mean ln_c1[row])
+        assert K == 1 and pad == 0 and stride == 1 and a["prologue"] == PRO_NONE
+        c1 = fix(view(a, "ln_c1", (M,), (1,))[0])
+        mean, var = x.mean(axis=1), x.var(axis=1)
+        rstd = 1.0 / np.sqrt(var + float(F32(a["ln_eps"])))
+        mean = fix(mean)
+        acc = rstd[:, None, :] * (acc + mean[:, None, :] * c1[None, :, None] * (1.0 if absolute else -1.0))
 
     rows = a["rows"]
     gated = rows in (ROWS_GATE_WN, ROWS_GATE_GLU)
@@ -186,7 +198,7 @@ def _evaluate(a, absolute=False):
         v = v * cs[bI, co_c[None]]
     v = v * abs(float(F32(a["scale"]))) if absolute else v * float(F32(a["scale"]))
     if a.get("res") is not None:
-        r, _ = view(a, "res", (B, Cout, Lout), (a["res_bs"], a["res_cs"], 1))
+        r, _ = view(a, "res", (B, Cout, Lout), (a["res_bs"], a["res_cs"], max(1, a.get("res_ts", 1))))   # res_ts: 0 or 1 = unit
         v = v + fix(r)[bI, co_c[None], to_c[None]]
     if mm & MASK_POST:
         v = v * mk

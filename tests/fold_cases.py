@@ -10,11 +10,10 @@ of 64 x 128 (except 9 x 8) and take the K-split tile, which does not implement t
 
 A case is (spec for conv_ref.build, split) with split = None or (split_row, mask_mode2, accumulate2): the two-output form
 of a 1x1 token GEMM, which conv_ref does not know, is stated as two launches of its contract (rows [0, split_row) with
-the case's epilogue, rows [split_row, Cout) into y2).
+the case's epilogue, rows [split_row, Cout) into y2): tokgemm_ref.evaluate.
 """
-import numpy as np
-
 import conv_ref as R
+import tokgemm_ref as T
 
 GEOMETRIES = ((3, 200), (5, 72), (9, 8), (1, 200), (3, 52), (3, 50))
 
@@ -85,51 +84,20 @@ assert len(set(IDS)) == len(IDS)
 _CACHE = {}
 
 
-def _second_half(a, split_row, mode2, acc2, r):
-    """The args dict of rows [split_row, Cout) written to a y2 canary buffer: bias only, mask per mask_mode2."""
-    B, rows2, Lout = a["B"], a["Cout"] - split_row, a["Lout"]
-    y2cs = a["y_cs"] + 12
-    buf = np.full((B, rows2 + 3, y2cs), R.SENT, R.F32)
-    if acc2:
-        buf[:, 1:rows2 + 1, 8:8 + Lout] = r.standard_normal((B, rows2, Lout)).astype(R.F32)
-    a2 = dict(a, M=rows2, Cout=rows2, w_off=a["w_off"] + split_row, bias_off=a["bias_off"] + split_row,
-              y=buf.reshape(-1), y_off=y2cs + 8, y_bs=(rows2 + 3) * y2cs, y_cs=y2cs, mask_mode=mode2,
-              accumulate=int(acc2), scale=1.0, post_scale=1.0, act=R.ACT_NONE)
-    for k in ("res", "res_off", "res_bs", "res_cs", "cbias", "cbias_off", "cbias_bs", "cscale", "cscale_off", "cscale_bs"):
-        a2.pop(k, None)
-    return a2
-
-
 def case(id):
-    """-> (a, a2 or None, split, refs): ``a`` the args of the launch (of its first half when split), ``a2`` those of the
-    second half, refs = [(buffer name, float64 reference buffer, written mask), ...].  Computed once, never modified."""
+    """-> (a, a2 or None, split, refs) as tokgemm_ref.evaluate gives them: ``a`` the args of the launch (of its first half
+    when split), ``a2`` those of the second half, refs = [(buffer name, float64 reference buffer, written mask), ...].
+    Computed once, never modified."""
     if id not in _CACHE:
         spec, split = SPECS[IDS.index(id)]
-        full = R.build(spec)
-        if split is None:
-            ref, written = R._evaluate(full)
-            out = (full, None, None, [("y", ref, written)])
-        else:
-            split_row, mode2, acc2 = split
-            a1 = dict(full, M=split_row, Cout=split_row)
-            a2 = _second_half(full, split_row, mode2, acc2, np.random.default_rng(spec["seed"] + 1))
-            r1, w1 = R._evaluate(a1)
-            r2, w2 = R._evaluate(a2)
-            out = (full, a2, split, [("y", r1, w1), ("y2", r2, w2)])
-        for _, ref, written in out[3]:
-            ref.setflags(write=False)
-            written.setflags(write=False)
-        _CACHE[id] = out
+        _CACHE[id] = T.evaluate(R.build(spec), split, spec["seed"])
     return _CACHE[id]
 
 
 def to_struct(id, base, fold):
     """hsp_conv1d_args of a case; ``base`` as conv_ref.to_struct, plus 'y2' for the split form."""
     a, a2, split, _ = case(id)
-    s = R.to_struct(a, base)
-    if split is not None:
-        s.split_row, s.mask_mode2, s.accumulate2 = split[0], split[1], int(split[2])
-        s.y2, s.y2_bs, s.y2_cs = base["y2"] + 4 * a2["y_off"], a2["y_bs"], a2["y_cs"]
+    s = T.to_struct(a, a2, split, base)
     s.fold_cols = int(fold)
     return s
 

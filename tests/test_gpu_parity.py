@@ -586,7 +586,8 @@ def test_abi_rejects_bad_arguments(device):
     (64, 68, 36, 2, "acc"),           # smallest K the kernel takes, accumulate + post_scale
 ])
 def test_token_gemm_vs_torch(cin, cout, N, B, flags, device):
-    """hsp_tokgemm.hip (reached through hsp_conv1d_mfma_f32 for short 1x1 convs) against torch fp32 on CPU."""
+    """The token GEMMs (hsp_rgemm.hip / hsp_bgemm.hip, reached through hsp_conv1d_mfma_f32 for 1x1 convs over token
+    columns) against torch fp32 on CPU."""
     from megatts2_hierspeechpp_amd import _lib as L
     from megatts2_hierspeechpp_amd.hip_layers import Conv1d, finalize
     g = torch.Generator().manual_seed(cin + N)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Token-GEMM shapes (1x1 convs over a column axis) timed by hipGraph replay of 50 back-to-back launches, so that the
 host's launch cost (3-15 us per Python call) is out of the number.  Variants = tuning words (libhsp_tune.so):
-0 = dispatcher default, 131072 = the LDS-DMA token GEMM, 4 / 8 / 16 = register-path GEMM with 64x64 / 64x32 / 32x32 tiles.
+0 = dispatcher default, 8 / 16 = register-path GEMM with 64x32 / 32x32 tiles (the bits: csrc/hsp_token_gemm.h).
     HSP_LIB=megatts2_hierspeechpp_amd/libhsp_tune.so python tools/gemm_bench.py --shapes K:N:M[:res[:B[:ln]]] ..."""
 import argparse
 import os
@@ -15,7 +15,7 @@ from megatts2_hierspeechpp_amd.ttv_v1.transformer_mega import LayerNorm  # noqa:
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", nargs="+", required=True)
-ap.add_argument("--debug", nargs="+", type=int, default=[0, 131072, 4, 8, 16])
+ap.add_argument("--debug", nargs="+", type=int, default=[0, 8, 16])
 ap.add_argument("--reps", type=int, default=50)
 a = ap.parse_args()
 dev = torch.device("cuda:0")

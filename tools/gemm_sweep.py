@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Is the 1x1 / nn.Linear dispatcher (hsp_conv1d_mfma_f32 -> bgemm / rgemm / tokgemm / conv tiles) within a few per cent
+"""Is the 1x1 / nn.Linear dispatcher (hsp_conv1d_mfma_f32 -> bgemm / rgemm / conv tiles) within a few per cent
 of the best kernel at EVERY (B, T), not only at the two workloads its thresholds were fitted to?  
 
     HSP_LIB=megatts2_hierspeechpp_amd/libhsp_tune.so python tools/gemm_sweep.py > profiles/r04_gemm_dispatch_table.txt
@@ -29,8 +29,8 @@ dev = torch.device("cuda:0")
 torch.manual_seed(0)
 NO_BG = 1 << 22
 VARIANTS = [("dispatcher", 0), ("bgemm 64x64", 1 << 23), ("bgemm 128x128", 1 << 18), ("rgemm 64x32", NO_BG | (1 << 24) | 8),
-            ("rgemm 32x32", NO_BG | (1 << 24) | 16), ("tokgemm", NO_BG | (1 << 24) | 131072), ("conv tiles", 128)]
-NAMES = {-2: "bgemm", -1: "rgemm", 0: "tokgemm"}
+            ("rgemm 32x32", NO_BG | (1 << 24) | 16), ("conv tiles", 128)]
+NAMES = {-2: "bgemm", -1: "rgemm"}
 # (label, Cin, Cout, fused LayerNorm, residual, activation, layout)
 SHAPES = [("PLM qkv (LN)", 276, 828, 1, 0, L.ACT_NONE, "cols"), ("PLM out_proj", 276, 276, 0, 1, L.ACT_NONE, "cols"),
           ("PLM ff.0 (LN, ReLU)", 276, 1104, 1, 0, L.ACT_RELU, "cols"), ("PLM ff.3", 1104, 276, 0, 1, L.ACT_NONE, "cols"),
