@@ -693,6 +693,41 @@ int hsp_maxpool1d_f32(const float* x, int64_t x_bs, int64_t x_cs, float* y, int3
  * x [B, D, T] with strides (x_bs, x_cs, 1), embed [bins, D], codes int64 rows of stride c_bs. */
 int hsp_vq_nearest_f32(const float* x, int64_t x_bs, int64_t x_cs, const float* embed, int64_t* codes, int64_t c_bs,
                        int32_t B, int32_t D, int32_t T, int32_t bins, int32_t rep, int32_t Tout, void* stream);
+/* Prosody codes of a mel in ONE launch (additive: HSP_VERSION unchanged; csrc/hsp_prosody.hip): the arithmetic of
+ * SynthesizerTrn.extract_tc_latent_code (ttv_v1/t2w2v_transformer.py:912-929) -- first D mel bins -> PLMConv ->
+ * MaxPool1d(8, 8) -> PLMConv -> nearest code, every code held for 8 frames -- for a ragged batch.
+ *   x        [B, D, T], strides (x_bs, x_cs, 1): the [:, :D] view of a mel, read in place.  T >= 1, any value.
+ *   lengths  device int64 [B], clamped to [0, T]; n below is a row's clamped length.
+ *   w1a b1a w1b b1b  conv1 / conv2 of the first PLMConv, w2a b2a w2b b2b of the second: taps [k][D][w_ld] (the packed
+ *            layout of hsp_conv1d_args.w with M = w_ld >= D), biases [D] or NULL.  k must be 5 (padding 2).
+ *   embed    [bins, D].
+ * Per row:  m(t) = t < n;  h = conv2(conv1(x m) m) m, zero padding outside [0, T);
+ *           p[c, j] = max_{r < 8} h[c, 8 j + r] for j < ceil(T / 8), frames >= T counting as zeros (the row is as if
+ *           zero-padded to a multiple of 8; a window that straddles the row's end takes its maximum over the masked
+ *           zeros too);  mp(j) = j < ceil(n / 8);  q = conv2'(conv1'(p mp) mp) mp;
+ *           code[j] = first maximum over e of -((|q_j|^2 - 2 q_j . embed[e]) + |embed[e]|^2).
+ * Masked values are zeros that the next conv reads, never skipped taps (conv(0) is its bias, hence the mask after
+ * every conv).  Every sum has a fixed order (taps ascending, input channels ascending inside a tap, bias last); the
+ * distance is the device function hsp_vq_nearest_f32 uses, so both choose the same code for the same q.  A row does not
+ * depend on the other rows nor on T beyond its own length.
+ * Outputs (either may be NULL, not both):
+ *   codes   int64 [B, T], row stride c_bs:            codes[b, t] = t < n ? code[t / 8] : 0   (the reference's lr_codes)
+ *   pooled  int64 [B, ceil(T / 8)], row stride p_bs:  pooled[b, j] = j < ceil(n / 8) ? code[j] : 0
+ * HSP_EINVAL before any HIP call: NULL a / x / lengths / embed / any of the four tap pointers, both outputs NULL,
+ * B <= 0 or > 65535, T <= 0, D <= 0 or > 32, bins <= 0 or > 1024, k != 5, w_ld < D. */
+typedef struct {
+  const float* x;
+  int64_t x_bs, x_cs;
+  const int64_t* lengths;
+  int32_t B, D, T, k, w_ld, bins;
+  const float *w1a, *b1a, *w1b, *b1b, *w2a, *b2a, *w2b, *b2b;
+  const float* embed;
+  int64_t* codes;
+  int64_t c_bs;
+  int64_t* pooled;
+  int64_t p_bs;
+} hsp_prosody_args;
+int hsp_prosody_encode_f32(const hsp_prosody_args* a, void* stream);
 /* GaussianUpsampling.forward (ttv_v1/Gaussian.py:35-69) with the range clamp
  * min(range, 2 dur), max(., 1e-5) of ttv_v1/t2w2v_transformer.py:961-963: x [B, C, N] (strides x_bs, x_cs, 1)
  * -> out [B, C, T] contiguous, frames t >= frames[b] zero. */

@@ -132,6 +132,16 @@ class PlmPrefillAttnArgs(C.Structure):
     ]
 
 
+class ProsodyArgs(C.Structure):
+    """Mirror of ``hsp_prosody_args``."""
+    _fields_ = [
+        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64), ("lengths", _fp),
+        ("B", C.c_int32), ("D", C.c_int32), ("T", C.c_int32), ("k", C.c_int32), ("w_ld", C.c_int32), ("bins", C.c_int32),
+        ("w1a", _fp), ("b1a", _fp), ("w1b", _fp), ("b1b", _fp), ("w2a", _fp), ("b2a", _fp), ("w2b", _fp), ("b2b", _fp),
+        ("embed", _fp), ("codes", _fp), ("c_bs", C.c_int64), ("pooled", _fp), ("p_bs", C.c_int64),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -227,6 +237,7 @@ SIGNATURES = {
     "hsp_maxpool1d_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_vq_nearest_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "hsp_prosody_encode_f32": (C.c_int, [C.POINTER(ProsodyArgs), _fp]),
     "hsp_add_cbias_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_zero_below_f32": (C.c_int, [_fp, C.c_float, _fp, C.c_int64, _fp]),
     "hsp_peak_int16": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),

@@ -112,6 +112,24 @@ __device__ __forceinline__ float hsp_snake_hw(float x, float kf, float kb) {
 
 __device__ __forceinline__ int hsp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The nearest-code arithmetic of EuclideanCodebook.quantize (ttv_v1/core_vq.py:175-183), stated once: |x|^2 and
+// dist(x, e) = -((|x|^2 - 2 x.e) + |e|^2) as ascending-d fmaf chains.  x has element stride xs (a [D, T] column in
+// global memory or in LDS), e is one contiguous codebook row.  vq_nearest_kernel (csrc/hsp_frontend.hip) and
+// prosody_encode_kernel (csrc/hsp_prosody.hip) both call these, so the same x gives both the same distances bit for bit.
+__device__ __forceinline__ float hsp_vq_sq(const float* x, int64_t xs, int D) {
+  float xx = 0.0f;
+  for (int d = 0; d < D; ++d) xx = fmaf(x[d * xs], x[d * xs], xx);
+  return xx;
+}
+__device__ __forceinline__ float hsp_vq_dist(const float* x, int64_t xs, float xx, const float* __restrict__ e, int D) {
+  float xe = 0.0f, ee = 0.0f;
+  for (int d = 0; d < D; ++d) {
+    xe = fmaf(x[d * xs], e[d], xe);
+    ee = fmaf(e[d], e[d], ee);
+  }
+  return -((xx - 2.0f * xe) + ee);
+}
+
 // Shared epilogue of both conv kernels for one output element in PLAIN/SHUFFLE row
 // modes (GATE modes combine two accumulators before calling with act = NONE).
 struct hsp_epi_ctx {

@@ -249,18 +249,11 @@ __global__ void vq_nearest_kernel(const float* __restrict__ x, int64_t x_bs, int
   if (i >= B * T) return;
   const int b = i / T, t = i - b * T;
   const float* xp = x + (int64_t)b * x_bs + t;
-  float xx = 0.0f;
-  for (int d = 0; d < D; ++d) xx = fmaf(xp[(int64_t)d * x_cs], xp[(int64_t)d * x_cs], xx);
+  const float xx = hsp_vq_sq(xp, x_cs, D);
   float best = -INFINITY;
   int arg = 0;
   for (int e = 0; e < bins; ++e) {
-    const float* ep = embed + (int64_t)e * D;
-    float xe = 0.0f, ee = 0.0f;
-    for (int d = 0; d < D; ++d) {
-      xe = fmaf(xp[(int64_t)d * x_cs], ep[d], xe);
-      ee = fmaf(ep[d], ep[d], ee);
-    }
-    const float dist = -((xx - 2.0f * xe) + ee);
+    const float dist = hsp_vq_dist(xp, x_cs, xx, embed + (int64_t)e * D, D);
     if (dist > best) { best = dist; arg = e; }
   }
   for (int r = 0; r < rep; ++r)

@@ -113,10 +113,61 @@ def _check_scale_norm(scale_norm: str) -> None:
 
 
 @torch.no_grad()
+def prosody_from_audio(models: TtsModels, mel_fn, audio, sr: int = 16000, lengths=None):
+    """Prosody codes of recorded speech: ``audio`` fp32 [B, n] (or [n]) on the GPU at rate ``sr``, ``lengths`` int64 [B]
+    samples per row (device tensor; None: every row is n samples) -> (codes int64 [B, T], frames int64 [B]).
+    Resampled to 16 kHz when ``sr`` differs (kaiser window, as the prompt ingest), mel by ``mel_fn`` (a finalized
+    Mels_preprocess.MelSpectrogramFixed), then ``SynthesizerTrn.prosody_codes``: every code held for 8 frames, zeros
+    from frames[b] on.  Nothing is read back to the host."""
+    if audio.dim() == 1:
+        audio = audio.unsqueeze(0)
+    if int(sr) != 16000:
+        audio = Fh.resample(audio, sr, 16000, resampling_method="kaiser_window", lengths=lengths)
+        if lengths is not None:
+            lengths = (lengths.to(torch.int64) * 16000 + int(sr) - 1) // int(sr)
+    if lengths is None:
+        mel = mel_fn(audio)
+        frames = torch.full((audio.shape[0],), mel.shape[2], dtype=torch.int64, device=audio.device)
+    else:
+        mel, frames = mel_fn(audio, lengths)
+    return models.ttv.prosody_codes(mel, frames), frames
+
+
+def fit_prosody_codes(codes, src_frames, dst_frames, width: Optional[int] = None):
+    """Stretch or compress held prosody codes to another frame count by centre-aligned nearest index: row b's target
+    frame t < Lt takes its source index ((2 t + 1) Ls) // (2 Lt), Ls = src_frames[b], Lt = dst_frames[b] (the identity
+    when Ls == Lt); entries from Lt on are zero.  codes int64 [B, Ts] (or [Ts]); the frame counts are int tensors [B]
+    (or ints).  -> int64 [B, width]; ``width`` None: max(dst_frames), which reads it back when it is a device tensor."""
+    if codes.dim() == 1:
+        codes = codes.unsqueeze(0)
+    B, dev = codes.shape[0], codes.device
+    as_col = lambda v: torch.as_tensor(v, dtype=torch.int64, device=dev).reshape(-1, 1).expand(B, 1)  # noqa: E731
+    ls, lt = as_col(src_frames), as_col(dst_frames)
+    if width is None:
+        width = int(lt.max().item())
+    t = torch.arange(width, dtype=torch.int64, device=dev).unsqueeze(0)
+    idx = torch.div((2 * t + 1) * ls, 2 * lt.clamp(min=1), rounding_mode="floor").clamp(max=codes.shape[1] - 1)
+    return torch.where(t < lt, torch.gather(codes, 1, idx), torch.zeros_like(idx))
+
+
+def _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal, takes: int = 1) -> None:
+    """``prosody_codes`` replaces the prosody LM: everything that steers the LM is refused next to it."""
+    if prosody_codes is None:
+        if prosody_lengths is not None:
+            raise L.HspError("prosody_lengths without prosody_codes")
+        return
+    for name, given in (("plm_sampling", plm_sampling is not None), ("plm_prefix", plm_prefix is not None),
+                        ("plm_causal", bool(plm_causal)), ("takes > 1", takes > 1)):
+        if given:
+            raise L.HspError(f"prosody_codes and {name} exclude each other: given codes skip the prosody LM")
+
+
+@torch.no_grad()
 def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
-        target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False):
+        target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
+        prosody_codes=None, prosody_lengths=None):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
     make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.  ``plm_causal``: the
     prosody LM decodes under the causal mask it is trained with, through a K/V cache (``infer(causal=True)``: other
@@ -125,6 +176,10 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     rest is decoded (``infer(prefix_codes=)``) -- durations do not depend on the codes, so the kept beginning of an
     earlier take of the same text and prompt fits frame for frame.  ``return_codes``: the PLM codes int64 [B, T] are
     appended to the result (the codes a later ``plm_prefix`` is cut from).
+    ``prosody_codes`` (int64 [B, Ts], e.g. from `prosody_from_audio`; ``prosody_lengths`` [B] their frame counts, None:
+    all Ts): the prosody LM is skipped and the given codes, fitted per row to that row's frame count
+    (`fit_prosody_codes`), are used instead -- excludes ``plm_sampling``, ``plm_prefix`` and ``plm_causal``;
+    ``return_codes`` then returns the fitted codes.
     ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
     peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
     length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
@@ -139,10 +194,18 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     _check_scale_norm(scale_norm)
     if plm_prefix is not None and not plm_causal:
         raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
+    _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
-    codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal, prefix_codes=plm_prefix)
+    if prosody_codes is None:
+        codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal, prefix_codes=plm_prefix)
+    else:
+        if prosody_codes.dim() != 2 or prosody_codes.shape[0] != B:
+            raise L.HspError(f"prosody_codes must be int64 [B = {B}, Ts], got {tuple(prosody_codes.shape)}")
+        src = prosody_codes.shape[1] if prosody_lengths is None else prosody_lengths
+        codes = fit_prosody_codes(prosody_codes.to(x_frame.device), src, torch.ceil(x_lengths).to(torch.int64),
+                                  width=x_frame.shape[2])
     out = tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
                          denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
                          gain=gain, scale_norm=scale_norm, target_lufs=target_lufs)
@@ -211,7 +274,7 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
                     takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
-                    return_codes: bool = False):
+                    return_codes: bool = False, prosody_codes=None, prosody_lengths=None):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -230,10 +293,15 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     ``noise`` with one row is used by every take; None: every take draws its own.
     ``plm_prefix`` (int64 [P] or [1, P], needs ``plm_causal``): the first P prosody codes are given (see `tts`); with
     ``takes`` = N the one prefix is shared by all N takes: N different endings of one beginning.  ``return_codes``
-    appends the PLM codes (int64 [T], or [N, T] with takes) to the result."""
+    appends the PLM codes (int64 [T], or [N, T] with takes) to the result.
+    ``prosody_codes`` (int64 [Ts] or [1, Ts]; ``prosody_lengths`` their frame count, None: Ts): given prosody codes
+    instead of the prosody LM (see `tts`); excludes ``plm_sampling``, ``plm_prefix``, ``plm_causal`` and ``takes`` > 1."""
     takes = int(takes)
     if takes < 1:
         raise L.HspError(f"takes must be >= 1, got {takes}")
+    _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal, takes)
+    if prosody_codes is not None:
+        prosody_codes = prosody_codes.reshape(1, -1)
     if takes > 1 and plm_sampling is None:
         raise L.HspError("takes > 1 needs plm_sampling: greedy decoding gives the same take every time")
     if plm_prefix is not None:
@@ -265,7 +333,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                             noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
                             noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
                             seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
-                            target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True)
+                            target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True,
+                            prosody_codes=prosody_codes, prosody_lengths=prosody_lengths)
     rate = output_sr if output_sr in (24000, 48000) else 16000
     if B == 1:
         wav, codes = wav[0], codes[0]
@@ -284,12 +353,14 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
 
 def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
                          plm_sampling=None, seed: int = 0, takes: int = 1, plm_causal: bool = False, plm_prefix=None,
-                         return_codes: bool = False, **kwargs):
+                         return_codes: bool = False, prosody_codes=None, prosody_lengths=None, **kwargs):
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
-    ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` and ``kwargs`` go to `tts_from_prompt`."""
+    ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` / ``prosody_codes`` / ``prosody_lengths`` and
+    ``kwargs`` go to `tts_from_prompt`."""
     from . import audio as A
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
-                           plm_prefix=plm_prefix, return_codes=return_codes, **kwargs)
+                           plm_prefix=plm_prefix, return_codes=return_codes, prosody_codes=prosody_codes,
+                           prosody_lengths=prosody_lengths, **kwargs)

@@ -793,18 +793,13 @@ class SynthesizerTrn(nn.Module):
         self.arena = _finalize(self, device, materialize)
         return self
 
-    @_entry
-    @torch.no_grad()
-    def inf_extract_tc_latent(self, x, x_lengths, y_mel, y_length, tone, language, mrte_mel=None, mrte_mel_lengths=None,
-                              length_scale=1, dur=None):
-        """(:937-982) ids/tone/language int64 [B, N], x_lengths [B], y_mel [B, 80, Tm], y_length [B] ->
-        x_frame [B, 256, T2], g [B, 256, 1], x_lengths (float, frames / 2) [B], x_mask BOOL [B, 1, T2] (the
-        reference's dtypes, :979-982; ``inf_plm_gen`` takes that mask or a float one).
-        ``dur`` [B, N] (optional) overrides the predicted durations (BASELINE config 3 pins them)."""
+    def _tc_latent(self, x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur):
+        """The text -> frame-rate front part shared by ``inf_extract_tc_latent`` and ``extract_tc_latent_code``: style and
+        MRTE from ``ref_mel``, predicted or given durations, range clamp, Gaussian upsampling, ``dur_downsample``.
+        -> x_frame [B, 256, T2], g [B, 256, 1], frame_lengths (float, host) [B], mask2 float [B, 1, T2]."""
         B, N = x.shape
         C = self.inter_channels
         x_lengths = x_lengths.to(torch.int64)
-        ref_mel, ref_len = (mrte_mel, mrte_mel_lengths) if mrte_mel is not None else (y_mel, y_length)
         g = self.emb_g(ref_mel, Fh.sequence_mask(ref_len, ref_mel.shape[2]), per_utterance=True).unsqueeze(-1)
         h, x_mask = self.enc_p(x, x_lengths, g, tone, language)
         mel_out, h_mask = self.mel_encoder(ref_mel, ref_len)
@@ -831,6 +826,18 @@ class SynthesizerTrn(nn.Module):
         len2 = torch.ceil(frame_lengths).to(torch.int64).to(x.device)
         mask2 = Fh.sequence_mask(len2, T2)
         x_frame = self.dur_downsample(x_frame[:, :, ::2], mask=mask2, mask_mode=L.MASK_POST)
+        return x_frame, g, frame_lengths, mask2
+
+    @_entry
+    @torch.no_grad()
+    def inf_extract_tc_latent(self, x, x_lengths, y_mel, y_length, tone, language, mrte_mel=None, mrte_mel_lengths=None,
+                              length_scale=1, dur=None):
+        """(:937-982) ids/tone/language int64 [B, N], x_lengths [B], y_mel [B, 80, Tm], y_length [B] ->
+        x_frame [B, 256, T2], g [B, 256, 1], x_lengths (float, frames / 2) [B], x_mask BOOL [B, 1, T2] (the
+        reference's dtypes, :979-982; ``inf_plm_gen`` takes that mask or a float one).
+        ``dur`` [B, N] (optional) overrides the predicted durations (BASELINE config 3 pins them)."""
+        ref_mel, ref_len = (mrte_mel, mrte_mel_lengths) if mrte_mel is not None else (y_mel, y_length)
+        x_frame, g, frame_lengths, mask2 = self._tc_latent(x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur)
         return x_frame, g, frame_lengths.to(x.device), mask2.to(torch.bool)   # a dtype cast, as the reference's (:982)
 
     @_entry
@@ -850,6 +857,50 @@ class SynthesizerTrn(nn.Module):
         lf0 = self.pp(w2v_pred, g, lengths=len2)
         mask4 = Fh.sequence_mask(4 * len2, 4 * T2)
         return w2v_pred, Fh.mask_mul(lf0, mask4).squeeze(1)
+
+    @_entry
+    @torch.no_grad()
+    def prosody_codes(self, mel, mel_lengths, pooled=False):
+        """Prosody codes of recorded speech (:912-929): mel [B, 80, T] fp32 (any T >= 1), mel_lengths [B] -> int64 [B, T],
+        every code held for 8 frames and zeros from a row's length on (the reference's ``lr_codes``), or with ``pooled``
+        int64 [B, ceil(T / 8)], one code per pooled frame.  One launch (hsp_prosody_encode_f32: first 20 bins ->
+        PLMConv -> max-pool 8 -> PLMConv -> nearest code), nothing read back; rows are independent utterances and a row
+        equals that row run alone.  A mel whose length is no multiple of 8 counts as zero-padded to the next one."""
+        D, cb = self.quantizer.dimension, self.quantizer.vq.layers[0]._codebook
+        if mel.dim() != 3 or mel.shape[1] < D or mel.shape[2] < 1:
+            raise L.HspError(f"prosody_codes(): mel must be [B, >= {D}, T >= 1], got {tuple(mel.shape)}")
+        B, _, T = mel.shape
+        if mel_lengths.shape != (B,):
+            raise L.HspError(f"prosody_codes(): mel_lengths must be [{B}], got {tuple(mel_lengths.shape)}")
+        if mel.stride(2) != 1:
+            mel = mel.contiguous()
+        lens = mel_lengths.to(device=mel.device, dtype=torch.int64).contiguous()
+        out = torch.empty(B, -(-T // self.stride) if pooled else T, dtype=torch.int64, device=mel.device)
+        convs = (self.plm_conv1.conv1, self.plm_conv1.conv2, self.plm_conv2.conv1, self.plm_conv2.conv2)
+        a = L.ProsodyArgs()
+        a.x, a.x_bs, a.x_cs, a.lengths = L.fptr(mel), mel.stride(0), mel.stride(1), L.ptr(lens)
+        a.B, a.D, a.T, a.k, a.w_ld, a.bins = B, D, T, convs[0].k, convs[0].M, self.quantizer.bins
+        for name, c in zip(("1a", "1b", "2a", "2b"), convs):
+            setattr(a, "w" + name, L.fptr(c._w))
+            setattr(a, "b" + name, L.fptr(c._b))
+        a.embed = L.fptr(cb._w)
+        if pooled:
+            a.pooled, a.p_bs = L.ptr(out), out.stride(0)
+        else:
+            a.codes, a.c_bs = L.ptr(out), out.stride(0)
+        L.check(L.lib().hsp_prosody_encode_f32(ctypes.byref(a), L.stream_ptr()), "hsp_prosody_encode_f32")
+        return out
+
+    @_entry
+    @torch.no_grad()
+    def extract_tc_latent_code(self, x, x_lengths, mel_spk, mel_spk_lengths, tone, language, dur, mrte_mel, mrte_mel_lengths):
+        """(:887-930) how the prosody LM's training pairs are made: -> (x_frame [B, 256, T2], lr_codes int64 [B, Tm]).
+        ``x_frame`` is the text-derived track at the GIVEN durations ``dur`` [B, N], style and MRTE from ``mrte_mel`` (what
+        ``inf_extract_tc_latent(..., dur=dur, mrte_mel=mrte_mel)`` returns); ``lr_codes`` are the prosody codes of
+        ``mel_spk`` (``prosody_codes``).  Aligning a recording to its text is the caller's: ``dur`` is an input, as in the
+        reference.  For B > 1 rows are independent utterances."""
+        x_frame = self._tc_latent(x, x_lengths, mrte_mel, mrte_mel_lengths, tone, language, 1, dur)[0]
+        return x_frame, self.prosody_codes(mel_spk, mel_spk_lengths)
 
     @_entry
     @torch.no_grad()
@@ -903,18 +954,7 @@ class SynthesizerTrn(nn.Module):
         x_frame = self.gaussian(xs, dcol, rng, x_lengths, frames, T)
         x_frame = self.dur_downsample(x_frame[:, :, ::2])
         # prosody codes of the prompt
-        q_in = self.plm_conv1(mel_spk[:, :20], mel_mask)
-        pooled = torch.empty(B, 20, Tm // self.stride, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_maxpool1d_f32(L.fptr(q_in), q_in.stride(0), q_in.stride(1), L.fptr(pooled), B, 20, Tm, self.stride,
-                                          L.stream_ptr()), "hsp_maxpool1d_f32")
-        pool_len = torch.div(mel_spk_lengths.to(torch.int64) + self.stride - 1, self.stride, rounding_mode="floor")
-        pool_mask = Fh.sequence_mask(pool_len, Tm // self.stride)   # t < len / 8 (float compare) == t < ceil(len / 8)
-        q_in = self.plm_conv2(pooled, pool_mask)
-        codes = torch.empty(B, Tm, dtype=torch.int64, device=x.device)
-        cb = self.quantizer.vq.layers[0]._codebook
-        L.check(L.lib().hsp_vq_nearest_f32(L.fptr(q_in), q_in.stride(0), q_in.stride(1), L.fptr(cb._w), L.ptr(codes),
-                                           codes.stride(0), B, 20, Tm // self.stride, self.quantizer.bins, self.stride, Tm,
-                                           L.stream_ptr()), "hsp_vq_nearest_f32")
+        codes = self.prosody_codes(mel_spk, mel_spk_lengths)
         q = self.quantizer.decode(codes)
         # x_frame + ssl_proj(q * mel_mask) * mel_mask [+ w2v_encoder.cond(g), fused]
         xq = self.ssl_proj(Fh.mask_mul(q, mel_mask), mask=mel_mask, mask_mode=L.MASK_PRE, res=x_frame,
