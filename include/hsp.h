@@ -229,8 +229,10 @@ int hsp_reflect_pad_f32(const float* x, int64_t x_bs, float* y, int32_t B, int32
  * elsewhere.  One utterance per call (the statistics are per utterance): f0_src [n_src], f0_trg [n_trg]. */
 int hsp_f0_convert_f32(const float* f0_src, int32_t n_src, const float* f0_trg, int32_t n_trg, float* out, void* stream);
 
-/* ------------------------------------------------ batched voice conversion (inference_vc.vc_batch; csrc/hsp_vcbatch.hip)
- * Per-row-length forms of the single-utterance steps above and below.  Row lengths are device int64 [B] (values are
+/* ------------------------------------------------ batched voice conversion (inference_vc.vc_batch; csrc/hsp_vcbatch.hip, and
+ * the ragged forms next to their plain ones in csrc/hsp_pointwise.hip and csrc/hsp_mel.hip)
+ * Per-row-length forms of the single-utterance steps above and below.  A plain entry point launches the kernel of its
+ * ragged form with NULL lengths, so a row of full length is bit-equal through both.  Row lengths are device int64 [B] (values are
  * clamped into [0, the buffer's capacity]), so a fixed-shape batch is capturable with no host read-back.
  * hsp_reflect_pad_ragged_f32: y[b, t] = x[b, reflect(t - pad)] over t < len_b + 2 pad with the reflection at row b's
  *   own end len_b (F.pad(x[b, :len_b], (pad, pad), "reflect")), y[b, t] = 0 on [len_b + 2 pad, Lo).  x rows of stride
@@ -291,7 +293,8 @@ int hsp_polar_f32(const float* mag, const float* pha, float power, float* re, in
 int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* scale, float* inv, int32_t B,
                              int64_t L, void* stream);
 /* hsp_stft_frames_ragged_f32 into ONE frame matrix [n_fft, f_ld]: row b's T_b = 1 + len_b / hop frames, reflected at
- * len_b and multiplied by scale[b] (NULL = no scaling; bit-equal to hsp_stft_frames_f32 on the row then), at columns
+ * len_b and multiplied by scale[b] (NULL = no scaling; bit-equal to hsp_stft_frames_f32 on the row then: the three
+ * framing entry points compute a column with one device function, csrc/hsp_mel.hip), at columns
  * [first_b, first_b + T_b); every other column, gaps included, is written as 0.  x rows of stride x_bs >= L. */
 int hsp_stft_frames_packed_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* scale,
                                const float* window, float* frames, const int32_t* seg, const int32_t* seg_host, int32_t B,

@@ -97,22 +97,18 @@ class MelSpectrogramFixed(nn.Module):
         T = 1 + Ls // self.hop_length
         f_ld = (T + 3) & ~3
         frames = torch.empty(B, self.n_fft, f_ld, dtype=torch.float32, device=xs.device)  # pitch columns zeroed by the kernel
-        if lengths is None:
-            L.check(L.lib().hsp_stft_frames_f32(L.fptr(xs), L.fptr(self._window), L.fptr(frames), B, Ls, self.n_fft,
-                                                self.hop_length, T, f_ld, L.stream_ptr()), "hsp_stft_frames_f32")
-        else:
+        rows, name = (L.fptr(xs),), "hsp_stft_frames_f32"
+        if lengths is not None:
             if x.dim() != 2 or lengths.shape != (B,):
                 raise L.HspError("MelSpectrogramFixed: lengths need x [B, L] and lengths [B]")
             lengths = lengths.to(torch.int64).contiguous()
-            L.check(L.lib().hsp_stft_frames_ragged_f32(L.fptr(xs), xs.stride(0), L.ptr(lengths), L.fptr(self._window),
-                                                       L.fptr(frames), B, Ls, self.n_fft, self.hop_length, T, f_ld,
-                                                       L.stream_ptr()), "hsp_stft_frames_ragged_f32")
+            rows, name = (L.fptr(xs), xs.stride(0), L.ptr(lengths)), "hsp_stft_frames_ragged_f32"
+        L.call(name, *rows, L.fptr(self._window), L.fptr(frames), B, Ls, self.n_fft, self.hop_length, T, f_ld)
         spec = self.dft(frames)                                   # [B, 2 n_freqs, f_ld]: real | imaginary rows
         T_out = T - 1                                             # the wrapper drops the last frame
         out = torch.empty(B, self.n_mels, max(T_out, 0), dtype=torch.float32, device=xs.device)
         if T_out > 0:
-            L.check(L.lib().hsp_power_mel_log_f32(L.fptr(spec), spec.stride(0), spec.stride(1), L.fptr(self._fb),
-                                                  L.ptr(self._lo), L.ptr(self._hi), L.fptr(out), B, self.n_freqs,
-                                                  self.n_mels, T_out, 0.001, L.stream_ptr()), "hsp_power_mel_log_f32")
+            L.call("hsp_power_mel_log_f32", L.fptr(spec), spec.stride(0), spec.stride(1), L.fptr(self._fb),
+                   L.ptr(self._lo), L.ptr(self._hi), L.fptr(out), B, self.n_freqs, self.n_mels, T_out, 0.001)
         out = out.reshape(*lead, self.n_mels, max(T_out, 0))
         return out if lengths is None else (out, lengths // self.hop_length)

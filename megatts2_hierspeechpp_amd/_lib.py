@@ -291,6 +291,29 @@ def check(code: int, what: str) -> None:
         raise HspError(f"{what} failed: {kind}")
 
 
+def call(name: str, *args) -> None:
+    """One launch on the current stream: ``lib().<name>(*args, stream_ptr())``, its status checked under that name."""
+    check(getattr(lib(), name)(*args, stream_ptr()), name)
+
+
+def timed(hook, kind: str, launch, soft: bool = False):
+    """The event bracket of a measured launch: ``launch()`` performs the C call and returns its status, checked under
+    ``kind``; when ``hook`` (the caller's measurement hook, or None) is set it runs between two timing events on the
+    current stream.  Without a hook no event is created.  ``soft``: a launch the library refuses with HSP_EINVAL is not
+    an error and has no events.  Returns (status, ev_start, ev_end); the caller reports them to its hook."""
+    e0 = e1 = None
+    if hook is not None:
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+    rc = launch()
+    if soft and rc == EINVAL:
+        return rc, None, None
+    check(rc, kind)
+    if hook is not None:
+        e1.record()
+    return 0, e0, e1
+
+
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     """Device pointer of an fp32 (or int) ROCm tensor; None passes through as NULL."""
     if t is None:

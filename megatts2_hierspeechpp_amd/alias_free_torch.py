@@ -52,9 +52,8 @@ class Activation1d(HipLayer):
     def hsp_fill(self, arena, materialize):
         self._ea, self._binv, self._filt = arena.view(self, "ea"), arena.view(self, "binv"), arena.view(self, "filt")
         if materialize:
-            L.check(L.lib().hsp_snake_consts_f32(L.fptr(self.act.alpha.data), L.fptr(self.act.beta.data),
-                                                 L.fptr(self._ea), L.fptr(self._binv), self.channels, L.stream_ptr()),
-                    "hsp_snake_consts_f32")
+            L.call("hsp_snake_consts_f32", L.fptr(self.act.alpha.data), L.fptr(self.act.beta.data), L.fptr(self._ea),
+                   L.fptr(self._binv), self.channels)
             self._filt[:12].copy_(self.upsample.filter.reshape(12))
             self._filt[12:].copy_(self.downsample.lowpass.filter.reshape(12))
 

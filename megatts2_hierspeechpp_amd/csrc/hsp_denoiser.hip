@@ -3,19 +3,9 @@
 // denoiser/generator.py and conformer.py.  Everything here is pointwise or a small reduction over a prompt of a few
 // seconds (a [64, T, 201] tensor is 40 MB at 5 s): latency, not throughput.  Reference call sites are listed next
 // to each entry point in include/hsp.h.
-#include "hsp_device.h"
+#include "hsp_rows.h"
 
 namespace {
-
-// one thread per element, no grid-stride loop in these kernels: the grid covers every element (the x dimension
-// of a grid holds 2^31 - 1 blocks) or the launcher refuses (dn_fits)
-constexpr int64_t DN_MAX_BLOCKS = 0x7fffffff;
-inline unsigned dn_grid(int64_t n, int threads) {
-  int64_t b = (n + threads - 1) / threads;
-  if (b < 1) b = 1;
-  return (unsigned)(b > DN_MAX_BLOCKS ? DN_MAX_BLOCKS : b);
-}
-inline bool dn_fits(int64_t n, int threads) { return (n + threads - 1) / threads <= DN_MAX_BLOCKS; }
 
 // block-wide sum of a double (1024 threads at most); every thread receives the total
 __device__ __forceinline__ double dn_block_sum(double v, double* sh) {
@@ -72,26 +62,7 @@ __global__ __launch_bounds__(256) void polar_kernel(const float* __restrict__ ma
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The T-crossing operations read their bounds from a segment table: B utterances laid end to end along
-// T with zero gap rows between them; one prompt is the table with one row.  seg = device int32 [B][2] = (first row,
-// T_b), ascending and disjoint (the launchers check the host copy).  B is a handful of prompts: the table is scanned
-// linearly, with addresses every lane shares.
-__device__ __forceinline__ int dn_seg_of(const int32_t* __restrict__ seg, int B, int t, int& t0, int& Tb) {
-  for (int b = 0; b < B; ++b) {
-    const int s = seg[2 * b], n = seg[2 * b + 1];
-    if (t < s) break;
-    if (t < s + n) {
-      t0 = s;
-      Tb = n;
-      return b;
-    }
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int64_t dn_clamp_len(const int64_t* len, int b, int64_t cap) {
-  return min(cap, max((int64_t)0, len[b]));
-}
+// The T-crossing operations read their bounds from a segment table (dn_seg_of, hsp_rows.h).
 
 // per row: ss = sum x^2 (double accumulation, rounded to fp32), then scale = sqrt(len / ss) and 1 / scale formed in
 // double and rounded once; a silent (or empty) row gets 0 for both
@@ -100,7 +71,7 @@ __global__ __launch_bounds__(1024) void norm_factor_rows_kernel(const float* __r
                                                                 float* __restrict__ inv, int64_t L) {
   __shared__ double sh[16];
   const int b = blockIdx.x;
-  const int64_t n = dn_clamp_len(lengths, b, L);
+  const int64_t n = hsp_row_len(lengths, b, L);
   const float* p = x + (int64_t)b * x_bs;
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += (double)p[i] * (double)p[i];
@@ -111,40 +82,6 @@ __global__ __launch_bounds__(1024) void norm_factor_rows_kernel(const float* __r
     const double norm = ok ? sqrt((double)n / (double)ss) : 0.0;
     scale[b] = (float)norm;
     inv[b] = ok ? (float)(1.0 / norm) : 0.0f;
-  }
-}
-
-// stft_frames_ragged_kernel of hsp_vcbatch.hip writing row b's frames at columns [t0_b, t0_b + T_b) of ONE
-// [n_fft, f_ld] matrix (times scale[b] when given: the norm factor folded into the framing); every other column 0
-__global__ __launch_bounds__(256) void stft_frames_packed_kernel(const float* __restrict__ x, int64_t x_bs,
-                                                                 const int64_t* __restrict__ lengths,
-                                                                 const float* __restrict__ scale, const float* __restrict__ w,
-                                                                 float* __restrict__ frames, const int32_t* __restrict__ seg,
-                                                                 int B, int64_t L, int n_fft, int hop, int f_ld) {
-  const int t = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int n0 = blockIdx.y * 256 + (threadIdx.x >> 6) * 64;
-  if (t >= f_ld) return;
-  int t0 = 0, Tb = 0;
-  const int b = dn_seg_of(seg, B, t, t0, Tb);
-  int64_t Lb = 0;
-  const float* xb = x;
-  float sc = 1.0f;
-  if (b >= 0) {
-    Lb = dn_clamp_len(lengths, b, L);
-    xb = x + (int64_t)b * x_bs;
-    if (scale) sc = scale[b];
-  }
-  const int64_t base = (int64_t)(t - t0) * hop - (n_fft >> 1);
-  for (int n = n0; n < min(n0 + 64, n_fft); ++n) {
-    float v = 0.0f;
-    if (b >= 0 && Lb > 0) {
-      int64_t i = base + n;
-      i = i < 0 ? -i : i;
-      i = i >= Lb ? 2 * (Lb - 1) - i : i;
-      i = min(max(i, (int64_t)0), Lb - 1);    // only for Lb <= n_fft / 2 or T_b > 1 + Lb / hop (outside the contract)
-      v = scale ? w[n] * (xb[i] * sc) : w[n] * xb[i];
-    }
-    frames[(int64_t)n * f_ld + t] = v;
   }
 }
 
@@ -262,8 +199,8 @@ __global__ __launch_bounds__(256) void istft_ola_seg_kernel(const float* __restr
 
 }  // namespace
 
-// the host copy of a segment table: B >= 1 segments (first row >= 0, T_b >= 1), ascending, disjoint, inside T_tot
-static bool dn_seg_ok(const int32_t* seg, const int32_t* seg_host, int32_t B, int64_t T_tot) {
+// declared in hsp_rows.h (hsp_stft_frames_packed_f32 of hsp_mel.hip checks its table with it too)
+bool dn_seg_ok(const int32_t* seg, const int32_t* seg_host, int32_t B, int64_t T_tot) {
   if (!seg || !seg_host || B < 1 || B > 65535 || T_tot < 1) return false;
   int64_t end = 0;
   for (int b = 0; b < B; ++b) {
@@ -280,8 +217,8 @@ extern "C" int hsp_mag_pha_f32(const float* spec, int64_t s_ld, float* mag, floa
                                float compress, void* stream) {
   if (!spec || !mag || !pha || n_freqs < 2 || T <= 0 || s_ld < T) return HSP_EINVAL;
   const int64_t total = (int64_t)n_freqs * T;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(mag_pha_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, spec, s_ld, mag, pha, n_freqs, T,
+  if (!hsp_grid_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(mag_pha_kernel, dim3(hsp_flat_grid(total, 256)), dim3(256), 0, HSP_STREAM, spec, s_ld, mag, pha, n_freqs, T,
                      compress);
   return (int)hipGetLastError();
 }
@@ -290,15 +227,15 @@ extern "C" int hsp_lsigmoid_mul_f32(const float* m, const float* slope, float be
                                     int32_t F, void* stream) {
   if (!m || !slope || !mag || !out || T <= 0 || F <= 0) return HSP_EINVAL;
   const int64_t total = (int64_t)T * F;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(lsigmoid_mul_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, m, slope, beta, mag, out, F, total);
+  if (!hsp_grid_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(lsigmoid_mul_kernel, dim3(hsp_flat_grid(total, 256)), dim3(256), 0, HSP_STREAM, m, slope, beta, mag, out, F, total);
   return (int)hipGetLastError();
 }
 
 extern "C" int hsp_atan2_f32(const float* y, const float* x, float* out, int64_t n, void* stream) {
   if (!y || !x || !out || n <= 0) return HSP_EINVAL;
-  if (!dn_fits(n, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(atan2_kernel, dim3(dn_grid(n, 256)), dim3(256), 0, HSP_STREAM, y, x, out, n);
+  if (!hsp_grid_fits(n, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(atan2_kernel, dim3(hsp_flat_grid(n, 256)), dim3(256), 0, HSP_STREAM, y, x, out, n);
   return (int)hipGetLastError();
 }
 
@@ -306,8 +243,8 @@ extern "C" int hsp_polar_f32(const float* mag, const float* pha, float power, fl
                              int64_t im_ld, int32_t F, int32_t T, void* stream) {
   if (!mag || !pha || !re || !im || F <= 0 || T <= 0 || re_ld < T || im_ld < T) return HSP_EINVAL;
   const int64_t total = (int64_t)F * T;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(polar_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, mag, pha, power, re, re_ld, im, im_ld, T,
+  if (!hsp_grid_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(polar_kernel, dim3(hsp_flat_grid(total, 256)), dim3(256), 0, HSP_STREAM, mag, pha, power, re, re_ld, im, im_ld, T,
                      total);
   return (int)hipGetLastError();
 }
@@ -316,20 +253,6 @@ extern "C" int hsp_norm_factor_rows_f32(const float* x, int64_t x_bs, const int6
                                         int32_t B, int64_t L, void* stream) {
   if (!x || !lengths || !scale || !inv || B < 1 || L <= 0 || x_bs < L) return HSP_EINVAL;
   hipLaunchKernelGGL(norm_factor_rows_kernel, dim3((unsigned)B), dim3(1024), 0, HSP_STREAM, x, x_bs, lengths, scale, inv, L);
-  return (int)hipGetLastError();
-}
-
-extern "C" int hsp_stft_frames_packed_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* scale,
-                                          const float* window, float* frames, const int32_t* seg, const int32_t* seg_host,
-                                          int32_t B, int64_t L, int32_t n_fft, int32_t hop, int32_t T_tot, int32_t f_ld,
-                                          void* stream) {
-  if (!x || !lengths || !window || !frames || n_fft <= 0 || hop <= 0 || f_ld < T_tot || x_bs < L) return HSP_EINVAL;
-  if (L <= n_fft / 2 || (n_fft + 255) / 256 > 65535) return HSP_EINVAL;
-  if (!dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
-  for (int b = 0; b < B; ++b)                                  // no row holds more frames than the longest can: 1 + L / hop
-    if (seg_host[2 * b + 1] > 1 + L / hop) return HSP_EINVAL;
-  hipLaunchKernelGGL(stft_frames_packed_kernel, dim3((f_ld + 63) / 64, (n_fft + 255) / 256), dim3(256), 0, HSP_STREAM, x,
-                     x_bs, lengths, scale, window, frames, seg, B, L, n_fft, hop, f_ld);
   return (int)hipGetLastError();
 }
 
@@ -348,8 +271,8 @@ extern "C" int hsp_zero_gaps_f32(float* x, int64_t x_cs, int32_t C, int32_t T_to
   if (!x || C <= 0 || F <= 0 || T_tot <= 0) return HSP_EINVAL;
   if (x_cs < (int64_t)T_tot * F || !dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
   const int64_t total = (int64_t)C * T_tot * F;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(zero_gaps_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, x_cs, T_tot, F, seg, B, total);
+  if (!hsp_grid_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(zero_gaps_kernel, dim3(hsp_flat_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, x_cs, T_tot, F, seg, B, total);
   return (int)hipGetLastError();
 }
 
@@ -360,8 +283,8 @@ extern "C" int hsp_dwconv_bn_silu_seg_f32(const float* x, const float* w, const 
   if (!x || !w || !bias || !bn_weight || !bn_bias || !bn_mean || !bn_var || !y) return HSP_EINVAL;
   if (A <= 0 || C <= 0 || N <= 0 || K <= 0 || (K & 1) == 0 || !dn_seg_ok(seg, seg_host, B, N)) return HSP_EINVAL;
   const int64_t total = (int64_t)A * C * N;
-  if (!dn_fits(total, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(dwconv_bn_silu_seg_kernel, dim3(dn_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, w, bias, bn_weight,
+  if (!hsp_grid_fits(total, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(dwconv_bn_silu_seg_kernel, dim3(hsp_flat_grid(total, 256)), dim3(256), 0, HSP_STREAM, x, w, bias, bn_weight,
                      bn_bias, bn_mean, bn_var, bn_eps, y, C, N, K, seg, B, total);
   return (int)hipGetLastError();
 }
@@ -373,8 +296,8 @@ extern "C" int hsp_istft_ola_seg_f32(const float* frames, int64_t f_ld, const fl
   if (n_max < 1 || out_bs < n_max || f_ld < T_tot || !dn_seg_ok(seg, seg_host, B, T_tot)) return HSP_EINVAL;
   for (int b = 0; b < B; ++b)
     if ((int64_t)hop * (seg_host[2 * b + 1] - 1) > n_max) return HSP_EINVAL;
-  if (!dn_fits(n_max, 256)) return HSP_EINVAL;
-  hipLaunchKernelGGL(istft_ola_seg_kernel, dim3(dn_grid(n_max, 256), (unsigned)B), dim3(256), 0, HSP_STREAM, frames, f_ld,
+  if (!hsp_grid_fits(n_max, 256)) return HSP_EINVAL;
+  hipLaunchKernelGGL(istft_ola_seg_kernel, dim3(hsp_flat_grid(n_max, 256), (unsigned)B), dim3(256), 0, HSP_STREAM, frames, f_ld,
                      window, inv, out, out_bs, n_max, n_fft, hop, seg);
   return (int)hipGetLastError();
 }

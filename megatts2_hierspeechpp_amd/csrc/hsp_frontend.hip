@@ -2,7 +2,7 @@
 // embedding sums, the bidirectional LSTM recurrence of the duration / range predictors, the
 // duration rounding and the Gaussian upsampling.  Everything is per utterance: a batch is B
 // independent sequences with their own lengths (the reference runs B = 1).
-#include "hsp_device.h"
+#include "hsp_rows.h"
 
 namespace {
 
@@ -219,8 +219,7 @@ __global__ __launch_bounds__(1024) void peak_int16_kernel(const float* __restric
                                                           const int64_t* __restrict__ len, float gain,
                                                           int16_t* __restrict__ out, int64_t o_bs, int64_t n) {
   const int b = blockIdx.x;
-  const int64_t L = len ? min(n, max((int64_t)0, len[b])) : n;
-  hsp_peak_int16_row(x + b * x_bs, L, gain, out + b * o_bs, n);
+  hsp_peak_int16_row(x + b * x_bs, hsp_row_len(len, b, n), gain, out + b * o_bs, n);
 }
 
 

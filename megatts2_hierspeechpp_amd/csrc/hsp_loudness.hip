@@ -12,7 +12,7 @@
 // All sums are taken in a fixed order (no atomics).  The recurrence, the carry and every sum run in fp64: the
 // high-pass poles sit at radius ~0.995 (48 kHz), where an fp32 direct form loses the low end of the state first, and
 // the scan is bound by the latency of its dependent chain, not by fp64 throughput.
-#include "hsp_device.h"
+#include "hsp_rows.h"
 
 #include <math.h>
 
@@ -39,10 +39,6 @@ __host__ __device__ __forceinline__ double kw_step(const kw_coef& k, double x, d
   return y2;
 }
 
-__device__ __forceinline__ int64_t clamp_len(const int64_t* len, int b, int64_t cap) {
-  return len ? min(cap, max((int64_t)0, len[b])) : cap;
-}
-
 // Steps (a) and (c).  Workgroup (blockIdx.x, b) = chunks [64 blockIdx.x, +64) of row b, lane t = one chunk.  The 64
 // chunks are staged TILE samples at a time: the wave reads 2 chunks x 32 consecutive samples (two full 128-B lines)
 // per load instruction into registers while it filters the tile before, then writes them to LDS, where lane t walks
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(CPB) void kw_chunk_kernel(const float* __restrict__
   __shared__ float tile[CPB * TPAD];
   const int b = blockIdx.y;
   const int lane = threadIdx.x;
-  const int64_t len = clamp_len(lengths, b, n);
+  const int64_t len = hsp_row_len(lengths, b, n);
   const int64_t nch = (len + CHUNK - 1) / CHUNK;
   const int64_t c0 = (int64_t)blockIdx.x * CPB;
   if (c0 >= nch) return;                                     // the whole workgroup lies past the row's end
@@ -116,7 +112,7 @@ __global__ __launch_bounds__(64) void kw_carry_kernel(const int64_t* __restrict_
   __shared__ double zs[64 * 4];
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
-  const int64_t nch = (clamp_len(lengths, b, n) + CHUNK - 1) / CHUNK;
+  const int64_t nch = (hsp_row_len(lengths, b, n) + CHUNK - 1) / CHUNK;
   double* st = state + (int64_t)b * nc * 4;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t c0 = 0; c0 < nch; c0 += 64) {
@@ -179,7 +175,7 @@ __global__ __launch_bounds__(256) void gate_kernel(const int64_t* __restrict__ l
   __shared__ float redf[256];
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
-  const int64_t len = clamp_len(lengths, b, n);
+  const int64_t len = hsp_row_len(lengths, b, n);
   const int64_t nch = (len + CHUNK - 1) / CHUNK;
   const double* cs = csum + (int64_t)b * nc;
   const float* cm = cmax + (int64_t)b * nc;

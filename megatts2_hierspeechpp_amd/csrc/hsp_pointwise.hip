@@ -1,15 +1,11 @@
 // HBM-bound pointwise / reduction kernels of the vocoder path (gfx950).
 // Reference call sites are listed next to each entry point in include/hsp.h.
-#include "hsp_device.h"
+#include "hsp_rows.h"
 
 namespace {
 
-inline unsigned grid_for(int64_t n, int threads, int64_t cap = 1048576) {
-  int64_t b = (n + threads - 1) / threads;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
-}
+// blocks of 256 threads for the kernels that walk n elements with a grid-stride loop
+inline unsigned loop_grid(int64_t n) { return hsp_flat_grid(n, 256, 1048576); }
 
 // ---------------------------------------------------------------- Activation1d
 // Stand-alone anti-aliased SnakeBeta (used where no conv follows, and -- measured faster on
@@ -193,7 +189,7 @@ __device__ __forceinline__ void act2_load(const float* __restrict__ x, const Act
 // the valid length of the row of work item w: len[b] clamped to [1, L] (ragged form)
 __device__ __forceinline__ int act2_row_len(const int64_t* __restrict__ lens, unsigned w, int nseg, int C, int L) {
   const unsigned b = (w / (unsigned)nseg) / (unsigned)C;
-  return (int)min(max(lens[b], (int64_t)1), (int64_t)L);
+  return (int)hsp_clamp_len(lens[b], L, 1);   // never NULL here (the launcher refuses): no test for it in the hot kernel
 }
 
 // RAG (hsp_act1d_snakebeta_ragged_f32): row b is valid over [0, lens[b]).  Reads clamp at lens[b] - 1 -- the replicate
@@ -423,42 +419,29 @@ __global__ void mask_mul_kernel(const float* __restrict__ x, const float* __rest
 // F.interpolate(mode='linear', align_corners=False) along T.  torch's CPU kernel evaluates the
 // source index in fp32 with ONE rounding, src = fmaf(scale, i + 0.5, -0.5), clamped at 0; a
 // separate mul + sub is off by 2e-3 at L = 64000 because ulp(src) ~ 4e-3 there.
-__global__ void linear_interp_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int Lin,
-                                     int Lout, float scale) {
+// RAG (hsp_linear_interp_ragged_f32): row b holds lin[b] valid inputs and lout[b] valid outputs (rows = B * C, b = r / C).
+// Same source position as the call on the row alone (the caller keeps Lin / Lout equal to that call's ratio), the
+// neighbours clamped at the row's last valid input, zeros past its last valid output.  RAG = false is the plain kernel
+// (`lin`, `lout` and C unread).
+template <bool RAG>
+__global__ void linear_interp_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int C, int Lin,
+                                     int Lout, float scale, const int64_t* __restrict__ lin,
+                                     const int64_t* __restrict__ lout) {
   const int64_t n = rows * Lout;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int t = (int)(i % Lout);
     const int64_t r = i / Lout;
-    float src = fmaf(scale, (float)t + 0.5f, -0.5f);
-    src = src < 0.0f ? 0.0f : src;
-    const int i0 = (int)src;
-    const int i1 = i0 + (i0 < Lin - 1 ? 1 : 0);
-    const float l1 = src - (float)i0, l0 = 1.0f - l1;
-    const float* xr = x + r * Lin;
-    y[i] = l0 * xr[i0] + l1 * xr[i1];
-  }
-}
-
-// the same on a ragged batch: row b holds lin[b] valid inputs and lout[b] valid outputs (rows = B * C, b = r / C).  Same
-// source position as the call on the row alone (the caller keeps Lin / Lout equal to that call's ratio), the upper
-// neighbour clamped at the row's last valid input, zeros past its last valid output
-__global__ void linear_interp_ragged_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t rows, int C, int Lin,
-                                            int Lout, float scale, const int64_t* __restrict__ lin,
-                                            const int64_t* __restrict__ lout) {
-  const int64_t n = rows * Lout;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int t = (int)(i % Lout);
-    const int64_t r = i / Lout;
-    const int64_t b = r / C;
-    const int lb_in = (int)min(max(lin[b], (int64_t)1), (int64_t)Lin);
-    const int lb_out = (int)min(max(lout[b], (int64_t)0), (int64_t)Lout);
-    if (t >= lb_out) {
-      y[i] = 0.0f;
-      continue;
+    int lb_in = Lin;
+    if constexpr (RAG) {
+      lb_in = (int)hsp_row_len(lin, r / C, Lin, 1);
+      if (t >= (int)hsp_row_len(lout, r / C, Lout)) {
+        y[i] = 0.0f;
+        continue;
+      }
     }
     float src = fmaf(scale, (float)t + 0.5f, -0.5f);
     src = src < 0.0f ? 0.0f : src;
-    const int i0 = min((int)src, lb_in - 1);
+    const int i0 = RAG ? min((int)src, lb_in - 1) : (int)src;
     const int i1 = i0 + (i0 < lb_in - 1 ? 1 : 0);
     const float l1 = src - (float)i0, l0 = 1.0f - l1;
     const float* xr = x + r * Lin;
@@ -471,17 +454,22 @@ __global__ void act_kernel(const float* x, float* y, int64_t n, int act) {
     y[i] = hsp_apply_act(x[i], act);
 }
 
-__global__ void reflect_pad_kernel(const float* x, int64_t x_bs, float* y, int B, int L, int pad) {
-  const int Lo = L + 2 * pad;
-  const int64_t n = (int64_t)B * Lo;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / Lo), t = (int)(i - (int64_t)b * Lo) - pad;
-    const int s = t < 0 ? -t : (t >= L ? 2 * (L - 1) - t : t);
-    y[i] = x[(int64_t)b * x_bs + s];
+// y[b][t] = x[b][reflect(t - pad)] over [0, len_b + 2 pad), zero on [len_b + 2 pad, Lo); NULL lengths: len_b = L (the
+// plain form, Lo = L + 2 pad: no zeros).  One thread per output sample of a row; blockIdx.y strides the rows.
+__global__ __launch_bounds__(256) void reflect_pad_kernel(const float* __restrict__ x, int64_t x_bs,
+                                                          const int64_t* __restrict__ lengths, float* __restrict__ y,
+                                                          int64_t y_bs, int B, int L, int pad, int Lo) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= Lo) return;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int n = (int)hsp_row_len(lengths, b, L);
+    float v = 0.0f;
+    if (n > 0 && t < n + 2 * pad) v = x[(int64_t)b * x_bs + hsp_reflect(t - pad, n)];
+    y[(int64_t)b * y_bs + t] = v;
   }
 }
 
-// one workgroup per call: hsp_f0_convert_row (hsp_device.h), shared with the batched form of hsp_vcbatch.hip
+// one workgroup per call: hsp_f0_convert_row (hsp_device.h), which each row of hsp_f0_convert_batch_f32 runs too
 __global__ __launch_bounds__(256) void f0_convert_kernel(const float* src, int ns, const float* trg, int nt, float* out) {
   hsp_f0_convert_row(src, ns, trg, nt, out, ns);
 }
@@ -489,6 +477,19 @@ __global__ __launch_bounds__(256) void f0_convert_kernel(const float* src, int n
 __global__ void axpby_kernel(const float* x, const float* z, float* y, float a, float b, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     y[i] = a * x[i] + b * z[i];
+}
+
+// What both LayerNorm kernels do with a loaded value v of channel c, batch b: normalise, the per-channel affine, the
+// column's mask factor mk, then the (b, c) modulation.
+__device__ __forceinline__ float ln_finish(float v, float mean, float rstd, int c, int b, float mk,
+                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                           const float* __restrict__ shift, const float* __restrict__ scale,
+                                           int64_t mod_bs) {
+  v = (v - mean) * rstd;
+  if (gamma) v = v * gamma[c] + beta[c];
+  v *= mk;
+  if (scale) v = v * (1.0f + scale[(int64_t)b * mod_bs + c]) + shift[(int64_t)b * mod_bs + c];
+  return v;
 }
 
 // LayerNorm over channels of a (B, C, T) tensor.  Block = 64 time steps x 4 channel
@@ -526,13 +527,8 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(const float* __restr
   const float rstd = 1.0f / sqrtf(var + eps);
   if (!live) return;
   const float mk = mask ? mask[(int64_t)b * T + t] : 1.0f;
-  for (int c = grp; c < C; c += 4) {
-    float v = (xb[(int64_t)c * T + t] - mean) * rstd;
-    if (gamma) v = v * gamma[c] + beta[c];
-    v *= mk;
-    if (scale) v = v * (1.0f + scale[(int64_t)b * mod_bs + c]) + shift[(int64_t)b * mod_bs + c];
-    yb[(int64_t)c * T + t] = v;
-  }
+  for (int c = grp; c < C; c += 4)
+    yb[(int64_t)c * T + t] = ln_finish(xb[(int64_t)c * T + t], mean, rstd, c, b, mk, gamma, beta, shift, scale, mod_bs);
 }
 
 // Register-resident variant for C <= 16 * LN_R = 512: a workgroup owns 16 time columns, its 256 threads
@@ -588,11 +584,7 @@ __global__ __launch_bounds__(256) void layernorm_reg_kernel(const float* __restr
   for (int r = 0; r < LN_R; ++r) {
     const int c = cg + 16 * r;
     if (c >= C) break;
-    float o = (v[r] - mean) * rstd;
-    if (gamma) o = o * gamma[c] + beta[c];
-    o *= mk;
-    if (scale) o = o * (1.0f + scale[(int64_t)b * mod_bs + c]) + shift[(int64_t)b * mod_bs + c];
-    yb[(int64_t)c * T] = o;
+    yb[(int64_t)c * T] = ln_finish(v[r], mean, rstd, c, b, mk, gamma, beta, shift, scale, mod_bs);
   }
 }
 
@@ -623,18 +615,27 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
 extern "C" int hsp_version(void) { return HSP_VERSION; }
 extern "C" const char* hsp_arch(void) { return "gfx950"; }
 
+// the wave-per-segment form on 16-B addressable rows with L % 4 == 0 (the callers have checked both)
+template <bool RAG>
+static int act1d_seg_launch(const float* x, float* y, int B, int C, int L, const int64_t* lens, const float* alpha_exp,
+                            const float* beta_inv, const float* filt, hipStream_t s) {
+  const int nseg = (L + ACT2_SEG - 1) / ACT2_SEG;
+  const int64_t nwork = (int64_t)nseg * B * C;
+  const int64_t blocks = (nwork + ACT2_WAVES * ACT2_ITEMS - 1) / (ACT2_WAVES * ACT2_ITEMS);
+  if (nwork > 0x7fffffff - ACT2_WAVES * ACT2_ITEMS) return HSP_EINVAL;
+  hipLaunchKernelGGL(act1d_seg_kernel<RAG>, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, s, x, y, C, L, alpha_exp,
+                     beta_inv, filt, nseg, (unsigned)nwork, lens);
+  return (int)hipGetLastError();
+}
+
+static bool act1d_seg_rows(const float* x, const float* y, int L) {
+  return (L & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+}
+
 extern "C" int hsp_act1d_snakebeta_f32(const float* x, float* y, int32_t B, int32_t C, int32_t L,
                                        const float* alpha_exp, const float* beta_inv, const float* filt, void* stream) {
   if (!x || !y || !alpha_exp || !beta_inv || !filt || B <= 0 || C <= 0 || L <= 0) return HSP_EINVAL;
-  if ((L & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-    const int nseg = (L + ACT2_SEG - 1) / ACT2_SEG;
-    const int64_t nwork = (int64_t)nseg * B * C;
-    const int64_t blocks = (nwork + ACT2_WAVES * ACT2_ITEMS - 1) / (ACT2_WAVES * ACT2_ITEMS);
-    if (nwork > 0x7fffffff - ACT2_WAVES * ACT2_ITEMS) return HSP_EINVAL;
-    hipLaunchKernelGGL(act1d_seg_kernel<false>, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, HSP_STREAM, x, y, C, L,
-                       alpha_exp, beta_inv, filt, nseg, (unsigned)nwork, nullptr);
-    return (int)hipGetLastError();
-  }
+  if (act1d_seg_rows(x, y, L)) return act1d_seg_launch<false>(x, y, B, C, L, nullptr, alpha_exp, beta_inv, filt, HSP_STREAM);
   const int n_tiles = (L + ACT_TILE - 1) / ACT_TILE;
   const int64_t blocks = (int64_t)n_tiles * B * C;
   if (blocks > 0x7fffffff) return HSP_EINVAL;
@@ -647,15 +648,9 @@ extern "C" int hsp_act1d_snakebeta_ragged_f32(const float* x, float* y, int32_t 
                                               const float* alpha_exp, const float* beta_inv, const float* filt,
                                               void* stream) {
   if (!x || !y || !lens || !alpha_exp || !beta_inv || !filt || B <= 0 || C <= 0 || L <= 0) return HSP_EINVAL;
-  // the wave-per-segment form only: 16-B addressable rows, L % 4 == 0 (the caller pads the batch to such a length)
-  if ((L & 3) != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0) return HSP_EINVAL;
-  const int nseg = (L + ACT2_SEG - 1) / ACT2_SEG;
-  const int64_t nwork = (int64_t)nseg * B * C;
-  const int64_t blocks = (nwork + ACT2_WAVES * ACT2_ITEMS - 1) / (ACT2_WAVES * ACT2_ITEMS);
-  if (nwork > 0x7fffffff - ACT2_WAVES * ACT2_ITEMS) return HSP_EINVAL;
-  hipLaunchKernelGGL(act1d_seg_kernel<true>, dim3((unsigned)blocks), dim3(64 * ACT2_WAVES), 0, HSP_STREAM, x, y, C, L,
-                     alpha_exp, beta_inv, filt, nseg, (unsigned)nwork, lens);
-  return (int)hipGetLastError();
+  // the wave-per-segment form only (the caller pads the batch to such a length)
+  if (!act1d_seg_rows(x, y, L)) return HSP_EINVAL;
+  return act1d_seg_launch<true>(x, y, B, C, L, lens, alpha_exp, beta_inv, filt, HSP_STREAM);
 }
 
 extern "C" int hsp_snake_consts_f32(const float* al, const float* bl, float* ea, float* binv, int32_t C, void* stream) {
@@ -673,7 +668,7 @@ extern "C" int hsp_fold_weight_norm_f32(const float* v, const float* g, float* w
 
 extern "C" int hsp_gather_f32(const float* src, const int32_t* map, float* dst, int64_t n, void* stream) {
   if (!src || !map || !dst || n <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(gather_kernel, dim3(grid_for(n, 256)), dim3(256), 0, HSP_STREAM, src, map, dst, n);
+  hipLaunchKernelGGL(gather_kernel, dim3(loop_grid(n)), dim3(256), 0, HSP_STREAM, src, map, dst, n);
   return (int)hipGetLastError();
 }
 
@@ -685,7 +680,7 @@ extern "C" int hsp_sequence_mask_f32(const int64_t* length, float* mask, int32_t
 
 extern "C" int hsp_flip_channels_f32(const float* x, float* y, int32_t B, int32_t C, int32_t T, void* stream) {
   if (!x || !y || x == y || B <= 0 || C <= 0 || T <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(flip_channels_kernel, dim3(grid_for((int64_t)B * C * T, 256)), dim3(256), 0, HSP_STREAM, x, y, B,
+  hipLaunchKernelGGL(flip_channels_kernel, dim3(loop_grid((int64_t)B * C * T)), dim3(256), 0, HSP_STREAM, x, y, B,
                      C, T);
   return (int)hipGetLastError();
 }
@@ -693,7 +688,7 @@ extern "C" int hsp_flip_channels_f32(const float* x, float* y, int32_t B, int32_
 extern "C" int hsp_sample_prior_f32(const float* stats, const float* noise, const float* mask, float* z, int32_t B,
                                     int32_t C, int32_t T, float noise_scale, void* stream) {
   if (!stats || !noise || !mask || !z || B <= 0 || C <= 0 || T <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(sample_prior_kernel, dim3(grid_for((int64_t)B * C * T, 256)), dim3(256), 0, HSP_STREAM, stats,
+  hipLaunchKernelGGL(sample_prior_kernel, dim3(loop_grid((int64_t)B * C * T)), dim3(256), 0, HSP_STREAM, stats,
                      noise, mask, z, B, C, T, noise_scale);
   return (int)hipGetLastError();
 }
@@ -701,39 +696,54 @@ extern "C" int hsp_sample_prior_f32(const float* stats, const float* noise, cons
 extern "C" int hsp_mask_mul_f32(const float* x, const float* mask, float* y, int32_t B, int32_t C, int32_t T,
                                 void* stream) {
   if (!x || !mask || !y || B <= 0 || C <= 0 || T <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(mask_mul_kernel, dim3(grid_for((int64_t)B * C * T, 256)), dim3(256), 0, HSP_STREAM, x, mask, y, B,
+  hipLaunchKernelGGL(mask_mul_kernel, dim3(loop_grid((int64_t)B * C * T)), dim3(256), 0, HSP_STREAM, x, mask, y, B,
                      C, T);
+  return (int)hipGetLastError();
+}
+
+template <bool RAG>
+static int linear_interp_launch(const float* x, float* y, int B, int C, int Lin, int Lout, const int64_t* lin,
+                                const int64_t* lout, hipStream_t s) {
+  const float scale = (float)Lin / (float)Lout;  // torch: area_pixel_compute_scale, align_corners=False
+  hipLaunchKernelGGL(linear_interp_kernel<RAG>, dim3(loop_grid((int64_t)B * C * Lout)), dim3(256), 0,
+                     s, x, y, (int64_t)B * C, C, Lin, Lout, scale, lin, lout);
   return (int)hipGetLastError();
 }
 
 extern "C" int hsp_linear_interp_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout,
                                     void* stream) {
   if (!x || !y || B <= 0 || C <= 0 || Lin <= 0 || Lout <= 0) return HSP_EINVAL;
-  const float scale = (float)Lin / (float)Lout;  // torch: area_pixel_compute_scale, align_corners=False
-  hipLaunchKernelGGL(linear_interp_kernel, dim3(grid_for((int64_t)B * C * Lout, 256)), dim3(256), 0, HSP_STREAM, x, y,
-                     (int64_t)B * C, Lin, Lout, scale);
-  return (int)hipGetLastError();
+  return linear_interp_launch<false>(x, y, B, C, Lin, Lout, nullptr, nullptr, HSP_STREAM);
 }
 
 extern "C" int hsp_linear_interp_ragged_f32(const float* x, float* y, int32_t B, int32_t C, int32_t Lin, int32_t Lout,
                                            const int64_t* lin, const int64_t* lout, void* stream) {
   if (!x || !y || !lin || !lout || B <= 0 || C <= 0 || Lin <= 0 || Lout <= 0) return HSP_EINVAL;
-  const float scale = (float)Lin / (float)Lout;
-  hipLaunchKernelGGL(linear_interp_ragged_kernel, dim3(grid_for((int64_t)B * C * Lout, 256)), dim3(256), 0, HSP_STREAM,
-                     x, y, (int64_t)B * C, C, Lin, Lout, scale, lin, lout);
-  return (int)hipGetLastError();
+  return linear_interp_launch<true>(x, y, B, C, Lin, Lout, lin, lout, HSP_STREAM);
 }
 
 extern "C" int hsp_act_f32(const float* x, float* y, int64_t n, int32_t act, void* stream) {
   if (!x || !y || n <= 0 || act < 0 || act > HSP_ACT_GELU_ERF) return HSP_EINVAL;
-  hipLaunchKernelGGL(act_kernel, dim3(grid_for(n, 256)), dim3(256), 0, HSP_STREAM, x, y, n, act);
+  hipLaunchKernelGGL(act_kernel, dim3(loop_grid(n)), dim3(256), 0, HSP_STREAM, x, y, n, act);
   return (int)hipGetLastError();
 }
 
+constexpr int PAD_MAX_ROWS = 65535;   // grid y; the kernel strides the rows beyond it
+
 extern "C" int hsp_reflect_pad_f32(const float* x, int64_t x_bs, float* y, int32_t B, int32_t L, int32_t pad, void* stream) {
   if (!x || !y || B <= 0 || L <= 0 || pad < 0 || pad >= L) return HSP_EINVAL;
-  hipLaunchKernelGGL(reflect_pad_kernel, dim3(grid_for((int64_t)B * (L + 2 * pad), 256)), dim3(256), 0, HSP_STREAM, x, x_bs,
-                     y, B, L, pad);
+  const int Lo = L + 2 * pad;
+  hipLaunchKernelGGL(reflect_pad_kernel, dim3(((int64_t)Lo + 255) / 256, B < PAD_MAX_ROWS ? B : PAD_MAX_ROWS), dim3(256), 0,
+                     HSP_STREAM, x, x_bs, nullptr, y, (int64_t)Lo, B, L, pad, Lo);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_reflect_pad_ragged_f32(const float* x, int64_t x_bs, const int64_t* lengths, float* y, int64_t y_bs,
+                                          int32_t B, int32_t L, int32_t pad, int32_t Lo, void* stream) {
+  if (!x || !y || B <= 0 || L <= 0 || pad < 0 || pad >= L || Lo <= 0) return HSP_EINVAL;
+  if (x_bs < L || y_bs < Lo || (int64_t)Lo > (int64_t)L + 2 * pad || B > PAD_MAX_ROWS) return HSP_EINVAL;
+  hipLaunchKernelGGL(reflect_pad_kernel, dim3((Lo + 255) / 256, B), dim3(256), 0, HSP_STREAM, x, x_bs, lengths, y, y_bs, B,
+                     L, pad, Lo);
   return (int)hipGetLastError();
 }
 
@@ -746,7 +756,7 @@ extern "C" int hsp_f0_convert_f32(const float* f0_src, int32_t n_src, const floa
 
 extern "C" int hsp_axpby_f32(const float* x, const float* z, float* y, float a, float b, int64_t n, void* stream) {
   if (!x || !z || !y || n <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n, 256)), dim3(256), 0, HSP_STREAM, x, z, y, a, b, n);
+  hipLaunchKernelGGL(axpby_kernel, dim3(loop_grid(n)), dim3(256), 0, HSP_STREAM, x, z, y, a, b, n);
   return (int)hipGetLastError();
 }
 

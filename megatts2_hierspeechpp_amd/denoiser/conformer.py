@@ -75,11 +75,9 @@ class ConformerConvModule(nn.Module):
         y = torch.empty_like(h)
         A, Cc, N = h.shape
         seg = one_segment(seg, N, x.device)
-        L.check(L.lib().hsp_dwconv_bn_silu_seg_f32(L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
-                                                   L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")),
-                                                   L.fptr(bn.dev("running_mean")), L.fptr(bn.dev("running_var")),
-                                                   float(bn.eps), L.fptr(y), A, Cc, N, dw.k, *seg.args(),
-                                                   L.stream_ptr()), "hsp_dwconv_bn_silu_seg_f32")
+        L.call("hsp_dwconv_bn_silu_seg_f32", L.fptr(h), L.fptr(dw.dev("weight")), L.fptr(dw.dev("bias")),
+               L.fptr(bn.dev("weight")), L.fptr(bn.dev("bias")), L.fptr(bn.dev("running_mean")),
+               L.fptr(bn.dev("running_var")), float(bn.eps), L.fptr(y), A, Cc, N, dw.k, *seg.args())
         return self.ccm["7"](y, res=x)
 
 

@@ -102,10 +102,8 @@ def _norm_act(norm: _InstanceNorm2d, act: _PReLU, x, seg=None):
     _, Cc, T, F_ = x.shape
     assert x.stride(3) == 1 and x.stride(2) == F_
     seg = one_segment(seg, T, x.device)
-    L.check(L.lib().hsp_instnorm_prelu_seg_f32(L.fptr(x), x.stride(1), Cc, T, F_, *seg.args(),
-                                               L.fptr(norm.dev("weight")), L.fptr(norm.dev("bias")),
-                                               L.fptr(act.dev("weight")), float(norm.eps), L.stream_ptr()),
-            "hsp_instnorm_prelu_seg_f32")
+    L.call("hsp_instnorm_prelu_seg_f32", L.fptr(x), x.stride(1), Cc, T, F_, *seg.args(), L.fptr(norm.dev("weight")),
+           L.fptr(norm.dev("bias")), L.fptr(act.dev("weight")), float(norm.eps))
     return x
 
 
@@ -135,8 +133,8 @@ class DenseBlock(nn.Module):
         _, Cc, T, F_ = x.shape
         assert x.stride(3) == 1 and x.stride(2) == F_
         buf = torch.empty(1, Cc * (self.depth + 1), T, F_, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_copy_strided_f32(L.fptr(x), x.stride(0), x.stride(1), 1, L.fptr(buf[:, self.depth * Cc:]), 1, Cc,
-                                             T * F_, L.stream_ptr()), "hsp_copy_strided_f32")
+        L.call("hsp_copy_strided_f32", L.fptr(x), x.stride(0), x.stride(1), 1, L.fptr(buf[:, self.depth * Cc:]), 1, Cc,
+               T * F_)
         for i in range(self.depth):
             blk = self.dense_block[i]
             o = buf[:, (self.depth - 1 - i) * Cc:(self.depth - i) * Cc]
@@ -211,8 +209,8 @@ class MaskDecoder(nn.Module):
         m = mc["4"](_norm_act(mc["2"], mc["3"], m, seg))             # [1, 1, T, F]
         T, F_ = mag_tf.shape
         out = torch.empty_like(mag_tf)
-        L.check(L.lib().hsp_lsigmoid_mul_f32(L.fptr(m), L.fptr(self.lsigmoid.dev("slope")), float(self.lsigmoid.beta),
-                                             L.fptr(mag_tf), L.fptr(out), T, F_, L.stream_ptr()), "hsp_lsigmoid_mul_f32")
+        L.call("hsp_lsigmoid_mul_f32", L.fptr(m), L.fptr(self.lsigmoid.dev("slope")), float(self.lsigmoid.beta),
+               L.fptr(mag_tf), L.fptr(out), T, F_)
         return out
 
 
@@ -233,7 +231,7 @@ class PhaseDecoder(nn.Module):
         p = _norm_act(pc["1"], pc["2"], pc["0"](self.dense_block(x, seg)), seg)
         x_r, x_i = self.phase_conv_r(p), self.phase_conv_i(p)
         out = torch.empty(x_r.shape[2], x_r.shape[3], dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_atan2_f32(L.fptr(x_i), L.fptr(x_r), L.fptr(out), out.numel(), L.stream_ptr()), "hsp_atan2_f32")
+        L.call("hsp_atan2_f32", L.fptr(x_i), L.fptr(x_r), L.fptr(out), out.numel())
         return out
 
 
@@ -316,8 +314,7 @@ class MPNet(nn.Module):
         x = torch.empty(1, 2, T, F_, dtype=torch.float32, device=noisy_mag.device)      # cat((mag, pha), 1) as [1, 2, T, F]
         for i, src in enumerate((noisy_mag, noisy_pha)):
             v = src.permute(0, 2, 1)                                                    # [1, T, F] view of [1, F, T]
-            L.check(L.lib().hsp_copy_strided_f32(L.fptr(v), v.stride(0), v.stride(1), v.stride(2), L.fptr(x[:, i]), 1, T, F_,
-                                                 L.stream_ptr()), "hsp_copy_strided_f32")
+            L.call("hsp_copy_strided_f32", L.fptr(v), v.stride(0), v.stride(1), v.stride(2), L.fptr(x[:, i]), 1, T, F_)
         h = self.dense_encoder(x, seg)
         # the conformers' other axis: once per pass, because a table made while a graph is captured is not cached
         seg_f = one_segment(None, h.shape[3], h.device)
@@ -325,8 +322,7 @@ class MPNet(nn.Module):
             h = blk(h, seg, seg_f)
         if seg.has_gaps:
             # the decoders' dense blocks shift along T and read h before any norm: zeros on its gap rows
-            L.check(L.lib().hsp_zero_gaps_f32(L.fptr(h), h.stride(1), h.shape[1], T, h.shape[3], *seg.args(),
-                                              L.stream_ptr()), "hsp_zero_gaps_f32")
+            L.call("hsp_zero_gaps_f32", L.fptr(h), h.stride(1), h.shape[1], T, h.shape[3], *seg.args())
         mag_tf = self.mask_decoder(h, x[0, 0], seg)                                      # [T, F]
         pha_tf = self.phase_decoder(h, seg)                                              # [T, F]
         d_mag = Fh.copy_strided(mag_tf.t().unsqueeze(0))                                 # [1, F, T]

@@ -135,14 +135,13 @@ def _stft_packed(y, lens, seg, st, compress_factor, scale=None):
     dlen = device_lengths(lens, y.device)
     f_ld = (seg.T_tot + 3) & ~3
     frames = torch.empty(1, n_fft, f_ld, dtype=torch.float32, device=y.device)
-    L.check(L.lib().hsp_stft_frames_packed_f32(L.fptr(y), y.stride(0), L.ptr(dlen), L.fptr(scale), L.fptr(st._window),
-                                               L.fptr(frames), *seg.args(), Lm, n_fft, hop, seg.T_tot, f_ld,
-                                               L.stream_ptr()), "hsp_stft_frames_packed_f32")
+    L.call("hsp_stft_frames_packed_f32", L.fptr(y), y.stride(0), L.ptr(dlen), L.fptr(scale), L.fptr(st._window),
+           L.fptr(frames), *seg.args(), Lm, n_fft, hop, seg.T_tot, f_ld)
     spec = st.dft(frames)                                          # [1, 2 F, f_ld]: column-wise, so it serves unchanged
     mag = torch.empty(1, nf, seg.T_tot, dtype=torch.float32, device=y.device)
     pha = torch.empty(1, nf, seg.T_tot, dtype=torch.float32, device=y.device)
-    L.check(L.lib().hsp_mag_pha_f32(L.fptr(spec), spec.stride(1), L.fptr(mag), L.fptr(pha), nf, seg.T_tot,
-                                    float(compress_factor), L.stream_ptr()), "hsp_mag_pha_f32")
+    L.call("hsp_mag_pha_f32", L.fptr(spec), spec.stride(1), L.fptr(mag), L.fptr(pha), nf, seg.T_tot,
+           float(compress_factor))
     return mag, pha
 
 
@@ -153,15 +152,14 @@ def _istft_packed(mag, pha, seg, st, compress_factor, inv=None):
     mag, pha = mag.contiguous(), pha.contiguous()
     t_ld = (T + 3) & ~3
     spec = torch.zeros(1, 2 * nf, t_ld, dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0 / float(compress_factor), L.fptr(spec), t_ld,
-                                  L.fptr(spec[0, nf:]), t_ld, nf, T, L.stream_ptr()), "hsp_polar_f32")
+    L.call("hsp_polar_f32", L.fptr(mag), L.fptr(pha), 1.0 / float(compress_factor), L.fptr(spec), t_ld,
+           L.fptr(spec[0, nf:]), t_ld, nf, T)
     frames = st.idft(spec)                                         # [1, n_fft, t_ld]
     out_len = [hop * (n - 1) for n in seg.frames]
     n_max = max(1, max(out_len))
     wav = torch.empty(seg.B, n_max, dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_istft_ola_seg_f32(L.fptr(frames), frames.stride(1), L.fptr(st._window), L.fptr(inv), L.fptr(wav),
-                                          n_max, n_max, n_fft, hop, *seg.args(), T, L.stream_ptr()),
-            "hsp_istft_ola_seg_f32")
+    L.call("hsp_istft_ola_seg_f32", L.fptr(frames), frames.stride(1), L.fptr(st._window), L.fptr(inv), L.fptr(wav),
+           n_max, n_max, n_fft, hop, *seg.args(), T)
     return wav, out_len
 
 
@@ -235,8 +233,8 @@ def _norm_factors(x, lens, hps, who):
     B, Lm = x.shape
     scale = torch.empty(B, dtype=torch.float32, device=x.device)
     inv = torch.empty(B, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_norm_factor_rows_f32(L.fptr(x), x.stride(0), L.ptr(device_lengths(lens, x.device)), L.fptr(scale),
-                                             L.fptr(inv), B, Lm, L.stream_ptr()), "hsp_norm_factor_rows_f32")
+    L.call("hsp_norm_factor_rows_f32", L.fptr(x), x.stride(0), L.ptr(device_lengths(lens, x.device)), L.fptr(scale),
+           L.fptr(inv), B, Lm)
     return scale, inv
 
 

@@ -57,6 +57,5 @@ def polar_pair(mag, pha):
     assert mag.is_contiguous() and pha.is_contiguous()
     re = torch.empty(B * F_, T, dtype=torch.float32, device=mag.device)
     im = torch.empty(B * F_, T, dtype=torch.float32, device=mag.device)
-    L.check(L.lib().hsp_polar_f32(L.fptr(mag), L.fptr(pha), 1.0, L.fptr(re), T, L.fptr(im), T, B * F_, T, L.stream_ptr()),
-            "hsp_polar_f32")
+    L.call("hsp_polar_f32", L.fptr(mag), L.fptr(pha), 1.0, L.fptr(re), T, L.fptr(im), T, B * F_, T)
     return torch.stack((re, im), dim=-1).reshape(B, F_, T, 2)       # a copy, no arithmetic

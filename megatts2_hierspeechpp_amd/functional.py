@@ -19,13 +19,28 @@ def _c(x: torch.Tensor) -> torch.Tensor:
     return x if x.is_contiguous() else x.contiguous()
 
 
+def _lengths(lengths, B=None):
+    """Row lengths as the kernels read them -- device int64 [B], contiguous -- or None (NULL: every row is whole).
+    Without ``B`` the tensor is cast and compacted as needed; with ``B`` it must already be so (checked, never copied:
+    the launches of the vocoder's row-exact path)."""
+    if lengths is None or B is None:
+        return lengths if lengths is None else _c(lengths.to(torch.int64))
+    assert lengths.dtype == torch.int64 and lengths.is_contiguous() and lengths.numel() == B
+    return lengths
+
+
+def _pick(plain: str, ragged: str, *lengths):
+    """All that a plain / ragged pair of entry points differs in: (the entry point, its length arguments) -- ``ragged``
+    with the device pointers of ``lengths``, or ``plain`` with none when there are no lengths."""
+    return (plain, ()) if lengths[0] is None else (ragged, tuple(L.ptr(t) for t in lengths))
+
+
 def sequence_mask(length: torch.Tensor, max_length: int) -> torch.Tensor:
     """commons.sequence_mask (reference commons.py:128-132) as a float mask [B, 1, T]."""
     length = _c(length.to(torch.int64))
     B = length.shape[0]
     mask = torch.empty(B, 1, max_length, dtype=torch.float32, device=length.device)
-    L.check(L.lib().hsp_sequence_mask_f32(L.ptr(length), L.fptr(mask), B, max_length, L.stream_ptr()),
-            "hsp_sequence_mask_f32")
+    L.call("hsp_sequence_mask_f32", L.ptr(length), L.fptr(mask), B, max_length)
     return mask
 
 
@@ -38,20 +53,11 @@ def act1d(x, ea, binv, filt, out=None, lens=None):
     x = _c(x)
     B, Cc, T = x.shape
     out = _new_like(x) if out is None else out
+    name, rag = _pick("hsp_act1d_snakebeta_f32", "hsp_act1d_snakebeta_ragged_f32", _lengths(lens, B))
+    args = (L.fptr(x), L.fptr(out), B, Cc, T, *rag, L.fptr(ea), L.fptr(binv), L.fptr(filt), L.stream_ptr())
     hook = ACT_HOOK
+    _, e0, e1 = L.timed(hook, name, lambda: getattr(L.lib(), name)(*args))
     if hook is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if lens is not None:
-        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == B
-        L.check(L.lib().hsp_act1d_snakebeta_ragged_f32(L.fptr(x), L.fptr(out), B, Cc, T, L.ptr(lens), L.fptr(ea),
-                                                       L.fptr(binv), L.fptr(filt), L.stream_ptr()),
-                "hsp_act1d_snakebeta_ragged_f32")
-    else:
-        L.check(L.lib().hsp_act1d_snakebeta_f32(L.fptr(x), L.fptr(out), B, Cc, T, L.fptr(ea), L.fptr(binv), L.fptr(filt),
-                                                L.stream_ptr()), "hsp_act1d_snakebeta_f32")
-    if hook is not None:
-        e1.record()
         hook(8 * B * Cc * T, e0, e1)   # one fp32 read + one fp32 write per element
     return out
 
@@ -60,7 +66,7 @@ def flip_channels(x):
     x = _c(x)
     B, Cc, T = x.shape
     y = _new_like(x)
-    L.check(L.lib().hsp_flip_channels_f32(L.fptr(x), L.fptr(y), B, Cc, T, L.stream_ptr()), "hsp_flip_channels_f32")
+    L.call("hsp_flip_channels_f32", L.fptr(x), L.fptr(y), B, Cc, T)
     return y
 
 
@@ -70,8 +76,8 @@ def sample_prior(stats, noise, mask, noise_scale: float):
     B, C2, T = stats.shape
     z = torch.empty(B, C2 // 2, T, dtype=torch.float32, device=stats.device)
     assert noise.shape == z.shape, (noise.shape, z.shape)
-    L.check(L.lib().hsp_sample_prior_f32(L.fptr(stats), L.fptr(noise), L.fptr(mask), L.fptr(z), B, C2 // 2, T,
-                                         float(noise_scale), L.stream_ptr()), "hsp_sample_prior_f32")
+    L.call("hsp_sample_prior_f32", L.fptr(stats), L.fptr(noise), L.fptr(mask), L.fptr(z), B, C2 // 2, T,
+           float(noise_scale))
     return z
 
 
@@ -86,15 +92,12 @@ def layernorm_mod(x, eps: float, mask=None, shift=None, scale=None, gamma=None, 
         mod_bs = shift.stride(0)
     from . import hip_layers
     if hip_layers.SURVEY_ABI and gamma is None and beta is None:   # SURVEY.md §8(b) name of the same launch
-        L.check(L.lib().hsp_layernorm_modulate_f32(L.fptr(x), L.fptr(y), B, Cc, T, float(eps),
-                                                   L.fptr(_c(mask)) if mask is not None else None,
-                                                   L.fptr(shift), L.fptr(scale), mod_bs, L.stream_ptr()),
-                "hsp_layernorm_modulate_f32")
+        L.call("hsp_layernorm_modulate_f32", L.fptr(x), L.fptr(y), B, Cc, T, float(eps),
+               L.fptr(_c(mask)) if mask is not None else None, L.fptr(shift), L.fptr(scale), mod_bs)
         return y
-    L.check(L.lib().hsp_layernorm_mod_f32(L.fptr(x), L.fptr(y), B, Cc, T, float(eps),
-                                          L.fptr(_c(mask)) if mask is not None else None,
-                                          L.fptr(shift), L.fptr(scale), mod_bs, L.fptr(gamma), L.fptr(beta),
-                                          L.stream_ptr()), "hsp_layernorm_mod_f32")
+    L.call("hsp_layernorm_mod_f32", L.fptr(x), L.fptr(y), B, Cc, T, float(eps),
+           L.fptr(_c(mask)) if mask is not None else None, L.fptr(shift), L.fptr(scale), mod_bs, L.fptr(gamma),
+           L.fptr(beta))
     return y
 
 
@@ -138,7 +141,7 @@ def mha(q, k, v, n_heads: int, qk_scale: float, mask_q=None, mask_k=None, rel_k=
         a.mask_dense, a.mask_dense_bs = L.fptr(md), md.stride(0)
     if force_stream:                              # tests: the key-streaming kernels at any length (hsp.h)
         a.window = -(a.window + 1)
-    L.check(L.lib().hsp_mha_f32(C.byref(a), L.stream_ptr()), "hsp_mha_f32")
+    L.call("hsp_mha_f32", C.byref(a))
     return o
 
 
@@ -179,7 +182,7 @@ def mha_proj(q, k, v, n_heads: int, qk_scale: float, wt, bias=None, mask=None, c
     if key_len is not None:
         assert key_len.dtype == torch.int64 and key_len.is_contiguous() and key_len.numel() == B
         a.key_len = L.ptr(key_len)
-    L.check(L.lib().hsp_mha_proj_f32(C.byref(a), L.stream_ptr()), "hsp_mha_proj_f32")
+    L.call("hsp_mha_proj_f32", C.byref(a))
     return y
 
 
@@ -187,8 +190,7 @@ def masked_mean(x, mask):
     x, mask = _c(x), _c(mask)
     B, Cc, T = x.shape
     out = torch.empty(B, Cc, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_masked_mean_f32(L.fptr(x), L.fptr(mask), L.fptr(out), B, Cc, T, L.stream_ptr()),
-            "hsp_masked_mean_f32")
+    L.call("hsp_masked_mean_f32", L.fptr(x), L.fptr(mask), L.fptr(out), B, Cc, T)
     return out
 
 
@@ -196,7 +198,7 @@ def mask_mul(x, mask):
     x, mask = _c(x), _c(mask)
     B, Cc, T = x.shape
     y = _new_like(x)
-    L.check(L.lib().hsp_mask_mul_f32(L.fptr(x), L.fptr(mask), L.fptr(y), B, Cc, T, L.stream_ptr()), "hsp_mask_mul_f32")
+    L.call("hsp_mask_mul_f32", L.fptr(x), L.fptr(mask), L.fptr(y), B, Cc, T)
     return y
 
 
@@ -204,8 +206,7 @@ def axpby(x, z, a: float, b: float):
     x, z = _c(x), _c(z)
     assert x.shape == z.shape
     y = _new_like(x)
-    L.check(L.lib().hsp_axpby_f32(L.fptr(x), L.fptr(z), L.fptr(y), float(a), float(b), x.numel(), L.stream_ptr()),
-            "hsp_axpby_f32")
+    L.call("hsp_axpby_f32", L.fptr(x), L.fptr(z), L.fptr(y), float(a), float(b), x.numel())
     return y
 
 
@@ -216,14 +217,9 @@ def linear_interp(x, out_len: int, lens_in=None, lens_out=None):
     x = _c(x)
     B, Cc, Lin = x.shape
     y = torch.empty(B, Cc, out_len, dtype=torch.float32, device=x.device)
-    if lens_in is not None:
-        for t_ in (lens_in, lens_out):
-            assert t_.dtype == torch.int64 and t_.is_contiguous() and t_.numel() == B
-        L.check(L.lib().hsp_linear_interp_ragged_f32(L.fptr(x), L.fptr(y), B, Cc, Lin, out_len, L.ptr(lens_in),
-                                                     L.ptr(lens_out), L.stream_ptr()), "hsp_linear_interp_ragged_f32")
-        return y
-    L.check(L.lib().hsp_linear_interp_f32(L.fptr(x), L.fptr(y), B, Cc, Lin, out_len, L.stream_ptr()),
-            "hsp_linear_interp_f32")
+    name, rag = _pick("hsp_linear_interp_f32", "hsp_linear_interp_ragged_f32", _lengths(lens_in, B),
+                      _lengths(lens_out, B))
+    L.call(name, L.fptr(x), L.fptr(y), B, Cc, Lin, out_len, *rag)
     return y
 
 
@@ -231,8 +227,7 @@ def copy_strided(x):
     """Contiguous copy of a strided [B, C, T] view (one launch, no torch arithmetic)."""
     B, Cc, T = x.shape
     y = torch.empty(B, Cc, T, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_copy_strided_f32(L.fptr(x), x.stride(0), x.stride(1), x.stride(2), L.fptr(y), B, Cc, T,
-                                         L.stream_ptr()), "hsp_copy_strided_f32")
+    L.call("hsp_copy_strided_f32", L.fptr(x), x.stride(0), x.stride(1), x.stride(2), L.fptr(y), B, Cc, T)
     return y
 
 
@@ -241,8 +236,7 @@ def add_cbias(x, cb):
     B, Cc, T = x.shape
     assert x.stride(2) == 1 and cb.stride(1) == 1 and cb.shape[:2] == (B, Cc)
     y = torch.empty(B, Cc, T, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_add_cbias_f32(L.fptr(x), x.stride(0), x.stride(1), L.fptr(cb), cb.stride(0), L.fptr(y), B, Cc, T,
-                                      L.stream_ptr()), "hsp_add_cbias_f32")
+    L.call("hsp_add_cbias_f32", L.fptr(x), x.stride(0), x.stride(1), L.fptr(cb), cb.stride(0), L.fptr(y), B, Cc, T)
     return y
 
 
@@ -255,10 +249,9 @@ def embedding_sum(ids, tables, n_rows, scale: float, channels: int, out=None):
     ids = [_c(i.to(torch.int64)) for i in ids] + [None] * (3 - len(ids))
     tables = list(tables) + [None] * (3 - len(tables))
     n_rows = list(n_rows) + [0] * (3 - len(n_rows))
-    L.check(L.lib().hsp_embedding_sum_f32(L.ptr(ids[0]), L.ptr(ids[1]), L.ptr(ids[2]), L.fptr(tables[0]),
-                                          L.fptr(tables[1]), L.fptr(tables[2]), n_rows[0], n_rows[1], n_rows[2],
-                                          float(scale), L.fptr(out), out.stride(0), out.stride(1), B, channels, T,
-                                          L.stream_ptr()), "hsp_embedding_sum_f32")
+    L.call("hsp_embedding_sum_f32", L.ptr(ids[0]), L.ptr(ids[1]), L.ptr(ids[2]), L.fptr(tables[0]), L.fptr(tables[1]),
+           L.fptr(tables[2]), n_rows[0], n_rows[1], n_rows[2], float(scale), L.fptr(out), out.stride(0), out.stride(1),
+           B, channels, T)
     return out
 
 
@@ -266,19 +259,24 @@ def act(x, kind: int):
     """y = act(x) elementwise (HSP_ACT_*)."""
     x = _c(x)
     y = torch.empty_like(x)
-    L.check(L.lib().hsp_act_f32(L.fptr(x), L.fptr(y), x.numel(), kind, L.stream_ptr()), "hsp_act_f32")
+    L.call("hsp_act_f32", L.fptr(x), L.fptr(y), x.numel(), kind)
     return y
 
 
-def reflect_pad(x, pad: int):
-    """F.pad(x, (pad, pad), "reflect") on the last axis of [B, L] / [B, 1, L] audio."""
+def reflect_pad(x, pad: int, lengths=None):
+    """F.pad(x, (pad, pad), "reflect") on the last axis of [B, L] / [B, 1, L] audio.  ``lengths`` (int64 [B]): row b is
+    F.pad(x[b, :lengths[b]], ...), zero after lengths[b] + 2 pad (hsp_reflect_pad_ragged_f32)."""
     shp = x.shape
     x2 = x.reshape(-1, shp[-1])
     assert x2.stride(1) == 1
-    y = torch.empty(x2.shape[0], shp[-1] + 2 * pad, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_reflect_pad_f32(L.fptr(x2), x2.stride(0), L.fptr(y), x2.shape[0], shp[-1], pad, L.stream_ptr()),
-            "hsp_reflect_pad_f32")
-    return y.reshape(*shp[:-1], shp[-1] + 2 * pad)
+    B, Lx = x2.shape
+    y = torch.empty(B, Lx + 2 * pad, dtype=torch.float32, device=x.device)
+    if lengths is None:
+        L.call("hsp_reflect_pad_f32", L.fptr(x2), x2.stride(0), L.fptr(y), B, Lx, pad)
+    else:
+        L.call("hsp_reflect_pad_ragged_f32", L.fptr(x2), x2.stride(0), L.ptr(_lengths(lengths)), L.fptr(y), y.stride(0), B,
+               Lx, pad, Lx + 2 * pad)
+    return y.reshape(*shp[:-1], Lx + 2 * pad)
 
 
 def f0_convert(f0_src, f0_trg):
@@ -286,24 +284,15 @@ def f0_convert(f0_src, f0_trg):
     target speaker's voiced mean / std."""
     s, t = _c(f0_src.reshape(-1)), _c(f0_trg.reshape(-1))
     out = torch.empty_like(s)
-    L.check(L.lib().hsp_f0_convert_f32(L.fptr(s), s.numel(), L.fptr(t), t.numel(), L.fptr(out), L.stream_ptr()),
-            "hsp_f0_convert_f32")
+    L.call("hsp_f0_convert_f32", L.fptr(s), s.numel(), L.fptr(t), t.numel(), L.fptr(out))
     return out.reshape(f0_src.shape)
 
 
 # ---------------------------------------------------------------- batched voice conversion (ragged rows, device lengths)
-def _lengths(lengths):
-    return _c(lengths.to(torch.int64))
-
-
 def reflect_pad_ragged(x, lengths, pad: int):
     """Row b of x [B, L] -> F.pad(x[b, :lengths[b]], (pad, pad), "reflect"), zero after lengths[b] + 2 pad: [B, L + 2 pad]."""
-    assert x.dim() == 2 and x.stride(1) == 1
-    B, Lx = x.shape
-    y = torch.empty(B, Lx + 2 * pad, dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_reflect_pad_ragged_f32(L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)), L.fptr(y), y.stride(0), B,
-                                               Lx, pad, Lx + 2 * pad, L.stream_ptr()), "hsp_reflect_pad_ragged_f32")
-    return y
+    assert x.dim() == 2
+    return reflect_pad(x, pad, lengths)
 
 
 def f0_convert_batch(f0_src, n_src, f0_trg, n_trg):
@@ -314,9 +303,8 @@ def f0_convert_batch(f0_src, n_src, f0_trg, n_trg):
     B, N = s.shape
     assert t.dim() == 2 and t.shape[0] in (1, B)
     out = torch.empty(B, N, dtype=torch.float32, device=s.device)
-    L.check(L.lib().hsp_f0_convert_batch_f32(L.fptr(s), s.stride(0), L.ptr(_lengths(n_src)), L.fptr(t),
-                                             0 if t.shape[0] == 1 else t.stride(0), L.ptr(_lengths(n_trg)), t.shape[1],
-                                             L.fptr(out), out.stride(0), B, N, L.stream_ptr()), "hsp_f0_convert_batch_f32")
+    L.call("hsp_f0_convert_batch_f32", L.fptr(s), s.stride(0), L.ptr(_lengths(n_src)), L.fptr(t),
+           0 if t.shape[0] == 1 else t.stride(0), L.ptr(_lengths(n_trg)), t.shape[1], L.fptr(out), out.stride(0), B, N)
     return out
 
 
@@ -324,20 +312,29 @@ def abs_max_rows(x, lengths=None):
     """max |x[b, :lengths[b]]| of every row of x [B, n] -> fp32 [B] on the device (no host read-back)."""
     assert x.dim() == 2 and x.stride(1) == 1
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    L.check(L.lib().hsp_abs_max_rows_f32(L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None,
-                                         L.fptr(out), x.shape[0], x.shape[1], L.stream_ptr()), "hsp_abs_max_rows_f32")
+    L.call("hsp_abs_max_rows_f32", L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)), L.fptr(out), x.shape[0], x.shape[1])
+    return out
+
+
+def peak_int16(audio, lengths=None, gain=0.999):
+    """[B, 1, n] / [B, n] fp32 -> int16 [B, n], every row scaled by its own peak (over ``lengths[b]`` samples) times
+    ``gain``: a float for every row (hsp_peak_int16) or a device fp32 [B], one per row (hsp_peak_int16_gains).
+    A silent row (peak 0) comes out as zeros, as the reference's ``(a / a.abs().max() ...).astype(int16)`` does."""
+    a = audio.reshape(audio.shape[0], -1)
+    assert a.stride(1) == 1
+    out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
+    if torch.is_tensor(gain):
+        assert gain.shape == (a.shape[0],)
+        name, g = "hsp_peak_int16_gains", L.fptr(_c(gain))
+    else:
+        name, g = "hsp_peak_int16", float(gain)
+    L.call(name, L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)), g, L.ptr(out), out.stride(0), a.shape[0], a.shape[1])
     return out
 
 
 def peak_int16_gains(audio, lengths, gains):
-    """inference_plm.peak_int16 with a per-row device gain: [B, 1, n] / [B, n] fp32, gains fp32 [B] -> int16 [B, n]."""
-    a = audio.reshape(audio.shape[0], -1)
-    assert a.stride(1) == 1 and gains.shape == (a.shape[0],)
-    out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
-    L.check(L.lib().hsp_peak_int16_gains(L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None,
-                                         L.fptr(_c(gains)), L.ptr(out), out.stride(0), a.shape[0], a.shape[1],
-                                         L.stream_ptr()), "hsp_peak_int16_gains")
-    return out
+    """`peak_int16` with a per-row device gain: gains fp32 [B]."""
+    return peak_int16(audio, lengths, gains)
 
 
 # ---------------------------------------------------------------- loudness (ITU-R BS.1770-4; scale_norm="lufs")
@@ -356,9 +353,8 @@ def loudness(audio, sample_rate: int, lengths=None):
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
     lufs = torch.empty(B, dtype=torch.float32, device=a.device)
     peak = torch.empty(B, dtype=torch.float32, device=a.device)
-    L.check(lib.hsp_loudness_f32(L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)) if lengths is not None else None, B, n,
-                                 int(sample_rate), L.ptr(ws), ws.numel() * 8, L.fptr(lufs), L.fptr(peak), L.stream_ptr()),
-            "hsp_loudness_f32")
+    L.call("hsp_loudness_f32", L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)), B, n,
+           int(sample_rate), L.ptr(ws), ws.numel() * 8, L.fptr(lufs), L.fptr(peak))
     return lufs, peak
 
 
@@ -370,8 +366,8 @@ def loudness_gains(lufs, peak, target_lufs: float = -23.0, ceiling: float = 0.99
     B = lufs.shape[0]
     gains = torch.empty(B, dtype=torch.float32, device=lufs.device)
     limited = torch.empty(B, dtype=torch.int32, device=lufs.device)
-    L.check(L.lib().hsp_loudness_gains_f32(L.fptr(_c(lufs)), L.fptr(_c(peak)), float(target_lufs), float(ceiling),
-                                           L.fptr(gains), L.ptr(limited), B, L.stream_ptr()), "hsp_loudness_gains_f32")
+    L.call("hsp_loudness_gains_f32", L.fptr(_c(lufs)), L.fptr(_c(peak)), float(target_lufs), float(ceiling),
+           L.fptr(gains), L.ptr(limited), B)
     return gains, limited
 
 
@@ -495,7 +491,6 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width: int = 6, rollo
         lens = _c(lengths.reshape(-1).to(device=x.device, dtype=torch.int64))
         if lens.shape[0] != B:
             raise L.HspError(f"resample: lengths has {lens.shape[0]} entries for {B} rows")
-    L.check(L.lib().hsp_resample_f32(L.fptr(x), x.stride(0), L.ptr(lens), B, Lx, L.fptr(bank), L.ptr(tap0), hb.n_taps,
-                                     hb.o, hb.n, hb.width, L.fptr(y), y.stride(0), T_out, L.stream_ptr()),
-            "hsp_resample_f32")
+    L.call("hsp_resample_f32", L.fptr(x), x.stride(0), L.ptr(lens), B, Lx, L.fptr(bank), L.ptr(tap0), hb.n_taps, hb.o,
+           hb.n, hb.width, L.fptr(y), y.stride(0), T_out)
     return y.reshape(*shp[:-1], T_out)

@@ -10,9 +10,10 @@ reference instead re-derives ``g*v/||v||`` on every forward.
 All packed tensors of a model live in one contiguous fp32 arena so that a multi-GPU
 job can ship them with a single RCCL broadcast.
 
-Every launch leaves through ``_bracket``, the one place that knows the measurement hook
-(``LAUNCH_HOOK``): a conv's argument struct by way of ``_launch``, which inside
-``deferred()`` records it for ``launch_group`` instead (per context, like ``row_exact``).
+Every launch of this module leaves through ``_bracket``, the one place that knows its measurement
+hook (``LAUNCH_HOOK``): a conv's argument struct by way of ``_launch``, which inside ``deferred()``
+records it for ``launch_group`` instead (per context, like ``row_exact``).  The event bracket itself is
+``_lib.timed``, which ``functional.act1d`` uses for its own hook (``ACT_HOOK``) too.
 """
 from __future__ import annotations
 
@@ -189,29 +190,20 @@ class deferred:
 
 
 def _bracket(kind: str, call, flops: int, nbytes: int, arg, soft: bool = False, span=None):
-    """The measurement bracket of every launch, and the only code that knows LAUNCH_HOOK: ``call()`` performs the C call
-    and returns its status; with a hook set it runs between two timing events on the launch stream and is reported as
-    hook(kind, flops, nbytes, ev_start, ev_end, arg).  Without a hook no event is created.  ``soft``: a launch the
-    library refuses with HSP_EINVAL reports nothing and its status is returned; every other failure raises.
-    ``call=None`` launches nothing: a summary record over ``span`` = (ev_start, ev_end) of earlier brackets.
-    Returns (status, ev_start, ev_end), the events None without a hook."""
+    """The measurement bracket of every launch of this module, and the only code that knows LAUNCH_HOOK: ``call()``
+    performs the C call and returns its status; with a hook set it runs between two timing events on the launch stream
+    (``_lib.timed``) and is reported as hook(kind, flops, nbytes, ev_start, ev_end, arg).  Without a hook no event is
+    created.  ``soft``: a launch the library refuses with HSP_EINVAL reports nothing and its status is returned; every
+    other failure raises.  ``call=None`` launches nothing: a summary record over ``span`` = (ev_start, ev_end) of
+    earlier brackets.  Returns (status, ev_start, ev_end), the events None without a hook."""
     hook = LAUNCH_HOOK
     if call is None:
-        if hook is not None and span[0] is not None:
-            hook(kind, flops, nbytes, span[0], span[1], arg)
-        return 0, span[0], span[1]
-    e0 = e1 = None
-    if hook is not None:
-        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
-        e0.record()
-    rc = call()
-    if soft and rc == L.EINVAL:
-        return rc, None, None
-    L.check(rc, kind)
-    if hook is not None:
-        e1.record()
+        rc, (e0, e1) = 0, span
+    else:
+        rc, e0, e1 = L.timed(hook, kind, call, soft)
+    if hook is not None and e0 is not None:
         hook(kind, flops, nbytes, e0, e1, arg)
-    return 0, e0, e1
+    return rc, e0, e1
 
 
 def launch_group(kind: str, fn, structs, *extra):
@@ -428,7 +420,7 @@ def _gather(src: torch.Tensor, idx_map: np.ndarray, dst: torch.Tensor):
     assert dst.is_contiguous() and src.is_contiguous(), "hsp_gather_f32 reads and writes flat buffers"
     assert idx_map.dtype == np.int32 and idx_map.size == dst.numel() and idx_map.flags["C_CONTIGUOUS"]
     mp = torch.from_numpy(idx_map).to(src.device)
-    L.check(L.lib().hsp_gather_f32(L.fptr(src), L.ptr(mp), L.fptr(dst), dst.numel(), L.stream_ptr()), "hsp_gather_f32")
+    L.call("hsp_gather_f32", L.fptr(src), L.ptr(mp), L.fptr(dst), dst.numel())
     # `mp` must outlive the asynchronous gather on the current stream
     torch.cuda.current_stream().synchronize()
 
@@ -441,8 +433,7 @@ def _fold(v: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     w = torch.empty(v.shape, dtype=v.dtype, device=v.device)
     vc, gc = v.contiguous(), g.contiguous()          # named: a copy made here must live until the launch is issued
     assert gc.numel() == rows
-    L.check(L.lib().hsp_fold_weight_norm_f32(L.fptr(vc), L.fptr(gc), L.fptr(w), rows, cols, L.stream_ptr()),
-            "hsp_fold_weight_norm_f32")
+    L.call("hsp_fold_weight_norm_f32", L.fptr(vc), L.fptr(gc), L.fptr(w), rows, cols)
     return w
 
 
@@ -573,9 +564,8 @@ class Conv1d(_ConvBase):
             raise L.HspError("ensure_wf() inside a stream capture: run one eager call first (or prepare_fft(model))")
         Cc, form = self.cin, self.fft_form()
         wf = torch.empty(64 * (3 if form == "three" else 4) * Cc * Cc, dtype=torch.float32, device=self._w.device)
-        L.check(L.lib().hsp_dftseg_weight_spectrum_f32(
-            L.fptr(self._w), self.k, Cc, self.M, L.ptr(_wspec_twiddles(self._w.device)), L.fptr(wf),
-            L.WSPEC_THREE if form == "three" else L.WSPEC_BLOCK, L.stream_ptr()), "hsp_dftseg_weight_spectrum_f32")
+        L.call("hsp_dftseg_weight_spectrum_f32", L.fptr(self._w), self.k, Cc, self.M,
+               L.ptr(_wspec_twiddles(self._w.device)), L.fptr(wf), L.WSPEC_THREE if form == "three" else L.WSPEC_BLOCK)
         self._wf, self._wf_form = wf, form
         return wf
 

@@ -49,20 +49,11 @@ class TtsModels(nn.Module):
 def zero_below(x, thr: float):
     x = x.contiguous()
     y = torch.empty_like(x)
-    L.check(L.lib().hsp_zero_below_f32(L.fptr(x), float(thr), L.fptr(y), x.numel(), L.stream_ptr()), "hsp_zero_below_f32")
+    L.call("hsp_zero_below_f32", L.fptr(x), float(thr), L.fptr(y), x.numel())
     return y
 
 
-def peak_int16(audio, lengths=None, gain: float = 0.999):
-    """[B, 1, n] / [B, n] fp32 -> int16 [B, n], every row scaled by its own peak (over ``lengths[b]`` samples).
-    A silent row (peak 0) comes out as zeros, as the reference's ``(a / a.abs().max() ...).astype(int16)`` does."""
-    a = audio.reshape(audio.shape[0], -1)
-    assert a.stride(1) == 1
-    out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
-    L.check(L.lib().hsp_peak_int16(L.fptr(a), a.stride(0), L.ptr(lengths.to(torch.int64).contiguous()) if lengths is not None else None,
-                                   float(gain), L.ptr(out), out.stride(0), a.shape[0], a.shape[1], L.stream_ptr()),
-            "hsp_peak_int16")
-    return out
+peak_int16 = Fh.peak_int16   # the int16 stage of the reference's tts() (inference_plm.py:185-188)
 
 
 def prompt_mels(mel_fn, audio, denoiser=None, hps_denoiser=None):

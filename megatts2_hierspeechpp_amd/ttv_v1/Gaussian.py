@@ -43,8 +43,6 @@ class GaussianUpsampling(nn.Module):
         B, C, N = x.shape
         assert x.stride(2) == 1 and dur.stride(-1) == 1 and rng.is_contiguous()
         out = torch.empty(B, C, T, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_gaussian_upsample_f32(L.fptr(x), x.stride(0), x.stride(1), L.fptr(dur), dur.stride(0),
-                                                  L.fptr(rng), rng.stride(0), L.ptr(input_lengths), L.fptr(frames),
-                                                  L.fptr(out), B, C, N, T, L.stream_ptr()),
-                "hsp_gaussian_upsample_f32")
+        L.call("hsp_gaussian_upsample_f32", L.fptr(x), x.stride(0), x.stride(1), L.fptr(dur), dur.stride(0),
+               L.fptr(rng), rng.stride(0), L.ptr(input_lengths), L.fptr(frames), L.fptr(out), B, C, N, T)
         return out

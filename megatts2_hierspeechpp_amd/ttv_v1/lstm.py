@@ -73,8 +73,7 @@ class LSTM(HipLayer):
         for l in range(self.num_layers):
             xp = self.proj[l](x)                                            # [B, 8H, N]
             y = torch.empty(B, 2 * H, N, dtype=torch.float32, device=x.device)
-            L.check(L.lib().hsp_lstm_bidir_f32(L.fptr(xp), xp.stride(0), L.fptr(self._whh[l]), L.fptr(self._bhh[l]),
-                                               L.ptr(lengths), L.fptr(y), y.stride(0), y.stride(1), B, H, N,
-                                               L.stream_ptr()), "hsp_lstm_bidir_f32")
+            L.call("hsp_lstm_bidir_f32", L.fptr(xp), xp.stride(0), L.fptr(self._whh[l]), L.fptr(self._bhh[l]),
+                   L.ptr(lengths), L.fptr(y), y.stride(0), y.stride(1), B, H, N)
             x = y
         return x

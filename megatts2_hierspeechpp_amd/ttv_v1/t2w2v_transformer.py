@@ -241,19 +241,17 @@ class PlmDecodeSession:
         m, S = self.plm, self.slots
         top = self.max_len - 1                          # the largest position a row may hold
         x = self.x[0]                                   # [D, S]: element (c, b) at c * S + b
-        L.check(L.lib().hsp_plm_embed_pos_f32(
-            L.fptr(self.tc), self.tc.stride(0), self.tc.stride(1), m.tc_latent_dim, L.ptr(self.codes),
-            self.codes.stride(0), L.fptr(m.pc_embedding._w), m.vq_dim, m.pc_embedding.num_embeddings,
-            L.fptr(m.pos_emb._pe_t), m.pos_emb.N_POS, L.fptr(m.pos_emb._alpha), L.fptr(x), x.stride(1), x.stride(0), S,
-            L.ptr(self.pos), top, L.stream_ptr()), "hsp_plm_embed_pos_f32")
+        L.call("hsp_plm_embed_pos_f32", L.fptr(self.tc), self.tc.stride(0), self.tc.stride(1), m.tc_latent_dim,
+               L.ptr(self.codes), self.codes.stride(0), L.fptr(m.pc_embedding._w), m.vq_dim,
+               m.pc_embedding.num_embeddings, L.fptr(m.pos_emb._pe_t), m.pos_emb.N_POS, L.fptr(m.pos_emb._alpha),
+               L.fptr(x), x.stride(1), x.stride(0), S, L.ptr(self.pos), top)
         for layer, (kc, vc) in zip(m.plm.layers, self.kv):
             layer.decode_step(x, x, kc, vc, top, self.ws, pos=self.pos)
         m.predict_layer(self.x if m.plm.norm is None else m.plm.norm(self.x), out=self.logits)
         lg = self.logits
-        L.check(L.lib().hsp_plm_choose_advance_f32(
-            L.fptr(lg), 1, lg.stride(1), S, m.vq_bins, L.ptr(self.codes), self.codes.stride(0), L.ptr(self.pos),
-            L.ptr(self.len), top, ctypes.byref(self._sample) if self._sample is not None else None, L.stream_ptr()),
-            "hsp_plm_choose_advance_f32")
+        L.call("hsp_plm_choose_advance_f32", L.fptr(lg), 1, lg.stride(1), S, m.vq_bins, L.ptr(self.codes),
+               self.codes.stride(0), L.ptr(self.pos), L.ptr(self.len), top,
+               ctypes.byref(self._sample) if self._sample is not None else None)
 
     def step(self):
         """One position of every busy slot: a replay of the captured graph, else the same launches eagerly.  No host
@@ -373,16 +371,15 @@ class Megatts2PLM1(nn.Module):
                 L.fptr(self.pc_embedding._w), self.vq_dim, self.pc_embedding.num_embeddings, L.fptr(pe_t),
                 self.pos_emb.N_POS, L.fptr(self.pos_emb._alpha), L.fptr(x), x_bs, x_cs, B, n)
         if prev_logits is None:
-            L.check(L.lib().hsp_plm_embed_f32(*head, L.stream_ptr()), "hsp_plm_embed_f32")
+            L.call("hsp_plm_embed_f32", *head)
             return
         lg = prev_logits
         assert lg.shape == (1, self.vq_bins, B) and lg.stride(2) == 1
         head += (L.fptr(lg), 1, lg.stride(1), self.vq_bins)
         if sample is None:
-            L.check(L.lib().hsp_plm_embed_step_f32(*head, L.stream_ptr()), "hsp_plm_embed_step_f32")
+            L.call("hsp_plm_embed_step_f32", *head)
         else:
-            L.check(L.lib().hsp_plm_embed_sample_f32(*head, j, ctypes.byref(sample), L.stream_ptr()),
-                    "hsp_plm_embed_sample_f32")
+            L.call("hsp_plm_embed_sample_f32", *head, j, ctypes.byref(sample))
 
     def _embed(self, tc, codes, n, prev_logits=None, sample=None):
         """[1, d_model, Np]: utterance b occupies columns b*n .. b*n+n-1; Np = B*n rounded up to a multiple
@@ -605,11 +602,10 @@ class Megatts2PLM1(nn.Module):
         """The choice of the last step (every earlier one is taken inside the next step's embedding launch)."""
         B, T = codes.shape[0], codes.shape[1] - 1
         if sampling is None:
-            L.check(L.lib().hsp_argmax_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0),
-                                           L.stream_ptr()), "hsp_argmax_f32")
+            L.call("hsp_argmax_f32", L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0))
         else:
-            L.check(L.lib().hsp_sample_f32(L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0), T,
-                                           ctypes.byref(sampling.c_args(seeds)), L.stream_ptr()), "hsp_sample_f32")
+            L.call("hsp_sample_f32", L.fptr(lg), 1, B, B, self.vq_bins, L.ptr(codes[:, T:]), codes.stride(0), T,
+                   ctypes.byref(sampling.c_args(seeds)))
         return (codes[:, 1:], all_logits.permute(2, 0, 1)) if all_logits is not None else codes[:, 1:]
 
 
@@ -815,8 +811,8 @@ class SynthesizerTrn(nn.Module):
         else:
             dcol.copy_(dur.to(torch.float32))
             lw = (None, 0)
-        L.check(L.lib().hsp_duration_f32(lw[0], lw[1], L.ptr(x_lengths), float(length_scale), L.fptr(dcol), dcol.stride(0),
-                                         L.fptr(frames), B, N, L.stream_ptr()), "hsp_duration_f32")
+        L.call("hsp_duration_f32", lw[0], lw[1], L.ptr(x_lengths), float(length_scale), L.fptr(dcol), dcol.stride(0),
+               L.fptr(frames), B, N)
         rng = self.RangePredictor(xd, x_lengths)
         frames_h = frames.cpu()                       # the reference's `.item()` (Gaussian.py:53): T is data dependent
         T = int(frames_h.max().item())
@@ -888,7 +884,7 @@ class SynthesizerTrn(nn.Module):
             a.pooled, a.p_bs = L.ptr(out), out.stride(0)
         else:
             a.codes, a.c_bs = L.ptr(out), out.stride(0)
-        L.check(L.lib().hsp_prosody_encode_f32(ctypes.byref(a), L.stream_ptr()), "hsp_prosody_encode_f32")
+        L.call("hsp_prosody_encode_f32", ctypes.byref(a))
         return out
 
     @_entry
@@ -937,13 +933,12 @@ class SynthesizerTrn(nn.Module):
         logw = self.duration_predictor(xs, x_mask, g=g, lengths=x_lengths)
         dpred = torch.empty(B, N, dtype=torch.float32, device=x.device)
         frames_pred = torch.empty(B, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_duration_f32(L.fptr(logw), logw.stride(0), L.ptr(x_lengths), 1.0, L.fptr(dpred), dpred.stride(0),
-                                         L.fptr(frames_pred), B, N, L.stream_ptr()), "hsp_duration_f32")
+        L.call("hsp_duration_f32", L.fptr(logw), logw.stride(0), L.ptr(x_lengths), 1.0, L.fptr(dpred), dpred.stride(0),
+               L.fptr(frames_pred), B, N)
         dcol = xd[:, C]
         dcol.copy_(dur.reshape(B, N).to(torch.float32))
         frames = torch.empty(B, dtype=torch.float32, device=x.device)
-        L.check(L.lib().hsp_duration_f32(None, 0, L.ptr(x_lengths), 1.0, L.fptr(dcol), dcol.stride(0), L.fptr(frames), B, N,
-                                         L.stream_ptr()), "hsp_duration_f32")
+        L.call("hsp_duration_f32", None, 0, L.ptr(x_lengths), 1.0, L.fptr(dcol), dcol.stride(0), L.fptr(frames), B, N)
         rng = self.RangePredictor(xd, x_lengths)
         frames_h = frames.cpu()
         T = int(frames_h.max().item())

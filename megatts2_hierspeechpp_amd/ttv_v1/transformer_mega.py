@@ -214,12 +214,11 @@ class TransformerEncoderLayer(nn.Module):
             setattr(a, name, L.fptr(w[name]))
         a.workspace, a.workspace_bytes = L.fptr(workspace), workspace.numel() * 4
         if pos is None:
-            L.check(L.lib().hsp_plm_decode_layer_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_decode_layer_f32")
+            L.call("hsp_plm_decode_layer_f32", ctypes.byref(a))
             return
         if pos.dtype != torch.int32 or pos.shape != (B,) or pos.stride(0) != 1:
             raise L.HspError("pos must be a contiguous int32 [B] tensor")
-        L.check(L.lib().hsp_plm_decode_layer_pos_f32(ctypes.byref(a), L.ptr(pos), L.stream_ptr()),
-                "hsp_plm_decode_layer_pos_f32")
+        L.call("hsp_plm_decode_layer_pos_f32", ctypes.byref(a), L.ptr(pos))
 
     def prefill_supported(self) -> bool:
         return bool(L.lib().hsp_plm_prefill_attn_supported(self.dim, self.n_heads))
@@ -246,7 +245,7 @@ class TransformerEncoderLayer(nn.Module):
         a.out, a.o_rs = (L.fptr(o), o.stride(1)) if o is not None else (None, 0)
         a.k_cache, a.v_cache, a.cs = L.fptr(k_row), L.fptr(v_row), k_row.stride(0)
         a.n, a.D, a.H, a.debug = n, D, self.n_heads, 0
-        L.check(L.lib().hsp_plm_prefill_attn_f32(ctypes.byref(a), L.stream_ptr()), "hsp_plm_prefill_attn_f32")
+        L.call("hsp_plm_prefill_attn_f32", ctypes.byref(a))
         if last:
             return None
         x = self.attn.out_proj[0](o, res=x)

@@ -1,12 +1,15 @@
 """Float64 restatements of the pointwise and glue operations of csrc/hsp_pointwise.hip, the four element-wise kernels
-of csrc/hsp_denoiser.hip and hsp_copy_strided_f32, plus the seeded inputs and case tables the host and GPU tests share.
+of csrc/hsp_denoiser.hip and hsp_copy_strided_f32, float32 restatements of the three STFT framing forms of
+csrc/hsp_mel.hip, plus the seeded inputs and case tables the host and GPU tests share.
 
 Every function is written from the formula in include/hsp.h and the kernel's header comment -- none calls the library
 and none uses torch.  tests/test_glue_ref_host.py pins them against torch's CPU operations in float64 and asserts the
-input conditions the GPU comparisons rely on; tests/test_gpu_glue_kernels.py compares the kernels with them.
+input conditions the GPU comparisons rely on; tests/test_gpu_glue_kernels.py and tests/test_gpu_framing_contract.py
+compare the kernels with them.
 
-Data movement (copy, flip, gather, mask, reflect pad) and the single fp32 multiply of mask_mul are restated in
-float32, because their results must be bit-equal; everything else is float64 on the fp32 inputs the kernel sees.
+Data movement (copy, flip, gather, mask, reflect pad), the single fp32 multiply of mask_mul and the one or two fp32
+multiplies of framing are restated in float32, because their results must be bit-equal; everything else is float64 on
+the fp32 inputs the kernel sees.
 linear_interp is the one mixed case: its source position is DEFINED in fp32 (one rounding of scale * (t + 0.5) - 0.5,
 SURVEY.md A15), so the position is formed in fp32 and the blend in float64.
 """
@@ -166,6 +169,53 @@ def flip_channels(x):
 
 def reflect_pad(x, pad):
     return np.pad(np.asarray(x, np.float32), ((0, 0), (pad, pad)), mode="reflect")
+
+
+def reflect_pad_ragged(x, lengths, pad):
+    """Row b = reflect_pad of its first lengths[b] samples, zeros after: [B, L + 2 pad]."""
+    x = np.asarray(x, np.float32)
+    y = np.zeros((x.shape[0], x.shape[1] + 2 * pad), np.float32)
+    for b, n in enumerate(lengths):
+        y[b, :n + 2 * pad] = reflect_pad(x[b:b + 1, :n], pad)[0]
+    return y
+
+
+def reflect_index(i, n):
+    """Sample i of a row of n samples under torch's "reflect" padding (the edge sample is not repeated), -n < i < 2n - 1."""
+    i = np.abs(i)
+    return np.where(i >= n, 2 * (n - 1) - i, i)
+
+
+def stft_frames(x, window, hop, scale=None):
+    """The frames torch.stft(center=True, pad_mode="reflect") multiplies by its DFT matrix, [n_fft, T] with
+    T = 1 + len(x) // hop: frames[n, t] = w[n] * x[reflect(t hop + n - n_fft / 2)], one fp32 multiply; with ``scale``
+    the sample is scaled first, w[n] * (x * scale): two fp32 multiplies in that order."""
+    x, w = np.asarray(x, np.float32), np.asarray(window, np.float32)
+    n_fft, T = len(w), 1 + len(x) // hop
+    v = x[reflect_index(np.arange(T)[None, :] * hop + np.arange(n_fft)[:, None] - n_fft // 2, len(x))]
+    if scale is not None:
+        v = v * F32(scale)
+    assert v.dtype == np.float32
+    return w[:, None] * v
+
+
+def stft_frames_ragged(x, lengths, window, hop, f_ld):
+    """[B, n_fft, f_ld]: row b holds stft_frames of its first lengths[b] samples, zeros on the columns after them."""
+    out = np.zeros((len(lengths), len(window), f_ld), np.float32)
+    for b, n in enumerate(lengths):
+        fr = stft_frames(x[b, :n], window, hop)
+        out[b, :, :fr.shape[1]] = fr
+    return out
+
+
+def stft_frames_packed(x, lengths, window, hop, first, f_ld, scale=None):
+    """ONE [n_fft, f_ld] matrix: the frames of row b (times scale[b]) at columns [first[b], first[b] + T_b), zeros on
+    every other column."""
+    out = np.zeros((len(window), f_ld), np.float32)
+    for b, n in enumerate(lengths):
+        fr = stft_frames(x[b, :n], window, hop, None if scale is None else scale[b])
+        out[:, first[b]:first[b] + fr.shape[1]] = fr
+    return out
 
 
 def mag_pha(re, im, compress):
@@ -389,6 +439,43 @@ def act_points():
 
 # magnitude bands in which the activation outputs are compared, each against the bar of its own reference values
 ACT_BANDS = ((0.0, 1.0), (1.0, 8.0), (8.0, 30.0), (30.0, 200.0))
+
+# ---- framing and reflect padding: exact operations
+# n_fft = 320, hop = 5.  L = 347: T = 70 frames -- a second, part-filled 64-frame tile; 320 window positions -- a second
+# 256-position block whose one 64-position group is whole (a third and fourth are empty); L = 161 = n_fft / 2 + 1: the
+# shortest legal row, both edges reflect inside one frame.  Ragged and packed forms: rows of 347, 161 and 200 samples.
+FRAME_N_FFT, FRAME_HOP = 320, 5
+FRAME_LS = (347, 161)
+FRAME_RAGGED = (347, 161, 200)
+FRAME_GAP = 3                                # columns between packed segments
+FRAME_SCALE = (0.5, 3.0, 1.25)
+PAD_SHAPES = ((300, 37), (2, 1))             # (L, pad)
+
+
+def frame_window(n_fft=FRAME_N_FFT):
+    """The periodic Hann window in fp32 from float64 (torch.hann_window's values are not needed: any fp32 window does)."""
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft)).astype(np.float32)
+
+
+def frame_rows(B, L, seed):
+    """B rows of L normals; no sample is 0, so a frame element is 0 only where the window is."""
+    x = np.random.default_rng(seed).standard_normal((B, L)).astype(np.float32)
+    return np.where(x == 0, F32(1.0), x)
+
+
+def frame_ld(T):
+    return (T + 3) & ~3
+
+
+def packed_table(lengths, hop=FRAME_HOP, gap=FRAME_GAP):
+    """(first column, frames) of every row laid end to end with ``gap`` columns between neighbours, and T_tot."""
+    frames = [1 + n // hop for n in lengths]
+    first, t = [], 0
+    for n in frames:
+        first.append(t)
+        t += n + gap
+    return first, frames, t - gap
+
 
 # ---- linear interpolation
 INTERP_PLAIN = ((1, 1), (1, 9), (9, 1), (7, 14), (50, 21), (33, 100), (100, 33))

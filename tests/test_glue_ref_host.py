@@ -7,7 +7,9 @@ entry points, which need no device:
     its own mean in any arithmetic, so the normalised value is exactly 0 on both sides),
   * no atan2 / mag_pha input other than the deliberate exact zeros lies within 1e-3 of the branch cut (im = 0, re < 0),
   * the rows of the ragged interpolation cases have the batch's fp32 ratio, so "bitwise equal to the call on the row
-    alone" is a fair demand.
+    alone" is a fair demand,
+  * the float32 framing and ragged reflect-pad restatements (tests/test_gpu_framing_contract.py) equal torch's
+    F.pad(mode="reflect") + unfold x window on the CPU exactly.
 
     python -m pytest tests/test_glue_ref_host.py -q
 """
@@ -196,6 +198,47 @@ def test_pointwise_restatements_match_torch():
     assert np.array_equal(R.mask_mul(xx, mk), (torch.from_numpy(xx) * torch.from_numpy(mk).unsqueeze(1)).numpy())
 
 
+@pytest.mark.parametrize("n_fft,hop,L", [(R.FRAME_N_FFT, R.FRAME_HOP, n) for n in R.FRAME_RAGGED] + [(100, 7, 120)])
+def test_framing_restatement_is_torchs_padded_unfold_times_window(n_fft, hop, L):
+    """F.pad(reflect) + unfold + one fp32 multiply on the CPU: exactly the restatement, with and without a scale."""
+    assert R.FRAME_LS[0] == max(R.FRAME_RAGGED) and R.FRAME_LS[1] == R.FRAME_N_FFT // 2 + 1 == min(R.FRAME_RAGGED)
+    x, w = R.frame_rows(1, L, seed=4000 + L)[0], R.frame_window(n_fft)
+    assert (x != 0).all() and w[0] == 0 and (w[1:] != 0).all()
+    for scale in (None, 3.0, 1.25):
+        xs = torch.from_numpy(x) if scale is None else torch.from_numpy(x) * torch.tensor(scale, dtype=torch.float32)
+        padded = TF.pad(xs[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
+        want = (padded.unfold(0, n_fft, hop) * torch.from_numpy(w)).t().numpy()            # [n_fft, T]
+        got = R.stft_frames(x, w, hop, scale)
+        assert got.dtype == np.float32 and got.shape == (n_fft, 1 + L // hop) == want.shape
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), scale
+
+
+def test_ragged_and_packed_framing_restatements_place_the_rows():
+    lens = list(R.FRAME_RAGGED)
+    first, frames, T_tot = R.packed_table(lens)
+    assert frames == [1 + n // R.FRAME_HOP for n in lens] and T_tot == sum(frames) + R.FRAME_GAP * 2
+    x, w = R.frame_rows(3, max(lens), seed=4200), R.frame_window()
+    f_ld = R.frame_ld(T_tot)
+    assert f_ld % 4 == 0 and 0 < f_ld - T_tot < 4
+    rag = R.stft_frames_ragged(x, lens, w, R.FRAME_HOP, R.frame_ld(frames[0]))
+    for scale in (None, R.FRAME_SCALE):
+        pk = R.stft_frames_packed(x, lens, w, R.FRAME_HOP, first, f_ld, scale)
+        used = np.zeros(f_ld, bool)
+        for b, (s, n) in enumerate(zip(first, frames)):
+            want = R.stft_frames(x[b, :lens[b]], w, R.FRAME_HOP, None if scale is None else scale[b])
+            assert np.array_equal(pk[:, s:s + n], want) and (scale is not None or np.array_equal(rag[b, :, :n], want))
+            assert not rag[b, :, n:].any()
+            used[s:s + n] = True
+        assert not pk[:, ~used].any() and (pk[1:, used] != 0).all()
+    for L, pad in R.PAD_SHAPES:
+        xx = R.frame_rows(3, L, seed=4400 + L)
+        lens = [L, pad + 1, max(pad + 1, (2 * L) // 3)]
+        y = R.reflect_pad_ragged(xx, lens, pad)
+        for b, n in enumerate(lens):
+            want = TF.pad(torch.from_numpy(xx[b:b + 1, :n].copy())[None], (pad, pad), mode="reflect")[0, 0].numpy()
+            assert np.array_equal(y[b, :n + 2 * pad], want) and not y[b, n + 2 * pad:].any()
+
+
 def test_copy_views_are_the_denoisers_layouts():
     for shape in ((3, 5, 7), (2, 33, 129)):
         views = R.copy_views(shape, seed=1)
@@ -353,3 +396,37 @@ def test_entry_points_refuse_inconsistent_arguments(lib):
     assert L.hsp_mag_pha_f32(*_with(mp, 4, 1)) == E                             # one bin: no DC / Nyquist pair
     po = GOOD["hsp_polar_f32"][0]
     assert L.hsp_polar_f32(*_with(po, 4, 3)) == E and L.hsp_polar_f32(*_with(po, 6, 3)) == E
+
+
+def test_framing_launchers_refuse_what_distinguishes_them(lib):
+    """Plain takes any T whose last frame's centre lies inside the signal, ragged exactly T = 1 + L / hop and a lengths
+    pointer, packed a checked segment table with no row above 1 + L / hop frames.  (The accepted controls need real
+    buffers: tests/test_gpu_framing_contract.py.)"""
+    import ctypes
+    E, L = lib.EINVAL, lib.lib()
+    n, n_fft, hop = 347, R.FRAME_N_FFT, R.FRAME_HOP
+    assert L.hsp_stft_frames_f32(P, P, Q, 1, n, n_fft, hop, 71, 72, None) == E            # (T - 1) hop > L
+    assert L.hsp_stft_frames_f32(P, P, Q, 1, n, n_fft, hop, 70, 69, None) == E            # f_ld < T
+    assert L.hsp_stft_frames_f32(P, P, Q, 1, n_fft // 2, n_fft, hop, 33, 36, None) == E   # L <= n_fft / 2
+    assert L.hsp_stft_frames_f32(P, P, Q, 65536, n, n_fft, hop, 70, 72, None) == E
+    for T in (69, 71):
+        assert L.hsp_stft_frames_ragged_f32(P, n, P, P, Q, 1, n, n_fft, hop, T, 72, None) == E
+    assert L.hsp_stft_frames_ragged_f32(P, n, None, P, Q, 1, n, n_fft, hop, 70, 72, None) == E     # NULL lengths
+    assert L.hsp_stft_frames_ragged_f32(P, n - 1, P, P, Q, 1, n, n_fft, hop, 70, 72, None) == E    # x_bs < L
+
+    def packed(table, T_tot, f_ld, n_=n, B=None):
+        host = (ctypes.c_int32 * len(table))(*table)
+        return L.hsp_stft_frames_packed_f32(P, n, P, None, P, Q, P, ctypes.cast(host, ctypes.c_void_p),
+                                            len(table) // 2 if B is None else B, n_, n_fft, hop, T_tot, f_ld, None)
+
+    assert packed([0, 71], 71, 72) == E                       # 71 frames > 1 + 347 / 5
+    assert packed([3, 70], 70, 72) == E                       # the segment ends past T_tot
+    assert packed([0, 70], 70, 69) == E                       # f_ld < T_tot
+    assert packed([0, 33], 33, 36, n_=160) == E               # L <= n_fft / 2
+    assert packed([0, 70, 69, 70], 139, 140) == E             # overlapping segments
+    assert packed([73, 70, 0, 70], 143, 144) == E             # not ascending
+    assert packed([0, 70], 70, 72, B=0) == E
+    assert L.hsp_stft_frames_packed_f32(P, n, P, None, P, Q, P, None, 1, n, n_fft, hop, 70, 72, None) == E   # no host table
+    rr = [P, 350, P, Q, 374, 2, 300, 37, 374, None]           # hsp_reflect_pad_ragged_f32: Lo = L + 2 pad, pitches above
+    for at, bad in ((1, 299), (4, 373), (8, 375), (7, 300), (7, -1), (5, 65536), (0, None), (3, None)):
+        assert L.hsp_reflect_pad_ragged_f32(*_with(rr, at, bad)) == E, (at, bad)

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): batched voice conversion.  The new entry points of csrc/hsp_vcbatch.hip against NumPy / torch
+"""GPU (-m gpu): batched voice conversion.  The per-row-length entry points of include/hsp.h against NumPy / torch
 restatements at ragged lengths, the ragged prompt mel and wav2vec2 against per-row calls, and inference_vc.vc_batch /
 vc_batch_files against the parity contract of DESIGN.md §4.5 (row b is held to vc() on row b alone)."""
 import types
