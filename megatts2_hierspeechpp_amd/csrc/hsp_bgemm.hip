@@ -491,10 +491,9 @@ int bg_go(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
 // Host side: eligibility + tile choice + launch; called by the conv dispatcher ahead of the latency-oriented
 // register path.  Returns -1 when the shape is not one this kernel takes.
 int hsp_bgemm_try(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (HSP_TG_DBG(a, HSP_TG_BG_OFF)) return -1;
   if (!hsp_tg_eligible(a) || a.x_ts != 1) return -1;
-  if ((a.Cin & 3) || (a.ncols & 3) || (a.x_bs & 3) || (a.x_cs & 3) || !al16(a.x) || !al16(a.w) || (a.w_ld & 3)) return -1;
+  if ((a.Cin & 3) || (a.ncols & 3) || (a.x_bs & 3) || (a.x_cs & 3) || !hsp_aligned16(a.x) || !hsp_aligned16(a.w) || (a.w_ld & 3)) return -1;
   if (a.Cin < 96 || a.Cin > 8192) return -1;
   if (a.act != HSP_ACT_NONE && a.act != HSP_ACT_RELU && a.act != HSP_ACT_GELU_TANH) return -1;
   // the epilogues address a row as uniform base + 32-bit lane offset and test bounds per group of four rows

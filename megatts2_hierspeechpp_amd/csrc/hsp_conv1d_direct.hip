@@ -215,10 +215,9 @@ bool linear_vec_fast(const hsp_conv1d_args& a) {
 }
 
 bool cout1_fast(const hsp_conv1d_args& a) {
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   return a.Cout == 1 && a.stride == 1 && a.dil == 1 && a.K <= 9 && (a.K & 1) && a.pad == (a.K - 1) / 2 && a.x_ts == 1 &&
-         a.Lin == a.Lout && (a.Lin & 3) == 0 && (a.x_cs & 3) == 0 && (a.x_bs & 3) == 0 && (a.y_bs & 3) == 0 && al16(a.x) &&
-         al16(a.y) && a.prologue == HSP_PRO_NONE && !a.cbias && !a.cscale && !a.res && !a.accumulate &&
+         a.Lin == a.Lout && (a.Lin & 3) == 0 && (a.x_cs & 3) == 0 && (a.x_bs & 3) == 0 && (a.y_bs & 3) == 0 && hsp_aligned16(a.x) &&
+         hsp_aligned16(a.y) && a.prologue == HSP_PRO_NONE && !a.cbias && !a.cscale && !a.res && !a.accumulate &&
          a.mask_mode == HSP_MASK_NONE && (int64_t)a.Cin * a.K <= C1_MAXW;
 }
 

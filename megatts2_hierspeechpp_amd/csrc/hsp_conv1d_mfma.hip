@@ -89,10 +89,10 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
     return gated ? hsp_conv_tile_S64GW(a, epi, act, s, plan_out) : hsp_conv_tile_S64W(a, epi, act, s, plan_out);
 #ifdef HSP_TUNING
   // force a tile shape (results stay right)
-  if (!gated && a.debug & 256) return hsp_conv_tile_M128(a, epi, act, s, plan_out);
-  if (!gated && a.debug & 1024) return hsp_conv_tile_M64(a, epi, act, s, plan_out);
-  if (!gated && a.debug & 4096) return hsp_conv_tile_S64(a, epi, act, s, plan_out);
-  if (!gated && a.debug & 8192) return hsp_conv_tile_M64P(a, epi, act, s, plan_out);
+  if (!gated && HSP_DBG(a, HSP_CV_TILE_M128)) return hsp_conv_tile_M128(a, epi, act, s, plan_out);
+  if (!gated && HSP_DBG(a, HSP_CV_TILE_M64)) return hsp_conv_tile_M64(a, epi, act, s, plan_out);
+  if (!gated && HSP_DBG(a, HSP_CV_TILE_S64)) return hsp_conv_tile_S64(a, epi, act, s, plan_out);
+  if (!gated && HSP_DBG(a, HSP_CV_TILE_M64P)) return hsp_conv_tile_M64P(a, epi, act, s, plan_out);
 #endif
   if (short_seq) {
     if (gated) {
@@ -101,10 +101,10 @@ int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
       // at 8 x 200 frames: 57.9 -> 40.3 us, at 1 x 200: 56.3 -> 39.0).  Only up to 48 such tiles (a request of up to four
       // utterances): in the 32-utterance step the four batch groups of the front part run on four streams and fill the idle
       // CUs with each other's launches -- there the wider footprint LOSES (same box: 57.5-57.6 -> 57.8 ms per step with
-      // the split tile on the 96-tile in-layers, profiles/r05_ab_s64g2*.json).  Tuning bits: 1 << 27 never, 1 << 28 up to
-      // 512 tiles.
+      // the split tile on the 96-tile in-layers, profiles/r05_ab_s64g2*.json).  Tuning bits: HSP_CV_NO_S64G2 never,
+      // HSP_CV_S64G2_512 up to 512 tiles.
       const int64_t t128 = hsp_tile_count(a, 64, 128);
-      if ((t128 <= 48 || (HSP_DBG(a, 1 << 28) && t128 <= 512)) && !HSP_DBG(a, 1 << 27)) {
+      if ((t128 <= 48 || (HSP_DBG(a, HSP_CV_S64G2_512) && t128 <= 512)) && !HSP_DBG(a, HSP_CV_NO_S64G2)) {
         if (a.fold_cols && hsp_conv_tile_S64G2(plain, epi, act, nullptr, probe) != HSP_EINVAL) return HSP_EINVAL;
         const int e = hsp_conv_tile_S64G2(a, epi, act, s, plan_out);
         if (e != HSP_EINVAL) return e;

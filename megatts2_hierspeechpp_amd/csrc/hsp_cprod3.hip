@@ -37,10 +37,17 @@ constexpr int CP_WS = 3 * CP_KC * CP_BM;          // floats of the weight slabs 
 constexpr int CP_XS = 2 * CP_KC * CP_BN;          // floats of the spectrum windows: [2][KC][BN]
 constexpr int CP_BUF = CP_WS + CP_XS;             // one half of the double buffer: 28 KB
 constexpr int CP_THREADS = 512;
-// tuning build only (hsp_cprod3_args.debug, refused by the release library): 1 producers stage chunk 0 only, 2 no MFMAs,
-// 16 no epilogue, 2048 no barriers, 4096 no narrow consumer for partial column tiles, 8192 no fragment sums, 16384 the plain block order -- results are
-// then wrong
-#define CP_BARRIER(a) do { if (!HSP_DBG(a, 2048)) lds_barrier(); } while (0)
+// tuning bits (hsp_cprod3_args.debug: this struct's own word; tuning build only, refused by the release library)
+enum : int32_t {
+  CP_DBG_ONE_CHUNK = 1,         // producers stage chunk 0 only (wrong results)
+  CP_DBG_NO_MFMA = 2,           // no MFMAs (wrong results)
+  CP_DBG_NO_EPILOGUE = 16,      // no epilogue (wrong results)
+  CP_DBG_NO_BARRIER = 2048,     // no chunk barriers (wrong results)
+  CP_DBG_NO_NARROW = 4096,      // no narrow consumer for partial column tiles
+  CP_DBG_NO_FRAG_SUMS = 8192,   // no VALU between the MFMAs: the fragment sums are skipped (wrong results)
+  CP_DBG_PLAIN_ORDER = 16384,   // the plain block order
+};
+#define CP_BARRIER(a) do { if (!HSP_DBG(a, CP_DBG_NO_BARRIER)) lds_barrier(); } while (0)
 
 template <int OFF>
 __device__ __forceinline__ void cp_rd(float& dst, unsigned addr) {
@@ -65,7 +72,7 @@ __device__ __forceinline__ void cp_issue(CpFrag<NB>& f, unsigned va, unsigned vb
   if constexpr (NB > 1) cp_rd<B0 + CP_KC * CP_BN * 4 + 128>(f.i[1], vb);
 }
 // the set is valid behind the wait; re-defining its registers there gives every consumer a data dependency on the wait
-// (hsp_conv1d_mfma_kernel.h: wait_frags)
+// (hsp_conv1d_consume.h: wait_frags)
 template <int NB>
 __device__ __forceinline__ void cp_bind(CpFrag<NB>& f) {
 #pragma unroll
@@ -101,13 +108,13 @@ __device__ __forceinline__ void cp_consume(const hsp_cprod3_args& a, float* cons
   const unsigned aB = lds_addr(lds + CP_WS + half * CP_BN + wn * 64 + l32);
   CpFrag<NB> f0, f1;
   auto mma = [&](CpFrag<NB>& f) __attribute__((always_inline)) {
-    if (HSP_DBG(a, 2)) return;
+    if (HSP_DBG(a, CP_DBG_NO_MFMA)) return;
     // Xr + Xi and Xi - Xr on the fragments: counted VALU instructions between the wait and the first MFMA
     float s[NB], d[NB];
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
-      s[n] = HSP_DBG(a, 8192) ? f.i[n] : f.r[n] + f.i[n];       // (tuning bit 8192: no VALU between the MFMAs)
-      d[n] = HSP_DBG(a, 8192) ? f.i[n] : f.i[n] - f.r[n];
+      s[n] = HSP_DBG(a, CP_DBG_NO_FRAG_SUMS) ? f.i[n] : f.r[n] + f.i[n];
+      d[n] = HSP_DBG(a, CP_DBG_NO_FRAG_SUMS) ? f.i[n] : f.i[n] - f.r[n];
     }
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
@@ -122,7 +129,7 @@ __device__ __forceinline__ void cp_consume(const hsp_cprod3_args& a, float* cons
   for (int c = 0; c < nchunks; ++c) {
     // eight k-steps, fully unrolled: the reads of step S + 1 go out behind the wait that retires step S's and BEFORE
     // step S's MFMAs; the barrier that hands over chunk c + 1 sits between the last two MFMA groups of chunk c, and the
-    // first reads of chunk c + 1 go out behind it (hsp_conv1d_mfma_kernel.h: the fragment pipeline runs across chunks)
+    // first reads of chunk c + 1 go out behind it (hsp_conv1d_consume.h: the fragment pipeline runs across chunks)
     static_for<CP_KC / 2>([&](auto SS) __attribute__((always_inline)) {
       constexpr int S = decltype(SS)::value;
       CpFrag<NB>& cur = (S & 1) ? f1 : f0;
@@ -147,7 +154,7 @@ __device__ __forceinline__ void cp_consume(const hsp_cprod3_args& a, float* cons
       __builtin_amdgcn_sched_barrier(0);
     });
   }
-  if (HSP_DBG(a, 16)) return;
+  if (HSP_DBG(a, CP_DBG_NO_EPILOGUE)) return;
 
   // ---- epilogue: Yr = k1 - k3 -> row m, Yi = k1 + k2 -> row C + m; stores straight from the accumulator layout (one
   // instruction = two rows x 128 B), uniform row pointer + one per-lane offset per column block
@@ -194,7 +201,7 @@ __global__ __launch_bounds__(CP_THREADS, 4) void cprod3_kernel(const hsp_cprod3_
   int mt, nt, bin;
   {
     const int bid = blockIdx.x, T = n_mt * n_nt;
-    if ((a.bins & 7) == 0 && !HSP_DBG(a, 16384)) {
+    if ((a.bins & 7) == 0 && !HSP_DBG(a, CP_DBG_PLAIN_ORDER)) {
       const int q = bid >> 3, t = q % T;
       bin = (q / T) * 8 + (bid & 7);
       mt = t % n_mt;
@@ -211,7 +218,7 @@ __global__ __launch_bounds__(CP_THREADS, 4) void cprod3_kernel(const hsp_cprod3_
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------------ producers
     // A DMA instruction moves 1 KB: four slab rows (64 floats each) or two window rows (128 floats).  A lane's byte
-    // offset is computed once; the scalar unit walks the wave-uniform row base (hsp_conv1d_mfma_kernel.h: dma_w_fast).
+    // offset is computed once; the scalar unit walks the wave-uniform row base (hsp_conv1d_produce.h: dma_w_fast).
     const int pw = wave - 4;
     const bool full = n0 + CP_BN <= Np;                         // workgroup-uniform: no column of the tile is past Np
     const float* const wb = a.w + (int64_t)bin * 3 * C * C + m0;
@@ -239,7 +246,7 @@ __global__ __launch_bounds__(CP_THREADS, 4) void cprod3_kernel(const hsp_cprod3_
     wait_vm0();
     CP_BARRIER(a);
     for (int c = 0; c < nchunks; ++c) {
-      if (c + 1 < nchunks && !HSP_DBG(a, 1)) {
+      if (c + 1 < nchunks && !HSP_DBG(a, CP_DBG_ONE_CHUNK)) {
         stage((c + 1) * CP_KC, lds + ((c + 1) & 1) * CP_BUF);
         wait_vm0();
       }
@@ -251,7 +258,7 @@ __global__ __launch_bounds__(CP_THREADS, 4) void cprod3_kernel(const hsp_cprod3_
   // -------------------------------------------------------------------------------------------------- consumers
   const int wm = wave >> 1, wn = wave & 1;
   const int left = Np - (n0 + wn * 64);                         // columns from this wave's first block to the end of the bin
-  if (left > 32 || HSP_DBG(a, 4096)) {
+  if (left > 32 || HSP_DBG(a, CP_DBG_NO_NARROW)) {
     cp_consume<2>(a, lds, bin, m0, n0, wm, wn, lane, nchunks);
   } else if (left > 0) {
     cp_consume<1>(a, lds, bin, m0, n0, wm, wn, lane, nchunks);

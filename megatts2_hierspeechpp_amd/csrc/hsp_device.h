@@ -6,6 +6,9 @@
 
 #define HSP_WAVE 64
 
+// 16-B addressable: what a float4 access or a 16-B LDS-DMA lane needs of a pointer
+inline bool hsp_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // Raise a kernel's dynamic-LDS limit to `bytes` once per device.  hipFuncSetAttribute applies to the current
 // device only, so the "already raised" flag is kept per device (`flags`: one zero-initialised static array per
 // kernel instantiation).  Idempotent and safe from several host threads; kept out of the launch path afterwards

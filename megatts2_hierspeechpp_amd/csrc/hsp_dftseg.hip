@@ -91,7 +91,7 @@ __device__ __forceinline__ void ds_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // B operands come out of LDS through inline-asm reads in a ring of three register groups, two groups ahead of the MFMAs
 // that consume them: ONE MFMA wave per SIMD has nobody to hide its LDS latency behind, and the compiler's own schedule
 // recycled two registers (read, one MFMA, wait: 1.5-2 x the MFMA time).  A group is valid behind ds_wait<N>, which
-// re-defines its registers so that the consumers carry a data dependency on the wait (hsp_conv1d_mfma_kernel.h).
+// re-defines its registers so that the consumers carry a data dependency on the wait (hsp_conv1d_consume.h: wait_frags).
 __device__ __forceinline__ unsigned ds_lds_addr(const float* p) {
   return (unsigned)(size_t)(const __attribute__((address_space(3))) float*)p;
 }

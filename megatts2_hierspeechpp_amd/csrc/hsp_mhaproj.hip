@@ -114,9 +114,10 @@ __global__ __launch_bounds__(64 * MP_NW) void mha_proj_kernel(const hsp_mha_proj
   if constexpr (KL) Tk = (int)min(max(a.key_len[b], (int64_t)1), (int64_t)a.Tk);
   const int qi = min(i0 + x, Tq - 1);                 // this lane's query (clamped: surplus columns compute garbage nobody stores)
 #ifdef HSP_TUNING
-  // tuning build, debug bit 1: cycle-counter stamps of the middle workgroup's wave 0 -> a.cscale (10 x uint64; cscale unused)
-  unsigned long long* stamps = ((a.debug & 1) && blockIdx.x == gridDim.x / 2 && tid == 0) ? (unsigned long long*)a.cscale : nullptr;
-  const float* const cscale = (a.debug & 1) ? nullptr : a.cscale;
+  // tuning build, debug bit MP_DBG_STAMPS: cycle-counter stamps of the middle workgroup's wave 0 -> a.cscale (10 x uint64; cscale unused)
+  constexpr int MP_DBG_STAMPS = 1;
+  unsigned long long* stamps = ((a.debug & MP_DBG_STAMPS) && blockIdx.x == gridDim.x / 2 && tid == 0) ? (unsigned long long*)a.cscale : nullptr;
+  const float* const cscale = (a.debug & MP_DBG_STAMPS) ? nullptr : a.cscale;
 #define MP_STAMP(i) do { if (stamps) stamps[i] = __builtin_readcyclecounter(); } while (0)
 #else
   const float* const cscale = a.cscale;

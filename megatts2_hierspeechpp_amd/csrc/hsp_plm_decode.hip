@@ -283,8 +283,6 @@ int64_t attn_lds_bytes(int64_t D, int64_t H, int64_t F, int64_t n) {
   return (2 * D + 3 * Dhp + kPartFloats + 4 + n) * 4;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int hsp_plm_decode_supported(int32_t D, int32_t H, int32_t F) {
@@ -309,8 +307,8 @@ int64_t decode_args_lds(const hsp_plm_decode_args* a) {
   if (a->debug != 0 || a->B <= 0 || a->B > 65535 || a->t < 0 || (int64_t)a->t >= a->cs || a->bs < 0) return -1;
   if (a->x_bs < 0 || a->x_cs < 0 || a->y_bs < 0 || a->y_cs < 0 || !(a->eps >= 0.0f)) return -1;
   if (!hsp_plm_decode_supported(a->D, a->H, a->F)) return -1;
-  if (a->workspace_bytes < hsp_plm_decode_workspace_bytes(a->B, a->D) || !aligned16(a->workspace)) return -1;
-  if (!aligned16(a->wqkv_t) || !aligned16(a->wo_t) || !aligned16(a->w1_t) || !aligned16(a->w2_t)) return -1;
+  if (a->workspace_bytes < hsp_plm_decode_workspace_bytes(a->B, a->D) || !hsp_aligned16(a->workspace)) return -1;
+  if (!hsp_aligned16(a->wqkv_t) || !hsp_aligned16(a->wo_t) || !hsp_aligned16(a->w1_t) || !hsp_aligned16(a->w2_t)) return -1;
   const int64_t lds = attn_lds_bytes(a->D, a->H, a->F, (int64_t)a->t + 1);
   return lds > kLdsMax ? -1 : lds;   // more keys than one compute unit's LDS holds scores for
 }

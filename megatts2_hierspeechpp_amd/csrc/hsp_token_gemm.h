@@ -20,13 +20,15 @@
 #include "hsp_device.h"
 
 // ---- tuning bits of this family (hsp_conv1d_args.debug; libhsp_tune.so only, libhsp.so refuses a non-zero word)
+// The conv tiles read the same word (HSP_CV_* of hsp_conv1d_mfma_kernel.h); "CV:" marks a value that family uses too.
 enum : int32_t {
-  HSP_TG_NO_DMA = 1,             // block GEMM: no re-issue of a stage slot (wrong results)
-  HSP_TG_NO_MFMA = 2,            // both kernels: skip the main loop (wrong results)
+  HSP_TG_NO_DMA = 1,             // block GEMM: no re-issue of a stage slot (wrong results).  CV: HSP_CV_ONE_CHUNK, the same meaning
+  HSP_TG_NO_MFMA = 2,            // both kernels: skip the main loop (wrong results).  CV: HSP_CV_NO_MFMA, the same meaning
   HSP_TG_RG_64x32 = 8,           // register path: force the 64 x 32 tile
-  HSP_TG_RG_32x32 = 16,          // register path: force the 32 x 32 tile
+  HSP_TG_RG_32x32 = 16,          // register path: force the 32 x 32 tile.  CV: HSP_CV_NO_EPILOGUE, ANOTHER meaning
   HSP_TG_OFF = 128,              // dispatcher: no token GEMM at all (conv tiles)
   HSP_TG_BG_128x128 = 1 << 18, HSP_TG_BG_128x64 = 1 << 19, HSP_TG_BG_64x128 = 1 << 21, HSP_TG_BG_64x64 = 1 << 23,   // block GEMM: force a tile shape
+                                 // CV: 1 << 18 is HSP_CV_SHUF_SCALAR and 1 << 21 is HSP_CV_NO_HALF_CU, OTHER meanings
   HSP_TG_STAMPS = 1 << 20,       // both kernels: cycle-counter stamps of one workgroup -> a.filt
   HSP_TG_BG_OFF = 1 << 22,       // block GEMM: takes nothing
   HSP_TG_RG_ANY_SIZE = 1 << 24,  // dispatcher: ask the register path whatever the launch size

@@ -249,7 +249,7 @@ def _al16(a, name):
 
 
 def epilogue_kind(a):
-    """select_epilogue of csrc/hsp_conv1d_mfma_kernel.h:1226-1237 and the ACT1D rule of hsp_conv1d_mfma.hip:74."""
+    """select_epilogue of csrc/hsp_conv1d_mfma_kernel.h and the ACT1D rule of dispatch() in hsp_conv1d_mfma.hip."""
     if a["rows"] in (ROWS_GATE_WN, ROWS_GATE_GLU):
         return EPI_GATE
     pointwise = a["act"] != ACT_NONE or a["mask_mode"] != MASK_NONE or a.get("cscale") is not None
@@ -269,19 +269,19 @@ def epilogue_kind(a):
 
 
 def xvec(a):
-    """The 16-B window DMA of launch_one (hsp_conv1d_mfma_kernel.h:1217-1220); the 4-B one otherwise."""
+    """The 16-B window DMA: window_dma16 of hsp_conv1d_mfma_kernel.h; the 4-B one otherwise."""
     return (a["prologue"] != PRO_ACT1D and a["x_ts"] == 1 and a["Lin"] % 4 == 0 and a["x_cs"] % 4 == 0 and
             a["x_bs"] % 4 == 0 and _al16(a, "x"))
 
 
 # what tells two shapes of one (BM, BN) apart: name -> (gated rows, ACT1D prologue, halo (K - 1) dil + 3 > 64), None =
-# either.  hsp_conv1d_mfma.hip:80-114 and the instantiation table of hsp_conv1d_tile.hip (M64 / M32 exist with the
+# either.  dispatch() of hsp_conv1d_mfma.hip and supported<>() of hsp_conv1d_tile.hip (M64 / M32 exist with the
 # ACT1D prologue only, M64P / M32P without it only; gated rows exist on M128, S64G, S64GW and S64G2 only)
 TILE_RULES = dict(M128=(None, None, False), M64=(False, True, False), M64P=(False, False, False), M32=(False, True, False),
                   M32P=(False, False, False), S32=(False, None, False), S64=(False, None, False), S64W=(False, None, True),
                   S64G=(True, False, False), S64GW=(True, False, True), S64G2=(True, False, False))
 
-# Cfg<> of hsp_conv1d_mfma_kernel.h:1240-1250: name -> (producer waves NPW, window row pitch XWP = BN + slack)
+# the tile shapes (Cfg<>) at the bottom of hsp_conv1d_mfma_kernel.h: name -> (producer waves NPW, window row pitch XWP = BN + slack)
 TILE_CFG = dict(M128=(4, 192), M64=(8, 320), M32=(8, 576), M64P=(4, 320), M32P=(4, 576), S64=(4, 128), S64G=(4, 192),
                 S32=(4, 192), S64W=(4, 192), S64GW=(4, 256), S64G2=(4, 128))
 
@@ -296,7 +296,7 @@ def tile_of(a, bm, bn):
 
 
 def lds_bytes(tile, a, kc):
-    """Dynamic LDS of a launch of ``tile`` at chunk depth kc: make_plan of hsp_conv1d_mfma_kernel.h:98-116 -- two weight
+    """Dynamic LDS of a launch of ``tile`` at chunk depth kc: make_plan of hsp_conv1d_mfma_kernel.h -- two weight
     slabs K kc BM, two windows kc XWP and, under ACT1D, one scratch per producer wave.  The fourth number of
     hsp_conv1d_mfma_plan; it depends on the shape's pitch and producer count, which (BM, BN) alone do not give."""
     (bm, bn), (npw, xwp) = TILES[tile], TILE_CFG[tile]
@@ -307,20 +307,20 @@ def lds_bytes(tile, a, kc):
 
 
 def tail_schedule(a, tile):
-    """launch_one, hsp_conv1d_mfma_kernel.h:1201-1202: the narrow last column tile of the 128 x 128 INIT shape."""
+    """`tail` of launch_one (hsp_conv1d_mfma_kernel.h): the narrow last column tile of the 128 x 128 INIT shape."""
     n_nt = -(-a["ncols"] // 128)
     rem = a["ncols"] - (n_nt - 1) * 128
     return tile == "M128" and epilogue_kind(a) == EPI_INIT and a["prologue"] != PRO_ACT1D and n_nt >= 2 and rem <= 32
 
 
 def linear_vec_fast(a):
-    """csrc/hsp_conv1d_direct.hip:213-215."""
+    """linear_vec_fast of csrc/hsp_conv1d_direct.hip."""
     return (a["K"] == 1 and a["Lin"] == 1 and a["Lout"] == 1 and a["stride"] == 1 and a["pad"] == 0 and
             64 <= a["Cin"] <= 1024 and a["Cout"] >= 64)
 
 
 def cout1_fast(a):
-    """csrc/hsp_conv1d_direct.hip:217-223."""
+    """cout1_fast of csrc/hsp_conv1d_direct.hip."""
     K = a["K"]
     return (a["Cout"] == 1 and a["stride"] == 1 and a["dil"] == 1 and K <= 9 and K % 2 == 1 and a["pad"] == (K - 1) // 2 and
             a["x_ts"] == 1 and a["Lin"] == a["Lout"] and a["Lin"] % 4 == 0 and a["x_cs"] % 4 == 0 and a["x_bs"] % 4 == 0 and
@@ -330,7 +330,7 @@ def cout1_fast(a):
 
 
 def direct_kernel(a):
-    """Which of the three kernels hsp_conv1d_direct_f32 launches (the order of csrc/hsp_conv1d_direct.hip:238-262)."""
+    """Which of the three kernels hsp_conv1d_direct_f32 launches (the order in that entry point)."""
     return "linear_vec" if linear_vec_fast(a) else ("cout1" if cout1_fast(a) else "generic")
 
 
@@ -469,6 +469,24 @@ def _mfma_specs():
     return s
 
 
+def _chunk_specs():
+    """MFMA cases that stage at least three chunks (every case of _mfma_specs stages one, its ACT1D ones at Cin = 12 two):
+    the producers' "stage c + 1 while c is multiplied" with its buffer flip, the consumers' fragment pipeline across the
+    chunk barrier, the ACT1D raw-row look-ahead to c + 2.  test_conv_ref_host.py reads each case's chunk depth from the
+    library's plan.  (Behind the direct cases in SPECS: a case's seed is its index there.)"""
+    lin = dict(bias=True, scale=0.75)
+    gfull = dict(bias=True, cbias=True, cscale=True, res=True, scale=0.75, post_scale=0.5, accumulate=True)
+    return [
+        _c("S64_INIT_chunks3_fast", "S64", Cin=192, Cout=64, L=72, bias=True, res=True),   # full row tile, Cin % KC == 0
+        _c("S64_VEC_chunks3_cin_tail", "S64", Cin=136, Cout=40, L=72, **lin),              # partial row tile, 8-channel tail
+        _c("S64_GEN_chunks3_dma4", "S64", Cin=136, Cout=40, L=73, **lin),                  # the same on the 4-B window DMA
+        _c("S64_INIT_act1d_chunks3", "S64", Cin=20, Cout=37, L=72, prologue=PRO_ACT1D, bias=True, res=True),
+        _c("S64G2_GATE_wn_h32_chunks3", "S64G2", H=32, Cin=136, L=72, rows=ROWS_GATE_WN, mask_mode=MASK_BOTH, **gfull),
+        _c("M128_INIT_chunks3_tail_rem1", "M128", Cin=40, Cout=68, B=1, L=LONG, bias=True, res=True),
+        _c("M128_INIT_act1d_chunks3", "M128", Cin=20, Cout=68, B=1, L=LONG + 35, prologue=PRO_ACT1D, bias=True, res=True),
+    ]
+
+
 def _direct_specs():
     chain = dict(FULL, mask_mode=MASK_BOTH, act=ACT_GELU_TANH)
     s = [
@@ -503,7 +521,7 @@ def _direct_specs():
     return s
 
 
-SPECS = _mfma_specs() + _direct_specs()
+SPECS = _mfma_specs() + _direct_specs() + _chunk_specs()
 for _i, _s in enumerate(SPECS):
     _s.setdefault("entry", "mfma")
     _s["seed"] = 5000 + _i

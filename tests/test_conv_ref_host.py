@@ -172,6 +172,28 @@ def test_mfma_case_takes_the_conv_tile_its_id_names(id, L):
     assert a["B"] * a["Cout"] * a["Lout"] <= 1_300_000
 
 
+CHUNKS3 = [id for id in MFMA if "chunks3" in id]
+
+
+def test_chunks3_cases_stage_at_least_three_chunks(L):
+    """The chunk depth KC is the library's own (third number of the plan): a `chunks3` case walks its input channels in
+    at least three chunks, so the producers refill both halves of the double buffer and the consumers' fragment pipeline
+    crosses two chunk barriers; under ACT1D the raw-row look-ahead to chunk c + 2 runs."""
+    assert len(CHUNKS3) == 7
+    for id in CHUNKS3:
+        a, _, _ = R.case(id)
+        rc, (_, _, kc, _) = _plan(L, a)
+        assert rc == 0 and kc > 0, (id, rc, kc)
+        assert -(-a["Cin"] // kc) >= 3, f"{id}: Cin {a['Cin']} at KC {kc} is {-(-a['Cin'] // kc)} chunk(s)"
+    by = {id: R.case(id)[0] for id in CHUNKS3}
+    assert sum(a["prologue"] == R.PRO_ACT1D for a in by.values()) == 2
+    fast = by["S64_INIT_chunks3_fast"]   # the fast staging's preconditions: no channel tail, 16-B window, full row tiles
+    assert fast["Cin"] % _plan(L, fast)[1][2] == 0 and R.xvec(fast) and fast["Cout"] % R.TILES["S64"][0] == 0
+    assert by["S64_VEC_chunks3_cin_tail"]["Cin"] % _plan(L, by["S64_VEC_chunks3_cin_tail"])[1][2] == 8
+    assert R.xvec(by["S64_VEC_chunks3_cin_tail"]) and not R.xvec(by["S64_GEN_chunks3_dma4"])
+    assert R.tail_schedule(by["M128_INIT_chunks3_tail_rem1"], "M128")
+
+
 # (shape, epilogue kind, ACT1D prologue) the library instantiates: supported<>() of csrc/hsp_conv1d_tile.hip
 PLAIN_SHAPES = ("M128", "M64P", "M32P", "S64", "S64W", "S32")
 EXISTS = {(t, e, False) for t in PLAIN_SHAPES for e in ("INIT", "VEC", "SHUF", "GEN")} | \

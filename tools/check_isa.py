@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """ISA lint of the hand-placed LDS fragment reads (`make -C megatts2_hierspeechpp_amd/csrc check-isa`).
 
-The MFMA consumer loops of hsp_conv1d_mfma_kernel.h, hsp_cprod3.hip, hsp_dftseg.hip, hsp_bgemm.hip and hsp_mhaproj.hip fetch
+The MFMA consumer loops of hsp_conv1d_consume.h, hsp_cprod3.hip, hsp_dftseg.hip, hsp_bgemm.hip and hsp_mhaproj.hip fetch
 their operands with inline-asm `ds_read_b32` and make them valid with an explicit `s_waitcnt lgkmcnt(N)` placed by hand.
 The compiler does not know that the "=v" output of such a read is not valid yet: nothing in the language stops it from
 COPYING the register (v_mov), SPILLING it (scratch_store / buffer_store) or feeding it to an instruction between the read
 and the wait -- silently wrong audio (hsp_bgemm.hip:69-72 records the one time it happened).  The sources bind every
-fragment register behind its wait (hsp_conv1d_mfma_kernel.h: wait_frags), which removes the known cause; this script turns
+fragment register behind its wait (hsp_conv1d_consume.h: wait_frags), which removes the known cause; this script turns
 the remaining "what if a future compiler / edit does it anyway" into a build error.
 
 For every kernel of every assembly file given (hipcc -S --cuda-device-only): walk the instructions in program order with

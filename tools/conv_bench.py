@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of one fused conv shape (for kernel tuning / PMC profiling).
-   python tools/conv_bench.py --cin 512 --cout 512 --k 11 --dil 1 --len 800 --batch 32 --act 1 --reps 20"""
+   python tools/conv_bench.py --cin 512 --cout 512 --k 11 --dil 1 --len 800 --batch 32 --act 1 --reps 20
+   python tools/conv_bench.py --gated 1 --cin 192 --cout 192 --k 5 --len 200 --batch 8 --act 0 --reps 200
+      (a WN in-layer: 2 x cout gated rows with bias and a conditioning bias, cout channels out)"""
 import argparse
 import os
 import sys
@@ -20,6 +22,7 @@ ap.add_argument("--len", type=int, default=800)
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--act", type=int, default=1)
 ap.add_argument("--res", type=int, default=0)
+ap.add_argument("--gated", type=int, default=0, help="WN gated rows: 2 * cout rows + conditioning bias -> cout channels")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--debug", type=int, default=0)
 ap.add_argument("--actonly", type=int, default=0, help="time the stand-alone activation kernel instead")
@@ -32,7 +35,8 @@ torch.manual_seed(0)
 class M(torch.nn.Module):
     def __init__(self):
         super().__init__()
-        self.conv = hip_layers.Conv1d(a.cin, a.cout, a.k, dilation=a.dil, padding=(a.k - 1) * a.dil // 2)
+        self.conv = hip_layers.Conv1d(a.cin, a.cout * (2 if a.gated else 1), a.k, dilation=a.dil, padding=(a.k - 1) * a.dil // 2,
+                                      rows=hip_layers.L.ROWS_GATE_WN if a.gated else hip_layers.L.ROWS_PLAIN)
         self.act = Activation1d(activations.SnakeBeta(a.cin, alpha_logscale=True))
 
 
@@ -45,7 +49,9 @@ hip_layers.finalize(m, dev)
 x = torch.randn(a.batch, a.cin, a.len, device=dev)
 res = torch.randn(a.batch, a.cout, a.len, device=dev) if a.res else None
 out = torch.empty(a.batch, a.cout, a.len, device=dev)
-run = (lambda: m.act(x)) if a.actonly else (lambda: m.conv(x, act1d=m.act if a.act else None, res=res, out=out))
+cbias = torch.randn(a.batch, 2 * a.cout, device=dev) if a.gated else None
+run = (lambda: m.act(x)) if a.actonly else \
+    (lambda: m.conv(x, act1d=m.act if a.act else None, res=res, out=out, cbias=cbias))
 for _ in range(3):
     run()
 torch.cuda.synchronize()
@@ -56,9 +62,10 @@ for _ in range(a.reps):
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / a.reps
-fl = 2.0 * a.batch * a.cout * a.cin * a.k * a.len
+fl = 2.0 * a.batch * a.cout * (2 if a.gated else 1) * a.cin * a.k * a.len
 if a.actonly:
     gb = 8.0 * a.batch * a.cin * a.len / 1e9
     print(f"act1d C {a.cin} L {a.len} B {a.batch}: {ms*1e3:9.1f} us  {gb/ms*1e3:7.1f} GB/s")
     sys.exit(0)
-print(f"cin {a.cin} cout {a.cout} k {a.k} dil {a.dil} L {a.len} B {a.batch} act {a.act} dbg {a.debug}: {ms*1e3:9.1f} us  {fl/ms/1e9:7.2f} TF/s")
+print(f"cin {a.cin} cout {a.cout}{' gated' if a.gated else ''} k {a.k} dil {a.dil} L {a.len} B {a.batch} act {a.act} dbg {a.debug}: "
+      f"{ms*1e3:9.2f} us  {fl/ms/1e9:7.2f} TF/s")
