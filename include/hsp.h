@@ -787,6 +787,76 @@ int hsp_loudness_f32(const float* x, int64_t x_bs, const int64_t* lengths, int32
 int hsp_loudness_gains_f32(const float* lufs, const float* peak, float target_lufs, float ceiling, float* gains,
                            int32_t* limited, int32_t B, void* stream);
 
+/* ------------------------------------------------ true-peak meter and look-ahead limiter (additive: HSP_VERSION
+ * unchanged; csrc/hsp_limiter.hip).  The gain above caps a whole row where its sample peak would pass
+ * the ceiling, and the row then comes out under the target.  The limiter pulls down the peaks alone, so that the row
+ * can take the gain its loudness asks for, and the ceiling it keeps is a true-peak ceiling.  Launches only, no
+ * read-back: the chain meter -> gain -> limiter -> meter -> ... -> int16 (functional.lufs_limit_int16) can be captured.
+ *
+ * Per row b: n_b = lengths[b] clamped into [0, n] (device int64 [B]; NULL = all n), G_b = gains[b] (device fp32 [B];
+ * NULL = 1), y[i] = fl(G_b x[b, i]) for 0 <= i < n_b and y = 0 elsewhere.  Samples at and after n_b are never read.
+ *
+ * Interpolator.  F = 192000 / rate phases (12, 8, 4 at 16, 24, 48 kHz: the standard's 4x at 48 kHz, held at 192 kHz
+ * for the lower rates), Z = 6, 2Z taps per phase: h_p[d] = sinc(d - p/F) kaiser_8(|d - p/F| / Z), d = -(Z-1) ... Z,
+ * kaiser_beta(u) = I0(beta sqrt(1 - u^2)) / I0(beta).  The bank is built by the caller in double and passed as device
+ * fp32 [F][2Z] (tap d at index d + Z - 1); phase 0 must be the unit impulse exactly, so that a true peak is never
+ * below the sample peak.  u[i, p] = sum_d h_p[d] y[i + d] (taps ascending, one fma chain from 0),
+ * P[i] = max_p |u[i, p]| for 0 <= i < n_b.
+ * True peak: tp[b] = max_i P[i], 0 for an empty row.
+ *
+ * Limiter.  Ceiling c > 0 (linear, 1 = full scale), look-ahead W samples, 1 <= W <= 480.
+ *   p2[i] = max(P[i-1], P[i]), P[-1] = 0
+ *   r[i]  = min(1, c / p2[i]), 1 where p2[i] = 0, and r = 1 outside [0, n_b).  The fp32 quotient is stepped down by
+ *           one float where fl(r p2) > c: rounding is monotone, so fl(s |y[i]|) <= c for every s <= r[i].
+ *   m[k]  = min_{|j| <= W} r[k + j] for every integer k (not only inside the row: padding m with ones at the row ends
+ *           would let the mean below rise above r over the last W samples)
+ *   s[i]  = min(r[i], 1 - sum_{|j| <= W} w[j] (1 - m[i + j])), w[j] = (1 + cos(pi j / (W + 1))) / (2 W + 2): the
+ *           weights sum to 1, so this is the weighted mean of m, formed from 1 - m so that it is exactly 1 where the
+ *           limiter is idle (w formed in double and rounded to fp32; the sum runs j ascending in one fma chain from 0)
+ *   z[i]  = fl(s[i] y[i]) for i < n_b, 0 for n_b <= i < n;  min_gain[b] = min_i s[i], 1 for an empty row.
+ * Every m[i + j] with |j| <= W contains r[i], so the weighted mean is at most r[i] in exact arithmetic; the outer min
+ * makes |z[i]| <= c hold in fp32 on every sample.  All windows are finite: one workgroup per (row, tile of 2048
+ * samples, origin at the row start) computes its tile from the samples around it.  tp and min_gain are a max and a
+ * min, folded over the tiles with integer atomics on the floats' bit patterns into outputs preset on the same stream:
+ * bit-reproducible, and row b of a batch is bit-identical to the call on row b alone.
+ * hsp_limiter_args.tp (may be NULL): the true peak of y, the limiter's input, from the P it computes anyway.
+ * HSP_EINVAL before any HIP call: a null pointer (lengths, gains and hsp_limiter_args.tp excepted), B < 1 or > 65535,
+ * n < 1, a row stride below n, F not in {4, 8, 12}, Z != 6, W < 1 or > 480, a ceiling that is not finite and positive. */
+typedef struct {
+  const float* x;
+  int64_t x_bs;
+  const int64_t* lengths;
+  const float* gains;
+  int32_t B;
+  int64_t n;
+  const float* bank;
+  int32_t F, Z, W;
+  float ceiling;
+  float* y; /* z of the text above: [B, n], row stride y_bs */
+  int64_t y_bs;
+  float* min_gain;
+  float* tp;
+} hsp_limiter_args;
+int hsp_true_peak_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* gains, int32_t B, int64_t n,
+                      const float* bank, int32_t F, int32_t Z, float* tp, void* stream);
+int hsp_limiter_f32(const hsp_limiter_args* a, void* stream);
+/* gains_out[b] = gains_in[b] 10^((target_lufs - lufs[b]) / 20), formed in double, rounded once; a loudness that is not
+ * finite leaves the gain unchanged.  gains_in NULL: the first gain of a row, from 1 -- and 0 for a row without a
+ * loudness (-inf: silence), which is then written as zeros.  gains_out may be gains_in.  HSP_EINVAL: NULL lufs or
+ * gains_out, B < 1, a target that is not finite. */
+int hsp_gain_update_f32(const float* gains_in, const float* lufs, float target_lufs, float* gains_out, int32_t B,
+                        void* stream);
+/* The safety scale that ends the chain, and the stats it reports: q[b] = min(1, ceiling / tp[b]) (1 where tp = 0;
+ * stepped down like r above, so fl(q tp) <= ceiling), achieved_lufs[b] = lufs[b] + 20 log10 q[b] (in double),
+ * true_peak[b] = fl(tp[b] q[b]).  HSP_EINVAL: a null pointer, B < 1, a ceiling that is not finite and positive. */
+int hsp_limiter_stats_f32(const float* lufs, const float* tp, float ceiling, float* q, float* achieved_lufs,
+                          float* true_peak, int32_t B, void* stream);
+/* out[b, i] = (int16) fl(fl(x[b, i] gains[b]) 32767) over the first lengths[b] samples (NULL = all n), zeros after:
+ * truncated toward zero and saturating, as hsp_peak_int16 converts.  HSP_EINVAL: NULL x, gains or out, B < 1 or
+ * > 65535, n < 1, x_bs < n, o_bs < n. */
+int hsp_gain_int16_f32(const float* x, int64_t x_bs, const int64_t* lengths, const float* gains, int16_t* out,
+                       int64_t o_bs, int32_t B, int64_t n, void* stream);
+
 /* ------------------------------------------------ prompt ingest: sinc resampling to 16 kHz
  * torchaudio.functional.resample (0.13.1: _get_sinc_resample_kernel + _apply_sinc_resample_kernel) of the reference
  * harnesses (inference_plm.py:124-126, inference.py:122-124, inference_vc.py:76-78,101-103, inference_speechsr.py:32-34):

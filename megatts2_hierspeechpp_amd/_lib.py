@@ -142,6 +142,15 @@ class ProsodyArgs(C.Structure):
     ]
 
 
+class LimiterArgs(C.Structure):
+    """Mirror of ``hsp_limiter_args``."""
+    _fields_ = [
+        ("x", _fp), ("x_bs", C.c_int64), ("lengths", _fp), ("gains", _fp), ("B", C.c_int32), ("n", C.c_int64),
+        ("bank", _fp), ("F", C.c_int32), ("Z", C.c_int32), ("W", C.c_int32), ("ceiling", C.c_float),
+        ("y", _fp), ("y_bs", C.c_int64), ("min_gain", _fp), ("tp", _fp),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -245,6 +254,11 @@ SIGNATURES = {
     "hsp_loudness_coefs_f64": (C.c_int, [C.c_int32, _fp]),
     "hsp_loudness_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp]),
     "hsp_loudness_gains_f32": (C.c_int, [_fp, _fp, C.c_float, C.c_float, _fp, _fp, C.c_int32, _fp]),
+    "hsp_true_peak_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp]),
+    "hsp_limiter_f32": (C.c_int, [C.POINTER(LimiterArgs), _fp]),
+    "hsp_gain_update_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, C.c_int32, _fp]),
+    "hsp_limiter_stats_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, _fp, _fp, C.c_int32, _fp]),
+    "hsp_gain_int16_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
     "hsp_resample_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, _fp, C.c_int64, C.c_int32, _fp]),
     "hsp_copy_strided_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32,

@@ -381,6 +381,145 @@ def lufs_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.0, cei
     return peak_int16_gains(a, lengths, gains)
 
 
+# ---------------------------------------------------------------- true peak and look-ahead limiter
+TRUE_PEAK_RATE = 192000   # the interpolated rate: the standard's 4x at 48 kHz, held for the lower rates
+TRUE_PEAK_Z = 6           # 2 Z taps per phase
+TRUE_PEAK_BETA = 8.0
+_TRUE_PEAK_BANKS = {}
+
+
+def true_peak_bank_f64(fs: int):
+    """The interpolator of include/hsp.h in float64: [F][2 Z], F = 192000 / fs, tap d = -(Z - 1) ... Z at index
+    d + Z - 1, h_p[d] = sinc(d - p / F) * kaiser_8(|d - p / F| / Z); phase 0 is the unit impulse exactly."""
+    import numpy as np
+    fs = int(fs)
+    if fs not in (16000, 24000, 48000):
+        raise L.HspError(f"true peak: sample rate {fs} is not 16000, 24000 or 48000")
+    F, Z = TRUE_PEAK_RATE // fs, TRUE_PEAK_Z
+    t = np.arange(-(Z - 1), Z + 1, dtype=np.float64)[None, :] - np.arange(F, dtype=np.float64)[:, None] / F
+    u = np.minimum(np.abs(t) / Z, 1.0)
+    bank = np.sinc(t) * np.i0(TRUE_PEAK_BETA * np.sqrt(1.0 - u * u)) / np.i0(TRUE_PEAK_BETA)
+    bank[0] = 0.0
+    bank[0, Z - 1] = 1.0
+    return bank
+
+
+def true_peak_bank(fs: int, device=None):
+    """-> (float64 bank [F][2 Z] on the host, the same bank as fp32 on ``device``), built once per (rate, device); a call
+    inside a stream capture needs that upload done by an eager call first."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (int(fs), device)
+    got = _TRUE_PEAK_BANKS.get(key)
+    if got is None:
+        hb = true_peak_bank_f64(fs)
+        if torch.cuda.is_current_stream_capturing():
+            raise L.HspError("true peak: the bank of this rate is not uploaded yet; make one eager call before "
+                             "capturing the stream")
+        got = (hb, torch.from_numpy(hb.astype("float32")).to(device))
+        _TRUE_PEAK_BANKS[key] = got
+    return got
+
+
+def _rows_gains(audio, gains):
+    a = audio.reshape(audio.shape[0], -1) if audio.dim() == 3 else audio
+    assert a.dim() == 2 and a.stride(1) == 1
+    if gains is not None:
+        assert gains.shape == (a.shape[0],)
+        gains = _c(gains)
+    return a, gains
+
+
+def true_peak(audio, sample_rate: int, lengths=None, gains=None):
+    """True peak of every row (hsp_true_peak_f32): [B, 1, n] / [B, n] fp32 at 16, 24 or 48 kHz, ``lengths`` int64 [B]
+    (None = all n), ``gains`` device fp32 [B] applied first (None = 1) -> fp32 [B] (linear, 1 = full scale) on the
+    device.  Never below the row's sample peak; 0 for an empty row."""
+    a, gains = _rows_gains(audio, gains)
+    B, n = a.shape
+    _, bank = true_peak_bank(sample_rate, a.device)
+    tp = torch.empty(B, dtype=torch.float32, device=a.device)
+    L.call("hsp_true_peak_f32", L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)), L.fptr(gains), B, n, L.fptr(bank),
+           bank.shape[0], bank.shape[1] // 2, L.fptr(tp))
+    return tp
+
+
+def lookahead_samples(lookahead_ms: float, sample_rate: int) -> int:
+    return int(round(float(lookahead_ms) * int(sample_rate) / 1000.0))
+
+
+def limit(audio, sample_rate: int, ceiling: float, lookahead_ms: float = 1.5, lengths=None, gains=None,
+          return_true_peak: bool = False):
+    """The look-ahead true-peak limiter of include/hsp.h (hsp_limiter_f32) on gains[b] * row b: -> (z fp32 [B, n] with
+    |z| <= ``ceiling`` on every sample and zeros from lengths[b] on, min_gain fp32 [B]: the smallest gain the limiter
+    applied, 1 where it never engaged).  ``ceiling`` is linear (1 = full scale); the look-ahead is
+    round(lookahead_ms * sample_rate / 1000) samples, 1 ... 480.  ``return_true_peak`` adds the true peak of the
+    limiter's input (gains[b] * row b)."""
+    a, gains = _rows_gains(audio, gains)
+    B, n = a.shape
+    _, bank = true_peak_bank(sample_rate, a.device)
+    z = torch.empty(B, n, dtype=torch.float32, device=a.device)
+    mg = torch.empty(B, dtype=torch.float32, device=a.device)
+    tp = torch.empty(B, dtype=torch.float32, device=a.device) if return_true_peak else None
+    lens = _lengths(lengths)
+    args = L.LimiterArgs()
+    args.x, args.x_bs, args.lengths, args.gains = L.fptr(a), a.stride(0), L.ptr(lens), L.fptr(gains)
+    args.B, args.n = B, n
+    args.bank, args.F, args.Z = L.fptr(bank), bank.shape[0], bank.shape[1] // 2
+    args.W, args.ceiling = lookahead_samples(lookahead_ms, sample_rate), float(ceiling)
+    args.y, args.y_bs, args.min_gain, args.tp = L.fptr(z), z.stride(0), L.fptr(mg), L.fptr(tp)
+    L.call("hsp_limiter_f32", C.byref(args))
+    return (z, mg, tp) if return_true_peak else (z, mg)
+
+
+def gain_update(gains, lufs, target_lufs: float):
+    """gains[b] * 10^((target_lufs - lufs[b]) / 20) -> fp32 [B] (hsp_gain_update_f32): a loudness that is not finite
+    leaves the gain as it is.  ``gains`` None: the first gain of every row, from 1 -- 0 for a row without a loudness."""
+    B = lufs.shape[0]
+    out = torch.empty(B, dtype=torch.float32, device=lufs.device)
+    L.call("hsp_gain_update_f32", L.fptr(None if gains is None else _c(gains)), L.fptr(_c(lufs)), float(target_lufs),
+           L.fptr(out), B)
+    return out
+
+
+def gain_int16(audio, lengths, gains):
+    """int16(audio[b] * gains[b] * 32767) over lengths[b] samples, zeros after (hsp_gain_int16_f32): truncating and
+    saturating like `peak_int16`, but with no peak normalisation."""
+    a, gains = _rows_gains(audio, gains)
+    out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
+    L.call("hsp_gain_int16_f32", L.fptr(a), a.stride(0), L.ptr(_lengths(lengths)), L.fptr(gains), L.ptr(out),
+           out.stride(0), a.shape[0], a.shape[1])
+    return out
+
+
+def lufs_limit_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.0, ceiling_db: float = -1.0,
+                     lookahead_ms: float = 1.5, passes: int = 2):
+    """The int16 stage of scale_norm="lufs" with the limiter: every row at ``target_lufs`` with its true peak at or
+    under ``ceiling_db`` dBTP, also where the row's crest factor puts the plain gain of `lufs_int16` over full scale.
+    A fixed chain of launches on the current stream, nothing read back:
+      L_0 = meter(x), G_1 = 10^((target - L_0) / 20);  for k = 1 ... passes: z_k = limit(G_k x), L_k = meter(z_k),
+      G_{k+1} = G_k 10^((target - L_k) / 20);  q = min(1, c / true_peak(z_K));  int16(z_K q 32767).
+    -> (int16 [B, n], stats: dict of fp32 [B] device tensors ``achieved_lufs`` (L_K + 20 log10 q), ``true_peak``
+    (linear, of z_K q) and ``min_gain`` (the smallest limiter gain of the last pass)).  A row without a loudness
+    (silence, or empty) is zeros and reads -inf / 0 / 1."""
+    passes = int(passes)
+    if not 1 <= passes <= 4:
+        raise L.HspError(f"lufs_limit_int16: passes = {passes} is not 1 ... 4")
+    c = 10.0 ** (float(ceiling_db) / 20.0)
+    a = audio.reshape(audio.shape[0], -1)
+    lufs, _ = loudness(a, sample_rate, lengths)
+    g = gain_update(None, lufs, target_lufs)
+    for k in range(passes):
+        if k:
+            g = gain_update(g, lufs, target_lufs)
+        z, min_gain = limit(a, sample_rate, c, lookahead_ms, lengths, g)
+        lufs, _ = loudness(z, sample_rate, lengths)
+    q = torch.empty_like(lufs)
+    achieved = torch.empty_like(lufs)
+    tpk = torch.empty_like(lufs)
+    L.call("hsp_limiter_stats_f32", L.fptr(lufs), L.fptr(true_peak(z, sample_rate, lengths)), c, L.fptr(q),
+           L.fptr(achieved), L.fptr(tpk), lufs.shape[0])
+    return gain_int16(z, lengths, q), {"achieved_lufs": achieved, "true_peak": tpk, "min_gain": min_gain}
+
+
 # ---------------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
 KAISER_BETA = 14.769656459379492   # torchaudio's beta for resampling_method="kaiser_window", beta=None
 

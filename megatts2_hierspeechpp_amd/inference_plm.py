@@ -56,6 +56,25 @@ def zero_below(x, thr: float):
 peak_int16 = Fh.peak_int16   # the int16 stage of the reference's tts() (inference_plm.py:185-188)
 
 
+def check_limiter(scale_norm: str, limiter: bool, return_stats: bool = False) -> None:
+    if limiter and scale_norm != "lufs":
+        raise L.HspError(f"limiter=True needs scale_norm='lufs', got {scale_norm!r}: the limiter serves the loudness target")
+    if return_stats and not limiter:
+        raise L.HspError("return_stats=True needs limiter=True: the stats are the limiter's")
+
+
+def int16_rows(audio, n_valid, rate: int, scale_norm: str, gain, target_lufs: float, limiter: bool = False,
+               ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2):
+    """The int16 stage of every harness -> (int16 rows, stats or None).  'max' / 'prompt': `peak_int16` times ``gain``;
+    'lufs': `functional.lufs_int16`, or with ``limiter`` `functional.lufs_limit_int16`, whose per-row stats (a dict of
+    fp32 [B] device tensors: achieved_lufs, true_peak, min_gain) are the second result."""
+    if scale_norm == "lufs" and limiter:
+        return Fh.lufs_limit_int16(audio, n_valid, rate, target_lufs, ceiling_db, lookahead_ms, limiter_passes)
+    if scale_norm == "lufs":
+        return Fh.lufs_int16(audio, n_valid, rate, target_lufs), None
+    return peak_int16(audio, n_valid, gain), None
+
+
 def prompt_mels(mel_fn, audio, denoiser=None, hps_denoiser=None):
     """The two prompt mels of inference_plm.py:130-150: ``src_mel_ttv`` from the prompt zero-padded to the next
     multiple of 1600 samples (always at least one sample of padding, :131-134), and ``src_mel`` [2, 80, T] from the
@@ -158,7 +177,8 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
         target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
-        prosody_codes=None, prosody_lengths=None):
+        prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
+        limiter_passes: int = 2, return_stats: bool = False):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
     make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.  ``plm_causal``: the
     prosody LM decodes under the causal mask it is trained with, through a K/V cache (``infer(causal=True)``: other
@@ -174,6 +194,10 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
     peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
     length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
+    ``limiter`` (needs scale_norm='lufs'): a row whose peaks would pass the ceiling is not held under the target but run
+    through the look-ahead true-peak limiter (``functional.lufs_limit_int16``: ``ceiling_db`` dBTP, ``lookahead_ms``,
+    ``limiter_passes`` meter-and-limit rounds); ``return_stats`` appends its per-row stats -- a dict of fp32 [B] device
+    tensors achieved_lufs, true_peak, min_gain -- after the audio and before any codes.
 
     text / tone / language int64 [B, N], text_length [B]; src_mel_ttv [B, 80, Tm'] (prompt mel for the
     front-end) with lengths; src_mel [2B, 80, Tm] = the B prompt mels followed by the B denoised prompt
@@ -183,6 +207,7 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
     _check_scale_norm(scale_norm)
+    check_limiter(scale_norm, limiter, return_stats)
     if plm_prefix is not None and not plm_causal:
         raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
@@ -199,19 +224,22 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
                                   width=x_frame.shape[2])
     out = tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
                          denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
-                         gain=gain, scale_norm=scale_norm, target_lufs=target_lufs)
+                         gain=gain, scale_norm=scale_norm, target_lufs=target_lufs, limiter=limiter, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, limiter_passes=limiter_passes, return_stats=return_stats)
     if not return_codes:
         return out
-    return (*out, codes) if return_float else (out, codes)
+    return (*out, codes) if isinstance(out, tuple) else (out, codes)
 
 
 @torch.no_grad()
 def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
                    noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
-                   return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0):
+                   return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
+                   limiter_passes: int = 2, return_stats: bool = False):
     """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
-    ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode."""
+    ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode.
+    ``limiter`` ... ``return_stats``: see `tts`; the stats dict is the last result."""
     _check_scale_norm(scale_norm)
+    check_limiter(scale_norm, limiter, return_stats)
     B = x_frame.shape[0]
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
     pitch = zero_below(pitch, math.log(55.0))                                  # :166 pitch clipping
@@ -232,11 +260,12 @@ def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_
         audio = models.sr(audio)
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
-    if scale_norm == "lufs":
-        wav = Fh.lufs_int16(audio, n_valid, output_sr if output_sr in (24000, 48000) else 16000, target_lufs)
-    else:
-        wav = peak_int16(audio, n_valid, gain)
-    return (wav, audio) if return_float else wav
+    wav, stats = int16_rows(audio, n_valid, output_sr if output_sr in (24000, 48000) else 16000, scale_norm, gain,
+                            target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes)
+    out = (wav, audio) if return_float else (wav,)
+    if return_stats:
+        out = (*out, stats)
+    return out if len(out) > 1 else out[0]
 
 
 @torch.no_grad()
@@ -265,7 +294,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
                     takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
-                    return_codes: bool = False, prosody_codes=None, prosody_lengths=None):
+                    return_codes: bool = False, prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
+                    limiter_passes: int = 2, return_stats: bool = False):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -286,8 +316,12 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     ``takes`` = N the one prefix is shared by all N takes: N different endings of one beginning.  ``return_codes``
     appends the PLM codes (int64 [T], or [N, T] with takes) to the result.
     ``prosody_codes`` (int64 [Ts] or [1, Ts]; ``prosody_lengths`` their frame count, None: Ts): given prosody codes
-    instead of the prosody LM (see `tts`); excludes ``plm_sampling``, ``plm_prefix``, ``plm_causal`` and ``takes`` > 1."""
+    instead of the prosody LM (see `tts`); excludes ``plm_sampling``, ``plm_prefix``, ``plm_causal`` and ``takes`` > 1.
+    ``limiter`` / ``ceiling_db`` / ``lookahead_ms`` / ``limiter_passes`` (need scale_norm='lufs'): the look-ahead
+    true-peak limiter of `tts`, every take limited over its own length; ``return_stats`` appends the stats dict (fp32
+    [takes] tensors) after the audio and before any codes."""
     takes = int(takes)
+    check_limiter(scale_norm, limiter, return_stats)
     if takes < 1:
         raise L.HspError(f"takes must be >= 1, got {takes}")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal, takes)
@@ -320,12 +354,13 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
-    wav, audio, codes = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
-                            noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
-                            noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
-                            seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
-                            target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True,
-                            prosody_codes=prosody_codes, prosody_lengths=prosody_lengths)
+    res = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
+              noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
+              noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
+              seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
+              target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True,
+              prosody_codes=prosody_codes, prosody_lengths=prosody_lengths, limiter=limiter, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, limiter_passes=limiter_passes, return_stats=return_stats)
+    wav, audio, codes = res[0], res[1], res[-1]
     rate = output_sr if output_sr in (24000, 48000) else 16000
     if B == 1:
         wav, codes = wav[0], codes[0]
@@ -337,6 +372,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
         for k in range(B):
             write_wav(f"{stem}_take{k}{ext}", rate, wav[k])
     out = (wav, audio) if return_float else (wav,)
+    if return_stats:
+        out = (*out, res[2])
     if return_codes:
         out = (*out, codes)
     return out if len(out) > 1 else out[0]
@@ -348,7 +385,8 @@ def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
     ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` / ``prosody_codes`` / ``prosody_lengths`` and
-    ``kwargs`` go to `tts_from_prompt`."""
+    ``kwargs`` (``scale_norm``, ``target_lufs``, ``limiter``, ``ceiling_db``, ``lookahead_ms``, ``limiter_passes``,
+    ``return_stats``, ...) go to `tts_from_prompt`."""
     from . import audio as A
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,

@@ -22,7 +22,7 @@ from torch import nn
 from . import _lib as L
 from . import functional as Fh
 from . import hip_layers
-from .inference_plm import SCALE_NORMS, output_gain, peak_int16
+from .inference_plm import SCALE_NORMS, check_limiter, int16_rows, output_gain, peak_int16
 
 SOURCE_HOP = 1280   # pad_source's multiple (inference_vc.py:74-75)
 W2V_PAD = 40        # reflect pad before wav2vec2 (:85)
@@ -72,14 +72,20 @@ def load_source(path, device):
 
 @torch.no_grad()
 def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noise_scale_vc=0.333, denoise_ratio=0.0,
-       denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000, target_lufs=-23.0):
+       denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000, target_lufs=-23.0,
+       limiter=False, ceiling_db=-1.0, lookahead_ms=1.5, limiter_passes=2, return_stats=False):
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``output_sr`` 24000 / 48000: SpeechSR (``models.sr``) runs after the vocoder (:147-151) -> [480 T] / [960 T].
     ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which is
     what the reference does at denoise_ratio == 0.  ``scale_norm`` 'prompt': the int16 gain is the peak of
     ``target_audio`` (inference_vc.py:104-105; read back to the host, see inference_plm.output_gain) instead of 0.999;
-    'lufs': the output is brought to ``target_lufs`` (BS.1770-4 at the output rate, ``functional.lufs_int16``)."""
+    'lufs': the output is brought to ``target_lufs`` (BS.1770-4 at the output rate, ``functional.lufs_int16``).
+    ``limiter`` (needs scale_norm='lufs'): peaks that would pass ``ceiling_db`` dBTP are pulled down by the look-ahead
+    true-peak limiter instead of holding the whole row under the target (``functional.lufs_limit_int16``, with
+    ``lookahead_ms`` and ``limiter_passes``); ``return_stats`` appends its stats, a dict of fp32 [1] device tensors
+    achieved_lufs, true_peak, min_gain."""
+    check_limiter(scale_norm, limiter, return_stats)
     gain = output_gain(scale_norm, target_audio)
     x_w2v = models.w2v(Fh.reflect_pad(source_audio, 40))                       # :85-86
     T = x_w2v.shape[2]
@@ -96,10 +102,14 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     if output_sr in (24000, 48000):
         audio = _sr_model(models)(audio)                                       # :147-151
     if scale_norm == "lufs":
-        wav = Fh.lufs_int16(audio.reshape(1, -1), None, output_rate(output_sr), target_lufs)
+        wav, stats = int16_rows(audio.reshape(1, -1), None, output_rate(output_sr), scale_norm, gain, target_lufs, limiter,
+                                ceiling_db, lookahead_ms, limiter_passes)
     else:
         wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device), gain)
-    return (wav.reshape(-1), audio) if return_float else wav.reshape(-1)
+    out = (wav.reshape(-1), audio) if return_float else (wav.reshape(-1),)
+    if return_stats:
+        out = (*out, stats)
+    return out if len(out) > 1 else out[0]
 
 
 def _sr_model(models):
@@ -279,7 +289,8 @@ def denoise_prompts(prompts, denoiser, hps):
 @torch.no_grad()
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
              denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
-             row_exact=False, denoiser=None, hps_denoiser=None, target_lufs=-23.0):
+             row_exact=False, denoiser=None, hps_denoiser=None, target_lufs=-23.0, limiter=False, ceiling_db=-1.0,
+             lookahead_ms=1.5, limiter_passes=2, return_stats=False):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -295,7 +306,10 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
              both ``denoised`` and ``denoiser``, or ``denoise_ratio != 0`` with neither, is an error;
     noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn;
     scale_norm  'max' / 'prompt' as in ``vc``; 'lufs': every row is brought to ``target_lufs`` over its own length
-             (``functional.loudness`` -> ``loudness_gains``: still no host read-back).
+             (``functional.loudness`` -> ``loudness_gains``: still no host read-back);
+    limiter / ceiling_db / lookahead_ms / limiter_passes  as in ``vc``: with scale_norm='lufs', every row goes through
+             the look-ahead true-peak limiter over its own length (``functional.lufs_limit_int16``: launches only);
+             ``return_stats`` appends its per-row stats (a dict of fp32 [B] device tensors) to the result.
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
     (320 T_b at 16 kHz, x1.5 / x3 with SpeechSR), zeros after; with ``return_float`` also the float audio
@@ -347,6 +361,7 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
                              f"{Ls // F0_HOP} columns, got {fs.shape[1]}")
     if scale_norm not in SCALE_NORMS:
         raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
+    check_limiter(scale_norm, limiter, return_stats)
     if output_sr in (24000, 48000):
         _sr_model(models)
 
@@ -398,16 +413,22 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     _stage("int16")
     n_valid = output_length(frames, output_sr)
     # int16 with each row's gain (:157-160): 0.999, the peak of the row's own prompt, or the one that meets target_lufs
-    if scale_norm == "max":
+    stats = None
+    if limiter:
+        wav, stats = Fh.lufs_limit_int16(audio, n_valid, output_rate(output_sr), target_lufs, ceiling_db, lookahead_ms,
+                                         limiter_passes)
+    elif scale_norm == "max":
         gains = torch.full((B,), 0.999, dtype=torch.float32, device=dev)
     elif scale_norm == "lufs":
         gains, _ = Fh.loudness_gains(*Fh.loudness(audio, output_rate(output_sr), n_valid), target_lufs)
     else:
         peaks = Fh.abs_max_rows(pm[0::2].contiguous(), pm_len[0::2].contiguous())
         gains = peaks.expand(B).contiguous() if P == 1 else torch.cat([peaks[index[b]:index[b] + 1] for b in range(B)])
-    wav = Fh.peak_int16_gains(audio, n_valid, gains)
+    if not limiter:
+        wav = Fh.peak_int16_gains(audio, n_valid, gains)
     _stage("end")
-    return (wav, n_valid, audio) if return_float else (wav, n_valid)
+    out = (wav, n_valid, audio) if return_float else (wav, n_valid)
+    return (*out, stats) if return_stats else out
 
 
 @torch.no_grad()
@@ -427,6 +448,8 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     faster, but every row shorter than the longest differs from its one-file conversion over its whole length (the
     flows' attention sees the batch's padding; contract item 3).  None (the default): True, unless ``row_exact=True``
     is given -- then ONE ragged batch whose rows each match their one-file conversion.
+    ``limiter`` / ``ceiling_db`` / ``lookahead_ms`` / ``limiter_passes`` go to ``vc_batch`` with ``kw``;
+    ``return_stats=True`` appends the limiter's per-row stats (fp32 [B] tensors in the order of ``source_paths``).
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device); the files hold wav[b, :lengths[b]]."""
     from .audio import load_16k
     from .inference_plm import write_wav
@@ -455,13 +478,21 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     f0_srcs = [track(p) for p in source_paths]
     groups = length_groups([s.shape[-1] for s in sources]) if group_by_length else [list(range(B))]
     noise = kw.pop("noise", None)
-    parts = []
+    return_stats = bool(kw.get("return_stats", False))
+    parts, part_stats = [], []
     for rows in groups:
         T = max(sources[b].shape[-1] for b in rows) // FRAME
         nz = None if noise is None else noise[torch.tensor(rows, device=noise.device), :, :T].contiguous()
         parts.append(vc_batch(models, mel_fn, [sources[b] for b in rows], [f0_srcs[b] for b in rows],
                               [prompts[trg_paths[b]] for b in rows], [tracks[trg_paths[b]] for b in rows], noise=nz,
                               **kw))
+        if return_stats:
+            part_stats.append(parts[-1][2])
+            parts[-1] = parts[-1][:2]
+    stats = None
+    if return_stats:
+        order = torch.tensor([b for rows in groups for b in rows], device=device).argsort()
+        stats = {k: torch.cat([ps[k] for ps in part_stats])[order] for k in part_stats[0]}
     if len(groups) == 1:
         wav, lengths = parts[0]
     else:
@@ -478,4 +509,4 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
         host = wav.cpu()
         for b in range(B):
             write_wav(os.path.join(str(out_dir), output_name(source_paths[b], trg_paths[b])), rate, host[b, :n[b]])
-    return wav, lengths
+    return (wav, lengths, stats) if return_stats else (wav, lengths)
