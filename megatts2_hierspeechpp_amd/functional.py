@@ -29,6 +29,13 @@ def _lengths(lengths, B=None):
     return lengths
 
 
+def _rows2d(audio):
+    """[B, 1, n] / [B, n] audio as the [B, n] view the row kernels read: unit stride in time, any row stride."""
+    a = audio.reshape(audio.shape[0], -1) if audio.dim() == 3 else audio
+    assert a.dim() == 2 and a.stride(1) == 1
+    return a
+
+
 def _pick(plain: str, ragged: str, *lengths):
     """All that a plain / ragged pair of entry points differs in: (the entry point, its length arguments) -- ``ragged``
     with the device pointers of ``lengths``, or ``plain`` with none when there are no lengths."""
@@ -44,7 +51,8 @@ def sequence_mask(length: torch.Tensor, max_length: int) -> torch.Tensor:
     return mask
 
 
-ACT_HOOK = None  # measurement hook (bench.py): hook(algorithmic_bytes, ev_start, ev_end) around every stand-alone activation
+# measurement hook (bench.py): hook(algorithmic_bytes, ev_start, ev_end) around every stand-alone activation
+ACT_HOOK = None
 
 
 def act1d(x, ea, binv, filt, out=None, lens=None):
@@ -274,8 +282,8 @@ def reflect_pad(x, pad: int, lengths=None):
     if lengths is None:
         L.call("hsp_reflect_pad_f32", L.fptr(x2), x2.stride(0), L.fptr(y), B, Lx, pad)
     else:
-        L.call("hsp_reflect_pad_ragged_f32", L.fptr(x2), x2.stride(0), L.ptr(_lengths(lengths)), L.fptr(y), y.stride(0), B,
-               Lx, pad, Lx + 2 * pad)
+        L.call("hsp_reflect_pad_ragged_f32", L.fptr(x2), x2.stride(0), L.ptr(_lengths(lengths)), L.fptr(y), y.stride(0),
+               B, Lx, pad, Lx + 2 * pad)
     return y.reshape(*shp[:-1], Lx + 2 * pad)
 
 
@@ -288,9 +296,10 @@ def f0_convert(f0_src, f0_trg):
     return out.reshape(f0_src.shape)
 
 
-# ---------------------------------------------------------------- batched voice conversion (ragged rows, device lengths)
+# --------------------------------------------------------- batched voice conversion (ragged rows, device lengths)
 def reflect_pad_ragged(x, lengths, pad: int):
-    """Row b of x [B, L] -> F.pad(x[b, :lengths[b]], (pad, pad), "reflect"), zero after lengths[b] + 2 pad: [B, L + 2 pad]."""
+    """Row b of x [B, L] -> F.pad(x[b, :lengths[b]], (pad, pad), "reflect"), zero after lengths[b] + 2 pad:
+    [B, L + 2 pad]."""
     assert x.dim() == 2
     return reflect_pad(x, pad, lengths)
 
@@ -312,7 +321,8 @@ def abs_max_rows(x, lengths=None):
     """max |x[b, :lengths[b]]| of every row of x [B, n] -> fp32 [B] on the device (no host read-back)."""
     assert x.dim() == 2 and x.stride(1) == 1
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    L.call("hsp_abs_max_rows_f32", L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)), L.fptr(out), x.shape[0], x.shape[1])
+    L.call("hsp_abs_max_rows_f32", L.fptr(x), x.stride(0), L.ptr(_lengths(lengths)), L.fptr(out), x.shape[0],
+           x.shape[1])
     return out
 
 
@@ -320,8 +330,7 @@ def peak_int16(audio, lengths=None, gain=0.999):
     """[B, 1, n] / [B, n] fp32 -> int16 [B, n], every row scaled by its own peak (over ``lengths[b]`` samples) times
     ``gain``: a float for every row (hsp_peak_int16) or a device fp32 [B], one per row (hsp_peak_int16_gains).
     A silent row (peak 0) comes out as zeros, as the reference's ``(a / a.abs().max() ...).astype(int16)`` does."""
-    a = audio.reshape(audio.shape[0], -1)
-    assert a.stride(1) == 1
+    a = _rows2d(audio)
     out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
     if torch.is_tensor(gain):
         assert gain.shape == (a.shape[0],)
@@ -343,8 +352,7 @@ def loudness(audio, sample_rate: int, lengths=None):
     ``sample_rate`` (a multiple of 8000 up to 48000), ``lengths`` int64 [B] valid samples (None = all n) ->
     (lufs fp32 [B], peak fp32 [B]) on the device, no host read-back.  A row under 400 ms is metered whole and ungated;
     a row with nothing above -70 LUFS reads -inf.  Row b equals the call on row b alone bit for bit."""
-    a = audio.reshape(audio.shape[0], -1) if audio.dim() == 3 else audio
-    assert a.dim() == 2 and a.stride(1) == 1
+    a = _rows2d(audio)
     B, n = a.shape
     lib = L.lib()
     nbytes = lib.hsp_loudness_workspace_bytes(B, n)
@@ -373,9 +381,9 @@ def loudness_gains(lufs, peak, target_lufs: float = -23.0, ceiling: float = 0.99
 
 def lufs_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.0, ceiling: float = 0.999):
     """The int16 stage of scale_norm="lufs": meter -> gains -> `peak_int16_gains`, three launches-only steps on the
-    current stream.  [B, 1, n] / [B, n] fp32 -> int16 [B, n], row b at ``target_lufs`` over its lengths[b] samples unless
-    its peak would pass ``ceiling`` of full scale."""
-    a = audio.reshape(audio.shape[0], -1)
+    current stream.  [B, 1, n] / [B, n] fp32 -> int16 [B, n], row b at ``target_lufs`` over its lengths[b] samples
+    unless its peak would pass ``ceiling`` of full scale."""
+    a = _rows2d(audio)
     lufs, peak = loudness(a, sample_rate, lengths)
     gains, _ = loudness_gains(lufs, peak, target_lufs, ceiling)
     return peak_int16_gains(a, lengths, gains)
@@ -405,8 +413,8 @@ def true_peak_bank_f64(fs: int):
 
 
 def true_peak_bank(fs: int, device=None):
-    """-> (float64 bank [F][2 Z] on the host, the same bank as fp32 on ``device``), built once per (rate, device); a call
-    inside a stream capture needs that upload done by an eager call first."""
+    """-> (float64 bank [F][2 Z] on the host, the same bank as fp32 on ``device``), built once per (rate, device); a
+    call inside a stream capture needs that upload done by an eager call first."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     key = (int(fs), device)
     got = _TRUE_PEAK_BANKS.get(key)
@@ -421,8 +429,7 @@ def true_peak_bank(fs: int, device=None):
 
 
 def _rows_gains(audio, gains):
-    a = audio.reshape(audio.shape[0], -1) if audio.dim() == 3 else audio
-    assert a.dim() == 2 and a.stride(1) == 1
+    a = _rows2d(audio)
     if gains is not None:
         assert gains.shape == (a.shape[0],)
         gains = _c(gains)
@@ -504,7 +511,7 @@ def lufs_limit_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.
     if not 1 <= passes <= 4:
         raise L.HspError(f"lufs_limit_int16: passes = {passes} is not 1 ... 4")
     c = 10.0 ** (float(ceiling_db) / 20.0)
-    a = audio.reshape(audio.shape[0], -1)
+    a = _rows2d(audio)
     lufs, _ = loudness(a, sample_rate, lengths)
     g = gain_update(None, lufs, target_lufs)
     for k in range(passes):
@@ -520,7 +527,7 @@ def lufs_limit_int16(audio, lengths, sample_rate: int, target_lufs: float = -23.
     return gain_int16(z, lengths, q), {"achieved_lufs": achieved, "true_peak": tpk, "min_gain": min_gain}
 
 
-# ---------------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
+# --------------------------------------------------------- sinc resampling (torchaudio 0.13.1 functional.resample)
 KAISER_BETA = 14.769656459379492   # torchaudio's beta for resampling_method="kaiser_window", beta=None
 
 
@@ -543,8 +550,8 @@ class ResampleBank:
 def sinc_resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
                        resampling_method: str = "sinc_interpolation", beta: Optional[float] = None) -> ResampleBank:
     """torchaudio 0.13.1 _get_sinc_resample_kernel in float64 (phase / new_freq formed in fp32 first, as there), then
-    compacted: per phase only the taps whose argument t was not clamped to +-lowpass_filter_width are kept (a clamped tap
-    is sinc(+-lpw) * window(+-lpw), below 1e-15), padded with zeros to a common count n_taps."""
+    compacted: per phase only the taps whose argument t was not clamped to +-lowpass_filter_width are kept (a clamped
+    tap is sinc(+-lpw) * window(+-lpw), below 1e-15), padded with zeros to a common count n_taps."""
     import math
     import numpy as np
     g = math.gcd(int(orig_freq), int(new_freq))

@@ -3,15 +3,16 @@ extraction and wav writing, :156-190, and the model bundle of ``model_load`` :20
 
 The prompt file ingest (:120-126: ``torchaudio.load``, first channel, kaiser-window resampling to 16 kHz) is
 ``audio.load`` + ``functional.resample`` (``tts_from_prompt_file``; ``tts_from_prompt(prompt_sr=...)``), and
-``scale_norm='prompt'`` (:127-128,185-186) is ``tts_from_prompt(scale_norm="prompt")``.  Out of scope here (host
-plumbing, not the hot path): text cleaning / phonemisation (``get_text``) -- callers hand over phone ids.  The prompt mel transform is ``Mels_preprocess.MelSpectrogramFixed``,
-the optional prompt denoiser ``denoiser.generator.MPNet`` + ``denoiser.infer.denoise`` (:142-147)."""
+``scale_norm='prompt'`` (:127-128,185-186) is ``tts_from_prompt(scale_norm="prompt")``; the int16 stage of every
+harness here is one `output.OutputStage`.  Out of scope here (host plumbing, not the hot path): text cleaning /
+phonemisation (``get_text``) -- callers hand over phone ids.  The prompt mel transform is
+``Mels_preprocess.MelSpectrogramFixed``, the optional prompt denoiser ``denoiser.generator.MPNet`` +
+``denoiser.infer.denoise`` (:142-147)."""
 from __future__ import annotations
 
 import math
 from typing import Optional
 
-import numpy as np
 import torch
 from torch import nn
 
@@ -19,13 +20,12 @@ from . import _lib as L
 from . import functional as Fh
 from .hierspeechpp_speechsynthesizer import SynthesizerTrn
 from .hip_layers import finalize as _finalize
+from .output import SCALE_NORMS, OutputStage, output_rate, pack, prompt_peak  # noqa: F401  (re-exported names)
 from .ttv_v1.t2w2v_transformer import Megatts2PLM1
 from .ttv_v1.t2w2v_transformer import SynthesizerTrn as Text2W2V
 
 # text/symbols_lmdh.py: len(symbols), len(tone_symbols), len(language_symbols)
 N_VOCAB, N_TONE, N_LANGUAGE = 126, 11, 4
-# the rules of the int16 stage: the reference's two peak rules (inference_plm.py:185-188) and the loudness target
-SCALE_NORMS = ("max", "prompt", "lufs")
 
 
 class TtsModels(nn.Module):
@@ -56,23 +56,18 @@ def zero_below(x, thr: float):
 peak_int16 = Fh.peak_int16   # the int16 stage of the reference's tts() (inference_plm.py:185-188)
 
 
+# the forms the output stage had before `output.OutputStage`, kept for their callers: thin delegates
 def check_limiter(scale_norm: str, limiter: bool, return_stats: bool = False) -> None:
-    if limiter and scale_norm != "lufs":
-        raise L.HspError(f"limiter=True needs scale_norm='lufs', got {scale_norm!r}: the limiter serves the loudness target")
-    if return_stats and not limiter:
-        raise L.HspError("return_stats=True needs limiter=True: the stats are the limiter's")
+    OutputStage(scale_norm, limiter=limiter, return_stats=return_stats).check()
 
 
-def int16_rows(audio, n_valid, rate: int, scale_norm: str, gain, target_lufs: float, limiter: bool = False,
-               ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2):
-    """The int16 stage of every harness -> (int16 rows, stats or None).  'max' / 'prompt': `peak_int16` times ``gain``;
-    'lufs': `functional.lufs_int16`, or with ``limiter`` `functional.lufs_limit_int16`, whose per-row stats (a dict of
-    fp32 [B] device tensors: achieved_lufs, true_peak, min_gain) are the second result."""
-    if scale_norm == "lufs" and limiter:
-        return Fh.lufs_limit_int16(audio, n_valid, rate, target_lufs, ceiling_db, lookahead_ms, limiter_passes)
-    if scale_norm == "lufs":
-        return Fh.lufs_int16(audio, n_valid, rate, target_lufs), None
-    return peak_int16(audio, n_valid, gain), None
+def int16_rows(audio, n_valid, rate: int, scale_norm: str, gain, target_lufs: float, *limiter_args, **limiter_kw):
+    """`OutputStage.int16`; ``limiter_args`` / ``limiter_kw``: the fields of the stage from ``limiter`` on."""
+    return OutputStage(scale_norm, target_lufs, *limiter_args, **limiter_kw).int16(audio, n_valid, rate, gain)
+
+
+def output_gain(scale_norm: str, prompt_audio) -> float:
+    return OutputStage(scale_norm).gain(prompt_audio)
 
 
 def prompt_mels(mel_fn, audio, denoiser=None, hps_denoiser=None):
@@ -115,11 +110,6 @@ def write_wav(path, sample_rate: int, pcm):
         f.setsampwidth(2)
         f.setframerate(int(sample_rate))
         f.writeframes(a.astype("<i2").tobytes())
-
-
-def _check_scale_norm(scale_norm: str) -> None:
-    if scale_norm not in SCALE_NORMS:
-        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
 
 
 @torch.no_grad()
@@ -177,12 +167,12 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, dur=None, noise=None,
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
         target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
-        prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
-        limiter_passes: int = 2, return_stats: bool = False):
-    """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and ``seeds``
-    make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.  ``plm_causal``: the
-    prosody LM decodes under the causal mask it is trained with, through a K/V cache (``infer(causal=True)``: other
-    codes than the reference's bidirectional loop gives); False: the reference's loop.
+        prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0,
+        lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False):
+    """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and
+    ``seeds`` make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
+    ``plm_causal``: the prosody LM decodes under the causal mask it is trained with, through a K/V cache
+    (``infer(causal=True)``: other codes than the reference's bidirectional loop gives); False: the reference's loop.
     ``plm_prefix`` (int64 [B, P], needs ``plm_causal``): the first P prosody codes of every row are given and only the
     rest is decoded (``infer(prefix_codes=)``) -- durations do not depend on the codes, so the kept beginning of an
     earlier take of the same text and prompt fits frame for frame.  ``return_codes``: the PLM codes int64 [B, T] are
@@ -191,55 +181,67 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     all Ts): the prosody LM is skipped and the given codes, fitted per row to that row's frame count
     (`fit_prosody_codes`), are used instead -- excludes ``plm_sampling``, ``plm_prefix`` and ``plm_causal``;
     ``return_codes`` then returns the fitted codes.
-    ``scale_norm`` 'max' / 'prompt': the int16 rows are peak-normalised times ``gain`` (the caller's 0.999 or prompt
-    peak); 'lufs': every row is brought to ``target_lufs`` (BS.1770-4, metered at the output rate over the row's own
-    length; ``functional.lufs_int16``), its peak held at 0.999 of full scale at the most.
-    ``limiter`` (needs scale_norm='lufs'): a row whose peaks would pass the ceiling is not held under the target but run
-    through the look-ahead true-peak limiter (``functional.lufs_limit_int16``: ``ceiling_db`` dBTP, ``lookahead_ms``,
-    ``limiter_passes`` meter-and-limit rounds); ``return_stats`` appends its per-row stats -- a dict of fp32 [B] device
-    tensors achieved_lufs, true_peak, min_gain -- after the audio and before any codes.
+    ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`; ``gain`` is the gain of 'max' /
+    'prompt' (the caller's 0.999 or prompt peak).  The stats follow the audio, the codes come last.
 
     text / tone / language int64 [B, N], text_length [B]; src_mel_ttv [B, 80, Tm'] (prompt mel for the
     front-end) with lengths; src_mel [2B, 80, Tm] = the B prompt mels followed by the B denoised prompt
     mels (the reference's ``torch.cat([audio, denoised])`` at B = 1) with ``src_length2`` [2B].
-    Returns int16 audio [B, n] (n = 320 * frames, x3 / x1.5 with SpeechSR), rows peak-normalised over
-    their own length (times ``gain``: 0.999, or the prompt's peak for scale_norm='prompt').  B > 1 runs the utterances side by side; rows are independent up to the
+    Returns int16 audio [B, n] (n = 320 * frames, x3 / x1.5 with SpeechSR), every row converted over its own length.
+    B > 1 runs the utterances side by side; rows are independent up to the
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
     ``infer`` does (equal-length batches are exact)."""
-    _check_scale_norm(scale_norm)
-    check_limiter(scale_norm, limiter, return_stats)
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
     if plm_prefix is not None and not plm_causal:
         raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
+    wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel,
+                                    src_length2, noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage, gain,
+                                    plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths)
+    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
+
+
+def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
+         noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage: OutputStage, gain, plm_sampling, seeds,
+         plm_causal, plm_prefix, prosody_codes, prosody_lengths):
+    """`tts` behind its argument checks -> (wav, audio, stats or None, codes)."""
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
                                                                      tone, language, dur=dur)
     if prosody_codes is None:
-        codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal, prefix_codes=plm_prefix)
+        codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal,
+                                 prefix_codes=plm_prefix)
     else:
         if prosody_codes.dim() != 2 or prosody_codes.shape[0] != B:
             raise L.HspError(f"prosody_codes must be int64 [B = {B}, Ts], got {tuple(prosody_codes.shape)}")
         src = prosody_codes.shape[1] if prosody_lengths is None else prosody_lengths
         codes = fit_prosody_codes(prosody_codes.to(x_frame.device), src, torch.ceil(x_lengths).to(torch.int64),
                                   width=x_frame.shape[2])
-    out = tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc=noise_scale_vc,
-                         denoise_ratio=denoise_ratio, output_sr=output_sr, noise=noise, return_float=return_float,
-                         gain=gain, scale_norm=scale_norm, target_lufs=target_lufs, limiter=limiter, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, limiter_passes=limiter_passes, return_stats=return_stats)
-    if not return_codes:
-        return out
-    return (*out, codes) if isinstance(out, tuple) else (out, codes)
+    return (*_tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc,
+                             denoise_ratio, output_sr, noise, stage, gain), codes)
 
 
 @torch.no_grad()
 def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
                    noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
-                   return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
-                   limiter_passes: int = 2, return_stats: bool = False):
+                   return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0,
+                   limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
+                   return_stats: bool = False):
     """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
     ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode.
-    ``limiter`` ... ``return_stats``: see `tts`; the stats dict is the last result."""
-    _check_scale_norm(scale_norm)
-    check_limiter(scale_norm, limiter, return_stats)
+    ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`; the stats dict is the last
+    result."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
+    wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
+                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain)
+    return pack(wav, (audio, return_float), (stats, return_stats))
+
+
+def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc, denoise_ratio,
+                    output_sr, noise, stage: OutputStage, gain):
+    """`tts_from_codes` behind its argument check -> (wav, audio, stats or None)."""
     B = x_frame.shape[0]
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
     pitch = zero_below(pitch, math.log(55.0))                                  # :166 pitch clipping
@@ -260,32 +262,8 @@ def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_
         audio = models.sr(audio)
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
-    wav, stats = int16_rows(audio, n_valid, output_sr if output_sr in (24000, 48000) else 16000, scale_norm, gain,
-                            target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes)
-    out = (wav, audio) if return_float else (wav,)
-    if return_stats:
-        out = (*out, stats)
-    return out if len(out) > 1 else out[0]
-
-
-@torch.no_grad()
-def prompt_peak(audio) -> float:
-    """``torch.max(audio.abs())`` of scale_norm='prompt' (inference_plm.py:127-128, inference_vc.py:104-105): the
-    reference takes it on the CPU copy of the 16 kHz prompt, so does this (one device-to-host copy of the prompt and a
-    host synchronise: not for use inside a captured graph)."""
-    return float(np.abs(audio.detach().cpu().numpy()).max())
-
-
-def output_gain(scale_norm: str, prompt_audio) -> float:
-    """The gain of the int16 conversion (inference_plm.py:185-188): 0.999 for 'max', the prompt's peak for 'prompt'.
-    A prompt whose peak is above 1 (full scale) is outside the contract: the reference's astype('int16') wraps such
-    samples around, hsp_peak_int16 saturates them.  'lufs' has no fixed gain (it is metered per row on the device,
-    ``functional.lufs_int16``); 0.999, its ceiling, is returned."""
-    if scale_norm in ("max", "lufs"):
-        return 0.999
-    if scale_norm == "prompt":
-        return prompt_peak(prompt_audio)
-    raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
+    wav, stats = stage.int16(audio, n_valid, output_rate(output_sr), gain)
+    return wav, audio, stats
 
 
 @torch.no_grad()
@@ -294,14 +272,13 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     denoise_ratio: float = 0.0, denoiser=None, hps_denoiser=None, prompt_sr: int = 16000,
                     scale_norm: str = "max", return_float: bool = False, plm_sampling=None, seed: int = 0,
                     takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
-                    return_codes: bool = False, prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
-                    limiter_passes: int = 2, return_stats: bool = False):
+                    return_codes: bool = False, prosody_codes=None, prosody_lengths=None, limiter: bool = False,
+                    ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
+                    return_stats: bool = False):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
-    f0 -> waveform (`tts`), int16 with the gain of ``scale_norm`` (:185-188, `output_gain`: 'prompt' reads the prompt's
-    peak back to the host; 'lufs': every row -- each take on its own -- at ``target_lufs``, see `tts`), optional 16-bit
-    WAV (:195-200).
+    f0 -> waveform (`tts`), int16 (:185-188), optional 16-bit WAV (:195-200).
     text / tone / language int64 [1, N] on the GPU; prompt_audio fp32 [1, n] at ``prompt_sr`` on the GPU;
     ``mel_fn`` a finalized Mels_preprocess.MelSpectrogramFixed.  Returns int16 [n_out] (and the float audio with
     ``return_float``).
@@ -317,11 +294,11 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     appends the PLM codes (int64 [T], or [N, T] with takes) to the result.
     ``prosody_codes`` (int64 [Ts] or [1, Ts]; ``prosody_lengths`` their frame count, None: Ts): given prosody codes
     instead of the prosody LM (see `tts`); excludes ``plm_sampling``, ``plm_prefix``, ``plm_causal`` and ``takes`` > 1.
-    ``limiter`` / ``ceiling_db`` / ``lookahead_ms`` / ``limiter_passes`` (need scale_norm='lufs'): the look-ahead
-    true-peak limiter of `tts`, every take limited over its own length; ``return_stats`` appends the stats dict (fp32
-    [takes] tensors) after the audio and before any codes."""
+    ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`, every take converted over its own
+    length (stats: fp32 [takes] tensors)."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
     takes = int(takes)
-    check_limiter(scale_norm, limiter, return_stats)
     if takes < 1:
         raise L.HspError(f"takes must be >= 1, got {takes}")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal, takes)
@@ -337,10 +314,11 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
             raise L.HspError("plm_prefix must be an int64 [P] or [1, P] tensor: one prefix, shared by every take")
         plm_prefix = plm_prefix.reshape(1, -1).expand(takes, -1).contiguous()
     if denoise_ratio != 0 and denoiser is None:
-        raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as inference_plm.py:144-147")
+        raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as "
+                         "inference_plm.py:144-147")
     if int(prompt_sr) != 16000:
         prompt_audio = Fh.resample(prompt_audio, prompt_sr, 16000, resampling_method="kaiser_window")
-    gain = output_gain(scale_norm, prompt_audio)
+    gain = stage.gain(prompt_audio)
     src_mel_ttv, src_mel = prompt_mels(mel_fn, prompt_audio, denoiser if denoise_ratio != 0 else None, hps_denoiser)
     dev = prompt_audio.device
     assert text.shape[0] == 1 and prompt_audio.shape[0] == 1, "the reference harness synthesises one utterance per call"
@@ -354,29 +332,20 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
-    res = tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel, src_length2,
-              noise_scale_vc=noise_scale_vc, denoise_ratio=float(denoise_ratio), output_sr=output_sr, dur=dur,
-              noise=noise, gain=gain, return_float=True, plm_sampling=plm_sampling,
-              seeds=int(seed) if plm_sampling is not None else None, scale_norm=scale_norm,
-              target_lufs=target_lufs, plm_causal=plm_causal, plm_prefix=plm_prefix, return_codes=True,
-              prosody_codes=prosody_codes, prosody_lengths=prosody_lengths, limiter=limiter, ceiling_db=ceiling_db, lookahead_ms=lookahead_ms, limiter_passes=limiter_passes, return_stats=return_stats)
-    wav, audio, codes = res[0], res[1], res[-1]
-    rate = output_sr if output_sr in (24000, 48000) else 16000
+    seeds = int(seed) if plm_sampling is not None else None
+    wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel,
+                                    src_length2, noise_scale_vc, float(denoise_ratio), output_sr, dur, noise, stage,
+                                    gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths)
     if B == 1:
         wav, codes = wav[0], codes[0]
         if output_path is not None:
-            write_wav(output_path, rate, wav)
+            write_wav(output_path, output_rate(output_sr), wav)
     elif output_path is not None:
         import os
         stem, ext = os.path.splitext(str(output_path))
         for k in range(B):
-            write_wav(f"{stem}_take{k}{ext}", rate, wav[k])
-    out = (wav, audio) if return_float else (wav,)
-    if return_stats:
-        out = (*out, res[2])
-    if return_codes:
-        out = (*out, codes)
-    return out if len(out) > 1 else out[0]
+            write_wav(f"{stem}_take{k}{ext}", output_rate(output_sr), wav[k])
+    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
 
 
 def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
@@ -385,9 +354,9 @@ def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
     ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` / ``prosody_codes`` / ``prosody_lengths`` and
-    ``kwargs`` (``scale_norm``, ``target_lufs``, ``limiter``, ``ceiling_db``, ``lookahead_ms``, ``limiter_passes``,
-    ``return_stats``, ...) go to `tts_from_prompt`."""
+    ``kwargs`` (the fields of `output.OutputStage`, ...) go to `tts_from_prompt`."""
     from . import audio as A
+    OutputStage.of(kwargs).check()      # before the file is read
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,

@@ -1,42 +1,34 @@
 """HIP mirror of the reference's inference_speechsr.py:SuperResoltuion (:21-50): speech at any rate -> channel 0 ->
 16 kHz (kaiser-window resampling, :28-34) -> SpeechSR (speechsr48k / speechsr24k) -> int16 peak-normalised with
-gain 0.999 (:37-40; or brought to a target loudness, scale_norm="lufs") -> optional 16-bit WAV at 48 or 24 kHz (:45-48)."""
+gain 0.999 (:37-40; or brought to a target loudness, scale_norm="lufs") -> optional 16-bit WAV at 48 or 24 kHz
+(:45-48)."""
 from __future__ import annotations
 
 import torch
 
-from . import _lib as L
 from . import functional as Fh
-from .inference_plm import check_limiter, int16_rows, peak_int16, write_wav
+from .inference_plm import write_wav
+from .output import OutputStage, pack
 
 
 @torch.no_grad()
 def super_resolution(sr_model, audio, sample_rate: int, output_sr: int = 48000, output_path=None,
-                     scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False, ceiling_db: float = -1.0,
-                     lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False):
+                     scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False,
+                     ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
+                     return_stats: bool = False):
     """``sr_model`` a finalized SpeechSR (speechsr48k / speechsr24k SynthesizerTrn); ``audio`` fp32 [channels, n] on
     the GPU at ``sample_rate`` (``audio.load(path)`` moved there).  Returns int16 [n_out].  As in the reference, the
     model fixes the upsampling factor and ``output_sr`` only labels the file: 48000, or 24000 for any other value.
-    ``scale_norm`` 'max': peak-normalised with gain 0.999; 'lufs': brought to ``target_lufs`` (BS.1770-4, metered at the
-    rate the model produced: 16 kHz times its upsampling factor), the peak held at 0.999 of full scale at the most.
-    ``limiter`` (needs scale_norm='lufs'): peaks that would pass ``ceiling_db`` dBTP are pulled down by the look-ahead
-    true-peak limiter instead (``functional.lufs_limit_int16``, with ``lookahead_ms`` and ``limiter_passes``);
-    ``return_stats``: returns (int16, stats), stats a dict of fp32 [1] device tensors achieved_lufs, true_peak,
-    min_gain."""
-    if scale_norm not in ("max", "lufs"):
-        raise L.HspError(f"unknown scale_norm {scale_norm!r} ('max' or 'lufs')")
-    check_limiter(scale_norm, limiter, return_stats)
+    ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage` -- 'max' or 'lufs' here (there is no
+    prompt), metered at the rate the model produced: 16 kHz times its upsampling factor."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes, return_stats)
+    stage.check(norms=("max", "lufs"))
     x = audio[:1]
     if int(sample_rate) != 16000:
         x = Fh.resample(x, sample_rate, 16000, resampling_method="kaiser_window")
     y = sr_model(x.unsqueeze(1))                                   # [1, 1, n_out]
-    stats = None
-    if scale_norm == "lufs":
-        wav, stats = int16_rows(y.reshape(1, -1), None, 16000 * y.shape[-1] // x.shape[-1], scale_norm, 0.999, target_lufs,
-                                limiter, ceiling_db, lookahead_ms, limiter_passes)
-        wav = wav.reshape(-1)
-    else:
-        wav = peak_int16(y.reshape(1, -1)).reshape(-1)
+    wav, stats = stage.int16(y, None, 16000 * y.shape[-1] // x.shape[-1])
+    wav = wav.reshape(-1)
     if output_path is not None:
         write_wav(output_path, 48000 if output_sr == 48000 else 24000, wav)
-    return (wav, stats) if return_stats else wav
+    return pack(wav, (stats, return_stats))

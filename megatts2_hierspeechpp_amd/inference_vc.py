@@ -22,7 +22,7 @@ from torch import nn
 from . import _lib as L
 from . import functional as Fh
 from . import hip_layers
-from .inference_plm import SCALE_NORMS, check_limiter, int16_rows, output_gain, peak_int16
+from .output import OutputStage, output_rate, pack
 
 SOURCE_HOP = 1280   # pad_source's multiple (inference_vc.py:74-75)
 W2V_PAD = 40        # reflect pad before wav2vec2 (:85)
@@ -30,8 +30,9 @@ FRAME = 320         # samples per w2v / vocoder frame
 F0_HOP = 80         # samples per YAAPT frame (5 ms): 4 per w2v frame
 
 STAGE_HOOK = None   # measurement hook (tools/vc_batch_bench.py): STAGE_HOOK(name) at the start of every vc_batch stage
-TAP_HOOK = None     # test hook: TAP_HOOK(name, tensor) with vc_batch's intermediates ('reflect_pad', 'w2v', 'lf0', 'mel',
-                    # 'style'; 'mel' once per distinct prompt: its [2, 80, Tm] prompt | denoised mels), no effect when None
+TAP_HOOK = None     # test hook: TAP_HOOK(name, tensor) with vc_batch's intermediates ('reflect_pad', 'w2v', 'lf0',
+                    # 'mel', 'style'; 'mel' once per distinct prompt: its [2, 80, Tm] prompt | denoised mels), no effect
+                    # when None
 
 
 class VcModels(nn.Module):
@@ -77,16 +78,12 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``output_sr`` 24000 / 48000: SpeechSR (``models.sr``) runs after the vocoder (:147-151) -> [480 T] / [960 T].
-    ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which is
-    what the reference does at denoise_ratio == 0.  ``scale_norm`` 'prompt': the int16 gain is the peak of
-    ``target_audio`` (inference_vc.py:104-105; read back to the host, see inference_plm.output_gain) instead of 0.999;
-    'lufs': the output is brought to ``target_lufs`` (BS.1770-4 at the output rate, ``functional.lufs_int16``).
-    ``limiter`` (needs scale_norm='lufs'): peaks that would pass ``ceiling_db`` dBTP are pulled down by the look-ahead
-    true-peak limiter instead of holding the whole row under the target (``functional.lufs_limit_int16``, with
-    ``lookahead_ms`` and ``limiter_passes``); ``return_stats`` appends its stats, a dict of fp32 [1] device tensors
-    achieved_lufs, true_peak, min_gain."""
-    check_limiter(scale_norm, limiter, return_stats)
-    gain = output_gain(scale_norm, target_audio)
+    ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which
+    is what the reference does at denoise_ratio == 0.  ``scale_norm`` ... ``return_stats``: the int16 stage, see
+    `output.OutputStage`; the prompt of 'prompt' is ``target_audio`` (inference_vc.py:104-105)."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
+    gain = stage.gain(target_audio)
     x_w2v = models.w2v(Fh.reflect_pad(source_audio, 40))                       # :85-86
     T = x_w2v.shape[2]
     x_length = torch.tensor([T], dtype=torch.int64, device=x_w2v.device)
@@ -98,18 +95,12 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     trg_mel = mel_fn(both)                                                     # [2, 80, Tm]  (:113-126)
     trg_len = torch.tensor([trg_mel.shape[2]] * 2, dtype=torch.int64, device=x_w2v.device)
     audio = models.voc.voice_conversion_noise_control(x_w2v, x_length, trg_mel, trg_len, lf0.reshape(1, -1)[:, :4 * T],
-                                                      noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio, noise=noise)
+                                                      noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
+                                                      noise=noise)
     if output_sr in (24000, 48000):
         audio = _sr_model(models)(audio)                                       # :147-151
-    if scale_norm == "lufs":
-        wav, stats = int16_rows(audio.reshape(1, -1), None, output_rate(output_sr), scale_norm, gain, target_lufs, limiter,
-                                ceiling_db, lookahead_ms, limiter_passes)
-    else:
-        wav = peak_int16(audio.reshape(1, -1), torch.tensor([audio.shape[-1]], device=audio.device), gain)
-    out = (wav.reshape(-1), audio) if return_float else (wav.reshape(-1),)
-    if return_stats:
-        out = (*out, stats)
-    return out if len(out) > 1 else out[0]
+    wav, stats = stage.int16(audio.reshape(1, -1), None, output_rate(output_sr), gain)
+    return pack(wav.reshape(-1), (audio, return_float), (stats, return_stats))
 
 
 def _sr_model(models):
@@ -146,11 +137,6 @@ def output_length(frames, output_sr: int = 16000):
     """Output samples of a row of ``frames`` vocoder frames at ``output_sr`` (SpeechSR: x1.5 / x3)."""
     n = frames * FRAME
     return n * output_sr // 16000 if output_sr in (24000, 48000) else n
-
-
-def output_rate(output_sr: int) -> int:
-    """The rate written to the WAV header (inference_vc.py:164-170): 48000, 24000, or 16000 for any other value."""
-    return output_sr if output_sr in (24000, 48000) else 16000
 
 
 def output_name(source_path, target_path) -> str:
@@ -214,14 +200,17 @@ def check_batch(src_lengths, f0_src_lengths, trg_lengths, f0_trg_lengths):
         raise L.HspError(f"vc_batch: {len(trg_lengths)} prompts but {len(f0_trg_lengths)} prompt F0 tracks")
     for b, (n, nf) in enumerate(zip(src_lengths, f0_src_lengths)):
         if n <= 0 or n % SOURCE_HOP:
-            raise L.HspError(f"vc_batch: source {b} has {n} samples; pad it with pad_source (a multiple of {SOURCE_HOP})")
+            raise L.HspError(f"vc_batch: source {b} has {n} samples; pad it with pad_source (a multiple of "
+                             f"{SOURCE_HOP})")
         if nf < f0_samples(n):
-            raise L.HspError(f"vc_batch: source {b}: F0 track of {nf} frames, needs >= {f0_samples(n)} (= {n} / {F0_HOP})")
+            raise L.HspError(f"vc_batch: source {b}: F0 track of {nf} frames, needs >= {f0_samples(n)} "
+                             f"(= {n} / {F0_HOP})")
     for p, (n, nf) in enumerate(zip(trg_lengths, f0_trg_lengths)):
         if n <= 640:
             raise L.HspError(f"vc_batch: prompt {p} has {n} samples; the mel transform needs more than 640")
         if nf < n // F0_HOP or nf <= 0:
-            raise L.HspError(f"vc_batch: prompt {p}: F0 track of {nf} frames, needs >= {n // F0_HOP} (= {n} / {F0_HOP})")
+            raise L.HspError(f"vc_batch: prompt {p}: F0 track of {nf} frames, needs >= {n // F0_HOP} "
+                             f"(= {n} / {F0_HOP})")
 
 
 # ---------------------------------------------------------------- batched conversion: device side
@@ -256,11 +245,13 @@ def _stack(rows, device, width=None):
 
 
 def _rows(arg, device, what):
-    """A list of rows, or (padded [B, N] tensor, int64 [B] lengths) -> (padded, device lengths, host lengths or None)."""
+    """A list of rows, or (padded [B, N] tensor, int64 [B] lengths) -> (padded, device lengths, host lengths or
+    None)."""
     if isinstance(arg, tuple):
         x, n = arg
         if x.dim() != 2 or n.shape != (x.shape[0],):
-            raise L.HspError(f"vc_batch: {what} as (padded [B, N], lengths [B]), got {tuple(x.shape)} / {tuple(n.shape)}")
+            raise L.HspError(f"vc_batch: {what} as (padded [B, N], lengths [B]), got {tuple(x.shape)} / "
+                             f"{tuple(n.shape)}")
         return x.to(torch.float32).contiguous(), n.to(device=device, dtype=torch.int64).contiguous(), None
     x, lens = _stack(list(arg), device)
     return x, _device_lengths(lens, device), lens
@@ -305,11 +296,8 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
              ``denoised``, every distinct prompt is denoised here in one packed pass (``denoise_prompts``).  Giving
              both ``denoised`` and ``denoiser``, or ``denoise_ratio != 0`` with neither, is an error;
     noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn;
-    scale_norm  'max' / 'prompt' as in ``vc``; 'lufs': every row is brought to ``target_lufs`` over its own length
-             (``functional.loudness`` -> ``loudness_gains``: still no host read-back);
-    limiter / ceiling_db / lookahead_ms / limiter_passes  as in ``vc``: with scale_norm='lufs', every row goes through
-             the look-ahead true-peak limiter over its own length (``functional.lufs_limit_int16``: launches only);
-             ``return_stats`` appends its per-row stats (a dict of fp32 [B] device tensors) to the result.
+    scale_norm ... return_stats  the int16 stage, see `output.OutputStage`: every row over its own length, 'prompt'
+             with the peak of the row's own prompt (taken on the device: no norm reads anything back to the host).
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
     (320 T_b at 16 kHz, x1.5 / x3 with SpeechSR), zeros after; with ``return_float`` also the float audio
@@ -317,12 +305,14 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     with per-row frame counts as ``tts`` does at B > 1.  ``row_exact``: the vocoder runs each row as
     at B = 1 too (key-masked flows, ragged activations, zeros past every row's end), so every row equals ``vc`` on it
     alone, at 16, 24 and 48 kHz."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
     voc = models.voc
     if denoised is not None and denoiser is not None:
         raise L.HspError("vc_batch: give the denoised prompts or a denoiser, not both")
     if denoise_ratio != 0 and denoised is None and denoiser is None:
-        raise L.HspError("vc_batch: denoise_ratio != 0 needs the denoised prompts (denoised=) or a denoiser (denoiser=, "
-                         "hps_denoiser=)")
+        raise L.HspError("vc_batch: denoise_ratio != 0 needs the denoised prompts (denoised=) or a denoiser "
+                         "(denoiser=, hps_denoiser=)")
     if denoiser is not None and hps_denoiser is None:
         raise L.HspError("vc_batch: a denoiser needs its config (hps_denoiser=)")
     dev = sources[0].device
@@ -359,9 +349,6 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
         if Ls % SOURCE_HOP or fs.shape[1] < Ls // F0_HOP:
             raise L.HspError(f"vc_batch: padded sources [B, {Ls}] need Ls % {SOURCE_HOP} == 0 and tracks of >= "
                              f"{Ls // F0_HOP} columns, got {fs.shape[1]}")
-    if scale_norm not in SCALE_NORMS:
-        raise L.HspError(f"unknown scale_norm {scale_norm!r} ({', '.join(map(repr, SCALE_NORMS))})")
-    check_limiter(scale_norm, limiter, return_stats)
     if output_sr in (24000, 48000):
         _sr_model(models)
 
@@ -412,23 +399,13 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
             audio = models.sr(audio)                                           # :147-151
     _stage("int16")
     n_valid = output_length(frames, output_sr)
-    # int16 with each row's gain (:157-160): 0.999, the peak of the row's own prompt, or the one that meets target_lufs
-    stats = None
-    if limiter:
-        wav, stats = Fh.lufs_limit_int16(audio, n_valid, output_rate(output_sr), target_lufs, ceiling_db, lookahead_ms,
-                                         limiter_passes)
-    elif scale_norm == "max":
-        gains = torch.full((B,), 0.999, dtype=torch.float32, device=dev)
-    elif scale_norm == "lufs":
-        gains, _ = Fh.loudness_gains(*Fh.loudness(audio, output_rate(output_sr), n_valid), target_lufs)
-    else:
+    gain = 0.999
+    if stage.scale_norm == "prompt":   # (:157-160) the peak of each row's own prompt, as a device fp32 [B]
         peaks = Fh.abs_max_rows(pm[0::2].contiguous(), pm_len[0::2].contiguous())
-        gains = peaks.expand(B).contiguous() if P == 1 else torch.cat([peaks[index[b]:index[b] + 1] for b in range(B)])
-    if not limiter:
-        wav = Fh.peak_int16_gains(audio, n_valid, gains)
+        gain = peaks.expand(B).contiguous() if P == 1 else torch.cat([peaks[index[b]:index[b] + 1] for b in range(B)])
+    wav, stats = stage.int16(audio, n_valid, output_rate(output_sr), gain)
     _stage("end")
-    out = (wav, n_valid, audio) if return_float else (wav, n_valid)
-    return (*out, stats) if return_stats else out
+    return pack(wav, (n_valid, True), (audio, return_float), (stats, return_stats))
 
 
 @torch.no_grad()
@@ -439,20 +416,20 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     path -> track) or else from the '.hf0.npy' file extract_f0.py writes beside each WAV (a missing track is an error
     naming the file), ``vc_batch`` calls (keywords ``kw``; ``noise`` [B, 192, T_max] is sliced per batch; ``denoiser=``
     and ``hps_denoiser=`` with ``denoise_ratio != 0`` denoise every distinct prompt file of a batch in one packed pass,
-    the reference harness's step :117-133), and with
-    ``out_dir`` one '<src>_to_<trg>.wav' per row at the output rate.  ``target_paths``: one prompt file for every source,
-    or one per source.
+    the reference harness's step :117-133), and with ``out_dir`` one '<src>_to_<trg>.wav' per row at the output rate.
+    ``target_paths``: one prompt file for every source, or one per source.
 
     ``group_by_length`` True: one vc_batch call per padded source length (`length_groups`), so every batch has equal
     rows and each output matches the one-file conversion (contract item 2).  False: ONE ragged batch,
     faster, but every row shorter than the longest differs from its one-file conversion over its whole length (the
     flows' attention sees the batch's padding; contract item 3).  None (the default): True, unless ``row_exact=True``
     is given -- then ONE ragged batch whose rows each match their one-file conversion.
-    ``limiter`` / ``ceiling_db`` / ``lookahead_ms`` / ``limiter_passes`` go to ``vc_batch`` with ``kw``;
-    ``return_stats=True`` appends the limiter's per-row stats (fp32 [B] tensors in the order of ``source_paths``).
+    The fields of `output.OutputStage` go to ``vc_batch`` with ``kw``; ``return_stats=True`` appends the limiter's
+    per-row stats (fp32 [B] tensors in the order of ``source_paths``).
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device); the files hold wav[b, :lengths[b]]."""
     from .audio import load_16k
     from .inference_plm import write_wav
+    return_stats = OutputStage.of(kw).check().return_stats                  # before any file is read
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     source_paths = [str(p) for p in source_paths]
@@ -478,7 +455,6 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     f0_srcs = [track(p) for p in source_paths]
     groups = length_groups([s.shape[-1] for s in sources]) if group_by_length else [list(range(B))]
     noise = kw.pop("noise", None)
-    return_stats = bool(kw.get("return_stats", False))
     parts, part_stats = [], []
     for rows in groups:
         T = max(sources[b].shape[-1] for b in rows) // FRAME
@@ -509,4 +485,4 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
         host = wav.cpu()
         for b in range(B):
             write_wav(os.path.join(str(out_dir), output_name(source_paths[b], trg_paths[b])), rate, host[b, :n[b]])
-    return (wav, lengths, stats) if return_stats else (wav, lengths)
+    return pack(wav, (lengths, True), (stats, return_stats))

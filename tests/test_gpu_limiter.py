@@ -233,6 +233,55 @@ def test_chain_capture_replays_equal_eager(device):
             assert torch.equal(e, r)
 
 
+# ---------------------------------------------------------------------------------------------- the output stage
+@pytest.mark.parametrize("fs,lens", [(16000, (9600, 7000, 3000, 0)), (48000, (24000, 20000))])
+def test_output_stage_int16_equals_the_functional_chains(fs, lens, device):
+    """OutputStage.int16 is a dispatch and nothing else: every norm gives the bits of the functional chain it names.
+    Row 0 (bursty) is over full scale at the target's plain gain, so the capped gain of 'lufs' and the limiter both
+    work on it; row 1 (speech at 0.9) needs neither; at 16 kHz row 2 is under 400 ms (the ungated meter) and row 3
+    is empty."""
+    from megatts2_hierspeechpp_amd import functional as Fh
+    from megatts2_hierspeechpp_amd.output import OutputStage
+    target, n = -16.0, max(lens)
+    sig = [M.bursty(n, 3, fs), R.speech(lens[1], 5, fs, level=0.9)]
+    buf = torch.full((len(lens), n), float("nan"), dtype=torch.float32)
+    for b, nb in enumerate(lens):
+        buf[b, :nb] = torch.from_numpy(sig[b % 2][:nb])
+    x, nv = buf.to(device), torch.tensor(lens, dtype=torch.int64, device=device)
+    row_gains = torch.tensor([0.5, 0.7, 0.9, 0.3][:len(lens)], dtype=torch.float32, device=device)
+
+    def equal(got, want):
+        (w, s), (w_ref, s_ref) = got, want
+        assert w.dtype == torch.int16 and w.shape == x.shape and torch.equal(w, w_ref)
+        assert (s is None) == (s_ref is None)
+        for k in ("achieved_lufs", "true_peak", "min_gain") if s is not None else ():
+            assert torch.equal(s[k], s_ref[k]), k
+
+    w_max = Fh.peak_int16(x, nv, 0.999)
+    equal(OutputStage(scale_norm="max").int16(x, nv, fs, 0.999), (w_max, None))
+    equal(OutputStage().int16(x, nv, fs), (w_max, None))
+    equal(OutputStage(scale_norm="max").int16(x, nv, fs, torch.full_like(row_gains, 0.999)), (w_max, None))
+    equal(OutputStage(scale_norm="prompt").int16(x, nv, fs, row_gains), (Fh.peak_int16_gains(x, nv, row_gains), None))
+    lufs = OutputStage(scale_norm="lufs", target_lufs=target)
+    equal(lufs.int16(x, nv, fs), (Fh.lufs_int16(x, nv, fs, target), None))
+    equal(lufs.int16(x.unsqueeze(1), nv, fs, row_gains), (Fh.lufs_int16(x, nv, fs, target), None))   # no gain in 'lufs'
+    wav, stats = OutputStage(scale_norm="lufs", target_lufs=target, limiter=True, return_stats=True).int16(x, nv, fs)
+    equal((wav, stats), Fh.lufs_limit_int16(x, nv, fs, target, -1.0, 1.5, 2))
+    equal(OutputStage(scale_norm="lufs", target_lufs=target, limiter=True, ceiling_db=-2.0, lookahead_ms=5.0,
+                      limiter_passes=1).int16(x, nv, fs), Fh.lufs_limit_int16(x, nv, fs, target, -2.0, 5.0, 1))
+    # not vacuous: the limiter engages on row 0 and idles on row 1, and 'lufs' alone caps row 0 and not row 1
+    l0, p0 = Fh.loudness(x, fs, nv)
+    gains, limited = Fh.loudness_gains(l0, p0, target)
+    print(f"fs {fs}: plain gain x peak {(10.0 ** ((target - l0[:2].double()) / 20.0) * p0[:2]).tolist()}, capped gains "
+          f"{gains.tolist()}, limited {limited.tolist()}, min_gain {stats['min_gain'].tolist()}")
+    assert float(stats["min_gain"][0]) < 1.0 and float(stats["min_gain"][1]) == 1.0
+    assert limited[:2].tolist() == [1, 0]
+    w_lufs = Fh.lufs_int16(x, nv, fs, target)
+    assert not torch.equal(wav, w_lufs) and not torch.equal(w_max, w_lufs)    # three norms, three different results
+    for b, nb in enumerate(lens):
+        assert not wav[b, nb:].any() and not w_max[b, nb:].any()
+
+
 # ---------------------------------------------------------------------------------------------- harnesses
 def _mel_fn(device):
     from megatts2_hierspeechpp_amd.Mels_preprocess import MelSpectrogramFixed
@@ -256,6 +305,15 @@ def _stats_equal_the_chain(stats, wav_rows, audio_rows, fs, target):
         print(f"row {b}: achieved {float(s1['achieved_lufs'][0]):.3f} LUFS, true peak {float(s1['true_peak'][0]):.4f}, "
               f"min_gain {float(s1['min_gain'][0]):.4f}")
         assert float(s1["true_peak"][0]) <= C32
+
+
+def _equals_the_chain(wav, stats, audio, n_valid, fs, target):
+    """what a harness returned equals lufs_limit_int16 on the float audio it returned, the whole batch in one call"""
+    from megatts2_hierspeechpp_amd import functional as Fh
+    w, s = Fh.lufs_limit_int16(audio, n_valid, fs, target)
+    assert torch.equal(w, wav)
+    for k in ("achieved_lufs", "true_peak", "min_gain"):
+        assert torch.equal(s[k], stats[k]), k
 
 
 def test_vc_batch_limiter(device):
@@ -284,9 +342,11 @@ def test_vc_batch_limiter(device):
                            16000, -16.0)
     for b, n in enumerate(lens):
         assert not wav[b, n:].any()
-    w1, s1 = IV.vc(models, mel_fn, srcs[1], f0s[1].reshape(1, -1), prompt, f0t.reshape(1, -1), noise=noise[1:2],
-                   scale_norm="lufs", target_lufs=-16, limiter=True, return_stats=True)
+    _equals_the_chain(wav, stats, audio, n_out, 16000, -16.0)                  # the ragged batch as one chain call
+    w1, a1, s1 = IV.vc(models, mel_fn, srcs[1], f0s[1].reshape(1, -1), prompt, f0t.reshape(1, -1), noise=noise[1:2],
+                       return_float=True, scale_norm="lufs", target_lufs=-16, limiter=True, return_stats=True)
     assert w1.dtype == torch.int16 and s1["achieved_lufs"].shape == (1,) and float(s1["true_peak"][0]) <= C32
+    _equals_the_chain(w1.reshape(1, -1), s1, a1, None, 16000, -16.0)
 
 
 def test_tts_from_prompt_limiter_and_takes(device):
@@ -312,11 +372,13 @@ def test_tts_from_prompt_limiter_and_takes(device):
     wav, audio, stats = IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, limiter=True, return_stats=True, **kw)
     assert wav.dtype == torch.int16 and wav.shape == w0.shape and torch.equal(audio, a0)
     _stats_equal_the_chain(stats, [wav], [audio[0]], 16000, -16.0)
+    _equals_the_chain(wav.reshape(1, -1), stats, audio, None, 16000, -16.0)
     sp = PlmSampling(temperature=1.1, top_k=40, top_p=0.95, repetition_penalty=1.2)
     wav2, audio2, stats2 = IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, limiter=True, return_stats=True,
                                               plm_sampling=sp, seed=3, takes=2, **kw)
     assert wav2.shape == (2, wav.shape[0]) and stats2["min_gain"].shape == (2,)
     _stats_equal_the_chain(stats2, [wav2[0], wav2[1]], [audio2[0], audio2[1]], 16000, -16.0)
+    _equals_the_chain(wav2, stats2, audio2, None, 16000, -16.0)                # both takes as one chain call
 
 
 def test_super_resolution_limiter(device):
@@ -333,3 +395,4 @@ def test_super_resolution_limiter(device):
     wav, stats = super_resolution(sr, x, 16000, scale_norm="lufs", target_lufs=-16.0, limiter=True, return_stats=True)
     assert wav.shape == (48000,) and wav.dtype == torch.int16
     _stats_equal_the_chain(stats, [wav], [sr(x.unsqueeze(1)).reshape(-1)], 48000, -16.0)
+    _equals_the_chain(wav.reshape(1, -1), stats, sr(x.unsqueeze(1)), None, 48000, -16.0)

@@ -185,7 +185,7 @@ def _reads_target(wav_row, fs, target, what):
 
 
 def test_vc_batch_scale_norm_lufs(device):
-    from megatts2_hierspeechpp_amd import _lib, inference_vc as IV, synth
+    from megatts2_hierspeechpp_amd import _lib, functional as Fh, inference_vc as IV, synth
     from oracle.hsp_oracle import default_config
     models = IV.VcModels(default_config())
     models.load_state_dict({k: torch.from_numpy(synth.synth_tensor(k, tuple(v.shape), 2))
@@ -206,16 +206,18 @@ def test_vc_batch_scale_norm_lufs(device):
     for b, n in enumerate(n_out.tolist()):
         _reads_target(wav[b, :n], 16000, -27.0, f"vc_batch row {b}")
         assert not wav[b, n:].any()
+    assert torch.equal(wav, Fh.lufs_int16(audio, n_out, 16000, -27.0))         # the stage is that chain on these rows
     # the single-utterance harness takes the same rule
-    w1 = IV.vc(models, mel_fn, srcs[1], f0s[1].reshape(1, -1), prompt, f0t.reshape(1, -1), noise=noise[1:2],
-               scale_norm="lufs", target_lufs=-27)
+    w1, a1 = IV.vc(models, mel_fn, srcs[1], f0s[1].reshape(1, -1), prompt, f0t.reshape(1, -1), noise=noise[1:2],
+                   return_float=True, scale_norm="lufs", target_lufs=-27)
     _reads_target(w1, 16000, -27.0, "vc")
+    assert torch.equal(w1, Fh.lufs_int16(a1, None, 16000, -27.0).reshape(-1))
     with pytest.raises(_lib.HspError, match="unknown scale_norm"):
         IV.vc_batch(models, mel_fn, srcs, f0s, prompt, f0t, noise=noise, scale_norm="rms")
 
 
 def test_tts_from_prompt_scale_norm_lufs(device):
-    from megatts2_hierspeechpp_amd import _lib, inference_plm as IP, synth
+    from megatts2_hierspeechpp_amd import _lib, functional as Fh, inference_plm as IP, synth
     from oracle.hsp_oracle import default_config
     models = IP.TtsModels(default_config(), H.TTV_MODEL)
     models.load_state_dict({k: torch.from_numpy(synth.synth_tensor(k, tuple(v.shape), 7))
@@ -234,8 +236,10 @@ def test_tts_from_prompt_scale_norm_lufs(device):
     wav, audio = IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, scale_norm="lufs", **kw)
     assert wav.dtype == torch.int16 and wav.shape == w_max.shape and torch.equal(audio, a_max)
     _reads_target(wav, 16000, -23.0, "tts_from_prompt")
-    w27, _ = IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, scale_norm="lufs", target_lufs=-27.0, **kw)
+    assert torch.equal(wav, Fh.lufs_int16(audio, None, 16000, -23.0).reshape(-1))
+    w27, a27 = IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, scale_norm="lufs", target_lufs=-27.0, **kw)
     _reads_target(w27, 16000, -27.0, "tts_from_prompt at -27")
+    assert torch.equal(w27, Fh.lufs_int16(a27, None, 16000, -27.0).reshape(-1))
     with pytest.raises(_lib.HspError, match="unknown scale_norm"):
         IP.tts_from_prompt(models, mel_fn, ids, tone, lang, prompt, scale_norm="rms", **kw)
 
