@@ -11,9 +11,9 @@ All packed tensors of a model live in one contiguous fp32 arena so that a multi-
 job can ship them with a single RCCL broadcast.
 
 Every launch of this module leaves through ``_bracket``, the one place that knows its measurement
-hook (``LAUNCH_HOOK``): a conv's argument struct by way of ``_launch``, which inside ``deferred()``
-records it for ``launch_group`` instead (per context, like ``row_exact``).  The event bracket itself is
-``_lib.timed``, which ``functional.act1d`` uses for its own hook (``ACT_HOOK``) too.
+hook (``LAUNCH_HOOK``).  A conv layer builds its launch (``prepare`` -> ``ConvLaunch``: the filled struct and the tensors
+it points at) and then issues it (``ConvLaunch.run``); a caller of an entry point that takes several structs prepares them
+itself for ``launch_group``.  The event bracket is ``_lib.timed``, which ``functional.act1d`` uses for ``ACT_HOOK`` too.
 """
 from __future__ import annotations
 
@@ -37,7 +37,7 @@ LAUNCH_HOOK = None
 # hsp_conv1d_args.debug of every conv launch.  Always 0 in the product: the release libhsp.so refuses anything
 # else.  tools/ set it programmatically together with HSP_LIB=.../libhsp_tune.so (kernel decomposition runs).
 DEBUG_FLAGS = 0
-# Folded columns (hsp_conv1d_args.fold_cols): Conv1d.forward sets the field on the B > 1 launches whose kernel implements
+# Folded columns (hsp_conv1d_args.fold_cols): Conv1d.prepare sets the field on the B > 1 launches whose kernel implements
 # it (fold_cols_wanted).  Results are bit-identical either way; HSP_FOLD_COLS is the switch of a same-box A/B
 # (tools/env_ab.py): "1" on, "0" off, "gemm" / "conv" the block token GEMM / the conv tiles alone.
 FOLD_COLS = os.environ.get("HSP_FOLD_COLS", "1")
@@ -161,32 +161,11 @@ def fft_act_fusable(x) -> bool:
             and x.data_ptr() % 16 == 0)
 
 
-# SURVEY.md §8(b) names its minimum C ABI (hsp_conv1d_f32, hsp_convtr1d_f32, hsp_wn_layer_f32,
-# hsp_layernorm_modulate_f32).  Those entry points dispatch to the kernel-level ones this module calls by
-# default; with SURVEY_ABI set (HSP_SURVEY_ABI=1) every launch goes through them instead - same kernels, same
-# results (tests/test_gpu_parity.py::test_survey_abi_names_give_identical_results): _launch() swaps the entry point of a
-# single conv, and modules.WN / modules.DiTConVBlock collect their layers' structs under deferred() for launch_group().
+# SURVEY.md §8(b) names its minimum C ABI (hsp_conv1d_f32, hsp_convtr1d_f32, hsp_wn_layer_f32, hsp_layernorm_modulate_f32).
+# Those entry points dispatch to the kernel-level ones this module calls by default; with SURVEY_ABI set (HSP_SURVEY_ABI=1)
+# every launch goes through them instead - same kernels, same results (test_survey_abi_names_give_identical_results):
+# ConvLaunch.run() swaps the entry point of a single conv; modules.WN / DiTConVBlock prepare a layer's launches for launch_group().
 SURVEY_ABI = os.environ.get("HSP_SURVEY_ABI", "0") == "1"
-# The list of the enclosing deferred() block, or None: while a caller collects the argument structs of several layers for
-# ONE fused entry point (modules.WN -> hsp_wn_layer_f32, modules.DiTConVBlock -> hsp_ffn_conv_f32; both only under
-# SURVEY_ABI) _launch() records instead of launching.  A context variable for the reason _ROWS is one: a second thread
-# that launches while the first is inside deferred() must launch.
-_DEFER: "contextvars.ContextVar[Optional[list]]" = contextvars.ContextVar("hsp_deferred", default=None)
-
-
-class deferred:
-    """``with deferred() as args:`` -- conv layers called inside only build their hsp_conv1d_args (outputs are
-    allocated as usual); the caller passes the collected structs to a fused entry point with launch_group()."""
-
-    def __enter__(self):
-        assert _DEFER.get() is None, "deferred() does not nest"
-        structs = []
-        self._token = _DEFER.set(structs)
-        return structs
-
-    def __exit__(self, *exc):
-        _DEFER.reset(self._token)
-        return False
 
 
 def _bracket(kind: str, call, flops: int, nbytes: int, arg, soft: bool = False, span=None):
@@ -206,29 +185,41 @@ def _bracket(kind: str, call, flops: int, nbytes: int, arg, soft: bool = False, 
     return rc, e0, e1
 
 
-def launch_group(kind: str, fn, structs, *extra):
-    """One call into a fused entry point taking several hsp_conv1d_args; measurement hook as for _launch().
-    ``structs``: the (args, flops, bytes, keep) entries collected by deferred(); a None entry is passed as NULL."""
-    flops = sum(e[1] for e in structs if e is not None)
-    nbytes = sum(e[2] for e in structs if e is not None)
-    ptrs = [C.byref(e[0]) if e is not None else None for e in structs]
-    _bracket(kind, lambda: fn(*ptrs, *extra, L.stream_ptr()), flops, nbytes, structs[0][0])
+class ConvLaunch:
+    """One conv launch, built (Conv1d.prepare, ConvTranspose1d.prepare) and not yet issued: the entry point ``fn``, its
+    ``kind`` for the hook, the filled hsp_conv1d_args ``args``, the algorithmic ``flops`` / ``nbytes``, the output ``out`` and
+    ``refs``: every tensor the struct's raw device pointers address (a residual gathered while preparing included), which
+    stays alive through them until the launch has been issued."""
+    __slots__ = ("kind", "fn", "args", "flops", "nbytes", "out", "refs")
+
+    def __init__(self, kind, fn, args, flops, nbytes, out, refs):
+        self.kind = kind
+        self.fn = fn
+        self.args = args
+        self.flops = flops
+        self.nbytes = nbytes
+        self.out = out
+        self.refs = refs
+
+    def run(self, soft: bool = False) -> int:
+        """Issue the launch.  ``soft``: return the status instead of raising on HSP_EINVAL (a shape the requested
+        fusion does not cover; the caller then issues the un-fused launches)."""
+        a, fn = self.args, self.fn
+        a.debug = DEBUG_FLAGS
+        if SURVEY_ABI:
+            fn = L.lib().hsp_convtr1d_f32 if a.rows == L.ROWS_SHUFFLE else L.lib().hsp_conv1d_f32
+        return _bracket(self.kind, lambda: fn(C.byref(a), L.stream_ptr()), self.flops, self.nbytes, a, soft=soft)[0]
 
 
-def _launch(kind: str, fn, a, flops: int, nbytes: int, soft: bool = False, keep=()):
-    """``soft``: return the status instead of raising on HSP_EINVAL (a shape the requested fusion does not
-    cover; the caller then issues the un-fused launches)."""
-    a.debug = DEBUG_FLAGS
-    structs = _DEFER.get()
-    if structs is not None:
-        # the struct holds raw device pointers: `keep` pins the tensors behind them until launch_group() has run
-        if soft or a.ln_c1 or a.split_row:    # not an assert: python -O would pass a fused-LayerNorm struct through
-            raise L.HspError("deferred(): no soft / fused-LayerNorm / split launches")
-        structs.append((a, flops, nbytes, keep))
-        return 0
-    if SURVEY_ABI:
-        fn = L.lib().hsp_convtr1d_f32 if a.rows == L.ROWS_SHUFFLE else L.lib().hsp_conv1d_f32
-    return _bracket(kind, lambda: fn(C.byref(a), L.stream_ptr()), flops, nbytes, a, soft=soft)[0]
+def launch_group(kind: str, fn, launches, *extra):
+    """One call into an entry point taking several hsp_conv1d_args (``launches``: ConvLaunch objects, None = a NULL
+    slot); one hook record with the summed flops / bytes and the first struct."""
+    live = [p for p in launches if p is not None]
+    for p in live:
+        p.args.debug = DEBUG_FLAGS
+    ptrs = [C.byref(p.args) if p is not None else None for p in launches]
+    _bracket(kind, lambda: fn(*ptrs, *extra, L.stream_ptr()), sum(p.flops for p in live), sum(p.nbytes for p in live),
+             launches[0].args)
 
 
 def _set_fold_cols(a) -> None:
@@ -676,8 +667,8 @@ class Conv1d(_ConvBase):
         a.M, a.w_ld, a.w_bs = 2 * Cc, 2 * Cc, 4 * Cc * Cc
         _set_out(a, yf, 64, 2 * Cc, Np)
         a.ncols, a.rows, a.scale, a.post_scale = Np, L.ROWS_PLAIN, 1.0, 1.0
-        _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, 2 * 64 * 4 * Cc * Cc * Np,
-                4 * (64 * 2 * 2 * Cc * Np + 64 * 4 * Cc * Cc))
+        ConvLaunch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, 2 * 64 * 4 * Cc * Cc * Np,
+                   4 * (64 * 2 * 2 * Cc * Np + 64 * 4 * Cc * Cc), yf, (xf, yf, wf)).run()
         return yf
 
     def _fft_inverse_args(self, yf, B, Lx):
@@ -772,15 +763,22 @@ class Conv1d(_ConvBase):
         return out
 
     # ----------------------------------------------------------------------------
-    def forward(self, x, *, act1d=None, lrelu: Optional[float] = None, silu_in=False, act=L.ACT_NONE, cbias=None,
+    def prepare(self, x, **kw) -> ConvLaunch:
+        """The launch ``forward(x, **kw)`` would issue, built and not issued, for a caller of launch_group -- which takes
+        plain GEMMs only: ``split_out`` and the fused input LayerNorm have launch protocols that are forward's alone."""
+        if self._pre_norm is not None or "split_out" in kw:
+            raise L.HspError("prepare(): split-row and fused-LayerNorm launches go through forward() only")
+        return self._prepare(x, **kw)
+
+    def _prepare(self, x, *, act1d=None, lrelu: Optional[float] = None, silu_in=False, act=L.ACT_NONE, cbias=None,
                 mask=None, mask_mode=L.MASK_NONE, cscale=None, scale=1.0, res=None, out=None, accumulate=False,
-                post_scale=1.0, force_direct=False, row_range=None, split_out=None, mask_mode2=L.MASK_NONE):
-        """``row_range=(r0, r1)`` computes only output channels [r0, r1) (PLAIN rows, r0 % 4 == 0):
-        the WN res/skip layer is one parameter set feeding two differently-fused launches.
+                post_scale=1.0, force_direct=False, row_range=None, split_out=None, mask_mode2=L.MASK_NONE) -> ConvLaunch:
+        """The launch of this conv on x [B, Cin, L], built and not issued: geometry, the output (allocated when None),
+        the filled struct, the direct-versus-MFMA choice.  ``row_range=(r0, r1)`` computes only output channels [r0, r1)
+        (PLAIN rows, r0 % 4 == 0): the WN res/skip layer is one parameter set feeding two differently-fused launches.
         ``split_out=(split_row, out2, accumulate2)``: ONE launch for both halves of such a layer
         (hsp_conv1d_args.split_row): rows [0, split_row) -> the usual output with this call's epilogue, rows
-        [split_row, cout) -> ``out2`` (+= if accumulate2; allocated when None).  Returns (out, out2), or None when
-        the library has no fused kernel for the shape (the caller then launches the halves separately)."""
+        [split_row, cout) -> ``out2`` (+= if accumulate2; allocated when None); the launch's ``out`` is then (out, out2)."""
         self._require_ready()
         if act1d is not None and _ROWS.get() is not None:
             raise L.HspError("row_exact: the conv-prologue Activation1d (HSP_FUSE_ACT_MAX_C > 0) has no ragged form")
@@ -835,37 +833,38 @@ class Conv1d(_ConvBase):
         # algorithmic traffic: input once, output once (+ residual / accumulate reads), weights once
         nbytes = 4 * (B * Cin * Lin + B * cout * Lout * (1 + (res is not None) + bool(accumulate))
                       + rows_full * Cin * self.k)
-        # every tensor the struct points at that a caller may drop before a deferred() group is launched (`res`: the
-        # gathered copy where one was made)
-        keep = (x, out, out2, res, cbias, mask, cscale)
-        kind, fn = ("hsp_conv1d_direct_f32", L.lib().hsp_conv1d_direct_f32) if direct else \
-            ("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32)
-        if split_out is not None:
+        if split_out is not None:                   # the split-row kernel is an MFMA one
+            direct = False
             a.Cout = self.cout                      # rows [split_row, cout) go to the second output
             a.split_row, a.accumulate2, a.mask_mode2 = split_row, int(bool(acc2)), mask_mode2   # (the second output shares `mask`)
             a.y2, a.y2_bs, a.y2_cs = L.fptr(out2), out2.stride(0), out2.stride(1)
             flops = 2 * B * self.cout * Cin * Lout
             nbytes += 4 * B * (self.cout - split_row) * Lout * (1 + bool(acc2))
-            _set_fold_cols(a)
-            rc = _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, soft=True, keep=keep)
-            return None if rc else (out, out2)
+        kind, fn = ("hsp_conv1d_direct_f32", L.lib().hsp_conv1d_direct_f32) if direct else \
+            ("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32)
         if not direct:
             _set_fold_cols(a)
-        if self._pre_norm is not None:
-            # fused input LayerNorm: token-GEMM shapes only (16-B addressable columns), and not inside deferred() (the
-            # fused entry points take plain GEMMs).  Anything else runs the normalisation as its own launch -- WITHOUT the
-            # affine part, which is folded into the packed weights (W diag(gamma), W beta + b) -- and then the same GEMM:
-            # identical arithmetic, one launch more.
-            if _DEFER.get() is None and not _launch(kind, fn, a, flops, nbytes, soft=True, keep=keep):
-                return out
+        return ConvLaunch(kind, fn, a, flops, nbytes, out if out2 is None else (out, out2),
+                          (x, out, out2, res, cbias, mask, cscale))
+
+    def forward(self, x, **kw):
+        """``_prepare`` (see there for the arguments) plus one of three launch protocols.  Returns the output; with ``split_out``
+        (out, out2), or None when the library has no fused kernel for the shape (the caller then launches the halves)."""
+        p = self._prepare(x, **kw)
+        if kw.get("split_out") is not None:
+            return None if p.run(soft=True) else p.out
+        if self._pre_norm is None:
+            p.run()
+        elif p.run(soft=True):
+            # fused input LayerNorm: token-GEMM shapes only (16-B addressable columns).  Anything else runs the
+            # normalisation as its own launch -- WITHOUT the affine part, which is folded into the packed weights
+            # (W diag(gamma), W beta + b) -- and then the same GEMM (an MFMA one: _wants_direct): identical arithmetic.
             xn = Fh.layernorm_mod(x, float(self._pre_norm.eps))
-            _set_in(a, xn)
-            a.ln_c1 = None
-            keep += (xn,)
-            if not direct:
-                _set_fold_cols(a)
-        _launch(kind, fn, a, flops, nbytes, keep=keep)
-        return out
+            _set_in(p.args, xn)
+            p.args.ln_c1 = None
+            _set_fold_cols(p.args)
+            p.run()
+        return p.out
 
 
 class ConvTranspose1d(_ConvBase):
@@ -887,7 +886,7 @@ class ConvTranspose1d(_ConvBase):
             if self._b is not None:
                 self._b.copy_(self.bias.data)
 
-    def forward(self, x, *, res=None, out=None, lrelu: Optional[float] = None):
+    def prepare(self, x, *, res=None, out=None, lrelu: Optional[float] = None) -> ConvLaunch:
         self._require_ready()
         B, Cin, Lin = x.shape
         assert Cin == self.cin
@@ -907,8 +906,12 @@ class ConvTranspose1d(_ConvBase):
             a.prologue, a.slope = L.PRO_LRELU, float(lrelu)
         flops = 2 * B * Cin * self.cout * self.k * Lin
         nbytes = 4 * (B * Cin * Lin + B * self.cout * Lout * (1 + (res is not None)) + Cin * self.cout * self.k)
-        _launch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes)
-        return out
+        return ConvLaunch("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32, a, flops, nbytes, out, (x, out, res))
+
+    def forward(self, x, **kw):
+        p = self.prepare(x, **kw)
+        p.run()
+        return p.out
 
 
 class _SubArena:
@@ -1056,8 +1059,9 @@ class StackedLinearCT(Conv1d):
 
 def _set_in(a, x):
     """The input side of hsp_conv1d_args for x [B, Cin, Lin] at any strides."""
-    a.x, a.x_bs, a.x_cs, a.x_ts = L.fptr(x), x.stride(0), x.stride(1), x.stride(2)
     a.B, a.Cin, a.Lin = x.shape
+    a.x_bs, a.x_cs, a.x_ts = x.stride()            # (one call, not three: this runs once per launch)
+    a.x = L.fptr(x)
     a.zeros = L.fptr(_zeros(x.device))
 
 
@@ -1066,7 +1070,7 @@ def _wants_direct(a, force_direct: bool, silu_in: bool) -> bool:
     not take: stride, degenerate channel / length counts, a SiLU prologue.  The same rule as wants_direct() in
     csrc/hsp_abi.hip, which decides again for a struct that arrives through hsp_conv1d_f32 (SURVEY_ABI) -- change the two
     together.  ``force_direct`` (a Linear's L = 1 products) is the host's alone.  Reads rows, prologue, ln_c1, stride,
-    Cin, Cout and Lout of ``a`` as Conv1d.forward has set them."""
+    Cin, Cout and Lout of ``a`` as Conv1d.prepare has set them."""
     gated = a.rows in (L.ROWS_GATE_WN, L.ROWS_GATE_GLU)
     return (not gated and a.prologue != L.PRO_ACT1D and not a.ln_c1 and
             bool(force_direct or a.stride != 1 or a.Cin < 8 or a.Cout < 8 or a.Lout < 8 or silu_in))
@@ -1074,8 +1078,9 @@ def _wants_direct(a, force_direct: bool, silu_in: bool) -> bool:
 
 def _set_out(a, out, B, cout, Lout):
     assert out.shape == (B, cout, Lout), (tuple(out.shape), (B, cout, Lout))
-    assert out.stride(2) == 1 or Lout == 1
-    a.y, a.y_bs, a.y_cs = L.fptr(out), out.stride(0), out.stride(1)
+    a.y_bs, a.y_cs, ts = out.stride()
+    assert ts == 1 or Lout == 1
+    a.y = L.fptr(out)
     a.Cout, a.Lout = cout, Lout
 
 

@@ -4,7 +4,6 @@ arguments and state-dict keys (reference: modules.py).  Every tensor stays chann
 changes only.  All arithmetic is in libhsp.so."""
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import os
 
@@ -21,13 +20,8 @@ LRELU_SLOPE = 0.1  # modules.py:17
 FOLD_MASK = os.environ.get("HSP_FOLD_MASK", "1") == "1"   # WN: the final mask multiply inside the skip launches
 FOLD_FLIP = os.environ.get("HSP_FOLD_FLIP", "1") == "1"   # coupling blocks: Flip inside the next layer's packed pre / post
 
-def _fuse(x) -> bool:
-    """Route a WN layer / DiT FFN through the entry points SURVEY.md 8(b) names for them (hsp_wn_layer_f32,
-    hsp_ffn_conv_f32) -- only under HSP_SURVEY_ABI: they issue the same launches the default path issues itself.
-    (Rounds 2-3 had a one-launch kernel behind them, csrc/hsp_gemm2.hip, chosen by a tile-count policy; it lost to the
-    separate launches at every batch grouping of the step and was retired in round 4:
-    profiles/r04_stage_split_policies.txt.)"""
-    return hip_layers.SURVEY_ABI
+# Under HSP_SURVEY_ABI a WN layer and the DiT FFN go through the entry points SURVEY.md 8(b) names for them (WN._named_layer,
+# DiTConVBlock._named_ffn), which issue the launches of the default path (the one-launch kernel of rounds 2-3: DESIGN.md 4.4)
 
 
 class LayerNorm(HipLayer):
@@ -87,44 +81,41 @@ class WN(nn.Module):
         gc = self.cond_layer(g) if g is not None else None  # [B, 2H*n, 1]
         out = None
         acts = torch.empty(x.shape[0], H, x.shape[2], dtype=torch.float32, device=x.device)
-        fuse = _fuse(x)
         # The final `output * x_mask` (modules.py:176) is applied where each skip contribution is produced: a 0/1 mask
         # times every term of the sum IS the mask times the sum, bit for bit (mask(s_1 + ... + s_n): the same additions on
         # the kept columns, exact zeros on the others) -- one launch per WN less (round 6; HSP_FOLD_MASK=0: the old form)
         skip_mask = L.MASK_PRE if (FOLD_MASK and x_mask is not None) else L.MASK_NONE
         for i in range(self.n_layers):
             cb = gc[:, 2 * H * i: 2 * H * (i + 1)] if gc is not None else None
-            last = i == self.n_layers - 1
-            if not fuse and not last and H % 64 == 0:
-                # layer by layer: gated conv, then BOTH halves of res_skip in one token-GEMM launch
-                # (hsp_conv1d_args.split_row; None = the library has no such kernel for this shape)
-                self.in_layers[i](x, cbias=cb, out=acts)
-                both = self.res_skip_layers[i](acts, res=x, mask=x_mask, mask_mode=L.MASK_POST,
-                                               split_out=(H, out, out is not None), mask_mode2=skip_mask)
-                if both is not None:
-                    x, out = both
-                    continue
-                x_new = self.res_skip_layers[i](acts, row_range=(0, H), res=x, mask=x_mask, mask_mode=L.MASK_POST)
-                out = self.res_skip_layers[i](acts, row_range=(H, 2 * H), out=out, accumulate=out is not None,
-                                              mask=x_mask, mask_mode=skip_mask)
-                x = x_new
+            if hip_layers.SURVEY_ABI:
+                x, out = self._named_layer(i, x, cb, acts, out, x_mask, skip_mask)
                 continue
-            with (hip_layers.deferred() if fuse else contextlib.nullcontext()) as args:
-                self.in_layers[i](x, cbias=cb, out=acts)
-                if not last:
-                    x_new = self.res_skip_layers[i](acts, row_range=(0, H), res=x, mask=x_mask, mask_mode=L.MASK_POST)
-                    out = self.res_skip_layers[i](acts, row_range=(H, 2 * H), out=out, accumulate=out is not None,
-                                                  mask=x_mask, mask_mode=skip_mask)
-                else:
-                    # last layer: output = output + rs (modules.py:175-176)
-                    out = self.res_skip_layers[i](acts, out=out, accumulate=out is not None, mask=x_mask,
-                                                  mask_mode=skip_mask)
-            if fuse:
-                hip_layers.launch_group("hsp_wn_layer_f32", L.lib().hsp_wn_layer_f32,
-                                        [args[0], args[1] if not last else None, args[-1]])
-            if not last:
-                x = x_new
+            self.in_layers[i](x, cbias=cb, out=acts)
+            rs = self.res_skip_layers[i]
+            if i == self.n_layers - 1:
+                # last layer: output = output + rs (modules.py:175-176)
+                out = rs(acts, out=out, accumulate=out is not None, mask=x_mask, mask_mode=skip_mask)
+                break
+            # BOTH halves of res_skip in one token-GEMM launch (hsp_conv1d_args.split_row; None = the library has no such
+            # kernel for this shape), else one launch per half
+            both = rs(acts, res=x, mask=x_mask, mask_mode=L.MASK_POST, split_out=(H, out, out is not None),
+                      mask_mode2=skip_mask) if H % 64 == 0 else None
+            if both is None:
+                both = (rs(acts, row_range=(0, H), res=x, mask=x_mask, mask_mode=L.MASK_POST),
+                        rs(acts, row_range=(H, 2 * H), out=out, accumulate=out is not None, mask=x_mask, mask_mode=skip_mask))
+            x, out = both
         return out if skip_mask != L.MASK_NONE else Fh.mask_mul(out, x_mask)
+
+    def _named_layer(self, i, x, cb, acts, out, x_mask, skip_mask):
+        """Layer i through hsp_wn_layer_f32 (HSP_SURVEY_ABI): the gated in-conv, then res and skip as row ranges of
+        res_skip -- the last layer has no res half (NULL slot), all its rows are skip.  Returns (x, out)."""
+        H, rs, last = self.hidden_channels, self.res_skip_layers[i], i == self.n_layers - 1
+        p_in = self.in_layers[i].prepare(x, cbias=cb, out=acts)
+        p_res = None if last else rs.prepare(acts, row_range=(0, H), res=x, mask=x_mask, mask_mode=L.MASK_POST)
+        p_skip = rs.prepare(acts, row_range=None if last else (H, 2 * H), out=out, accumulate=out is not None, mask=x_mask,
+                            mask_mode=skip_mask)
+        hip_layers.launch_group("hsp_wn_layer_f32", L.lib().hsp_wn_layer_f32, [p_in, p_res, p_skip])
+        return (x if p_res is None else p_res.out), p_skip.out
 
 
 class Flip(nn.Module):
@@ -207,13 +198,17 @@ class DiTConVBlock(nn.Module):
         if key_len is not None:
             h = Fh.mask_mul(h, x_mask)
         # fc1 -> GELU -> fc2; fc2(y * mask) * mask == (W y + b) * mask for a 1x1 conv and a 0/1 mask
-        fuse = _fuse(x)
-        with (hip_layers.deferred() if fuse else contextlib.nullcontext()) as args:
-            y = self.mlp.fc1(h, act=L.ACT_GELU_TANH)
-            out = self.mlp.fc2(y, mask=x_mask, mask_mode=L.MASK_PRE, cscale=g_m, res=x)
-        if fuse:
-            hip_layers.launch_group("hsp_ffn_conv_f32", L.lib().hsp_ffn_conv_f32, args)
-        return out
+        if hip_layers.SURVEY_ABI:
+            return self._named_ffn(h, x, x_mask, g_m)
+        y = self.mlp.fc1(h, act=L.ACT_GELU_TANH)
+        return self.mlp.fc2(y, mask=x_mask, mask_mode=L.MASK_PRE, cscale=g_m, res=x)
+
+    def _named_ffn(self, h, x, x_mask, g_m):
+        """The FFN through hsp_ffn_conv_f32 (HSP_SURVEY_ABI): fc1 and fc2 prepared, one call."""
+        p1 = self.mlp.fc1.prepare(h, act=L.ACT_GELU_TANH)
+        p2 = self.mlp.fc2.prepare(p1.out, mask=x_mask, mask_mode=L.MASK_PRE, cscale=g_m, res=x)
+        hip_layers.launch_group("hsp_ffn_conv_f32", L.lib().hsp_ffn_conv_f32, [p1, p2])
+        return p2.out
 
 
 class ResidualCouplingLayer_Transformer_simple(nn.Module):

@@ -99,3 +99,24 @@ def test_every_launch_site_reports_once_and_the_hook_changes_no_bit(device, monk
     assert len(plain) == len(hooked) == 8
     for i, (p_, h_) in enumerate(zip(plain, hooked)):
         assert torch.equal(p_, h_), i
+
+
+def test_a_prepared_launch_run_is_the_forward_call(device, monkeypatch):
+    """Conv1d.prepare(x).run() is what forward(x) does: the same hook record, the same bits."""
+    from megatts2_hierspeechpp_amd import hip_layers as HL
+    monkeypatch.setattr(HL, "SURVEY_ABI", False)
+    g = torch.Generator().manual_seed(23)
+    conv = HL.Conv1d(64, 64, 3, padding=1)
+    _fill(conv, g)
+    HL.finalize(conv, device)
+    x = torch.randn(2, 64, 64, generator=g).to(device)
+    rec = []
+    monkeypatch.setattr(HL, "LAUNCH_HOOK", lambda *r: rec.append(r))
+    p = conv.prepare(x)
+    assert rec == []                                      # prepared, not issued
+    assert p.run() == 0
+    y = conv(x)
+    torch.cuda.synchronize()
+    got = [(k, fl, nb, type(a).__name__) for k, fl, nb, _, _, a in rec]
+    assert got == [EXPECTED[0], EXPECTED[0]], got
+    assert y.data_ptr() != p.out.data_ptr() and torch.equal(p.out, y) and bool(y.abs().sum() > 0)

@@ -404,8 +404,7 @@ def test_wn_layers_and_dit_ffn_reach_their_named_entry_points_only_under_survey_
     monkeypatch.setattr(M.Fh, "layernorm_mod", lambda x, *a, **k: torch.empty_like(x))
     monkeypatch.setattr(M.Fh, "mha", lambda q, k, v, *a, **kw: torch.empty_like(q))
     monkeypatch.setattr(M.Fh, "mha_proj_supported", lambda *a: False)   # the attention launches are not this test's subject
-    monkeypatch.setattr(HL, "_launch", lambda kind, fn, a, fl, nb, soft=False, keep=(): (
-        HL._DEFER.get().append((a, fl, nb, keep)) if HL._DEFER.get() is not None else plain.append(kind)) and 0 or 0)
+    monkeypatch.setattr(HL.ConvLaunch, "run", lambda self, soft=False: plain.append(self.kind) or 0)
     wn = M.WN(192, 5, 1, 3, gin_channels=0)
     blk = M.DiTConVBlock(192, 2, mlp_ratio=4.0, kernel=5)
     for m in list(wn.modules()) + list(blk.modules()):
@@ -425,32 +424,44 @@ def test_wn_layers_and_dit_ffn_reach_their_named_entry_points_only_under_survey_
     assert seen[0][1] == [True, True, True] and seen[2][1] == [True, False, True]   # last WN layer: skip only
 
 
-def test_deferred_collects_only_the_launches_of_its_own_thread(monkeypatch):
-    """deferred() is per context (like row_exact): while thread A collects structs, a Conv1d called on thread B is launched,
-    not recorded, and A's list holds A's structs only.  Host logic only, `_launch` stubbed as in the test above."""
+def _host_conv_stubs(monkeypatch):
+    """Device pointers replaced by host addresses, and the bracket by a recorder of (thread, kind, flops, bytes, a copy of
+    every field of the struct): nothing is launched."""
     import threading
     from megatts2_hierspeechpp_amd import _lib as L_, hip_layers as HL
     monkeypatch.setattr(L_, "ptr", lambda t: None if t is None else t.data_ptr())
     monkeypatch.setattr(L_, "fptr", lambda t: None if t is None else t.data_ptr())
-    monkeypatch.setattr(HL, "_zeros", lambda dev: torch.zeros(64))
+    monkeypatch.setattr(HL, "_zeros", lambda dev, z=torch.zeros(64): z)
     issued = []
-    monkeypatch.setattr(HL, "_launch", lambda kind, fn, a, fl, nb, soft=False, keep=(): (
-        HL._DEFER.get().append((a, fl, nb, keep)) if HL._DEFER.get() is not None
-        else issued.append((threading.current_thread().name, a.Cin))) and 0 or 0)
-    convs = {}
-    for name, cin in (("A", 16), ("B", 24)):
-        c = convs[name] = HL.Conv1d(cin, 32, 3, padding=1)
-        c._w, c._b = torch.zeros(c.k * c.cin * c.M), torch.zeros(c.cout)
+    monkeypatch.setattr(HL, "_bracket", lambda kind, call, fl, nb, a, soft=False, span=None: (
+        issued.append((threading.current_thread().name, kind, fl, nb, {f[0]: getattr(a, f[0]) for f in a._fields_})) or 0,
+        None, None))
+    return HL, issued
+
+
+def _ready(c):
+    c._w, c._b = torch.zeros(c.kp * c.cin * c.M if hasattr(c, "kp") else c.k * c.cin * c.M), torch.zeros(c.cout)
+    return c
+
+
+def test_a_prepared_launch_is_issued_only_when_its_owner_runs_it(monkeypatch):
+    """A prepared launch belongs to whoever prepared it: while thread A holds two ConvLaunch objects un-run, a Conv1d called
+    on thread B is issued at once; A's two structs are A's own, and nothing of A's is issued until A runs them."""
+    import threading
+    HL, issued = _host_conv_stubs(monkeypatch)
+    convs = {name: _ready(HL.Conv1d(cin, 32, 3, padding=1)) for name, cin in (("A", 16), ("B", 24))}
     inside, b_done, got, errors = threading.Event(), threading.Event(), {}, []
 
     def run_a():
         try:
-            with HL.deferred() as structs:
-                convs["A"](torch.zeros(2, 16, 40))
-                inside.set()
-                assert b_done.wait(30)
-                convs["A"](torch.zeros(2, 16, 40))
-            got["A"] = [e[0].Cin for e in structs]
+            held = [convs["A"].prepare(torch.zeros(2, 16, 40))]
+            inside.set()
+            assert b_done.wait(30)
+            held.append(convs["A"].prepare(torch.zeros(2, 16, 40)))
+            got["A"] = [p.args.Cin for p in held]
+            got["before_A_runs"] = list(issued)
+            for p in held:
+                p.run()
         except BaseException as e:      # noqa: BLE001  (reported on the main thread)
             errors.append(e)
             inside.set()
@@ -458,7 +469,6 @@ def test_deferred_collects_only_the_launches_of_its_own_thread(monkeypatch):
     def run_b():
         try:
             assert inside.wait(30)
-            got["B_deferring"] = HL._DEFER.get()
             convs["B"](torch.zeros(2, 24, 40))
         except BaseException as e:      # noqa: BLE001
             errors.append(e)
@@ -469,13 +479,51 @@ def test_deferred_collects_only_the_launches_of_its_own_thread(monkeypatch):
     ta.start(), tb.start()
     ta.join(60), tb.join(60)
     assert not errors, errors
-    assert got["B_deferring"] is None and issued == [("B", 24)]     # B's launch was issued ...
-    assert got["A"] == [16, 16]                                     # ... and A recorded its own two structs only
-    assert HL._DEFER.get() is None
-    with HL.deferred():
-        with pytest.raises(AssertionError):                         # nested use still fails loudly
-            HL.deferred().__enter__()
-    assert HL._DEFER.get() is None
+    assert got["A"] == [16, 16]                                              # A's two prepared structs are its own ...
+    assert [(t, f["Cin"]) for t, _, _, _, f in got["before_A_runs"]] == [("B", 24)]     # ... B's launch was issued at once,
+    assert [(t, f["Cin"]) for t, _, _, _, f in issued] == [("B", 24), ("A", 16), ("A", 16)]    # A's only when A ran them
+
+
+def test_prepare_fills_the_struct_that_forward_issues(monkeypatch):
+    """Conv1d.prepare / ConvTranspose1d.prepare launch nothing and return the launch forward issues for the same arguments:
+    same kind, flops, bytes and every field of hsp_conv1d_args (but the pointers into the freshly allocated outputs), and
+    the object holds the tensors the struct points at -- input, output, the gathered copy of a strided residual."""
+    HL, issued = _host_conv_stubs(monkeypatch)
+    gathered = []
+    monkeypatch.setattr(HL.Fh, "copy_strided", lambda t: gathered.append(t.contiguous()) or gathered[-1])
+    held = lambda p, t: any(r is t for r in p.refs)
+    conv, convtr = _ready(HL.Conv1d(16, 32, 3, padding=1)), _ready(HL.ConvTranspose1d(16, 8, 4, 2, padding=1))
+    x = torch.zeros(2, 16, 40)
+    res = torch.zeros(2, 16, 80)[:, :, ::2]    # time stride 2 on the direct path: gathered while preparing
+    # a few fields by hand, so that the comparison below does not rest on the code under test alone: 32 packed rows (16 of
+    # them launched in a row range, the leading dimension stays 32), one column per output sample; the transposed conv as
+    # ceil(4 / 2) = 2 polyphase taps over 16 = 8 * 2 shuffled rows and (80 - 1 + 1) // 2 + 1 = 41 columns for 80 outputs
+    literal = (dict(M=32, w_ld=32, K=3, Cout=32, ncols=40, Lout=40, split_row=0), dict(M=16, w_ld=32, Cout=16, ncols=40, res_ts=0),
+               dict(M=16, w_ld=32, Cout=16, ncols=40, fold_cols=0), dict(M=16, w_ld=16, K=2, pad=1, up=2, Cout=8, ncols=41,
+                                                                        Lout=80, fold_cols=0))
+    for (layer, kw), want in zip(((conv, {}), (conv, dict(row_range=(0, 16), res=torch.zeros(2, 16, 40))),
+                                  (conv, dict(row_range=(0, 16), res=res, force_direct=True)), (convtr, {})), literal):
+        del issued[:], gathered[:]
+        p = layer.prepare(x, **kw)
+        assert issued == [] and isinstance(p, HL.ConvLaunch)
+        assert {n: getattr(p.args, n) for n in want} == want
+        assert held(p, x) and held(p, p.out) and p.args.y == p.out.data_ptr()
+        if "res" in kw:
+            assert held(p, gathered[0] if gathered else kw["res"]) and p.args.res == (gathered[0] if gathered else kw["res"]).data_ptr()
+        assert len(gathered) == ("force_direct" in kw) and (not gathered or p.args.res_ts == 0)
+        out = layer(x, **kw)
+        (_, kind, fl, nb, fields), = issued
+        assert (kind, fl, nb) == (p.kind, p.flops, p.nbytes) and out.shape == p.out.shape
+        names = [f[0] for f in HL.L.Conv1dArgs._fields_]
+        assert sorted(fields) == sorted(names)
+        for n in names:
+            if n != "y" and not (n == "res" and gathered):      # (each call gathers a copy of its own)
+                assert fields[n] == getattr(p.args, n), (type(layer).__name__, kw, n)
+    assert p.kind == "hsp_conv1d_mfma_f32" and p.args.rows == HL.L.ROWS_SHUFFLE
+    ln = _ready(HL.Conv1d(16, 32, 1))
+    ln.fuse_input_layernorm(torch.nn.LayerNorm(16))
+    with pytest.raises(HL.L.HspError):         # the fused-LayerNorm protocol (soft launch, fallback) is forward's alone
+        ln.prepare(x)
 
 
 def test_adaln_linears_keep_parameters_only_and_their_rows_are_packed_once():

@@ -10,16 +10,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from megatts2_hierspeechpp_amd import hip_layers  # noqa: E402
 
 dev = torch.device("cuda:0")
-orig = hip_layers._launch
+orig = hip_layers.ConvLaunch.run
 st = torch.zeros(8, dtype=torch.int64, device=dev)
 
 
-def launch(kind, fn, a, flops, nbytes, soft=False, keep=()):
-    a.filt = st.data_ptr()
-    return orig(kind, fn, a, flops, nbytes, soft, keep)
+def run(self, soft=False):
+    self.args.filt = st.data_ptr()
+    return orig(self, soft)
 
 
-hip_layers._launch = launch
+hip_layers.ConvLaunch.run = run
 for tile, bit in (("128x128", 1 << 18), ("128x64", 1 << 19), ("64x64", 1 << 23)):
     for extra in (0, 1, 2):
         hip_layers.DEBUG_FLAGS = (1 << 20) | bit | extra

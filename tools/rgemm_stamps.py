@@ -10,16 +10,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from megatts2_hierspeechpp_amd import _lib as L, hip_layers  # noqa: E402
 
 dev = torch.device("cuda:0")
-orig = hip_layers._launch
+orig = hip_layers.ConvLaunch.run
 st = torch.zeros(8, dtype=torch.int64, device=dev)
 
 
-def launch(kind, fn, a, flops, nbytes, soft=False, keep=()):
-    a.filt = st.data_ptr()
-    return orig(kind, fn, a, flops, nbytes, soft, keep)
+def run(self, soft=False):
+    self.args.filt = st.data_ptr()
+    return orig(self, soft)
 
 
-hip_layers._launch = launch
+hip_layers.ConvLaunch.run = run
 hip_layers.DEBUG_FLAGS = 1 << 20
 for K, N, M in ((276, 160, 828), (276, 1600, 828), (276, 1600, 276), (1104, 1600, 276), (1104, 160, 276), (276, 16, 1024)):
     lin = hip_layers.LinearCT(K, M)

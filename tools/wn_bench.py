@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""One modules.WN (H = 192, 8 layers, k = 5: the vocoder's posterior encoders) at T = 200: time per forward, one
-hsp_wn_layer_f32 call per layer.  --debug words (tuning build only, HSP_LIB=.../libhsp_tune.so; results are then
-wrong): 1 = producers stage the first two chunks only, 2 = consumers skip their MFMAs, 3 = both."""
+"""One modules.WN (H = 192, 8 layers, k = 5: the vocoder's posterior encoders) at T = 200: time per forward, two launches
+per layer (gated in-conv, split-row res_skip; under HSP_SURVEY_ABI=1 one hsp_wn_layer_f32 call per layer).  --debug words
+(tuning build only, HSP_LIB=.../libhsp_tune.so; results are then wrong): 1 = producers stage the first two chunks only,
+2 = consumers skip their MFMAs, 3 = both."""
 import argparse
 import os
 import sys
