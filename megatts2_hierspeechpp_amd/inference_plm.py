@@ -7,7 +7,10 @@ The prompt file ingest (:120-126: ``torchaudio.load``, first channel, kaiser-win
 harness here is one `output.OutputStage`.  Out of scope here (host plumbing, not the hot path): text cleaning /
 phonemisation (``get_text``) -- callers hand over phone ids.  The prompt mel transform is
 ``Mels_preprocess.MelSpectrogramFixed``, the optional prompt denoiser ``denoiser.generator.MPNet`` +
-``denoiser.infer.denoise`` (:142-147)."""
+``denoiser.infer.denoise`` (:142-147).
+
+``tts_batch`` / ``tts_lines`` / ``tts_batch_files`` speak many different lines in ragged batches (the reference speaks
+one line per call); row b of a batch is held to ``tts_from_prompt`` on line b alone."""
 from __future__ import annotations
 
 import math
@@ -18,6 +21,7 @@ from torch import nn
 
 from . import _lib as L
 from . import functional as Fh
+from . import hip_layers
 from .hierspeechpp_speechsynthesizer import SynthesizerTrn
 from .hip_layers import finalize as _finalize
 from .output import SCALE_NORMS, OutputStage, output_rate, pack, prompt_peak  # noqa: F401  (re-exported names)
@@ -168,7 +172,8 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         return_float: bool = False, gain: float = 0.999, plm_sampling=None, seeds=None, scale_norm: str = "max",
         target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
         prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0,
-        lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False):
+        lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, row_exact: bool = False,
+        style=None):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and
     ``seeds`` make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
     ``plm_causal``: the prosody LM decodes under the causal mask it is trained with, through a K/V cache
@@ -190,7 +195,10 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     Returns int16 audio [B, n] (n = 320 * frames, x3 / x1.5 with SpeechSR), every row converted over its own length.
     B > 1 runs the utterances side by side; rows are independent up to the
     vocoder, whose convolutions see a shorter row's zero padding exactly as the reference's own batched
-    ``infer`` does (equal-length batches are exact)."""
+    ``infer`` does (equal-length batches are exact).  ``row_exact`` (B > 1): the vocoder and SpeechSR run every row as
+    at B = 1 too, so row b of a ragged batch equals the call on row b alone; `row_exact_refusal`
+    applies.  ``style`` [B, 256, 1]: the vocoder's style vectors, precomputed per prompt at the prompt's own length
+    (``voc.style_vector``); ``src_mel`` / ``src_length2`` are not read then.  ``gain`` may be a device fp32 [B] tensor."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
     if plm_prefix is not None and not plm_causal:
@@ -198,13 +206,14 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
     wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel,
                                     src_length2, noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage, gain,
-                                    plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths)
+                                    plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths,
+                                    row_exact, style)
     return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
 
 
 def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
          noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage: OutputStage, gain, plm_sampling, seeds,
-         plm_causal, plm_prefix, prosody_codes, prosody_lengths):
+         plm_causal, plm_prefix, prosody_codes, prosody_lengths, row_exact=False, style=None):
     """`tts` behind its argument checks -> (wav, audio, stats or None, codes)."""
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
@@ -219,7 +228,7 @@ def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_len
         codes = fit_prosody_codes(prosody_codes.to(x_frame.device), src, torch.ceil(x_lengths).to(torch.int64),
                                   width=x_frame.shape[2])
     return (*_tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc,
-                             denoise_ratio, output_sr, noise, stage, gain), codes)
+                             denoise_ratio, output_sr, noise, stage, gain, row_exact, style), codes)
 
 
 @torch.no_grad()
@@ -227,20 +236,20 @@ def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_
                    noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
                    return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0,
                    limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
-                   return_stats: bool = False):
+                   return_stats: bool = False, row_exact: bool = False, style=None):
     """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
     ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode.
     ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`; the stats dict is the last
-    result."""
+    result.  ``row_exact`` / ``style``: as for `tts`."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
     wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
-                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain)
+                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact, style)
     return pack(wav, (audio, return_float), (stats, return_stats))
 
 
 def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc, denoise_ratio,
-                    output_sr, noise, stage: OutputStage, gain):
+                    output_sr, noise, stage: OutputStage, gain, row_exact=False, style=None):
     """`tts_from_codes` behind its argument check -> (wav, audio, stats or None)."""
     B = x_frame.shape[0]
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
@@ -250,18 +259,24 @@ def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_l
         src_length = torch.full((1,), T2, dtype=torch.int64, device=w2v_x.device)   # :163 the whole padded length
         audio = models.voc.voice_conversion_noise_control(w2v_x, src_length, src_mel, src_length2, pitch,
                                                           noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
-                                                          noise=noise)
+                                                          noise=noise, style=style)
         n_valid = None
     else:
         frames = torch.ceil(x_lengths).to(torch.int64)
         audio = models.voc.voice_conversion_noise_control(w2v_x, frames, src_mel, src_length2, pitch.unsqueeze(1),
                                                           noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
-                                                          noise=noise)
+                                                          noise=noise, style=style, row_exact=row_exact)
         n_valid = frames * 320
     if output_sr in (24000, 48000):
-        audio = models.sr(audio)
+        if row_exact and B > 1:        # SpeechSR on the ragged rows, each as on its own (as inference_vc.vc_batch)
+            with hip_layers.row_exact(hip_layers.RowLengths(frames, audio.shape[2] // 320)):
+                audio = models.sr(audio)
+        else:
+            audio = models.sr(audio)
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
+    if stage is None:                  # `tts_lines(join=True)`: the programme is converted, not its lines
+        return None, audio, None
     wav, stats = stage.int16(audio, n_valid, output_rate(output_sr), gain)
     return wav, audio, stats
 
@@ -362,3 +377,417 @@ def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
                            plm_prefix=plm_prefix, return_codes=return_codes, prosody_codes=prosody_codes,
                            prosody_lengths=prosody_lengths, **kwargs)
+
+
+# ---------------------------------------------------------------- a page of lines: ragged batches
+MAX_PHONES = 438    # phones per line: the Gaussian upsampler's bound
+
+STAGE_HOOK = None   # measurement hook (tools/tts_ragged_bench.py): STAGE_HOOK(name) at the start of every tts_batch stage
+
+
+def _stage(name):
+    if STAGE_HOOK is not None:
+        STAGE_HOOK(name)
+
+
+def line_chunks(phone_counts, max_batch: int):
+    """The batches of `tts_lines`, from the phone counts alone: the lines sorted by phone count (a stable sort: equal
+    counts keep the caller's order) and cut into chunks of at most ``max_batch`` -> a list of index lists.  Every index
+    appears once; `chunk_order` of the result restores the caller's order."""
+    if int(max_batch) < 1:
+        raise L.HspError(f"max_batch must be >= 1, got {max_batch}")
+    order = sorted(range(len(phone_counts)), key=lambda i: int(phone_counts[i]))
+    return [order[i:i + int(max_batch)] for i in range(0, len(order), int(max_batch))]
+
+
+def chunk_order(chunks):
+    """The inverse permutation of `line_chunks`: ``inv[k]`` is the place of the caller's line k among the chunks' rows
+    taken in order, so ``[flat[i] for i in inv]`` is in the caller's order."""
+    flat = [k for rows in chunks for k in rows]
+    inv = [0] * len(flat)
+    for place, k in enumerate(flat):
+        inv[k] = place
+    return inv
+
+
+def join_plan(lengths, rate: int, pause_ms: float):
+    """Where the lines of a programme start: ``lengths`` output samples per line at ``rate``, ``round(pause_ms * rate /
+    1000)`` zero samples between consecutive lines -> (offsets, total samples)."""
+    if not pause_ms >= 0:
+        raise L.HspError(f"pause_ms must be >= 0, got {pause_ms}")
+    pause = round(float(pause_ms) * int(rate) / 1000)
+    offsets, pos = [], 0
+    for n in lengths:
+        offsets.append(pos)
+        pos += int(n) + pause
+    return offsets, (pos - pause if offsets else 0)
+
+
+def _row(x):
+    return x.reshape(-1)
+
+
+def _per_line(arg, B: int, what: str):
+    """A per-line keyword: None, or a list of B entries."""
+    if arg is None:
+        return None
+    if not isinstance(arg, (list, tuple)) or len(arg) != B:
+        got = len(arg) if isinstance(arg, (list, tuple)) else type(arg).__name__
+        raise L.HspError(f"{what} must be a list of one entry per line ({B}), got {got}")
+    return list(arg)
+
+
+def check_lines(lines, prompts, dur=None, plm_sampling=None, plm_causal=False, plm_prefixes=None, prosody_codes=None,
+                prosody_lengths=None, denoised=None):
+    """The argument checks of `tts_batch` / `tts_lines`, from shapes alone (no device work): B triples (ids, tone,
+    language) of one length each in [1, MAX_PHONES], one prompt or B, per-line keywords as lists of B, ``plm_prefixes``
+    only with ``plm_causal``, ``prosody_codes`` with nothing that steers the prosody LM.  -> the phone counts."""
+    if not isinstance(lines, (list, tuple)) or not lines:
+        raise L.HspError("lines must be a non-empty list of (ids, tone, language) triples")
+    B, counts = len(lines), []
+    for b, line in enumerate(lines):
+        if not isinstance(line, (list, tuple)) or len(line) != 3:
+            raise L.HspError(f"line {b} must be a triple (ids, tone, language)")
+        for x in line:
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or x.dim() not in (1, 2) or \
+                    (x.dim() == 2 and x.shape[0] != 1):
+                raise L.HspError(f"line {b}: ids / tone / language must be int64 [N] or [1, N] tensors")
+        n = [x.shape[-1] for x in line]
+        if n[0] == 0:
+            raise L.HspError(f"line {b} is empty: a line needs at least one phone")
+        if n[1] != n[0] or n[2] != n[0]:
+            raise L.HspError(f"line {b}: ids, tone and language have different lengths {tuple(n)}")
+        if n[0] > MAX_PHONES:
+            raise L.HspError(f"line {b} has {n[0]} phones; the Gaussian upsampler takes {MAX_PHONES} at the most")
+        counts.append(n[0])
+    if isinstance(prompts, (list, tuple)) and len(prompts) not in (1, B):
+        raise L.HspError(f"give one prompt or one per line ({B}), got {len(prompts)}")
+    if isinstance(denoised, (list, tuple)) and len(denoised) not in (1, B):
+        raise L.HspError(f"give one denoised prompt or one per line ({B}), got {len(denoised)}")
+    dur = _per_line(dur, B, "dur")
+    if dur is not None:
+        for b, d in enumerate(dur):
+            if d.numel() != counts[b]:
+                raise L.HspError(f"line {b}: {d.numel()} durations for {counts[b]} phones")
+    plm_prefixes = _per_line(plm_prefixes, B, "plm_prefixes")
+    if plm_prefixes is not None and not plm_causal:
+        raise L.HspError("plm_prefixes needs plm_causal=True: only the causal decoder can continue from given codes")
+    prosody_codes = _per_line(prosody_codes, B, "prosody_codes")
+    lengths = _per_line(prosody_lengths, B, "prosody_lengths")
+    _check_given_prosody(prosody_codes, lengths, plm_sampling, plm_prefixes, plm_causal)
+    return counts
+
+
+def _check_denoiser(denoise_ratio, denoised, denoiser, hps_denoiser, who: str) -> None:
+    """`inference_vc.vc_batch`'s rules for the second prompt mel."""
+    if denoised is not None and denoiser is not None:
+        raise L.HspError(f"{who}: give the denoised prompts or a denoiser, not both")
+    if denoise_ratio != 0 and denoised is None and denoiser is None:
+        raise L.HspError(f"{who}: denoise_ratio != 0 needs the denoised prompts (denoised=) or a denoiser "
+                         "(denoiser=, hps_denoiser=)")
+    if denoiser is not None and hps_denoiser is None:
+        raise L.HspError(f"{who}: a denoiser needs its config (hps_denoiser=)")
+
+
+def _pad_rows(rows, width: int, dtype, device):
+    """Zero-padded [len(rows), width] copy of 1-D (or [1, n]) rows."""
+    out = torch.zeros(len(rows), width, dtype=dtype, device=device)
+    for b, r in enumerate(rows):
+        r = _row(r)
+        out[b, :r.shape[0]].copy_(r)
+    return out
+
+
+def _encode_prompts(models, mel_fn, prompts, B, prompt_sr, denoise_ratio, denoised, denoiser, hps_denoiser):
+    """Every distinct prompt of B lines (`group_prompts`) encoded once and exactly as `tts_from_prompt` encodes it
+    (`prompt_mels`): -> (per distinct prompt its ``(src_mel_ttv [1, 80, Tm'], style [1, 256, 1], the 16 kHz waveform
+    [1, n])``, line -> index).  With a denoiser all distinct prompts are denoised in one packed pass."""
+    from .inference_vc import denoise_prompts, group_prompts
+    distinct, index = group_prompts(prompts, B)
+    P = len(distinct)
+    first = [index.index(p) for p in range(P)]
+    dev = distinct[0].device
+    rows = []
+    for p, a in enumerate(distinct):
+        a = _row(a).to(torch.float32).reshape(1, -1)
+        if int(prompt_sr) != 16000:
+            a = Fh.resample(a, prompt_sr, 16000, resampling_method="kaiser_window")
+        if a.shape[-1] <= 640:
+            raise L.HspError(f"prompt {p} has {a.shape[-1]} samples at 16 kHz; the mel transform needs more than 640")
+        rows.append(a.contiguous())
+    seconds = [None] * P
+    if denoise_ratio != 0 and denoiser is not None:
+        seconds = denoise_prompts(rows, denoiser, hps_denoiser)          # one packed pass over the distinct prompts
+    elif denoise_ratio != 0 and denoised is not None:
+        given = denoised if isinstance(denoised, (list, tuple)) else [denoised]
+        if len(given) == 1 and P != 1:
+            raise L.HspError(f"{P} distinct prompts need denoised as a list of one entry per line")
+        seconds = [given[first[p]] if len(given) == B and B > 1 else given[0] for p in range(P)]
+    encoded = []
+    for p, a in enumerate(rows):
+        n = a.shape[-1]
+        if seconds[p] is None:
+            mel_ttv, mel = prompt_mels(mel_fn, a)
+        else:
+            s = _row(seconds[p])
+            if s.shape[0] < n:
+                raise L.HspError(f"denoised prompt {p} is shorter than its prompt")
+            padded = torch.zeros(1, (n // 1600 + 1) * 1600, dtype=torch.float32, device=dev)
+            padded[:, :n].copy_(a)
+            mel_ttv = mel_fn(padded)
+            mel = mel_fn(torch.cat([a, s[:n].reshape(1, -1).to(torch.float32)], 0).contiguous())
+        style = models.voc.style_vector(mel, torch.full((2,), mel.shape[2], dtype=torch.int64, device=dev),
+                                        denoise_ratio)
+        encoded.append((mel_ttv, style, a))
+    return encoded, index
+
+
+def _prompt_rows(encoded, index, want_peaks):
+    """The rows of a batch from its lines' encoded prompts (``index``: line -> entry of ``encoded``): -> (src_mel_ttv
+    [B, 80, Tm'] zero-padded, its lengths int64 [B], style [B, 256, 1], prompt peaks fp32 [B] or None)."""
+    from .inference_vc import _device_lengths, _stack
+    B, dev = len(index), encoded[0][0].device
+    widths = [encoded[i][0].shape[2] for i in index]
+    src_mel_ttv = torch.zeros(B, 80, max(widths), dtype=torch.float32, device=dev)
+    for b, i in enumerate(index):
+        src_mel_ttv[b, :, :widths[b]].copy_(encoded[i][0][0])
+    style = torch.cat([encoded[i][1] for i in index])
+    peaks = None
+    if want_peaks:                     # the peak of each row's own prompt, taken on the device
+        pm, lens = _stack([encoded[i][2] for i in index], dev)
+        peaks = Fh.abs_max_rows(pm, _device_lengths(lens, dev))
+    return src_mel_ttv, _device_lengths(widths, dev), style, peaks
+
+
+def _plm_codes(models, x_frame, frames, plm_sampling, seeds, plm_causal, plm_prefixes, prosody_codes, prosody_lengths):
+    """The prosody codes int64 [B, T2] of a ragged batch (``frames``: host frame counts); entries from a row's frame
+    count on are not meaningful."""
+    B, _, T2 = x_frame.shape
+    dev = x_frame.device
+    if prosody_codes is not None:
+        src = [_row(c).shape[0] for c in prosody_codes] if prosody_lengths is None else [int(n) for n in prosody_lengths]
+        given = _pad_rows(prosody_codes, max(_row(c).shape[0] for c in prosody_codes), torch.int64, dev)
+        return fit_prosody_codes(given, torch.tensor(src, dtype=torch.int64).to(dev),
+                                 torch.tensor(frames, dtype=torch.int64).to(dev), width=T2)
+    if plm_prefixes is None:
+        return models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal)
+    given = [None if p is None else _row(p) for p in plm_prefixes]
+    for b, p in enumerate(given):
+        if p is not None and not 1 <= p.shape[0] < frames[b]:
+            raise L.HspError(f"line {b}: a prefix needs 1 <= P < {frames[b]} codes (the line's frames), got "
+                             f"{p.shape[0]}")
+    if all(p is not None and p.shape[0] == given[0].shape[0] for p in given):
+        return models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=True,
+                                prefix_codes=torch.stack(given).to(dev))
+    # prefixes of different lengths: every line at its own position, through one decode session
+    rows = models.plm.infer_many([x_frame[b, :, :frames[b]] for b in range(B)], slots=B, sampling=plm_sampling,
+                                 seeds=seeds, prefixes=given)
+    return _pad_rows(rows, T2, torch.int64, dev)
+
+
+def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=1.0, noise=None, noise_scale_vc=0.333,
+               denoise_ratio=0.0, denoised=None, denoiser=None, hps_denoiser=None, prompt_sr=16000, output_sr=16000,
+               plm_sampling=None, seeds=0, plm_causal=False, plm_prefixes=None, prosody_codes=None,
+               prosody_lengths=None, row_exact=True, int16=True, encoded=None):
+    """`tts_batch` behind the check of its output stage -> (wav or None, lengths int64 [B], audio, stats or None,
+    codes (a list of B), the frame counts on the host).  ``int16`` False: the int16 stage is left to the caller.
+    ``encoded``: what `_encode_prompts` made of the lines' prompts (`tts_lines` encodes a page's prompts once)."""
+    counts = check_lines(lines, prompts, dur, plm_sampling, plm_causal, plm_prefixes, prosody_codes, prosody_lengths,
+                         denoised)
+    _check_denoiser(denoise_ratio, denoised, denoiser, hps_denoiser, "tts_batch")
+    B, N = len(lines), max(counts)
+    if isinstance(seeds, torch.Tensor) and seeds.shape != (B,):
+        raise L.HspError(f"seeds must be an int or an int64 [{B}] tensor, got shape {tuple(seeds.shape)}")
+    if noise is not None and (noise.dim() != 3 or noise.shape[0] != B or noise.shape[1] != 192):
+        raise L.HspError(f"noise must be fp32 [{B}, 192, >= T_max], got {tuple(noise.shape)}")
+    if row_exact and B > 1:
+        from .hierspeechpp_speechsynthesizer import row_exact_refusal
+        why = row_exact_refusal()
+        if why is not None:
+            raise L.HspError(f"row_exact is not available with {why}")
+    if output_sr in (24000, 48000) and getattr(models, "sr", None) is None:
+        raise L.HspError("output_sr 24000 / 48000 needs TtsModels(..., speechsr=<SpeechSR model>)")
+    from .inference_vc import _device_lengths, output_length
+    dev = lines[0][0].device
+    _stage("prompts")
+    if encoded is None:
+        encoded = _encode_prompts(models, mel_fn, prompts, B, prompt_sr, denoise_ratio, denoised, denoiser, hps_denoiser)
+    src_mel_ttv, ttv_len, style, peaks = _prompt_rows(*encoded, stage.scale_norm == "prompt")
+    _stage("front")
+    text, tone, language = (_pad_rows([line[i] for line in lines], N, torch.int64, dev) for i in range(3))
+    text_length = _device_lengths(counts, dev)
+    durs = None if dur is None else _pad_rows([d.to(torch.float32) for d in dur], N, torch.float32, dev)
+    x_frame, g, x_lengths, x_mask, frame_lengths = models.ttv.inf_extract_tc_latent(
+        text, text_length, src_mel_ttv, ttv_len, tone, language, length_scale=length_scale, dur=durs, host_lengths=True)
+    frames = [int(math.ceil(v)) for v in frame_lengths.tolist()]
+    T2 = x_frame.shape[2]
+    if noise is not None:
+        if noise.shape[2] < T2:
+            raise L.HspError(f"noise has {noise.shape[2]} columns; the longest line has {T2} frames")
+        noise = noise[:, :, :T2].to(torch.float32).contiguous()
+    _stage("plm")
+    codes = _plm_codes(models, x_frame, frames, plm_sampling, seeds, plm_causal, plm_prefixes, prosody_codes,
+                       prosody_lengths)
+    _stage("vocoder")
+    wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, None, None, noise_scale_vc,
+                                        float(denoise_ratio), output_sr, noise, stage if int16 else None,
+                                        0.999 if peaks is None else peaks, row_exact, style)
+    _stage("end")
+    lengths = output_length(torch.ceil(x_lengths).to(torch.int64), output_sr)
+    return wav, lengths, audio, stats, [codes[b, :frames[b]] for b in range(B)], frames
+
+
+@torch.no_grad()
+def tts_batch(models: TtsModels, mel_fn, lines, prompts, *, return_float: bool = False, return_codes: bool = False,
+              scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False, ceiling_db: float = -1.0,
+              lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, **kw):
+    """`tts_from_prompt` for B different lines in one ragged batch; row b equals the one-line call on line b (same
+    ``dur``, ``noise[b:b+1, :, :T_b]``, prompt and seed) -- DESIGN.md §4.3, INTEGRATION.md "reading a page".
+
+    lines    B triples (ids, tone, language), each an int64 [N_b] or [1, N_b] device tensor, 1 <= N_b <= 438;
+    prompts  one waveform (fp32 [n] / [1, n] at ``prompt_sr``, more than 640 samples at 16 kHz) shared by every line,
+             or a list of B: lines holding the same tensor object share the prompt, whose mels, denoised form and
+             style vector are computed once, as `tts_from_prompt` computes them;
+    dur      a list of B [N_b] pinned durations, None: predicted (``length_scale``: the speaking rate, as
+             ``inf_extract_tc_latent`` takes it);
+    noise    fp32 [B, 192, >= T_max] (columns past the longest line's frames are ignored), None: drawn;
+    denoise_ratio, denoised / denoiser / hps_denoiser  as `inference_vc.vc_batch`: the denoised prompts in the form
+             of ``prompts``, or the denoiser that makes them in one packed pass (``denoise_prompts``);
+    plm_sampling, seeds  sampled prosody codes; ``seeds`` an int s (line b draws with s + b) or an int64 [B] tensor;
+    plm_causal, plm_prefixes  causal decoding; a list of B given beginnings (int64 [P_b], None entries allowed when
+             the lengths differ), decoded by ``infer(prefix_codes=)`` when all have one length, else ``infer_many``;
+    prosody_codes / prosody_lengths  lists of B: given codes instead of the prosody LM (the exclusions of `tts`);
+    row_exact  True (the default): the vocoder and SpeechSR run every row as at B = 1; False: the padded-batch
+             semantics of `tts`, exact only for equal frame counts and, as measured, no faster (DESIGN.md §5.1);
+    scale_norm ... return_stats  the int16 stage (`output.OutputStage`, validated before anything else): every row
+             over its own length, 'prompt' with the peak of the row's own prompt, taken on the device.
+
+    Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b is wav[b, :lengths[b]], zeros after; then,
+    where asked and in this order, the float audio [B, 1, n_max], the stats dict, the codes as a list of B int64
+    [T_b]."""
+    stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
+                        return_stats).check()
+    wav, lengths, audio, stats, codes, _ = _tts_batch(models, mel_fn, lines, prompts, stage, **kw)
+    return pack(wav, (lengths, True), (audio, return_float), (stats, return_stats), (codes, return_codes))
+
+
+def _take(arg, rows):
+    return None if arg is None else [arg[k] for k in rows]
+
+
+@torch.no_grad()
+def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16, join: bool = False,
+              pause_ms: float = 300.0, return_float: bool = False, return_codes: bool = False, dur=None, noise=None,
+              seeds=0, plm_prefixes=None, prosody_codes=None, prosody_lengths=None, denoised=None, **kw):
+    """Any number of lines: sorted by phone count, cut into chunks of at most ``max_batch`` (`line_chunks`), one
+    `tts_batch` per chunk (the per-line keywords ``dur``, ``noise`` rows, ``seeds``, ``plm_prefixes``,
+    ``prosody_codes`` / ``prosody_lengths`` sliced per chunk; an int ``seeds`` = s gives the caller's line k the seed
+    s + k), results in the caller's order.  Every distinct prompt of the page is encoded, and with a denoiser denoised,
+    once per call, whatever chunks its lines fall into.  Other keywords go to `tts_batch`.
+
+    ``join`` False: a list of N int16 rows [n_k]; then, where asked, the float rows (a list of [n_k]), the stats (a
+    dict of [N] tensors) and the codes (a list).  ``join`` True: one programme, int16 [n]: the float rows concatenated
+    at the output rate with ``round(pause_ms * rate / 1000)`` zero samples between consecutive lines (`join_plan`) and
+    converted by one `OutputStage.int16` call, so scale_norm='lufs' meters the programme, not each line ('prompt' is
+    refused: a programme has no single prompt); then the float programme [1, 1, n], the stats and the codes where
+    asked.  The lines' lengths come from the front-end's own read-back, so the join is slices and copies."""
+    stage = OutputStage.of(kw).check()
+    for name in ("scale_norm", "target_lufs", "limiter", "ceiling_db", "lookahead_ms", "limiter_passes", "return_stats"):
+        kw.pop(name, None)
+    if int(max_batch) < 1:
+        raise L.HspError(f"max_batch must be >= 1, got {max_batch}")
+    if not pause_ms >= 0:
+        raise L.HspError(f"pause_ms must be >= 0, got {pause_ms}")
+    if join and stage.scale_norm == "prompt":
+        raise L.HspError("join=True takes scale_norm 'max' or 'lufs': a programme has no single prompt")
+    counts = check_lines(lines, prompts, dur, kw.get("plm_sampling"), kw.get("plm_causal", False), plm_prefixes,
+                         prosody_codes, prosody_lengths, denoised)
+    _check_denoiser(kw.get("denoise_ratio", 0.0), denoised, kw.get("denoiser"), kw.get("hps_denoiser"), "tts_lines")
+    from .inference_vc import output_length
+    N, output_sr = len(lines), kw.get("output_sr", 16000)
+    if isinstance(seeds, torch.Tensor):
+        if seeds.shape != (N,):
+            raise L.HspError(f"seeds must be an int or an int64 [{N}] tensor, got shape {tuple(seeds.shape)}")
+        line_seeds = seeds.to(torch.int64)
+    else:
+        line_seeds = torch.arange(int(seeds), int(seeds) + N, dtype=torch.int64)
+    dev = lines[0][0].device
+    chunks = line_chunks(counts, max_batch)
+    per_prompt = isinstance(prompts, (list, tuple)) and len(prompts) == N and N > 1
+    per_denoised = isinstance(denoised, (list, tuple)) and len(denoised) == N and N > 1
+    # every distinct prompt of the page is encoded (and denoised) once, whatever chunks its lines fall into
+    encoded, index = _encode_prompts(models, mel_fn, prompts, N, kw.get("prompt_sr", 16000), kw.get("denoise_ratio", 0.0),
+                                     denoised, kw.get("denoiser"), kw.get("hps_denoiser"))
+    wavs, floats, codes, n_out, part_stats = [], [], [], [], []
+    for rows in chunks:
+        idx = torch.tensor(rows, dtype=torch.int64)
+        wav, _, audio, stats, cds, frames = _tts_batch(
+            models, mel_fn, [lines[k] for k in rows], _take(prompts, rows) if per_prompt else prompts,
+            stage, dur=_take(dur, rows), noise=None if noise is None else noise[idx.to(noise.device)],
+            seeds=line_seeds[idx.to(line_seeds.device)].to(dev), plm_prefixes=_take(plm_prefixes, rows),
+            prosody_codes=_take(prosody_codes, rows), prosody_lengths=_take(prosody_lengths, rows),
+            denoised=_take(denoised, rows) if per_denoised else denoised, int16=not join,
+            encoded=(encoded, [index[k] for k in rows]), **kw)
+        for i in range(len(rows)):
+            n = output_length(frames[i], output_sr)
+            n_out.append(n)
+            floats.append(audio[i, 0, :n])
+            if not join:
+                wavs.append(wav[i, :n])
+        codes += cds
+        part_stats.append(stats)
+    inv = chunk_order(chunks)
+    back = lambda flat: [flat[i] for i in inv]  # noqa: E731
+    floats, codes, n_out = back(floats), back(codes), back(n_out)
+    if not join:
+        stats = None
+        if stage.return_stats:
+            order = torch.tensor(inv, device=dev)
+            stats = {k: torch.cat([ps[k] for ps in part_stats])[order] for k in part_stats[0]}
+        return pack(back(wavs), (floats, return_float), (stats, stage.return_stats), (codes, return_codes))
+    rate = output_rate(output_sr)
+    offsets, total = join_plan(n_out, rate, pause_ms)
+    programme = torch.zeros(1, 1, total, dtype=torch.float32, device=dev)
+    for off, n, row in zip(offsets, n_out, floats):
+        programme[0, 0, off:off + n].copy_(row)
+    wav, stats = stage.int16(programme, None, rate, 0.999)
+    return pack(wav.reshape(-1), (programme, return_float), (stats, stage.return_stats), (codes, return_codes))
+
+
+def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None, names=None, device=None, **kw):
+    """`tts_lines` from prompt FILES: ``prompt_paths`` one WAV file for every line or a list of one per line, at any
+    sample rate; every distinct file is loaded once (``audio.load_16k``: channel 0, kaiser-window resampling to
+    16 kHz) and shared by the lines that name it.  Keywords ``kw`` go to `tts_lines`.  With ``out_dir`` the rows are
+    written as ``<out_dir>/<names[k]>.wav`` (``names`` None: ``line_0000.wav``, ...) at the output rate, or as one
+    ``programme.wav`` with ``join=True``.  Returns what `tts_lines` returns."""
+    import os
+    from . import audio as A
+    OutputStage.of(kw).check()          # before any file is read
+    if not isinstance(lines, (list, tuple)) or not lines:
+        raise L.HspError("lines must be a non-empty list of (ids, tone, language) triples")
+    N = len(lines)
+    per_line = isinstance(prompt_paths, (list, tuple))
+    paths = [str(p) for p in prompt_paths] if per_line else [str(prompt_paths)]
+    if len(paths) not in (1, N):
+        raise L.HspError(f"give one prompt file or one per line ({N}), got {len(paths)}")
+    if names is not None and len(names) != N:
+        raise L.HspError(f"names must hold one name per line ({N}), got {len(names)}")
+    if kw.get("prompt_sr", 16000) != 16000:
+        raise L.HspError("tts_batch_files reads the rate from each file: prompt_sr is not a keyword here")
+    check_lines(lines, paths, kw.get("dur"), kw.get("plm_sampling"), kw.get("plm_causal", False),
+                kw.get("plm_prefixes"), kw.get("prosody_codes"), kw.get("prosody_lengths"), kw.get("denoised"))
+    if device is None:
+        device = lines[0][0].device
+    loaded = {p: A.load_16k(p, device) for p in dict.fromkeys(paths)}       # each distinct prompt file loaded once
+    out = tts_lines(models, mel_fn, lines, [loaded[p] for p in paths] if len(paths) > 1 else loaded[paths[0]], **kw)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        rate = output_rate(kw.get("output_sr", 16000))
+        first = out[0] if isinstance(out, tuple) else out
+        if kw.get("join", False):
+            write_wav(os.path.join(str(out_dir), "programme.wav"), rate, first)
+        else:
+            for k, row in enumerate(first):
+                write_wav(os.path.join(str(out_dir), f"{names[k] if names is not None else f'line_{k:04d}'}.wav"),
+                          rate, row)
+    return out

@@ -827,14 +827,17 @@ class SynthesizerTrn(nn.Module):
     @_entry
     @torch.no_grad()
     def inf_extract_tc_latent(self, x, x_lengths, y_mel, y_length, tone, language, mrte_mel=None, mrte_mel_lengths=None,
-                              length_scale=1, dur=None):
+                              length_scale=1, dur=None, host_lengths=False):
         """(:937-982) ids/tone/language int64 [B, N], x_lengths [B], y_mel [B, 80, Tm], y_length [B] ->
         x_frame [B, 256, T2], g [B, 256, 1], x_lengths (float, frames / 2) [B], x_mask BOOL [B, 1, T2] (the
         reference's dtypes, :979-982; ``inf_plm_gen`` takes that mask or a float one).
-        ``dur`` [B, N] (optional) overrides the predicted durations (BASELINE config 3 pins them)."""
+        ``dur`` [B, N] (optional) overrides the predicted durations (BASELINE config 3 pins them).
+        ``host_lengths``: a fifth result, the same x_lengths as the CPU tensor the front-end read back (callers that
+        slice rows by their frame counts need no second read-back)."""
         ref_mel, ref_len = (mrte_mel, mrte_mel_lengths) if mrte_mel is not None else (y_mel, y_length)
         x_frame, g, frame_lengths, mask2 = self._tc_latent(x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur)
-        return x_frame, g, frame_lengths.to(x.device), mask2.to(torch.bool)   # a dtype cast, as the reference's (:982)
+        out = (x_frame, g, frame_lengths.to(x.device), mask2.to(torch.bool))   # a dtype cast, as the reference's (:982)
+        return (*out, frame_lengths) if host_lengths else out
 
     @_entry
     @torch.no_grad()
