@@ -183,6 +183,7 @@ def test_amp_block_vs_oracle(C_, k, L, B, fuse_max_c, device):
     (1, 1492, 2),     # three full segments + 4
     (2, 4000, 3),     # 9 segments per row: waves walk several rows' segments (4 consecutive items each)
     (3, 37, 2), (2, 1027, 1), (1, 2050, 1),   # L % 4 != 0: workgroup-tile kernel
+    (1, 2051, 1),     # the first length at which a tile of that kernel (the second of three) takes its interior branch
 ])
 def test_standalone_activation_vs_oracle(C_, L, B, device):
     """hsp_act1d_snakebeta_f32 alone (alias_free_torch/act.py:23-28) against the oracle; lengths sit on the
