@@ -79,7 +79,23 @@ enum {
   HSP_ACT_MISH = 4,      /* StyleEncoder, styleencoder.py:9-10 */
   HSP_ACT_SILU = 5,      /* cond_block, hierspeechpp_speechsynthesizer.py:72 */
   HSP_ACT_SOFTPLUS = 6,
-  HSP_ACT_GELU_ERF = 7   /* exact GELU x Phi(x) of the wav2vec2 producer (HF ACT2FN["gelu"]) */
+  HSP_ACT_GELU_ERF = 7,  /* exact GELU x Phi(x) of the wav2vec2 producer (HF ACT2FN["gelu"]) */
+  /* Not pointwise: the whole anti-aliased Activation1d(SnakeBeta) of hsp_act1d_snakebeta_f32 (2x polyphase up-sample ->
+   * snake -> 2x low-pass down-sample, replicate-padded at both ends of every row), applied to the conv's own OUTPUT rows
+   * before they leave the workgroup:  y = Activation1d(conv(x) + bias).  It is what the NEXT conv of an AMP pair reads
+   * (hierspeechpp_speechsynthesizer.py:380-384: xt = c1(a1(x)); xt = a2(xt)), so xt itself is never written.
+   * alpha_exp, beta_inv (per OUTPUT channel, [Cout]) and filt are the activation's; the prologue must be NONE.
+   * Column tiles overlap by 16: a tile of BN columns computes conv columns [t (BN - 16) - 8, t (BN - 16) + BN - 8) and
+   * stores the BN - 16 activated columns from t (BN - 16) on.  The order of the sum behind every conv column is the
+   * plain launch's on the same tile shape and the activation runs the stand-alone kernel's arithmetic: the result is
+   * bit-identical to that launch followed by hsp_act1d_snakebeta_f32.
+   * hsp_conv1d_mfma_f32 only, on its 32 x 512 and 64 x 256 plain-prologue tiles: a launch with this value always takes
+   * one of them (hsp_conv1d_mfma_plan reports it).  Required, else HSP_EINVAL: alpha_exp, beta_inv and filt set;
+   * PLAIN rows with M <= 64; stride 1 and "same" padding (Lin == Lout == ncols, 2 pad == (K - 1) dil, (K - 1) dil <= 61);
+   * ncols % 4 == 0; y 16-B addressable (y, y_bs, y_cs); an epilogue of bias alone (no cbias, mask, cscale, res,
+   * accumulate; scale == post_scale == 1); no fold_cols, w_bs, ln_c1, split_row.  Every other entry point that takes
+   * an `act` refuses the value. */
+  HSP_ACT_ACT1D = 8
 };
 
 /* how packed weight rows map to output channels */

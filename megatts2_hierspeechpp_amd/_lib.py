@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("HSP_LIB", os.path.join(_HERE, "libhsp.so"))  # HSP_LI
 # enums of include/hsp.h
 PRO_NONE, PRO_LRELU, PRO_ACT1D, PRO_SILU = 0, 1, 2, 3
 ACT_NONE, ACT_TANH, ACT_GELU_TANH, ACT_RELU, ACT_MISH, ACT_SILU, ACT_SOFTPLUS, ACT_GELU_ERF = 0, 1, 2, 3, 4, 5, 6, 7
+ACT_ACT1D = 8          # the next Activation1d from the conv epilogue (hsp.h: HSP_ACT_ACT1D)
 ROWS_PLAIN, ROWS_GATE_WN, ROWS_GATE_GLU, ROWS_SHUFFLE = 0, 1, 2, 3
 MASK_NONE, MASK_PRE, MASK_POST, MASK_BOTH = 0, 1, 2, 3
 EINVAL = -1

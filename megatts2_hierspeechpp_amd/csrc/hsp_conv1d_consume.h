@@ -201,6 +201,19 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][n][r] = 0.0f;
     }
+  } else if constexpr (EPI == HSP_EPI_ACT) {
+    // 0 + bias, what HSP_EPI_INIT's preload makes of a launch without residual: the same start of the same chain
+    static_for<TM>([&](auto ii) __attribute__((always_inline)) {
+      constexpr int i = decltype(ii)::value;
+      static_for<16>([&](auto rr) __attribute__((always_inline)) {
+        constexpr int r = decltype(rr)::value;
+        const float bz = 0.0f + (a.bias ? a.bias[min(mw + i * 32 + HSP_ACC_ROW(r, half), a.Cout - 1)] : 0.0f);
+        static_for<TN>([&](auto nn) __attribute__((always_inline)) {
+          constexpr int n = decltype(nn)::value;
+          acc[i][n][r] = bz;
+        });
+      });
+    });
   } else {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -356,7 +369,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
       acc[i][n][r] += red[((i * TN + n) * 16 + r) * 64];
     });
   }
-  if (HSP_DBG(a, HSP_CV_NO_EPILOGUE)) return;
+  if (HSP_DBG(a, HSP_CV_NO_EPILOGUE) && EPI != HSP_EPI_ACT) return;   // (HSP_EPI_ACT: the producers wait at its barriers)
   if constexpr (EPI == HSP_EPI_INIT) {  // ---- HSP_EPI_INIT: stores only (see the top of this file)
     const int mw = L.mw, half = L.half, tw = L.tw, bl = L.bl;
     // stores only, straight from the accumulator layout: one instruction = two rows x 128 B
@@ -401,6 +414,7 @@ __device__ __forceinline__ void conv_consume(const hsp_conv1d_args& a, const Lds
   else if constexpr (EPI == HSP_EPI_VEC) epi_vec<FOLD>(a, L, lds, acc);
   else if constexpr (EPI == HSP_EPI_GATE) epi_gate(a, L, acc);
   else if constexpr (EPI == HSP_EPI_SHUF) epi_shuf(a, L, acc);
+  else if constexpr (EPI == HSP_EPI_ACT) EpiAct<C>::consumer(a, L, lds, m0, wm * C::kWN + wn, acc);
   else epi_gen(a, L, acc);
 }
 

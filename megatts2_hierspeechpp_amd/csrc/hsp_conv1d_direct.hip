@@ -235,6 +235,7 @@ extern "C" int hsp_conv1d_direct_f32(const hsp_conv1d_args* ap, void* stream) {
   if (a.w_bs) return HSP_EINVAL;                  // per-batch weights (frequency bins): the implicit-GEMM kernel only
   if (a.ln_c1 || a.split_row) return HSP_EINVAL;  // fused LayerNorm / second output: token-GEMM path only
   if (a.fold_cols) return HSP_EINVAL;             // folded columns: kernels behind hsp_conv1d_mfma_f32 only
+  if (a.act == HSP_ACT_ACT1D) return HSP_EINVAL;  // activation epilogue: likewise
   if (linear_vec_fast(a)) {
     const unsigned gx = (unsigned)((a.Cout + 63) / 64), gy = (unsigned)((a.B + LV_BB - 1) / LV_BB);
     if (gy > 65535) return HSP_EINVAL;

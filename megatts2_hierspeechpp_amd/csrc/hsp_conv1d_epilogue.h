@@ -1,7 +1,7 @@
 // The EPILOGUES of the fused conv kernel, one per HSP_EPI_* kind, on the accumulator registers of a consumer wave
 // (part of hsp_conv1d_mfma_kernel.h), with what they share with the rest of the consumer role: where a lane's
 // accumulators sit in the output (ConsLane, fold_lane) and the loops over the accumulator file (for_acc and friends).
-// HSP_EPI_INIT's stores are in conv_consume (hsp_conv1d_consume.h says why).
+// HSP_EPI_INIT's stores are in conv_consume (hsp_conv1d_consume.h says why).  HSP_EPI_ACT (EpiAct, at the end) is the one epilogue the producer waves take part in.
 #pragma once
 
 namespace hspconv {
@@ -304,5 +304,155 @@ __device__ __forceinline__ void epi_gen(const hsp_conv1d_args& a, const ConsLane
     }
   });
 }
+
+// ---- HSP_EPI_ACT (hsp_conv1d_args.act == HSP_ACT_ACT1D): the NEXT Activation1d of an AMP pair, applied to the conv's own output
+// rows before they leave the workgroup.  Plain direct conv, bias only, on the 32 x 512 / 64 x 256 plain-prologue shapes
+// (WM == 1: every consumer wave holds all BM rows of its BN / 4 columns).  Column tiles advance by SEG = BN - 16: the
+// tile computes conv columns [p0 - 8, p0 - 8 + BN), p0 = nt SEG -- the raw window of the stand-alone kernel's segment
+// [p0, p0 + SEG) (act1d_seg_kernel, hsp_pointwise.hip; at BN = 512 its very geometry) -- and stores the activated columns
+// [p0, min(p0 + SEG, L)).  The accumulators start at the bias, as HSP_EPI_INIT's do, and the K loop is the plain one: a
+// conv column is bit for bit what the plain launch stores.  The arithmetic behind it is hsp_act1d_arith.h's.
+//
+// The tile goes through LDS RP rows at a time -- 16 at BN = 512 (registers 8 rh .. 8 rh + 7 of a 32 x 32 block are rows
+// 16 rh .. 16 rh + 15), a whole block at BN = 256 -- into the chunk buffers, which are free behind the K loop's last barrier (every fragment read is retired, no
+// DMA is in flight).  ALL waves of the workgroup then take rows (the producers stay for this): a wave owns whole rows
+// and its own 2x-rate buffer, so the phases of a row need wave-local ordering only, as in the stand-alone kernel.
+//   LDS: stage[RP][BN] + a2[waves][RIF][2 BN + 16] floats = 66 048 B at BN = 512 (RP 16, RIF 1), 66 560 B at BN = 256
+//   (RP 32, RIF 2: two rows of a wave in flight): under the 80 KB of two workgroups per CU; launch_one requests the larger
+//   of this and the K loop's plan.
+template <class C>
+struct EpiAct {
+  static_assert(C::kWM == 1 && C::kKS == 1 && C::BM % 32 == 0 && C::BN % 256 == 0, "whole rows per consumer wave; float4 row images");
+  static constexpr int BN = C::BN, SEG = C::BN - 16;   // conv columns / activated columns of a tile
+  // Rows of a wave IN FLIGHT: a row is a chain of LDS round trips (raw -> FIR -> a2 -> FIR -> store) and a wave has one
+  // neighbour per SIMD to hide them behind.  At BN = 256 a row is half as long and a tile has twice as many: two rows
+  // walk the phases together there, each with its own 2x-rate buffer (one row at a time: 64 -> 64 channels k = 3 at
+  // 32 x 32 000 was 24 us SLOWER fused than as two launches, profiles/epi_act_bench.txt).  At BN = 512 the second buffer
+  // does not fit the 80 KB of two workgroups per CU.
+  static constexpr int RIF = BN <= 256 ? 2 : 1;
+  static constexpr int RP = BN <= 256 ? 32 : 16;       // rows per pass: a whole 32-row block, or the half of registers 8 rh ...
+  static constexpr int NPASS = C::BM / RP;
+  static constexpr int NW = C::THREADS / 64;           // waves that take rows: all of them
+  static constexpr int A2W = 2 * BN + 16;              // one 2x-rate buffer (ACT2_A2 at BN = 512)
+  static constexpr int NV = BN / 256;                  // float4s of a raw row per lane
+  static constexpr int NC = (SEG / 2 + 63) / 64;       // phase-C iterations
+  static constexpr int LDS_FLOATS = RP * BN + NW * RIF * A2W;
+  static_assert(RP % (NW * RIF) == 0 && LDS_FLOATS * 4 <= 80 * 1024, "every wave has RIF rows per round; two workgroups per CU");
+
+  // rows `wave` + NW j, j < RIF, of every round of pass `pass`: replicate padding, up-2 FIR -> SnakeBeta -> down-2 FIR,
+  // stores.  A row past Cout (a launch with Cout < BM) walks along on the finite values the MFMAs left and stores nothing.
+  static __device__ __forceinline__ void rows(const hsp_conv1d_args& a, float* const lds, int b, int m0, int t0, int pass,
+                                              int wave, int lane, const act_f32x2 (&hu)[6], const act_f32x2 (&hd)[6]) {
+    const int L = a.ncols;
+    const int p0 = t0 + 8;                   // the tile's first activated column; p0 < L (launch_one's tile count)
+    const int n_out = min(SEG, L - p0);      // multiple of 4
+    for (int rl = wave; rl < RP; rl += NW * RIF) {
+      const int co0 = m0 + pass * RP + rl;
+      if (co0 >= a.Cout) break;              // wave-uniform
+      float* raw[RIF];                       // raw[j][c] = conv column p0 - 8 + c of row co0 + NW j
+      float* a2[RIF];
+      float kf[RIF], kb[RIF];
+      bool ok[RIF];
+#pragma unroll
+      for (int j = 0; j < RIF; ++j) {
+        const int co = co0 + NW * j;
+        ok[j] = co < a.Cout;
+        raw[j] = lds + (rl + NW * j) * BN;
+        a2[j] = lds + RP * BN + (wave * RIF + j) * A2W;
+        kf[j] = a.alpha_exp[min(co, a.Cout - 1)] * 0.318309886183790672f;
+        kb[j] = 0.5f * a.beta_inv[min(co, a.Cout - 1)];
+      }
+      // ---- phase A: the replicate padding of the raw row, xt[0] left of column 0 and xt[L - 1] from column L on (the
+      // MFMAs computed something there: a conv of the zero padding).  L % 4 == 0 and p0 % 4 == 0: whole float4s.
+      if (p0 == 0 || p0 - 8 + BN > L) {      // wave-uniform
+#pragma unroll
+        for (int j = 0; j < RIF; ++j) {
+          const float x0 = raw[j][8];
+          const float xl = raw[j][min(L - 1 - p0 + 8, BN - 1)];
+          float4 t[NV];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) t[v] = *reinterpret_cast<const float4*>(raw[j] + 4 * (lane + 64 * v));
+          asm volatile("" ::: "memory");
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            const int idx = p0 - 8 + 4 * (lane + 64 * v);
+            t[v] = idx < 0 ? make_float4(x0, x0, x0, x0) : t[v];
+            t[v] = idx >= L ? make_float4(xl, xl, xl, xl) : t[v];
+            *reinterpret_cast<float4*>(raw[j] + 4 * (lane + 64 * v)) = t[v];
+          }
+        }
+        asm volatile("" ::: "memory");
+      }
+      // ---- phase B: slots [0, 2 n_out + 10) of the 2x-rate signal
+      const int npairs = (2 * n_out + 13) >> 2;
+#pragma unroll 2
+      for (int pi = lane; pi < npairs; pi += 64) {
+#pragma unroll
+        for (int j = 0; j < RIF; ++j) HSP_ACT2_UP(a2[j], raw[j], pi, hu, kf[j], kb[j])
+      }
+      asm volatile("" ::: "memory");
+      // replicate padding of the 2x-rate signal: a[-5 .. -1] = a[0], a[2L .. 2L+4] = a[2L-1]
+      if (p0 == 0 || p0 + n_out == L) {
+#pragma unroll
+        for (int j = 0; j < RIF; ++j) {
+          if (p0 == 0 && lane < 5) a2[j][lane] = a2[j][5];
+          if (p0 + n_out == L && lane >= 8 && lane < 13) a2[j][2 * n_out + lane - 3] = a2[j][2 * n_out + 4];
+        }
+        asm volatile("" ::: "memory");
+      }
+      // ---- phase C: two outputs per lane, non-temporal (the next conv reads them from HBM / Infinity Cache anyway)
+      float* const yrow = a.y + (int64_t)b * a.y_bs + (int64_t)co0 * a.y_cs + p0;
+#pragma unroll
+      for (int it = 0; it < NC; ++it) {
+        const int l2 = lane + 64 * it;
+        if (2 * l2 >= n_out) continue;
+#pragma unroll
+        for (int j = 0; j < RIF; ++j) {
+          float2 yo;
+          HSP_ACT2_DOWN(yo, a2[j], l2, hd)
+          if (ok[j])
+            __builtin_nontemporal_store(act_f32x2{yo.x, yo.y}, reinterpret_cast<act_f32x2*>(yrow + (int64_t)(NW * j) * a.y_cs + 2 * l2));
+        }
+      }
+      asm volatile("" ::: "memory");   // raw / a2 are rewritten by the next round
+    }
+  }
+
+  // the producer waves' part: the consumers' barriers, and their share of the rows
+  static __device__ __forceinline__ void producer(const hsp_conv1d_args& a, float* const lds, int b, int m0, int t0,
+                                                  int wave, int lane) {
+    act_f32x2 hu[6], hd[6];
+    HSP_ACT2_TAPS(a.filt, hu, hd)
+    for (int pass = 0; pass < NPASS; ++pass) {
+      lds_barrier();                           // the pass's rows are staged
+      rows(a, lds, b, m0, t0, pass, wave, lane, hu, hd);
+      if (pass + 1 < NPASS) lds_barrier();     // ... and read: the stage may be rewritten
+    }
+  }
+
+  // the consumer waves' part: stage RP rows of the accumulators -- registers RP / 2 of a 32 x 32 block -- then rows like
+  // everybody
+  template <int TM, int TN>
+  static __device__ __forceinline__ void consumer(const hsp_conv1d_args& a, const ConsLane& L, float* const lds, int m0,
+                                                  int wave, const f32x16 (&acc)[TM][TN]) {
+    static_assert(TM * 32 == NPASS * RP, "the passes cover the wave's blocks");
+    act_f32x2 hu[6], hd[6];
+    HSP_ACT2_TAPS(a.filt, hu, hd)
+    float* const col = lds + L.wcol + L.l32;
+    static_for<NPASS>([&](auto pp) __attribute__((always_inline)) {
+      constexpr int pass = pp, i = (pass * RP) / 32, row0 = (pass * RP) % 32;   // block and first row of the pass in it
+      static_for<TN>([&](auto nn) __attribute__((always_inline)) {
+        constexpr int n = nn;
+        static_for<RP / 2>([&](auto rr) __attribute__((always_inline)) {
+          constexpr int r = row0 / 2 + rr;
+          col[(HSP_ACC_ROW(r, L.half) - row0) * BN + 32 * n] = acc[i][n][r];
+        });
+      });
+      lds_barrier();
+      rows(a, lds, L.b, m0, L.t0, pass, wave, L.lane, hu, hd);
+      if (pass + 1 < NPASS) lds_barrier();
+    });
+  }
+};
 
 }  // namespace hspconv

@@ -43,7 +43,24 @@ int validate(const hsp_conv1d_args& a) {
   return 0;
 }
 
+// The activation epilogue (hsp_conv1d_args.act == HSP_ACT_ACT1D, include/hsp.h): a launch with that value takes the form or is
+// refused -- no other kernel behind this entry point (token GEMMs, gated / ConvTranspose rows, K-split, folded columns,
+// the wide shapes) ever sees it.
+int dispatch_epi_act(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
+  if (!a.alpha_exp || !a.beta_inv || !a.filt) return HSP_EINVAL;
+  if (a.rows != HSP_ROWS_PLAIN || a.M > 64 || a.Cout > a.M || a.prologue != HSP_PRO_NONE) return HSP_EINVAL;
+  if (a.Lin != a.ncols || a.Lout != a.ncols || 2 * a.pad != (a.K - 1) * a.dil || (a.K - 1) * a.dil > 61 || (a.ncols & 3))
+    return HSP_EINVAL;   // stride 1 (validate), "same" padding, a halo within the window pitch, whole float4s
+  if (!hsp_aligned16(a.y) || (a.y_bs & 3) || (a.y_cs & 3)) return HSP_EINVAL;
+  if (a.cbias || a.mask_mode != HSP_MASK_NONE || a.cscale || a.res || a.accumulate ||
+      a.scale != 1.0f || a.post_scale != 1.0f)
+    return HSP_EINVAL;   // bias alone
+  if (a.fold_cols || a.w_bs || a.ln_c1 || a.split_row) return HSP_EINVAL;
+  return a.M > 32 ? hsp_conv_tile_M64P(a, HSP_EPI_ACT, false, s, plan_out) : hsp_conv_tile_M32P(a, HSP_EPI_ACT, false, s, plan_out);
+}
+
 int dispatch(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
+  if (epi_act_set(a)) return dispatch_epi_act(a, s, plan_out);
   const bool gated = a.rows == HSP_ROWS_GATE_WN || a.rows == HSP_ROWS_GATE_GLU;
   const bool act = a.prologue == HSP_PRO_ACT1D;
   // "short": 128 x 128 tiles would leave at least half of the 256 CUs idle; prefer 64 x 64 tiles with deep

@@ -33,7 +33,7 @@
 // This header is the one to include: tile configuration (Cfg), LDS plan, the kernel, the host-side launch (launch_one,
 // select_epilogue) and the tile list.  It includes the kernel's three parts:
 //   hsp_conv1d_produce.h    producer waves: the staging routines of a chunk (the chunk loops are in the kernel below)
-//   hsp_conv1d_epilogue.h   consumer waves: lane map, accumulator loops, the VEC / GATE / SHUF / GEN epilogues
+//   hsp_conv1d_epilogue.h   consumer waves: lane map, accumulator loops, the VEC / GATE / SHUF / GEN epilogues, the activation epilogue (all waves)
 //   hsp_conv1d_consume.h    consumer waves: fragment reads, conv_consume with the INIT preload and stores and the MFMA loop
 // hsp_conv1d_tile.hip instantiates the kernel once per tile shape (one translation unit each, so the build
 // parallelises) and hsp_conv1d_mfma.hip holds validation and the shape / epilogue selection.
@@ -41,6 +41,7 @@
 #include <atomic>
 #include <type_traits>
 #include "hsp_device.h"
+#include "hsp_act1d_arith.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -84,7 +85,9 @@ enum {
   HSP_EPI_VEC = 1,   // plain rows, any pointwise epilogue, 16-B addressable tensors: LDS transpose + float4
   HSP_EPI_GATE = 2,  // gated rows (WN / GLU)
   HSP_EPI_SHUF = 3,  // ConvTranspose phase shuffle, bias only
-  HSP_EPI_GEN = 4    // everything else (scalar)
+  HSP_EPI_GEN = 4,   // everything else (scalar)
+  HSP_EPI_ACT = 5    // plain rows, bias only, then the next Activation1d on the tile's rows (act == HSP_ACT_ACT1D;
+                     // overlapping column tiles: hsp_conv1d_epilogue.h, EpiAct)
 };
 
 namespace hspconv {
@@ -261,7 +264,9 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
     nt = ct % n_nt;
     b = ct / n_nt;
   }
-  const int m0 = mt * BM, t0 = nt * BN;
+  int t0c = nt * BN;
+  if constexpr (EPI == HSP_EPI_ACT) t0c = nt * (BN - 16) - 8;   // overlapping tiles: 8 halo columns of the activation on either side
+  const int m0 = mt * BM, t0 = t0c;
   const int p0 = t0 - a.pad;  // first activated-input position of the window
   const int ts0 = FOLD ? t0 - b * a.ncols : 0;   // FOLD: t0 is a virtual column, at time ts0 of utterance b
 
@@ -336,6 +341,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
           }
           HSP_BARRIER(a);
         }
+        if constexpr (EPI == HSP_EPI_ACT) EpiAct<C>::producer(a, lds, b, m0, t0, wave, lane);
         return;
       }
       PR::dma_w(pa, P, Ws0, 0, m0, pw, lane);
@@ -378,6 +384,7 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void conv1d_mfma_kernel(const 
         HSP_BARRIER(a);
       }
     }
+    if constexpr (EPI == HSP_EPI_ACT) EpiAct<C>::producer(a, lds, b, m0, t0, wave, lane);
     return;
   }
 
@@ -443,10 +450,14 @@ bool fold_fits(const hsp_conv1d_args& a, bool xvec) {
   return (int64_t)a.B * T <= 0x3fffffff;
 }
 
+// the activation epilogue: does the launch ask for it (hsp_conv1d_args.act == HSP_ACT_ACT1D)?
+inline bool epi_act_set(const hsp_conv1d_args& a) { return a.act == HSP_ACT_ACT1D; }
+
 // Launch one instantiation.  EPI / ACT must already match the arguments (select_epilogue()).
 template <class C, int EPI, bool ACT>
 int launch_one(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   if (a.fold_cols && !has_fold_path<C, EPI, ACT>()) return HSP_EINVAL;   // this kernel does not implement the form
+  if (epi_act_set(a) != (EPI == HSP_EPI_ACT)) return HSP_EINVAL;         // likewise (dispatch() has checked the form's conditions)
   // a shape whose register budget admits two workgroups per CU keeps its LDS under half the
   // CU's; the others take the deepest chunk the whole 160 KB can stage (fewer barriers, and the
   // DMA of a chunk gets a longer MFMA phase to land under)
@@ -463,12 +474,14 @@ int launch_one(const hsp_conv1d_args& a, hipStream_t s, int32_t* plan_out) {
   if (lkc < 0) lkc = pick_lkc<C>(a, kMaxLdsBytes);
   if (lkc < 0) return HSP_EINVAL;
   int lds_bytes = make_plan<C>(a.K, a.dil, a.prologue, lkc).total * (int)sizeof(float);
+  if constexpr (EPI == HSP_EPI_ACT) lds_bytes = lds_bytes > EpiAct<C>::LDS_FLOATS * (int)sizeof(float) ? lds_bytes : EpiAct<C>::LDS_FLOATS * (int)sizeof(float);
   if (plan_out) {
     plan_out[0] = C::BM; plan_out[1] = C::BN; plan_out[2] = 1 << lkc; plan_out[3] = lds_bytes;
     return 0;
   }
   const int n_mt = (a.M + C::BM - 1) / C::BM;
-  const int n_nt = (a.ncols + C::BN - 1) / C::BN;
+  constexpr int kColStep = EPI == HSP_EPI_ACT ? C::BN - 16 : C::BN;   // HSP_EPI_ACT: overlapping column tiles
+  const int n_nt = (a.ncols + kColStep - 1) / kColStep;
   // block schedule (see the kernel): row tiles per XCD group, narrow tail tiles
   const int64_t n_ct = (int64_t)n_nt * a.B;
   // g > 0 (XCD-grouped row tiles) is a measured LOSS and exists in the tuning build only (HSP_CV_XCD_GROUPS):

@@ -17,6 +17,7 @@ constexpr bool same = std::is_same<A, B>::value;
 
 template <int EPI, bool ACT>
 constexpr bool supported() {
+  if (EPI == HSP_EPI_ACT) return !ACT && (same<T, M64P> || same<T, M32P>);  // the activation epilogue: its two shapes
   if (same<T, S64G> || same<T, S64GW> || same<T, S64G2>) return EPI == HSP_EPI_GATE && !ACT;
   if (same<T, M64> || same<T, M32>) return ACT && (EPI == HSP_EPI_INIT || EPI == HSP_EPI_GEN);  // activation shapes
   if (ACT) return (same<T, M128> || same<T, S64> || same<T, S64W> || same<T, S32>) && (EPI == HSP_EPI_INIT || EPI == HSP_EPI_GEN);
@@ -47,6 +48,7 @@ int HSP_CAT(hsp_conv_tile_, HSP_TILE)(const hsp_conv1d_args& a, int epi, bool ac
     case HSP_EPI_GATE: return by_act<HSP_EPI_GATE>(a, act, s, plan_out);
     case HSP_EPI_SHUF: return by_act<HSP_EPI_SHUF>(a, act, s, plan_out);
     case HSP_EPI_GEN: return by_act<HSP_EPI_GEN>(a, act, s, plan_out);
+    case HSP_EPI_ACT: return by_act<HSP_EPI_ACT>(a, act, s, plan_out);
     default: return HSP_EINVAL;
   }
 }

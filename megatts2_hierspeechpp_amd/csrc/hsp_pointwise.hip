@@ -1,6 +1,7 @@
 // HBM-bound pointwise / reduction kernels of the vocoder path (gfx950).
 // Reference call sites are listed next to each entry point in include/hsp.h.
 #include "hsp_rows.h"
+#include "hsp_act1d_arith.h"
 
 namespace {
 
@@ -17,8 +18,6 @@ inline unsigned loop_grid(int64_t n) { return hsp_flat_grid(n, 256, 1048576); }
 constexpr int ACT_TILE = 1024;
 constexpr int ACT_THREADS = 256;
 constexpr int ACT_HALO = 8;  // raw window starts at p0 - 8 (16-B aligned); 5 are needed
-
-typedef float act_f32x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(ACT_THREADS) void act1d_kernel(const float* __restrict__ x, float* __restrict__ y, int C,
                                                             int L, const float* __restrict__ alpha_exp,
@@ -211,11 +210,7 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
   float* raw = raw_all[wave];
   float* a2 = a2_all[wave];
   act_f32x2 hu[6], hd[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    hu[i] = act_f32x2{2.0f * filt[10 - 2 * i], 2.0f * filt[11 - 2 * i]};
-    hd[i] = act_f32x2{filt[12 + 2 * i], filt[13 + 2 * i]};
-  }
+  HSP_ACT2_TAPS(filt, hu, hd)   // (hsp_act1d_arith.h)
 
   // A wave walks ACT2_ITEMS consecutive segments; the raw window of the next one is in flight
   // (registers) while the current one is computed, so HBM latency is off the critical path.
@@ -283,17 +278,7 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
     const int npairs = (2 * n_out + 13) >> 2;  // slots [0, 2 n_out + 10)
 #pragma unroll 2
     for (int pi = lane; pi < npairs; pi += 64) {
-      const act_f32x2* rp = reinterpret_cast<const act_f32x2*>(raw + 2 * pi + 2);
-      const act_f32x2 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-      const float xv[7] = {r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y};  // x[q-2 .. q+4]
-      act_f32x2 u0 = {0.0f, 0.0f}, u1 = {0.0f, 0.0f};
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        u0 = __builtin_elementwise_fma(act_f32x2{xv[i], xv[i]}, hu[i], u0);          // a[2q+1], a[2q+2]
-        u1 = __builtin_elementwise_fma(act_f32x2{xv[i + 1], xv[i + 1]}, hu[i], u1);  // a[2q+3], a[2q+4]
-      }
-      *reinterpret_cast<float4*>(a2 + 4 * pi) = make_float4(hsp_snake_hw(u0.x, kf, kb), hsp_snake_hw(u0.y, kf, kb),
-                                                            hsp_snake_hw(u1.x, kf, kb), hsp_snake_hw(u1.y, kf, kb));
+      HSP_ACT2_UP(a2, raw, pi, hu, kf, kb)   // (hsp_act1d_arith.h)
     }
     act2_compiler_fence();
     // replicate padding of the 2x-rate signal: a[-5 .. -1] = a[0], a[2L .. 2L+4] = a[2L-1]
@@ -318,17 +303,7 @@ __global__ __launch_bounds__(64 * ACT2_WAVES) void act1d_seg_kernel(const float*
     for (int it = 0; it < NC; ++it) {
       const int l2 = lane + 64 * it;
       if (2 * l2 >= n_out) continue;
-      const float4* ap = reinterpret_cast<const float4*>(a2 + 4 * l2);
-      const float4 q0 = ap[0], q1 = ap[1], q2 = ap[2];
-      const act_f32x2 q3 = *reinterpret_cast<const act_f32x2*>(a2 + 4 * l2 + 12);
-      const act_f32x2 aw[7] = {{q0.x, q0.y}, {q0.z, q0.w}, {q1.x, q1.y}, {q1.z, q1.w}, {q2.x, q2.y}, {q2.z, q2.w}, q3};
-      act_f32x2 s0 = {0.0f, 0.0f}, s1 = {0.0f, 0.0f};
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        s0 = __builtin_elementwise_fma(aw[k], hd[k], s0);
-        s1 = __builtin_elementwise_fma(aw[k + 1], hd[k], s1);
-      }
-      yo[it] = make_float2(s0.x + s0.y, s1.x + s1.y);
+      HSP_ACT2_DOWN(yo[it], a2, l2, hd)   // (hsp_act1d_arith.h)
       if constexpr (RAG) {
         yo[it].x = 2 * l2 < n_in ? yo[it].x : 0.0f;
         yo[it].y = 2 * l2 + 1 < n_in ? yo[it].y : 0.0f;

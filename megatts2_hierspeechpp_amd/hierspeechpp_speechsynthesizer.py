@@ -185,6 +185,15 @@ def amp_pair(c1, c2, a1, a2, x, *, form=None, before_last=None, **kw):
         return c1.forward_fft_pair(c2, x, act_first=a1, act_second=a2, before_inverse=before_last, **kw)
     if form == "pair":
         raise L.HspError("amp_pair(form='pair'): hsp_dftseg_pair_supported says no for this geometry")
+    if form is None and hip_layers.epi_act_eligible(
+            c1.cin, c1.cout, x.shape[2], fft_first=w1, fft_second=w2,
+            row_exact=hip_layers.row_lengths() is not None,
+            plan=c1.plain_plan(x) if (hip_layers.EPI_ACT and c1.cin == c1.cout <= 64) else None):
+        # low-channel pair: c1 stores a2(xt) from its epilogue (hsp_conv1d_args.act = HSP_ACT_ACT1D): no xt in HBM, no a2 launch
+        xt = c1(a1(x), epi_act=a2)
+        if before_last is not None:
+            torch.cuda.current_stream(x.device).wait_event(before_last)
+        return c2(xt, **kw)
     if w1:
         xt = c1.forward_fft(x, act1d=a1) if fft_act(x) else c1.forward_fft(a1(x))
     else:

@@ -258,6 +258,40 @@ def fold_cols_wanted(plan, B: int, ncols: int, gated: bool = False, halo: int = 
 
 
 # ------------------------------------------------------------------ index maps (host logic)
+# Activation epilogue (hsp_conv1d_args.act = HSP_ACT_ACT1D): the first conv of a low-channel AMP pair applies the
+# pair's second Activation1d to its own output tile, so xt = c1(a1(x)) is never written and a2 is no launch.  Bit-identical
+# to the two launches, and faster than them on both shapes that carry the form (profiles/epi_act_bench.txt).
+# HSP_EPI_ACT=0 switches the form off (A/B runs, parity tests of both forms).
+EPI_ACT = os.environ.get("HSP_EPI_ACT", "1") == "1"
+EPI_ACT_TILES = ((32, 512), (64, 256))       # (BM, BN) of the two shapes whose kernels implement the form
+EPI_ACT_FLOPS = 60                           # per output sample: 2 x 6-tap up-FIR, two snakes, 12-tap down-FIR
+
+
+def epi_act_tiling(ncols: int, bn: int):
+    """The overlapping column tiles of the form: [(first conv column, first stored column, stored columns)], tile t
+    computing conv columns [t (bn - 16) - 8, t (bn - 16) + bn - 8) and storing from t (bn - 16) on."""
+    seg = bn - 16
+    return [(t * seg - 8, t * seg, min(seg, ncols - t * seg)) for t in range(-(-ncols // seg))]
+
+
+def epi_act_plan_ok(plan) -> bool:
+    """Does the PLAIN launch of the conv take one of the two shapes that carry the form (``plan``: the four numbers of
+    hsp_conv1d_mfma_plan)?  Only then is the fused launch the same sum, in the same order, as the plain one."""
+    return int(plan[2]) > 0 and (int(plan[0]), int(plan[1])) in EPI_ACT_TILES
+
+
+def epi_act_eligible(cin: int, cout: int, L_: int, *, fft_first: bool, fft_second: bool, row_exact: bool, plan) -> bool:
+    """amp_pair's rule for c2(c1(a1(x), epi_act=a2)): the form switched on, both convs direct, at most 64 channels, whole
+    float4 rows, no row-exact batch (the ragged activation has no epilogue form), the plain launch of c1 on one of the
+    form's shapes (epi_act_plan_ok).  No shape is excluded by measurement: the fused launch beat conv + activation on
+    every one of profiles/epi_act_bench.txt."""
+    if not EPI_ACT or fft_first or fft_second or row_exact:
+        return False
+    if cin > 64 or cout > 64 or L_ % 4 != 0:
+        return False
+    return plan is not None and epi_act_plan_ok(plan)
+
+
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
@@ -772,13 +806,16 @@ class Conv1d(_ConvBase):
 
     def _prepare(self, x, *, act1d=None, lrelu: Optional[float] = None, silu_in=False, act=L.ACT_NONE, cbias=None,
                 mask=None, mask_mode=L.MASK_NONE, cscale=None, scale=1.0, res=None, out=None, accumulate=False,
-                post_scale=1.0, force_direct=False, row_range=None, split_out=None, mask_mode2=L.MASK_NONE) -> ConvLaunch:
+                post_scale=1.0, force_direct=False, row_range=None, split_out=None, mask_mode2=L.MASK_NONE,
+                epi_act=None) -> ConvLaunch:
         """The launch of this conv on x [B, Cin, L], built and not issued: geometry, the output (allocated when None),
         the filled struct, the direct-versus-MFMA choice.  ``row_range=(r0, r1)`` computes only output channels [r0, r1)
         (PLAIN rows, r0 % 4 == 0): the WN res/skip layer is one parameter set feeding two differently-fused launches.
         ``split_out=(split_row, out2, accumulate2)``: ONE launch for both halves of such a layer
         (hsp_conv1d_args.split_row): rows [0, split_row) -> the usual output with this call's epilogue, rows
-        [split_row, cout) -> ``out2`` (+= if accumulate2; allocated when None); the launch's ``out`` is then (out, out2)."""
+        [split_row, cout) -> ``out2`` (+= if accumulate2; allocated when None); the launch's ``out`` is then (out, out2).
+        ``epi_act=<Activation1d>``: the launch stores that activation of the conv's output (hsp_conv1d_args.act = HSP_ACT_ACT1D);
+        the caller has checked the form's conditions (epi_act_eligible), the library refuses anything else."""
         self._require_ready()
         if act1d is not None and _ROWS.get() is not None:
             raise L.HspError("row_exact: the conv-prologue Activation1d (HSP_FUSE_ACT_MAX_C > 0) has no ragged form")
@@ -840,12 +877,33 @@ class Conv1d(_ConvBase):
             a.y2, a.y2_bs, a.y2_cs = L.fptr(out2), out2.stride(0), out2.stride(1)
             flops = 2 * B * self.cout * Cin * Lout
             nbytes += 4 * B * (self.cout - split_row) * Lout * (1 + bool(acc2))
+        if epi_act is not None:
+            if direct or _ROWS.get() is not None:
+                raise L.HspError("epi_act: the activation epilogue is the MFMA path's, and has no ragged form")
+            if act != L.ACT_NONE or a.prologue != L.PRO_NONE:
+                raise L.HspError("epi_act: no pointwise act and no prologue beside the activation epilogue")
+            a.act = L.ACT_ACT1D                          # (alpha_exp / beta_inv / filt are the epilogue's then: per OUTPUT channel)
+            a.alpha_exp, a.beta_inv, a.filt = L.fptr(epi_act._ea), L.fptr(epi_act._binv), L.fptr(epi_act._filt)
+            flops += EPI_ACT_FLOPS * B * cout * Lout     # (nbytes as they are: input once, output once -- now the activated one)
         kind, fn = ("hsp_conv1d_direct_f32", L.lib().hsp_conv1d_direct_f32) if direct else \
             ("hsp_conv1d_mfma_f32", L.lib().hsp_conv1d_mfma_f32)
         if not direct:
             _set_fold_cols(a)
         return ConvLaunch(kind, fn, a, flops, nbytes, out if out2 is None else (out, out2),
-                          (x, out, out2, res, cbias, mask, cscale))
+                          (x, out, out2, res, cbias, mask, cscale, epi_act))
+
+    def plain_plan(self, x):
+        """(BM, BN, KC, LDS bytes) of the plain MFMA launch of this conv on x, or None where the library has none (or the
+        VALU kernel takes it): what amp_pair asks before it fuses the next activation into the launch.  Cached per shape."""
+        key = (tuple(x.shape), x.stride(), x.data_ptr() % 16)
+        cache = self.__dict__.setdefault("_plain_plans", {})
+        if key not in cache:
+            p = self._prepare(x, out=x)          # (no launch: the output pointer only stands for an aligned buffer)
+            plan = (C.c_int32 * 4)()
+            p.args.debug = DEBUG_FLAGS
+            ok = p.kind == "hsp_conv1d_mfma_f32" and L.lib().hsp_conv1d_mfma_plan(C.byref(p.args), C.byref(plan)) == 0
+            cache[key] = tuple(plan) if ok else None
+        return cache[key]
 
     def forward(self, x, **kw):
         """``_prepare`` (see there for the arguments) plus one of three launch protocols.  Returns the output; with ``split_out``
