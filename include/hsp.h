@@ -374,6 +374,33 @@ int hsp_flip_channels_f32(const float* x, float* y, int32_t B, int32_t C, int32_
  * hierspeechpp_speechsynthesizer.py:201-202, 687 */
 int hsp_sample_prior_f32(const float* stats, const float* noise, const float* mask, float* z,
                          int32_t B, int32_t C, int32_t T, float noise_scale, void* stream);
+
+/* ------------------------------------------------ seeded prior noise (additive: HSP_VERSION unchanged)
+ * The standard-normal noise n[b, c, t] of the prior sample as a counter-based stream.  Row b, channel c (0-based),
+ * frame t (0-based), seed s = seeds[b] (int64, two's complement):
+ *   key     = (low 32 bits of s, high 32 bits of s)
+ *   counter = (t >> 2, c, 0, 1).  The last word names this stream: the draws of "sampled PLM decoding" below use
+ *             (i >> 2, j, 0, 0), so one seed serves both without a shared counter.
+ *   w0..w3  = Philox4x32-10(counter, key).  Frames with t & 3 in {0, 1} use the pair (w0, w1), frames with t & 3 in
+ *             {2, 3} the pair (w2, w3).  For a pair (wa, wb):
+ *               u1 = ((wa >> 9) + 0.5) 2^-23   in (0, 1), exact in fp32
+ *               u2 = (wb >> 8) 2^-24           in [0, 1), exact
+ *               r  = sqrt(-2 ln u1)            <= sqrt(48 ln 2) = 5.768
+ *             the even frame of the pair gets r cos(2 pi u2), the odd frame r sin(2 pi u2) (Box-Muller).  The device
+ *             evaluates these in fp32 as cospi / sinpi of 2 u2, so no rounded 2 pi enters.
+ * n[b, c, t] depends on (s, c, t) only: not on B, T, the row's position in the batch, the launch geometry or the call
+ * history; frames 0 .. T - 1 of a longer row are its first T frames.  `seeds` is read from device memory when the
+ * kernel runs (a captured graph replays with new seeds after a copy).  One thread owns a group of four frames of one
+ * (b, c) and moves it with one 16-byte access where every row is 16-byte addressable (T % 4 == 0, 16-byte aligned
+ * bases), with scalar accesses otherwise.  HSP_EINVAL (nothing launched) on a NULL pointer or a size <= 0.
+ *
+ * out[b, c, t] = n[b, c, t], contiguous [B, C, T]. */
+int hsp_randn_rows_f32(const int64_t* seeds, float* out, int32_t B, int32_t C, int32_t T, void* stream);
+/* hsp_sample_prior_f32 with the noise drawn in registers: z = (m + n * exp(logs) * noise_scale) * mask with n as above;
+ * no noise tensor is written or read.  The draw and the formula are the functions the two launches above run, so the
+ * result equals hsp_sample_prior_f32 on the output of hsp_randn_rows_f32 for the same seeds bit for bit. */
+int hsp_sample_prior_seeded_f32(const float* stats, const int64_t* seeds, const float* mask, float* z,
+                                int32_t B, int32_t C, int32_t T, float noise_scale, void* stream);
 /* LayerNorm over C (no affine) then optional mask, then x*(1+scale)+shift with per-(b,c)
  * scale/shift: modules.py:346-347, 396, 398, 409-410.  gamma/beta (per-channel affine,
  * modules.py:19-31) optional. */

@@ -170,6 +170,8 @@ SIGNATURES = {
     "hsp_sequence_mask_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, _fp]),
     "hsp_flip_channels_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_sample_prior_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
+    "hsp_randn_rows_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "hsp_sample_prior_seeded_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
     "hsp_layernorm_mod_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp, _fp,
                                         C.c_int64, _fp, _fp, _fp]),
     "hsp_mha_f32": (C.c_int, [C.POINTER(MhaArgs), _fp]),

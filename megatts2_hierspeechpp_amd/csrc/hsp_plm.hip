@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "hsp_device.h"
+#include "hsp_philox.h"   // philox4x32_10: the stream of the sampled decision
 
 namespace {
 
@@ -153,17 +154,6 @@ struct SampleSmem {
 __device__ __forceinline__ unsigned order_key(float f) {
   const unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-    const unsigned lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
 }
 
 // inclusive scan of v over the 256 threads in thread order; every thread gets its own prefix, *total the sum

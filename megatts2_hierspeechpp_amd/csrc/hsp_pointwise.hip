@@ -2,6 +2,7 @@
 // Reference call sites are listed next to each entry point in include/hsp.h.
 #include "hsp_rows.h"
 #include "hsp_act1d_arith.h"
+#include "hsp_philox.h"
 
 namespace {
 
@@ -366,6 +367,11 @@ __global__ void flip_channels_kernel(const float* __restrict__ x, float* __restr
   }
 }
 
+// THE prior sample of one element: (m + n exp(logs) noise_scale) mask, for a given and for a drawn n alike
+__device__ __forceinline__ float prior_value(float m, float logs, float n, float noise_scale, float mk) {
+  return (m + n * expf(logs) * noise_scale) * mk;
+}
+
 __global__ void sample_prior_kernel(const float* __restrict__ stats, const float* __restrict__ noise,
                                     const float* __restrict__ mask, float* __restrict__ z, int B, int C, int T,
                                     float noise_scale) {
@@ -377,7 +383,59 @@ __global__ void sample_prior_kernel(const float* __restrict__ stats, const float
     const int64_t b = r / C;
     const float m = stats[(b * 2 * C + c) * T + t];
     const float logs = stats[(b * 2 * C + C + c) * T + t];
-    z[i] = (m + noise[i] * expf(logs) * noise_scale) * mask[b * T + t];
+    z[i] = prior_value(m, logs, noise[i], noise_scale, mask[b * T + t]);
+  }
+}
+
+// Seeded prior noise (hsp.h): one thread owns the group of four frames 4 g .. 4 g + 3 of one (b, c) -- one Philox call,
+// two Box-Muller pairs (hsp_normal4).  VEC: every row is 16-B addressable (T % 4 == 0 and 16-B aligned bases, so
+// every group is whole), and a group moves as one float4; else scalar accesses, cut at the row's end.
+template <bool VEC>
+__device__ __forceinline__ void group_load(const float* __restrict__ p, int left, float v[4]) {
+  if (VEC) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = k < left ? p[k] : 0.0f;
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void group_store(float* __restrict__ p, int left, const float v[4]) {
+  if (VEC) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < left) p[k] = v[k];
+  }
+}
+
+// FUSED: z = prior_value of the drawn noise (hsp_sample_prior_seeded_f32; `out` is z); else out = the noise itself
+// (hsp_randn_rows_f32; stats and mask unread).  G = groups per row; `seeds` is read here, when the kernel runs.
+template <bool FUSED, bool VEC>
+__global__ __launch_bounds__(256) void randn_rows_kernel(const int64_t* __restrict__ seeds,
+                                                         const float* __restrict__ stats,
+                                                         const float* __restrict__ mask, float* __restrict__ out, int B,
+                                                         int C, int T, int G, float noise_scale) {
+  const int64_t n = (int64_t)B * C * G;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int g = (int)(i % G);
+    const int64_t r = i / G;
+    const int c = (int)(r % C);
+    const int64_t b = r / C;
+    const int t = 4 * g, left = T - t;   // left >= 1: the frames of this group inside the row
+    float v[4];
+    hsp_normal4(seeds[b], (unsigned)c, (unsigned)g, v);
+    if (FUSED) {
+      float m[4], logs[4], mk[4];
+      group_load<VEC>(stats + (b * 2 * C + c) * T + t, left, m);
+      group_load<VEC>(stats + (b * 2 * C + C + c) * T + t, left, logs);
+      group_load<VEC>(mask + b * T + t, left, mk);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = prior_value(m[k], logs[k], v[k], noise_scale, mk[k]);
+    }
+    group_store<VEC>(out + (b * C + c) * T + t, left, v);
   }
 }
 
@@ -666,6 +724,29 @@ extern "C" int hsp_sample_prior_f32(const float* stats, const float* noise, cons
   hipLaunchKernelGGL(sample_prior_kernel, dim3(loop_grid((int64_t)B * C * T)), dim3(256), 0, HSP_STREAM, stats,
                      noise, mask, z, B, C, T, noise_scale);
   return (int)hipGetLastError();
+}
+
+// both seeded launches: one thread per group of four frames, on the grid of every grid-stride kernel of this file
+template <bool FUSED>
+static int randn_rows_launch(const int64_t* seeds, const float* stats, const float* mask, float* out, int B, int C, int T,
+                             float noise_scale, hipStream_t s) {
+  const int G = T / 4 + ((T & 3) != 0);
+  const bool vec = (T & 3) == 0 && hsp_aligned16(out) && (!FUSED || (hsp_aligned16(stats) && hsp_aligned16(mask)));
+  const auto kernel = vec ? randn_rows_kernel<FUSED, true> : randn_rows_kernel<FUSED, false>;
+  hipLaunchKernelGGL(kernel, dim3(loop_grid((int64_t)B * C * G)), dim3(256), 0, s, seeds, stats, mask, out, B, C, T, G,
+                     noise_scale);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_randn_rows_f32(const int64_t* seeds, float* out, int32_t B, int32_t C, int32_t T, void* stream) {
+  if (!seeds || !out || B <= 0 || C <= 0 || T <= 0) return HSP_EINVAL;
+  return randn_rows_launch<false>(seeds, nullptr, nullptr, out, B, C, T, 0.0f, HSP_STREAM);
+}
+
+extern "C" int hsp_sample_prior_seeded_f32(const float* stats, const int64_t* seeds, const float* mask, float* z,
+                                           int32_t B, int32_t C, int32_t T, float noise_scale, void* stream) {
+  if (!stats || !seeds || !mask || !z || B <= 0 || C <= 0 || T <= 0) return HSP_EINVAL;
+  return randn_rows_launch<true>(seeds, stats, mask, z, B, C, T, noise_scale, HSP_STREAM);
 }
 
 extern "C" int hsp_mask_mul_f32(const float* x, const float* mask, float* y, int32_t B, int32_t C, int32_t T,

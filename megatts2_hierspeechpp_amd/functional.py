@@ -78,11 +78,68 @@ def flip_channels(x):
     return y
 
 
-def sample_prior(stats, noise, mask, noise_scale: float):
-    """z = (m + noise * exp(logs) * noise_scale) * mask; stats = [B, 2C, T]."""
-    stats, noise, mask = _c(stats), _c(noise), _c(mask)
+def row_seeds(seeds, B: int, device) -> torch.Tensor:
+    """int64 [B] seeds on ``device``, THE rule of every seed argument (the prosody LM's ``seeds``, the prior noise's
+    ``noise_seeds``): an int s gives row b the seed s + b (one fill kernel, capturable); a tensor is used
+    as it is when it already is a contiguous int64 [B] device tensor -- so a captured loop replays with the values
+    a later ``seeds.copy_()`` put there."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.shape != (B,):
+            raise L.HspError(f"seeds must have shape ({B},), got {tuple(seeds.shape)}")
+        if seeds.dtype == torch.int64 and seeds.device == torch.device(device) and seeds.is_contiguous():
+            return seeds
+        return seeds.to(device=device, dtype=torch.int64).contiguous()
+    s = int(0 if seeds is None else seeds)
+    return torch.arange(s, s + B, dtype=torch.int64, device=device)
+
+
+def check_noise_seeds(noise, noise_seeds, B: Optional[int] = None, what: str = "noise_seeds") -> None:
+    """The argument check of every call that takes ``noise`` and ``noise_seeds`` (from shapes alone, no device work):
+    the tensor and the seeds that would draw it exclude each other; the seeds are an int or a 1-D integer tensor, of
+    ``B`` entries where the caller knows its rows."""
+    if noise_seeds is None:
+        return
+    if noise is not None:
+        raise L.HspError(f"give noise or {what}, not both: the seeds draw the tensor that noise would replace")
+    if isinstance(noise_seeds, torch.Tensor):
+        if noise_seeds.dim() != 1 or noise_seeds.dtype.is_floating_point or \
+                (B is not None and noise_seeds.shape[0] != B):
+            raise L.HspError(f"{what} must be an int or an int64 [{'B' if B is None else B}] tensor, got "
+                             f"{noise_seeds.dtype} {tuple(noise_seeds.shape)}")
+    elif isinstance(noise_seeds, bool) or not isinstance(noise_seeds, int):
+        raise L.HspError(f"{what} must be an int or an int64 [B] tensor, got {type(noise_seeds).__name__}")
+
+
+def randn_rows(seeds, C: int, T: int, device=None):
+    """The seeded prior noise [B, C, T] (include/hsp.h "seeded prior noise"): row b is a function of (seeds[b], c, t)
+    alone.  ``seeds``: an int64 [B] tensor (B from its length; a CPU tensor goes to ``device``, default the current
+    GPU), read in place when it lives on the device."""
+    if not isinstance(seeds, torch.Tensor) or seeds.dim() != 1:
+        raise L.HspError("randn_rows takes its seeds as an int64 [B] tensor")
+    if device is None:
+        device = seeds.device if seeds.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    seeds = row_seeds(seeds, seeds.shape[0], device)
+    out = torch.empty(seeds.shape[0], int(C), int(T), dtype=torch.float32, device=seeds.device)
+    L.call("hsp_randn_rows_f32", L.ptr(seeds), L.fptr(out), seeds.shape[0], int(C), int(T))
+    return out
+
+
+def sample_prior(stats, noise, mask, noise_scale: float, seeds=None):
+    """z = (m + noise * exp(logs) * noise_scale) * mask; stats = [B, 2C, T].  Exactly one of ``noise`` ([B, C, T]) and
+    ``seeds`` (an int or an int64 [B] tensor, `row_seeds`): with seeds the noise of `randn_rows` is drawn inside the
+    launch and no noise tensor exists; the result is the same bit for bit."""
     B, C2, T = stats.shape
+    check_noise_seeds(noise, seeds, B, "seeds")
+    if noise is None and seeds is None:
+        raise L.HspError("sample_prior needs noise or seeds")
+    stats, mask = _c(stats), _c(mask)
     z = torch.empty(B, C2 // 2, T, dtype=torch.float32, device=stats.device)
+    if seeds is not None:
+        seeds = row_seeds(seeds, B, stats.device)
+        L.call("hsp_sample_prior_seeded_f32", L.fptr(stats), L.ptr(seeds), L.fptr(mask), L.fptr(z), B, C2 // 2, T,
+               float(noise_scale))
+        return z
+    noise = _c(noise)
     assert noise.shape == z.shape, (noise.shape, z.shape)
     L.call("hsp_sample_prior_f32", L.fptr(stats), L.fptr(noise), L.fptr(mask), L.fptr(z), B, C2 // 2, T,
            float(noise_scale))

@@ -124,13 +124,23 @@ class PosteriorSFEncoder(nn.Module):
         x = self.enc(Fh.axpby(x_src, x_ftr, 1.0, 1.0), x_mask, g=g)
         return self.proj(x, mask=x_mask, mask_mode=L.MASK_PRE)  # [B, 2*out, T] = (m, logs)
 
-    def forward(self, x_src, x_ftr, x_mask, g=None, noise=None):
+    def forward(self, x_src, x_ftr, x_mask, g=None, noise=None, noise_seeds=None):
+        Fh.check_noise_seeds(noise, noise_seeds)
         stats = self.stats(x_src, x_ftr, x_mask, g)
         C = self.out_channels
-        if noise is None:
-            noise = torch.randn(stats.shape[0], C, stats.shape[2], dtype=torch.float32, device=stats.device)
-        z = Fh.sample_prior(stats, noise, x_mask, 1.0)
+        z = _sample_prior(stats, C, x_mask, noise, noise_seeds, 1.0)
         return z, stats[:, :C], stats[:, C:]
+
+
+def _sample_prior(stats, C, mask, noise, noise_seeds, noise_scale):
+    """The prior sample from its statistics: with the given ``noise``, with the seeded noise drawn inside the launch
+    (``noise_seeds``: an int or an int64 [B] tensor, `functional.row_seeds`), or -- neither given, the reference's
+    ``randn_like`` -- with a draw from torch's process-wide generator."""
+    if noise_seeds is not None:
+        return Fh.sample_prior(stats, None, mask, noise_scale, seeds=noise_seeds)
+    if noise is None:
+        noise = torch.randn(stats.shape[0], C, stats.shape[2], dtype=torch.float32, device=stats.device)
+    return Fh.sample_prior(stats, noise, mask, noise_scale)
 
 
 class AMPBlock1(nn.Module):
@@ -478,32 +488,34 @@ class SynthesizerTrn(nn.Module):
         return _finalize(self, device, materialize)
 
     # ---------------------------------------------------------------- inference
-    def _prior(self, w2v, f0, y_mask, g, noise, noise_scale):
+    def _prior(self, w2v, f0, y_mask, g, noise, noise_scale, noise_seeds=None):
         stats = self.enc_p_l.stats(w2v, f0, y_mask, g)
-        C = self.inter_channels
-        if noise is None:
-            noise = torch.randn(stats.shape[0], C, stats.shape[2], dtype=torch.float32, device=stats.device)
-        return Fh.sample_prior(stats, noise, y_mask, noise_scale)
+        return _sample_prior(stats, self.inter_channels, y_mask, noise, noise_seeds, noise_scale)
 
-    def _latent(self, w2v, f0, y_mask, g, noise, noise_scale, lengths=None):
+    def _latent(self, w2v, f0, y_mask, g, noise, noise_scale, lengths=None, noise_seeds=None):
         """prior sample -> both reversed flows.  Everything here works on 50 Hz frames (a few
         hundred columns per utterance): ~250 small, latency-bound launches.  Utterances are
         independent, so the batch is cut into FRONT_SPLITS groups issued on separate streams;
         their launches overlap on the GPU instead of each one draining the chip.
         ``lengths`` (device int64 [B], row-exact mode): w2v and f0 are zeroed past each row's end (the prior encoder's
-        stride-4 k = 9 conv reads f0 there) and the flows' attention masks the keys past it."""
+        stride-4 k = 9 conv reads f0 there) and the flows' attention masks the keys past it.
+        ``noise_seeds``: the prior noise of row b is the stream of its seed (include/hsp.h "seeded prior noise"), drawn
+        inside each group's prior launch from that group's slice of the seeds; no [B, 192, T] tensor exists."""
         B = w2v.shape[0]
         n = min(FRONT_SPLITS, B)
+        if noise_seeds is not None:
+            noise_seeds = Fh.row_seeds(noise_seeds, B, w2v.device)
         if lengths is not None:
             w2v = Fh.mask_mul(w2v, y_mask)
             f0 = Fh.mask_mul(f0, Fh.sequence_mask(4 * lengths, f0.shape[2]))
         kl = (lambda lo, hi: None) if lengths is None else (lambda lo, hi: lengths[lo:hi])
         if n <= 1:
-            z = self._prior(w2v, f0, y_mask, g, noise, noise_scale)
+            z = self._prior(w2v, f0, y_mask, g, noise, noise_scale, noise_seeds)
             return self.flow(self.flow_l(z, y_mask, g=g, reverse=True, owned=True, key_len=kl(0, B)), y_mask, g=g,
                              reverse=True, owned=True, key_len=kl(0, B))
-        if noise is None:
+        if noise is None and noise_seeds is None:
             noise = torch.randn(B, self.inter_channels, w2v.shape[2], dtype=torch.float32, device=w2v.device)
+        cut = lambda x, lo, hi: None if x is None else x[lo:hi]  # noqa: E731
         main = torch.cuda.current_stream(w2v.device)
         side = [main] * (n - 1) if SERIAL_STREAMS else _side_streams(w2v.device, n - 1)
         fork = torch.cuda.Event()
@@ -516,7 +528,8 @@ class SynthesizerTrn(nn.Module):
             with torch.cuda.stream(st):
                 if i > 0 and st is not main:
                     st.wait_event(fork)
-                zi = self._prior(w2v[lo:hi], f0[lo:hi], y_mask[lo:hi], g[lo:hi], noise[lo:hi], noise_scale)
+                zi = self._prior(w2v[lo:hi], f0[lo:hi], y_mask[lo:hi], g[lo:hi], cut(noise, lo, hi), noise_scale,
+                                 cut(noise_seeds, lo, hi))
                 zi = self.flow_l(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True, key_len=kl(lo, hi))
                 zi = self.flow(zi, y_mask[lo:hi], g=g[lo:hi], reverse=True, owned=True, key_len=kl(lo, hi))
                 z[lo:hi].copy_(zi)
@@ -549,29 +562,37 @@ class SynthesizerTrn(nn.Module):
 
     @_entry
     @torch.no_grad()
-    def infer(self, x_mel, w2v, length, f0, noise: Optional[torch.Tensor] = None, row_exact: bool = False):
+    def infer(self, x_mel, w2v, length, f0, noise: Optional[torch.Tensor] = None, row_exact: bool = False,
+              noise_seeds=None):
         """:635-651 -> (o [B,1,320T], e_ [B,1,4T]).  ``noise`` ([B,192,T]) replaces the
         randn_like draw of :202 for reproducible parity runs.  ``row_exact`` (ragged batches): row b
         equals this call on row b alone (its inputs cut to length[b] frames, noise[b:b+1, :, :length[b]]), zero past
-        320 length[b]; ``length`` counts w2v frames and is also the prompt mel's length, as in the reference."""
+        320 length[b]; ``length`` counts w2v frames and is also the prompt mel's length, as in the reference.
+        ``noise_seeds`` (an int s: row b draws with s + b; or an int64 [B] tensor, read in place on the device; excludes
+        ``noise``): the draw is the seeded stream of include/hsp.h "seeded prior noise", a function of (seed, channel,
+        frame) alone -- the call with ``noise=functional.randn_rows(seeds, 192, T)`` bit for bit, without that tensor;
+        with ``row_exact`` the solo call on row b takes ``noise_seeds=seeds[b:b+1]`` (or the int s + b)."""
+        Fh.check_noise_seeds(noise, noise_seeds)
         lengths = _row_exact_lengths(row_exact, length, w2v.shape[2], w2v.device)
         x_mask = commons.sequence_mask(length, x_mel.size(2))
         g = self.emb_g(x_mel, x_mask, per_utterance=row_exact).unsqueeze(-1)
-        z = self._latent(w2v, f0, x_mask, g, noise, 1.0, lengths=lengths)
+        z = self._latent(w2v, f0, x_mask, g, noise, 1.0, lengths=lengths, noise_seeds=noise_seeds)
         return self._decode(z, g, lengths)
 
     @_entry
     @torch.no_grad()
     def voice_conversion(self, src, src_length, trg_mel, trg_length, f0, noise_scale=0.333, uncond=False,
-                         noise: Optional[torch.Tensor] = None, row_exact: bool = False):
+                         noise: Optional[torch.Tensor] = None, row_exact: bool = False, noise_seeds=None):
         """:652-673.  ``uncond`` (a model built with cfg=True): the source network and the generator are conditioned
         on the null embedding ``emb(0) * sqrt(256)`` instead of the prompt's style vector (:669-671); the prior encoder
-        and the flows still see the prompt.  ``row_exact``: as for ``infer`` (row b = the call on row b alone)."""
+        and the flows still see the prompt.  ``row_exact`` / ``noise_seeds``: as for ``infer`` (row b = the call on
+        row b alone; the seeded draw instead of ``noise``)."""
+        Fh.check_noise_seeds(noise, noise_seeds)
         lengths = _row_exact_lengths(row_exact, src_length, src.shape[2], src.device)
         trg_mask = commons.sequence_mask(trg_length, trg_mel.size(2))
         g = self.emb_g(trg_mel, trg_mask, per_utterance=row_exact).unsqueeze(-1)
         y_mask = commons.sequence_mask(src_length, src.size(2))
-        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths)
+        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths, noise_seeds=noise_seeds)
         if uncond:
             g = self._null_g(src.shape[0])
         return self._decode(z, g, lengths)[0]
@@ -598,14 +619,16 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def voice_conversion_noise_control(self, src, src_length, trg_mel, trg_length, f0, noise_scale=0.333,
                                        uncond=False, denoise_ratio=0, noise: Optional[torch.Tensor] = None,
-                                       style: Optional[torch.Tensor] = None, row_exact: bool = False):
+                                       style: Optional[torch.Tensor] = None, row_exact: bool = False,
+                                       noise_seeds=None):
         """:674-699.  trg_mel holds two prompts (original, denoised); their style vectors
         are interpolated with ``denoise_ratio`` (B = 1 by construction in the reference, SURVEY.md
         App. B1).  With B source utterances trg_mel is [2B, 80, T]: the B prompts, then the B denoised
         prompts, and f0 is [B, 1, 4T].  ``style`` [B, 256, 1]: that interpolated style vector, precomputed
         (inference_vc.vc_batch takes it per distinct prompt at the prompt's own length); emb_g and the
         interpolation are skipped and trg_mel / trg_length are not read.  ``row_exact``: as for ``infer`` (row b = the
-        call on row b alone with the same prompt pair)."""
+        call on row b alone with the same prompt pair).  ``noise_seeds``: as for ``infer`` (excludes ``noise``)."""
+        Fh.check_noise_seeds(noise, noise_seeds)
         if uncond and not self.cfg:   # the reference evaluates self.emb here (:693-695) and then does not use the result
             raise AttributeError("'SynthesizerTrn' object has no attribute 'emb' (uncond needs a model built with cfg=True)")
         B = src.shape[0]
@@ -619,7 +642,7 @@ class SynthesizerTrn(nn.Module):
             # inside the pair -- the B = 1 call on the same trg_mel rows)
             g = self.style_vector(trg_mel, trg_length, denoise_ratio)
         y_mask = commons.sequence_mask(src_length, src.size(2))
-        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths)
+        z = self._latent(src, _f0_3d(f0), y_mask, g, noise, noise_scale, lengths=lengths, noise_seeds=noise_seeds)
         return self._decode(z, g, lengths)[0]
 
 

@@ -173,7 +173,7 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
         prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0,
         lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, row_exact: bool = False,
-        style=None):
+        style=None, noise_seeds=None):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and
     ``seeds`` make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
     ``plm_causal``: the prosody LM decodes under the causal mask it is trained with, through a K/V cache
@@ -198,22 +198,26 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     ``infer`` does (equal-length batches are exact).  ``row_exact`` (B > 1): the vocoder and SpeechSR run every row as
     at B = 1 too, so row b of a ragged batch equals the call on row b alone; `row_exact_refusal`
     applies.  ``style`` [B, 256, 1]: the vocoder's style vectors, precomputed per prompt at the prompt's own length
-    (``voc.style_vector``); ``src_mel`` / ``src_length2`` are not read then.  ``gain`` may be a device fp32 [B] tensor."""
+    (``voc.style_vector``); ``src_mel`` / ``src_length2`` are not read then.  ``gain`` may be a device fp32 [B] tensor.
+    ``noise_seeds`` (an int s: row b draws with s + b; or an int64 [B] tensor; excludes ``noise``): the vocoder's prior
+    noise is the seeded stream of include/hsp.h "seeded prior noise", so the waveform is a function of (weights, inputs,
+    seeds) alone; None: ``noise``, or a draw from torch's process-wide generator."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    Fh.check_noise_seeds(noise, noise_seeds, None if noise_seeds is None else text.shape[0])
     if plm_prefix is not None and not plm_causal:
         raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
     wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel,
                                     src_length2, noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage, gain,
                                     plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths,
-                                    row_exact, style)
+                                    row_exact, style, noise_seeds)
     return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
 
 
 def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
          noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage: OutputStage, gain, plm_sampling, seeds,
-         plm_causal, plm_prefix, prosody_codes, prosody_lengths, row_exact=False, style=None):
+         plm_causal, plm_prefix, prosody_codes, prosody_lengths, row_exact=False, style=None, noise_seeds=None):
     """`tts` behind its argument checks -> (wav, audio, stats or None, codes)."""
     B = text.shape[0]
     x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
@@ -228,7 +232,7 @@ def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_len
         codes = fit_prosody_codes(prosody_codes.to(x_frame.device), src, torch.ceil(x_lengths).to(torch.int64),
                                   width=x_frame.shape[2])
     return (*_tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc,
-                             denoise_ratio, output_sr, noise, stage, gain, row_exact, style), codes)
+                             denoise_ratio, output_sr, noise, stage, gain, row_exact, style, noise_seeds), codes)
 
 
 @torch.no_grad()
@@ -236,20 +240,22 @@ def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_
                    noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
                    return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0,
                    limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
-                   return_stats: bool = False, row_exact: bool = False, style=None):
+                   return_stats: bool = False, row_exact: bool = False, style=None, noise_seeds=None):
     """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
     ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode.
     ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`; the stats dict is the last
-    result.  ``row_exact`` / ``style``: as for `tts`."""
+    result.  ``row_exact`` / ``style`` / ``noise_seeds``: as for `tts`."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    Fh.check_noise_seeds(noise, noise_seeds, None if noise_seeds is None else x_frame.shape[0])
     wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
-                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact, style)
+                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact, style,
+                                        noise_seeds)
     return pack(wav, (audio, return_float), (stats, return_stats))
 
 
 def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc, denoise_ratio,
-                    output_sr, noise, stage: OutputStage, gain, row_exact=False, style=None):
+                    output_sr, noise, stage: OutputStage, gain, row_exact=False, style=None, noise_seeds=None):
     """`tts_from_codes` behind its argument check -> (wav, audio, stats or None)."""
     B = x_frame.shape[0]
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
@@ -259,13 +265,14 @@ def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_l
         src_length = torch.full((1,), T2, dtype=torch.int64, device=w2v_x.device)   # :163 the whole padded length
         audio = models.voc.voice_conversion_noise_control(w2v_x, src_length, src_mel, src_length2, pitch,
                                                           noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
-                                                          noise=noise, style=style)
+                                                          noise=noise, style=style, noise_seeds=noise_seeds)
         n_valid = None
     else:
         frames = torch.ceil(x_lengths).to(torch.int64)
         audio = models.voc.voice_conversion_noise_control(w2v_x, frames, src_mel, src_length2, pitch.unsqueeze(1),
                                                           noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
-                                                          noise=noise, style=style, row_exact=row_exact)
+                                                          noise=noise, style=style, row_exact=row_exact,
+                                                          noise_seeds=noise_seeds)
         n_valid = frames * 320
     if output_sr in (24000, 48000):
         if row_exact and B > 1:        # SpeechSR on the ragged rows, each as on its own (as inference_vc.vc_batch)
@@ -289,7 +296,7 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
                     return_codes: bool = False, prosody_codes=None, prosody_lengths=None, limiter: bool = False,
                     ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
-                    return_stats: bool = False):
+                    return_stats: bool = False, noise_seed: Optional[int] = None):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -304,6 +311,10 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     (each take equals the solo call with that seed: the rows of a batch are independent and have one length, since the
     durations do not depend on the codes); returns int16 [N, n_out] and writes ``<stem>_take<k><ext>``.  An explicit
     ``noise`` with one row is used by every take; None: every take draws its own.
+    ``noise_seed`` (an int; excludes ``noise``): the vocoder's prior noise is the seeded stream of that seed (`tts`),
+    take k drawing with ``noise_seed + k`` -- so with ``seed`` and ``noise_seed`` a take is reproducible down to the
+    waveform, and take k equals the solo call with ``seed + k`` and ``noise_seed + k``.  None: drawn from torch's
+    process-wide generator, another waveform on every call.
     ``plm_prefix`` (int64 [P] or [1, P], needs ``plm_causal``): the first P prosody codes are given (see `tts`); with
     ``takes`` = N the one prefix is shared by all N takes: N different endings of one beginning.  ``return_codes``
     appends the PLM codes (int64 [T], or [N, T] with takes) to the result.
@@ -316,6 +327,9 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     takes = int(takes)
     if takes < 1:
         raise L.HspError(f"takes must be >= 1, got {takes}")
+    if isinstance(noise_seed, torch.Tensor):
+        raise L.HspError("noise_seed is one int (take k draws with noise_seed + k)")
+    Fh.check_noise_seeds(noise, noise_seed, what="noise_seed")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal, takes)
     if prosody_codes is not None:
         prosody_codes = prosody_codes.reshape(1, -1)
@@ -350,7 +364,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     seeds = int(seed) if plm_sampling is not None else None
     wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel,
                                     src_length2, noise_scale_vc, float(denoise_ratio), output_sr, dur, noise, stage,
-                                    gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths)
+                                    gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths,
+                                    noise_seeds=noise_seed)
     if B == 1:
         wav, codes = wav[0], codes[0]
         if output_path is not None:
@@ -369,9 +384,10 @@ def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
     ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` / ``prosody_codes`` / ``prosody_lengths`` and
-    ``kwargs`` (the fields of `output.OutputStage`, ...) go to `tts_from_prompt`."""
+    ``kwargs`` (the fields of `output.OutputStage`, ``noise`` / ``noise_seed``, ...) go to `tts_from_prompt`."""
     from . import audio as A
     OutputStage.of(kwargs).check()      # before the file is read
+    Fh.check_noise_seeds(kwargs.get("noise"), kwargs.get("noise_seed"), what="noise_seed")
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
@@ -588,7 +604,7 @@ def _plm_codes(models, x_frame, frames, plm_sampling, seeds, plm_causal, plm_pre
 def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=1.0, noise=None, noise_scale_vc=0.333,
                denoise_ratio=0.0, denoised=None, denoiser=None, hps_denoiser=None, prompt_sr=16000, output_sr=16000,
                plm_sampling=None, seeds=0, plm_causal=False, plm_prefixes=None, prosody_codes=None,
-               prosody_lengths=None, row_exact=True, int16=True, encoded=None):
+               prosody_lengths=None, row_exact=True, int16=True, encoded=None, noise_seeds=None):
     """`tts_batch` behind the check of its output stage -> (wav or None, lengths int64 [B], audio, stats or None,
     codes (a list of B), the frame counts on the host).  ``int16`` False: the int16 stage is left to the caller.
     ``encoded``: what `_encode_prompts` made of the lines' prompts (`tts_lines` encodes a page's prompts once)."""
@@ -600,6 +616,7 @@ def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=
         raise L.HspError(f"seeds must be an int or an int64 [{B}] tensor, got shape {tuple(seeds.shape)}")
     if noise is not None and (noise.dim() != 3 or noise.shape[0] != B or noise.shape[1] != 192):
         raise L.HspError(f"noise must be fp32 [{B}, 192, >= T_max], got {tuple(noise.shape)}")
+    Fh.check_noise_seeds(noise, noise_seeds, B)
     if row_exact and B > 1:
         from .hierspeechpp_speechsynthesizer import row_exact_refusal
         why = row_exact_refusal()
@@ -631,7 +648,7 @@ def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=
     _stage("vocoder")
     wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, None, None, noise_scale_vc,
                                         float(denoise_ratio), output_sr, noise, stage if int16 else None,
-                                        0.999 if peaks is None else peaks, row_exact, style)
+                                        0.999 if peaks is None else peaks, row_exact, style, noise_seeds)
     _stage("end")
     lengths = output_length(torch.ceil(x_lengths).to(torch.int64), output_sr)
     return wav, lengths, audio, stats, [codes[b, :frames[b]] for b in range(B)], frames
@@ -651,6 +668,8 @@ def tts_batch(models: TtsModels, mel_fn, lines, prompts, *, return_float: bool =
     dur      a list of B [N_b] pinned durations, None: predicted (``length_scale``: the speaking rate, as
              ``inf_extract_tc_latent`` takes it);
     noise    fp32 [B, 192, >= T_max] (columns past the longest line's frames are ignored), None: drawn;
+    noise_seeds  an int s (line b draws its prior noise with s + b) or an int64 [B] tensor, instead of ``noise``: the
+             seeded stream of `tts`, so row b equals ``tts_from_prompt(noise_seed=s + b)`` and no noise tensor exists;
     denoise_ratio, denoised / denoiser / hps_denoiser  as `inference_vc.vc_batch`: the denoised prompts in the form
              of ``prompts``, or the denoiser that makes them in one packed pass (``denoise_prompts``);
     plm_sampling, seeds  sampled prosody codes; ``seeds`` an int s (line b draws with s + b) or an int64 [B] tensor;
@@ -675,15 +694,27 @@ def _take(arg, rows):
     return None if arg is None else [arg[k] for k in rows]
 
 
+def _line_seeds(seeds, N: int, what: str):
+    """The per-line seeds int64 [N] of a page (``seeds`` / ``noise_seeds`` alike): an int s gives the caller's line k
+    the seed s + k; a tensor [N] holds one per line.  `tts_lines` slices them per chunk."""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.shape != (N,):
+            raise L.HspError(f"{what} must be an int or an int64 [{N}] tensor, got shape {tuple(seeds.shape)}")
+        return seeds.to(torch.int64)
+    return torch.arange(int(seeds), int(seeds) + N, dtype=torch.int64)
+
+
 @torch.no_grad()
 def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16, join: bool = False,
               pause_ms: float = 300.0, return_float: bool = False, return_codes: bool = False, dur=None, noise=None,
-              seeds=0, plm_prefixes=None, prosody_codes=None, prosody_lengths=None, denoised=None, **kw):
+              seeds=0, plm_prefixes=None, prosody_codes=None, prosody_lengths=None, denoised=None, noise_seeds=None,
+              **kw):
     """Any number of lines: sorted by phone count, cut into chunks of at most ``max_batch`` (`line_chunks`), one
-    `tts_batch` per chunk (the per-line keywords ``dur``, ``noise`` rows, ``seeds``, ``plm_prefixes``,
-    ``prosody_codes`` / ``prosody_lengths`` sliced per chunk; an int ``seeds`` = s gives the caller's line k the seed
-    s + k), results in the caller's order.  Every distinct prompt of the page is encoded, and with a denoiser denoised,
-    once per call, whatever chunks its lines fall into.  Other keywords go to `tts_batch`.
+    `tts_batch` per chunk (the per-line keywords ``dur``, ``noise`` rows, ``seeds``, ``noise_seeds``, ``plm_prefixes``,
+    ``prosody_codes`` / ``prosody_lengths`` sliced per chunk; an int ``seeds`` / ``noise_seeds`` = s gives the caller's
+    line k the seed s + k whatever chunk it lands in), results in the caller's order.  Every distinct prompt of the
+    page is encoded, and with a denoiser denoised, once per call, whatever chunks its lines fall into.  Other keywords
+    go to `tts_batch`.
 
     ``join`` False: a list of N int16 rows [n_k]; then, where asked, the float rows (a list of [n_k]), the stats (a
     dict of [N] tensors) and the codes (a list).  ``join`` True: one programme, int16 [n]: the float rows concatenated
@@ -705,12 +736,9 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
     _check_denoiser(kw.get("denoise_ratio", 0.0), denoised, kw.get("denoiser"), kw.get("hps_denoiser"), "tts_lines")
     from .inference_vc import output_length
     N, output_sr = len(lines), kw.get("output_sr", 16000)
-    if isinstance(seeds, torch.Tensor):
-        if seeds.shape != (N,):
-            raise L.HspError(f"seeds must be an int or an int64 [{N}] tensor, got shape {tuple(seeds.shape)}")
-        line_seeds = seeds.to(torch.int64)
-    else:
-        line_seeds = torch.arange(int(seeds), int(seeds) + N, dtype=torch.int64)
+    Fh.check_noise_seeds(noise, noise_seeds, N)
+    line_seeds = _line_seeds(seeds, N, "seeds")
+    line_noise_seeds = None if noise_seeds is None else _line_seeds(noise_seeds, N, "noise_seeds")
     dev = lines[0][0].device
     chunks = line_chunks(counts, max_batch)
     per_prompt = isinstance(prompts, (list, tuple)) and len(prompts) == N and N > 1
@@ -724,7 +752,9 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
         wav, _, audio, stats, cds, frames = _tts_batch(
             models, mel_fn, [lines[k] for k in rows], _take(prompts, rows) if per_prompt else prompts,
             stage, dur=_take(dur, rows), noise=None if noise is None else noise[idx.to(noise.device)],
-            seeds=line_seeds[idx.to(line_seeds.device)].to(dev), plm_prefixes=_take(plm_prefixes, rows),
+            seeds=line_seeds[idx.to(line_seeds.device)].to(dev),
+            noise_seeds=None if line_noise_seeds is None else line_noise_seeds[idx.to(line_noise_seeds.device)].to(dev),
+            plm_prefixes=_take(plm_prefixes, rows),
             prosody_codes=_take(prosody_codes, rows), prosody_lengths=_take(prosody_lengths, rows),
             denoised=_take(denoised, rows) if per_denoised else denoised, int16=not join,
             encoded=(encoded, [index[k] for k in rows]), **kw)
@@ -757,7 +787,8 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
 def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None, names=None, device=None, **kw):
     """`tts_lines` from prompt FILES: ``prompt_paths`` one WAV file for every line or a list of one per line, at any
     sample rate; every distinct file is loaded once (``audio.load_16k``: channel 0, kaiser-window resampling to
-    16 kHz) and shared by the lines that name it.  Keywords ``kw`` go to `tts_lines`.  With ``out_dir`` the rows are
+    16 kHz) and shared by the lines that name it.  Keywords ``kw`` go to `tts_lines` (``noise`` rows and
+    ``noise_seeds`` are indexed by the caller's line order).  With ``out_dir`` the rows are
     written as ``<out_dir>/<names[k]>.wav`` (``names`` None: ``line_0000.wav``, ...) at the output rate, or as one
     ``programme.wav`` with ``join=True``.  Returns what `tts_lines` returns."""
     import os
@@ -766,6 +797,7 @@ def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None
     if not isinstance(lines, (list, tuple)) or not lines:
         raise L.HspError("lines must be a non-empty list of (ids, tone, language) triples")
     N = len(lines)
+    Fh.check_noise_seeds(kw.get("noise"), kw.get("noise_seeds"), N)
     per_line = isinstance(prompt_paths, (list, tuple))
     paths = [str(p) for p in prompt_paths] if per_line else [str(prompt_paths)]
     if len(paths) not in (1, N):

@@ -74,15 +74,20 @@ def load_source(path, device):
 @torch.no_grad()
 def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noise_scale_vc=0.333, denoise_ratio=0.0,
        denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000, target_lufs=-23.0,
-       limiter=False, ceiling_db=-1.0, lookahead_ms=1.5, limiter_passes=2, return_stats=False):
+       limiter=False, ceiling_db=-1.0, lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seed=None):
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``output_sr`` 24000 / 48000: SpeechSR (``models.sr``) runs after the vocoder (:147-151) -> [480 T] / [960 T].
     ``denoised_audio``: the denoiser's output for the prompt (inference_vc.py:118-121); None = the prompt itself, which
     is what the reference does at denoise_ratio == 0.  ``scale_norm`` ... ``return_stats``: the int16 stage, see
-    `output.OutputStage`; the prompt of 'prompt' is ``target_audio`` (inference_vc.py:104-105)."""
+    `output.OutputStage`; the prompt of 'prompt' is ``target_audio`` (inference_vc.py:104-105).
+    ``noise_seed`` (an int; excludes ``noise``): the vocoder's prior noise is the seeded stream of include/hsp.h "seeded
+    prior noise", so the same call gives the same waveform; None: ``noise``, or torch's process-wide generator."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    if isinstance(noise_seed, torch.Tensor):
+        raise L.HspError("noise_seed is one int")
+    Fh.check_noise_seeds(noise, noise_seed, what="noise_seed")
     gain = stage.gain(target_audio)
     x_w2v = models.w2v(Fh.reflect_pad(source_audio, 40))                       # :85-86
     T = x_w2v.shape[2]
@@ -96,7 +101,7 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     trg_len = torch.tensor([trg_mel.shape[2]] * 2, dtype=torch.int64, device=x_w2v.device)
     audio = models.voc.voice_conversion_noise_control(x_w2v, x_length, trg_mel, trg_len, lf0.reshape(1, -1)[:, :4 * T],
                                                       noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
-                                                      noise=noise)
+                                                      noise=noise, noise_seeds=noise_seed)
     if output_sr in (24000, 48000):
         audio = _sr_model(models)(audio)                                       # :147-151
     wav, stats = stage.int16(audio.reshape(1, -1), None, output_rate(output_sr), gain)
@@ -281,7 +286,7 @@ def denoise_prompts(prompts, denoiser, hps):
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
              denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
              row_exact=False, denoiser=None, hps_denoiser=None, target_lufs=-23.0, limiter=False, ceiling_db=-1.0,
-             lookahead_ms=1.5, limiter_passes=2, return_stats=False):
+             lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seeds=None):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -296,6 +301,9 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
              ``denoised``, every distinct prompt is denoised here in one packed pass (``denoise_prompts``).  Giving
              both ``denoised`` and ``denoiser``, or ``denoise_ratio != 0`` with neither, is an error;
     noise    fp32 [B, 192, T_max] (T_max = Ls / 320), None = drawn;
+    noise_seeds  an int s (row b draws its prior noise with s + b) or an int64 [B] tensor, instead of ``noise``: the
+             seeded stream of ``vc(noise_seed=)``; with ``row_exact`` row b equals ``vc`` on it alone with its seed, and
+             no noise tensor is built;
     scale_norm ... return_stats  the int16 stage, see `output.OutputStage`: every row over its own length, 'prompt'
              with the peak of the row's own prompt (taken on the device: no norm reads anything back to the host).
 
@@ -307,6 +315,8 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     alone, at 16, 24 and 48 kHz."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    if noise_seeds is not None:
+        Fh.check_noise_seeds(noise, noise_seeds, sources[0].shape[0] if isinstance(sources, tuple) else len(sources))
     voc = models.voc
     if denoised is not None and denoiser is not None:
         raise L.HspError("vc_batch: give the denoised prompts or a denoiser, not both")
@@ -389,7 +399,7 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
     _stage("vocoder")
     audio = voc.voice_conversion_noise_control(x_w2v, frames, None, None, lf0, noise_scale=noise_scale_vc,
                                                denoise_ratio=denoise_ratio, noise=noise, style=style,
-                                               row_exact=row_exact)
+                                               row_exact=row_exact, noise_seeds=noise_seeds)
     if output_sr in (24000, 48000):
         _stage("speechsr")
         if row_exact:                  # SpeechSR on the ragged rows, each as on its own (lengths at 16 kHz: 320 T_b)
@@ -414,9 +424,10 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     """The reference's per-file loop (inference_vc.py:70-170, one process call per file) as batches: every source and
     prompt WAV at any sample rate (``audio.load_16k``; sources padded by pad_source), F0 tracks from ``f0`` (a mapping
     path -> track) or else from the '.hf0.npy' file extract_f0.py writes beside each WAV (a missing track is an error
-    naming the file), ``vc_batch`` calls (keywords ``kw``; ``noise`` [B, 192, T_max] is sliced per batch; ``denoiser=``
-    and ``hps_denoiser=`` with ``denoise_ratio != 0`` denoise every distinct prompt file of a batch in one packed pass,
-    the reference harness's step :117-133), and with ``out_dir`` one '<src>_to_<trg>.wav' per row at the output rate.
+    naming the file), ``vc_batch`` calls (keywords ``kw``; ``noise`` [B, 192, T_max] and ``noise_seeds`` -- an int s:
+    source b draws with s + b; or an int64 [B] tensor -- are indexed by ``source_paths`` and sliced per batch;
+    ``denoiser=`` and ``hps_denoiser=`` with ``denoise_ratio != 0`` denoise every distinct prompt file of a batch in one
+    packed pass, the reference harness's step :117-133), and with ``out_dir`` one '<src>_to_<trg>.wav' per row at the output rate.
     ``target_paths``: one prompt file for every source, or one per source.
 
     ``group_by_length`` True: one vc_batch call per padded source length (`length_groups`), so every batch has equal
@@ -430,6 +441,7 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     from .audio import load_16k
     from .inference_plm import write_wav
     return_stats = OutputStage.of(kw).check().return_stats                  # before any file is read
+    Fh.check_noise_seeds(kw.get("noise"), kw.get("noise_seeds"), len(source_paths))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     source_paths = [str(p) for p in source_paths]
@@ -455,13 +467,17 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     f0_srcs = [track(p) for p in source_paths]
     groups = length_groups([s.shape[-1] for s in sources]) if group_by_length else [list(range(B))]
     noise = kw.pop("noise", None)
+    seeds = kw.pop("noise_seeds", None)
+    if seeds is not None:                                                   # one seed per file, whatever batch it joins
+        seeds = Fh.row_seeds(seeds, B, "cpu")
     parts, part_stats = [], []
     for rows in groups:
         T = max(sources[b].shape[-1] for b in rows) // FRAME
         nz = None if noise is None else noise[torch.tensor(rows, device=noise.device), :, :T].contiguous()
+        sd = None if seeds is None else seeds[torch.tensor(rows)]
         parts.append(vc_batch(models, mel_fn, [sources[b] for b in rows], [f0_srcs[b] for b in rows],
                               [prompts[trg_paths[b]] for b in rows], [tracks[trg_paths[b]] for b in rows], noise=nz,
-                              **kw))
+                              noise_seeds=sd, **kw))
         if return_stats:
             part_stats.append(parts[-1][2])
             parts[-1] = parts[-1][:2]

@@ -116,18 +116,7 @@ class PlmSampling:
                             L.ptr(seeds), L.fptr(probs), probs.stride(0) if probs is not None else 0)
 
 
-def plm_seeds(seeds, B: int, device) -> torch.Tensor:
-    """int64 [B] seeds on ``device``: an int s gives row b the seed s + b (one fill kernel, capturable); a tensor is used
-    as it is when it already is a contiguous int64 [B] device tensor -- so a captured loop replays with the values
-    a later ``seeds.copy_()`` put there."""
-    if isinstance(seeds, torch.Tensor):
-        if seeds.shape != (B,):
-            raise L.HspError(f"seeds must have shape ({B},), got {tuple(seeds.shape)}")
-        if seeds.dtype == torch.int64 and seeds.device == torch.device(device) and seeds.is_contiguous():
-            return seeds
-        return seeds.to(device=device, dtype=torch.int64).contiguous()
-    s = int(0 if seeds is None else seeds)
-    return torch.arange(s, s + B, dtype=torch.int64, device=device)
+plm_seeds = Fh.row_seeds   # the seed rule of the prosody LM is the one of every seed argument (functional.row_seeds)
 
 
 def session_plan(lengths, slots: int):
