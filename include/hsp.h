@@ -729,6 +729,16 @@ int hsp_lstm_bidir_f32(const float* xproj, int64_t xp_bs, const float* whh_t, co
  * zeroes the padding / sums. */
 int hsp_duration_f32(const float* logw, int64_t lw_bs, const int64_t* lengths, float length_scale, float* dur,
                      int64_t d_bs, float* frames, int32_t B, int32_t N, void* stream);
+/* hsp_duration_f32 with a scale per phone (additive: HSP_VERSION unchanged), scale fp32 [B, N] of row stride sc_bs:
+ *   dur[b, n] = ceilf((expf(logw[b, n]) * length_scale) * scale[b, n]) for n < lengths[b], from predicted log-durations;
+ *   dur[b, n] = ceilf(dur[b, n] * scale[b, n]) for caller-supplied durations (logw == NULL);
+ * zeros from lengths[b] on, frames[b] = sum_n dur[b, n].  Every product is a rounded fp32 product, formed in the order
+ * written.  With every scale equal to 1 the result is bit-identical to hsp_duration_f32 (x * 1.0f is x; supplied
+ * durations are whole frame counts, which ceilf leaves alone).  HSP_EINVAL: NULL lengths, dur, frames or scale, B < 1,
+ * N < 1, sc_bs < N. */
+int hsp_duration_scaled_f32(const float* logw, int64_t lw_bs, const int64_t* lengths, float length_scale, float* dur,
+                            int64_t d_bs, float* frames, int32_t B, int32_t N, const float* scale, int64_t sc_bs,
+                            void* stream);
 /* y[b, c, t] = max_{j < k} x[b, c, k t + j], t < L / k : nn.MaxPool1d(kernel_size = 8, stride = 8) of the legacy
  * prosody path (ttv_v1/t2w2v_transformer.py:795,1046).  y contiguous [B, C, L / k]. */
 int hsp_maxpool1d_f32(const float* x, int64_t x_bs, int64_t x_cs, float* y, int32_t B, int32_t C, int32_t L,
@@ -795,6 +805,48 @@ int hsp_zero_below_f32(const float* x, float thr, float* y, int64_t n, void* str
  * (a gain above 1) saturate.  hsp_peak_int16_gains (above) shares the row function and both rules. */
 int hsp_peak_int16(const float* x, int64_t x_bs, const int64_t* lengths, float gain, int16_t* out, int64_t o_bs,
                    int32_t B, int64_t n, void* stream);
+
+/* ------------------------------------------------ pitch edit of a log-F0 track (additive: HSP_VERSION unchanged;
+ * csrc/hsp_f0_edit.hip).  Neither harness of the reference can move the pitch of a take: the track the
+ * vocoder is given -- l = log(f0 + 1), fp32, 0 = unvoiced, 200 frames a second -- is shifted, widened or flattened
+ * about its own mean, moved to a target register and drawn over, per row, in ONE launch of one workgroup per row.
+ *
+ * Per row b: n_b = lengths[b] clamped into [0, n] (device int64 [B]; NULL = all n).  Frame i is voiced when i < n_b and
+ * l[b, i] > 0.  Frames at and after n_b are never read.  All arithmetic below is double.
+ *   p_i   = log(expm1(l_i))                                  ln Hz of a voiced frame
+ *   m_b   = mean of p_i over the voiced frames: each of the 256 threads sums its frames i = t, t + 256, ... in
+ *           ascending order, then a halving tree over the threads (128, 64, ..., 1); the voiced count likewise.  The
+ *           order depends on the row alone, so row b of a batch is bit-identical to the call on row b alone.
+ *   c_b   = log(target_hz[b]) where target_hz[b] > 0, else m_b
+ *   p'_i  = c_b + range[b] (p_i - m_b) + (shift[b] + offsets[b, i]) ln2 / 12, clamped into [log f_min, log f_max]
+ *   out[b, i] = (float) log1p(exp(p'_i)) for a voiced frame, 0 for an unvoiced one, 0 for n_b <= i < n
+ *   mean_hz[b] (may be NULL) = (float) exp(m_b): the geometric mean of the voiced frames in Hz; 0 for a row without one.
+ * shift (semitones), range, target_hz: device fp32 [B], each may be NULL = 0, 1, no target.  offsets (semitones): device
+ * fp32 [B, n] of row stride off_bs, may be NULL.
+ * Identity rule: a row with shift == 0, range == 1, no target (target_hz NULL or not > 0) and offsets == NULL is copied
+ * bit for bit over [0, n_b) -- no clamp, whatever the values -- so it takes part in a mixed batch without changing.
+ * offsets != NULL is NOT an identity row even where every offset is zero: its voiced frames go through the arithmetic
+ * above (and the clamp), and come back within one fp32 ulp, not bit for bit.
+ * out may be lf0 (same pointer and row stride).
+ * HSP_EINVAL before any HIP call: NULL a, lf0 or out, B < 1 or > 65535, n < 1, a row stride (lf0_bs, out_bs, off_bs
+ * with offsets) below n, f_min or f_max not finite, f_min <= 0, f_min >= f_max. */
+typedef struct {
+  const float* lf0;
+  int64_t lf0_bs;
+  const int64_t* lengths;
+  int32_t B;
+  int64_t n;
+  const float* shift;
+  const float* range;
+  const float* target_hz;
+  const float* offsets;
+  int64_t off_bs;
+  float f_min, f_max;
+  float* out;
+  int64_t out_bs;
+  float* mean_hz;
+} hsp_f0_edit_args;
+int hsp_f0_edit_rows_f32(const hsp_f0_edit_args* a, void* stream);
 
 /* ------------------------------------------------ loudness-normalised output (additive: HSP_VERSION unchanged;
  * csrc/hsp_loudness.hip).  Neither harness of the reference has a loudness rule: scale_norm="lufs" of

@@ -152,6 +152,15 @@ class LimiterArgs(C.Structure):
     ]
 
 
+class F0EditArgs(C.Structure):
+    """Mirror of ``hsp_f0_edit_args``."""
+    _fields_ = [
+        ("lf0", _fp), ("lf0_bs", C.c_int64), ("lengths", _fp), ("B", C.c_int32), ("n", C.c_int64),
+        ("shift", _fp), ("range", _fp), ("target_hz", _fp), ("offsets", _fp), ("off_bs", C.c_int64),
+        ("f_min", C.c_float), ("f_max", C.c_float), ("out", _fp), ("out_bs", C.c_int64), ("mean_hz", _fp),
+    ]
+
+
 WSPEC_BLOCK, WSPEC_THREE = 0, 1
 
 
@@ -219,6 +228,8 @@ SIGNATURES = {
     "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_int32, _fp]),
     "hsp_duration_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp]),
+    "hsp_duration_scaled_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp,
+                                          C.c_int64, _fp]),
     "hsp_gaussian_upsample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp,
                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_act_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int32, _fp]),
@@ -253,6 +264,7 @@ SIGNATURES = {
     "hsp_add_cbias_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
     "hsp_zero_below_f32": (C.c_int, [_fp, C.c_float, _fp, C.c_int64, _fp]),
     "hsp_peak_int16": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
+    "hsp_f0_edit_rows_f32": (C.c_int, [C.POINTER(F0EditArgs), _fp]),
     "hsp_loudness_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
     "hsp_loudness_coefs_f64": (C.c_int, [C.c_int32, _fp]),
     "hsp_loudness_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp]),

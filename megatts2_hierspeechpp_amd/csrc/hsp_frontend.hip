@@ -85,8 +85,12 @@ __global__ __launch_bounds__(1024) void lstm_bidir_kernel(const float* __restric
 
 // dur[b, n] = n < len[b] ? ceil(exp(logw[b, n]) * length_scale) : 0 ; frames[b] = sum_n dur[b, n]
 // (t2w2v_transformer.py:955-957,972-975).  One workgroup per utterance.
+// SCALED (hsp_duration_scaled_f32): the value is multiplied by scale[b, n] before the ceil, and given durations are
+// scaled and rounded up as well; x * 1.0f is x, so scales of 1 give the bits of the unscaled kernel.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void duration_kernel(const float* __restrict__ logw, int64_t lw_bs,
                                                        const int64_t* __restrict__ len, float length_scale,
+                                                       const float* __restrict__ scale, int64_t sc_bs,
                                                        float* __restrict__ dur, int64_t d_bs, float* __restrict__ frames,
                                                        int N, int from_logw) {
   __shared__ float red[4];
@@ -95,8 +99,13 @@ __global__ __launch_bounds__(256) void duration_kernel(const float* __restrict__
   float s = 0.0f;
   for (int n = tid; n < N; n += 256) {
     float d;
-    if (from_logw) d = n < L ? ceilf(expf(logw[b * lw_bs + n]) * length_scale) : 0.0f;
-    else d = n < L ? dur[b * d_bs + n] : 0.0f;   // caller-supplied durations: only clear the padding
+    if (SCALED) {
+      if (from_logw) d = n < L ? ceilf((expf(logw[b * lw_bs + n]) * length_scale) * scale[b * sc_bs + n]) : 0.0f;
+      else d = n < L ? ceilf(dur[b * d_bs + n] * scale[b * sc_bs + n]) : 0.0f;
+    } else {
+      if (from_logw) d = n < L ? ceilf(expf(logw[b * lw_bs + n]) * length_scale) : 0.0f;
+      else d = n < L ? dur[b * d_bs + n] : 0.0f;   // caller-supplied durations: only clear the padding
+    }
     dur[b * d_bs + n] = d;
     s += d;
   }
@@ -289,8 +298,17 @@ extern "C" int hsp_lstm_bidir_f32(const float* xproj, int64_t xp_bs, const float
 extern "C" int hsp_duration_f32(const float* logw, int64_t lw_bs, const int64_t* lengths, float length_scale, float* dur,
                                 int64_t d_bs, float* frames, int32_t B, int32_t N, void* stream) {
   if (!lengths || !dur || !frames || B <= 0 || N <= 0) return HSP_EINVAL;
-  hipLaunchKernelGGL(duration_kernel, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logw, lw_bs, lengths, length_scale,
-                     dur, d_bs, frames, N, logw ? 1 : 0);
+  hipLaunchKernelGGL(duration_kernel<false>, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logw, lw_bs, lengths,
+                     length_scale, (const float*)nullptr, (int64_t)0, dur, d_bs, frames, N, logw ? 1 : 0);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hsp_duration_scaled_f32(const float* logw, int64_t lw_bs, const int64_t* lengths, float length_scale,
+                                       float* dur, int64_t d_bs, float* frames, int32_t B, int32_t N, const float* scale,
+                                       int64_t sc_bs, void* stream) {
+  if (!lengths || !dur || !frames || !scale || B <= 0 || N <= 0 || sc_bs < N) return HSP_EINVAL;
+  hipLaunchKernelGGL(duration_kernel<true>, dim3((unsigned)B), dim3(256), 0, HSP_STREAM, logw, lw_bs, lengths, length_scale,
+                     scale, sc_bs, dur, d_bs, frames, N, logw ? 1 : 0);
   return (int)hipGetLastError();
 }
 

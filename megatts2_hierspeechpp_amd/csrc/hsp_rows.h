@@ -1,6 +1,7 @@
 // Row helpers of the pointwise, framing and row-glue kernels: what "row b of a ragged or packed batch" means, stated
-// once for hsp_pointwise.hip, hsp_mel.hip, hsp_vcbatch.hip, hsp_denoiser.hip, hsp_frontend.hip and hsp_loudness.hip.
-// The block sums of those files (dn_block_sum, block_sum_256, the reduction inside hsp_f0_convert_row) are NOT here: they
+// once for hsp_pointwise.hip, hsp_mel.hip, hsp_vcbatch.hip, hsp_denoiser.hip, hsp_frontend.hip, hsp_loudness.hip and
+// hsp_f0_edit.hip.
+// The block sums of those files (dn_block_sum, block_sum_256, the reductions inside hsp_f0_convert_row and f0_edit_rows_kernel) are NOT here: they
 // add in different orders, so one shared sum would change result bits.
 #pragma once
 #include "hsp_device.h"

@@ -353,6 +353,37 @@ def f0_convert(f0_src, f0_trg):
     return out.reshape(f0_src.shape)
 
 
+def f0_edit(lf0, lengths=None, shift=None, range=None, target_hz=None, offsets=None, f_min: float = 55.0,
+            f_max: float = 1100.0, out=None, return_mean: bool = False):
+    """The pitch edit of include/hsp.h (hsp_f0_edit_rows_f32) on the rows of ``lf0`` fp32 [B, n] (log(f0 + 1), 0 =
+    unvoiced; unit stride in time, any row stride), row b over ``lengths[b]`` frames (device int64 [B]; None: all n):
+    ``shift`` (semitones), ``range``, ``target_hz`` device fp32 [B] or None (0, 1, no target), ``offsets`` (semitones)
+    device fp32 [B, n] or None.  One launch.  -> the edited track [B, n] (``out``: written there; it may be ``lf0``),
+    zeros from a row's length on; with ``return_mean`` also mean_hz fp32 [B], the geometric mean of every row's voiced
+    frames in Hz BEFORE the edit (0 for a row without one).  `prosody_controls.PitchEdit` is the validated form."""
+    if lf0.dim() != 2 or lf0.stride(1) != 1:
+        raise L.HspError(f"f0_edit takes lf0 as fp32 [B, n] with unit stride in time, got {tuple(lf0.shape)}")
+    B, n = lf0.shape
+    out = torch.empty(B, n, dtype=torch.float32, device=lf0.device) if out is None else out
+    if out.shape != lf0.shape or out.stride(1) != 1:
+        raise L.HspError(f"f0_edit: out must be fp32 {tuple(lf0.shape)} with unit stride in time")
+    for name, v in (("shift", shift), ("range", range), ("target_hz", target_hz)):
+        if v is not None and (v.shape != (B,) or not v.is_contiguous()):
+            raise L.HspError(f"f0_edit: {name} must be a contiguous fp32 [{B}] tensor, got {tuple(v.shape)}")
+    if offsets is not None and (offsets.shape != lf0.shape or offsets.stride(1) != 1):
+        raise L.HspError(f"f0_edit: offsets must be fp32 {tuple(lf0.shape)} with unit stride in time, got "
+                         f"{tuple(offsets.shape)}")
+    mean = torch.empty(B, dtype=torch.float32, device=lf0.device) if return_mean else None
+    a = L.F0EditArgs()
+    a.lf0, a.lf0_bs, a.lengths, a.B, a.n = L.fptr(lf0), lf0.stride(0) if B > 1 else n, L.ptr(_lengths(lengths)), B, n
+    a.shift, a.range, a.target_hz = L.fptr(shift), L.fptr(range), L.fptr(target_hz)
+    a.offsets, a.off_bs = L.fptr(offsets), 0 if offsets is None else (offsets.stride(0) if B > 1 else n)
+    a.f_min, a.f_max = float(f_min), float(f_max)
+    a.out, a.out_bs, a.mean_hz = L.fptr(out), out.stride(0) if B > 1 else n, L.fptr(mean)
+    L.call("hsp_f0_edit_rows_f32", C.byref(a))
+    return (out, mean) if return_mean else out
+
+
 # --------------------------------------------------------- batched voice conversion (ragged rows, device lengths)
 def reflect_pad_ragged(x, lengths, pad: int):
     """Row b of x [B, L] -> F.pad(x[b, :lengths[b]], (pad, pad), "reflect"), zero after lengths[b] + 2 pad:

@@ -22,6 +22,7 @@ from torch import nn
 from . import _lib as L
 from . import functional as Fh
 from . import hip_layers
+from . import prosody_controls as PC
 from .hierspeechpp_speechsynthesizer import SynthesizerTrn
 from .hip_layers import finalize as _finalize
 from .output import SCALE_NORMS, OutputStage, output_rate, pack, prompt_peak  # noqa: F401  (re-exported names)
@@ -173,7 +174,8 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
         target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None, return_codes: bool = False,
         prosody_codes=None, prosody_lengths=None, limiter: bool = False, ceiling_db: float = -1.0,
         lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, row_exact: bool = False,
-        style=None, noise_seeds=None):
+        style=None, noise_seeds=None, pitch=None, lf0=None, return_lf0: bool = False, length_scale=1.0,
+        phone_scale=None):
     """inference_plm.py:tts :156-190 on tensors.  ``plm_sampling`` (a ttv_v1.t2w2v_transformer.PlmSampling) and
     ``seeds`` make the prosody LM sample its codes (``Megatts2PLM1.infer``); None: greedy, as the reference.
     ``plm_causal``: the prosody LM decodes under the causal mask it is trained with, through a K/V cache
@@ -201,27 +203,57 @@ def tts(models: TtsModels, text, text_length, tone, language, src_mel_ttv, src_m
     (``voc.style_vector``); ``src_mel`` / ``src_length2`` are not read then.  ``gain`` may be a device fp32 [B] tensor.
     ``noise_seeds`` (an int s: row b draws with s + b; or an int64 [B] tensor; excludes ``noise``): the vocoder's prior
     noise is the seeded stream of include/hsp.h "seeded prior noise", so the waveform is a function of (weights, inputs,
-    seeds) alone; None: ``noise``, or a draw from torch's process-wide generator."""
+    seeds) alone; None: ``noise``, or a draw from torch's process-wide generator.
+    Prosody controls (all off by default, and then no launch is added):
+    ``pitch`` (a `prosody_controls.PitchEdit`): the log-F0 track the vocoder is given -- the pitch predictor's, clipped
+    below 55 Hz (:166) -- is edited over every row's own 4 * frames (one launch; None or an identity edit: none).
+    ``lf0`` (fp32 [B, 4 * T2]): replaces the predicted track; durations do not depend on codes or pitch, so a track
+    read from an earlier take of the same text, prompt and scales fits frame for frame; ``pitch`` then edits it.
+    ``return_lf0``: the track the vocoder was given, fp32 [B, 4 * T2], is the last result, after the codes.
+    ``length_scale`` (a float or a [B] sequence) and ``phone_scale`` (a list of B rows of text_length[b] factors, or
+    None; reads ``text_length`` back): the pace of a row and of its phones, each in [0.25, 4]
+    (`prosody_controls.check_scales`); given durations ``dur`` are scaled by ``phone_scale`` alone."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
     Fh.check_noise_seeds(noise, noise_seeds, None if noise_seeds is None else text.shape[0])
     if plm_prefix is not None and not plm_causal:
         raise L.HspError("plm_prefix needs plm_causal=True: only the causal decoder can continue from given codes")
     _check_given_prosody(prosody_codes, prosody_lengths, plm_sampling, plm_prefix, plm_causal)
-    wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel,
-                                    src_length2, noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage, gain,
-                                    plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths,
-                                    row_exact, style, noise_seeds)
-    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
+    pitch = PC.check_pitch(pitch, text.shape[0])
+    length_scale, scale = PC.check_scales(
+        length_scale, phone_scale, [text.shape[1]] * text.shape[0] if phone_scale is None else text_length.tolist(),
+        dur is not None)
+    wav, audio, stats, codes, track = _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length,
+                                           src_mel, src_length2, noise_scale_vc, denoise_ratio, output_sr, dur, noise,
+                                           stage, gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes,
+                                           prosody_lengths, row_exact, style, noise_seeds, pitch, lf0, length_scale,
+                                           scale)
+    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes), (track, return_lf0))
+
+
+def _front(models, text, text_length, src_mel_ttv, src_mel_ttv_length, tone, language, dur, length_scale, scale, **kw):
+    """``inf_extract_tc_latent`` as the harnesses call it: without pace controls (``length_scale`` 1.0 and no ``scale``,
+    the float32 [B, N] numpy array of `prosody_controls.check_scales`) the call there has always been."""
+    if scale is not None:
+        width = text.shape[1]
+        if scale.shape[1] < width:      # a padded batch wider than its longest line
+            import numpy as np
+            scale = np.pad(scale, ((0, 0), (0, width - scale.shape[1])), constant_values=1.0)
+        kw["phone_scale"] = torch.from_numpy(scale[:, :width].copy()).to(text.device)
+    if length_scale != 1.0:
+        kw["length_scale"] = length_scale
+    return models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length, tone, language, dur=dur,
+                                            **kw)
 
 
 def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_length, src_mel, src_length2,
          noise_scale_vc, denoise_ratio, output_sr, dur, noise, stage: OutputStage, gain, plm_sampling, seeds,
-         plm_causal, plm_prefix, prosody_codes, prosody_lengths, row_exact=False, style=None, noise_seeds=None):
-    """`tts` behind its argument checks -> (wav, audio, stats or None, codes)."""
+         plm_causal, plm_prefix, prosody_codes, prosody_lengths, row_exact=False, style=None, noise_seeds=None,
+         pitch=None, lf0=None, length_scale=1.0, scale=None):
+    """`tts` behind its argument checks -> (wav, audio, stats or None, codes, the vocoder's log-F0 track)."""
     B = text.shape[0]
-    x_frame, g, x_lengths, x_mask = models.ttv.inf_extract_tc_latent(text, text_length, src_mel_ttv, src_mel_ttv_length,
-                                                                     tone, language, dur=dur)
+    x_frame, g, x_lengths, x_mask = _front(models, text, text_length, src_mel_ttv, src_mel_ttv_length, tone, language,
+                                           dur, length_scale, scale)
     if prosody_codes is None:
         codes = models.plm.infer(x_frame, sampling=plm_sampling, seeds=seeds, causal=plm_causal,
                                  prefix_codes=plm_prefix)
@@ -231,8 +263,10 @@ def _tts(models, text, text_length, tone, language, src_mel_ttv, src_mel_ttv_len
         src = prosody_codes.shape[1] if prosody_lengths is None else prosody_lengths
         codes = fit_prosody_codes(prosody_codes.to(x_frame.device), src, torch.ceil(x_lengths).to(torch.int64),
                                   width=x_frame.shape[2])
-    return (*_tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc,
-                             denoise_ratio, output_sr, noise, stage, gain, row_exact, style, noise_seeds), codes)
+    wav, audio, stats, track = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
+                                               noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact,
+                                               style, noise_seeds, pitch, lf0)
+    return wav, audio, stats, codes, track
 
 
 @torch.no_grad()
@@ -240,27 +274,39 @@ def tts_from_codes(models: TtsModels, x_frame, g, codes, x_lengths, x_mask, src_
                    noise_scale_vc: float = 0.333, denoise_ratio: float = 0.0, output_sr: int = 16000, noise=None,
                    return_float: bool = False, gain: float = 0.999, scale_norm: str = "max", target_lufs: float = -23.0,
                    limiter: bool = False, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
-                   return_stats: bool = False, row_exact: bool = False, style=None, noise_seeds=None):
+                   return_stats: bool = False, row_exact: bool = False, style=None, noise_seeds=None, pitch=None,
+                   lf0=None, return_lf0: bool = False):
     """`tts` from the prosody codes on (inference_plm.py:161-190): ``x_frame, g, x_lengths, x_mask`` as
     ``inf_extract_tc_latent`` returned them, ``codes`` int64 [B, T] from ``Megatts2PLM1.infer`` in either mode.
     ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`; the stats dict is the last
-    result.  ``row_exact`` / ``style`` / ``noise_seeds``: as for `tts`."""
+    result.  ``row_exact`` / ``style`` / ``noise_seeds`` / ``pitch`` / ``lf0`` / ``return_lf0`` (the track comes
+    last): as for `tts`."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    pitch = PC.check_pitch(pitch, x_frame.shape[0])
     Fh.check_noise_seeds(noise, noise_seeds, None if noise_seeds is None else x_frame.shape[0])
-    wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
-                                        noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact, style,
-                                        noise_seeds)
-    return pack(wav, (audio, return_float), (stats, return_stats))
+    wav, audio, stats, track = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2,
+                                               noise_scale_vc, denoise_ratio, output_sr, noise, stage, gain, row_exact,
+                                               style, noise_seeds, pitch, lf0)
+    return pack(wav, (audio, return_float), (stats, return_stats), (track, return_lf0))
 
 
 def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_length2, noise_scale_vc, denoise_ratio,
-                    output_sr, noise, stage: OutputStage, gain, row_exact=False, style=None, noise_seeds=None):
-    """`tts_from_codes` behind its argument check -> (wav, audio, stats or None)."""
-    B = x_frame.shape[0]
+                    output_sr, noise, stage: OutputStage, gain, row_exact=False, style=None, noise_seeds=None,
+                    edit=None, lf0=None):
+    """`tts_from_codes` behind its argument check -> (wav, audio, stats or None, the vocoder's log-F0 track [B, 4 T2]).
+    ``edit``: a checked `PitchEdit` that is no identity, or None; ``lf0``: a given track instead of the predicted one."""
+    B, T2 = x_frame.shape[0], x_frame.shape[2]
+    if lf0 is not None:
+        lf0 = PC.check_lf0(lf0, B, T2)                                         # before any launch
     w2v_x, pitch = models.ttv.inf_plm_gen(x_frame, g, codes.unsqueeze(1) if B == 1 else codes, x_lengths, x_mask)
     pitch = zero_below(pitch, math.log(55.0))                                  # :166 pitch clipping
-    T2 = w2v_x.shape[2]
+    frames = None if B == 1 else torch.ceil(x_lengths).to(torch.int64)
+    if lf0 is not None:             # a given track, held to zero past every row's own frames as the predicted one is
+        pitch = lf0.to(pitch.device) if B == 1 else \
+            Fh.mask_mul(lf0.to(pitch.device).unsqueeze(1), Fh.sequence_mask(4 * frames, 4 * T2)).squeeze(1)
+    if edit is not None:
+        pitch = edit.apply(pitch, None if B == 1 else 4 * frames)
     if B == 1:
         src_length = torch.full((1,), T2, dtype=torch.int64, device=w2v_x.device)   # :163 the whole padded length
         audio = models.voc.voice_conversion_noise_control(w2v_x, src_length, src_mel, src_length2, pitch,
@@ -268,7 +314,6 @@ def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_l
                                                           noise=noise, style=style, noise_seeds=noise_seeds)
         n_valid = None
     else:
-        frames = torch.ceil(x_lengths).to(torch.int64)
         audio = models.voc.voice_conversion_noise_control(w2v_x, frames, src_mel, src_length2, pitch.unsqueeze(1),
                                                           noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
                                                           noise=noise, style=style, row_exact=row_exact,
@@ -283,9 +328,9 @@ def _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, src_mel, src_l
         if n_valid is not None:
             n_valid = n_valid * output_sr // 16000
     if stage is None:                  # `tts_lines(join=True)`: the programme is converted, not its lines
-        return None, audio, None
+        return None, audio, None, pitch
     wav, stats = stage.int16(audio, n_valid, output_rate(output_sr), gain)
-    return wav, audio, stats
+    return wav, audio, stats, pitch
 
 
 @torch.no_grad()
@@ -296,7 +341,8 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
                     takes: int = 1, target_lufs: float = -23.0, plm_causal: bool = False, plm_prefix=None,
                     return_codes: bool = False, prosody_codes=None, prosody_lengths=None, limiter: bool = False,
                     ceiling_db: float = -1.0, lookahead_ms: float = 1.5, limiter_passes: int = 2,
-                    return_stats: bool = False, noise_seed: Optional[int] = None):
+                    return_stats: bool = False, noise_seed: Optional[int] = None, pitch=None, lf0=None,
+                    return_lf0: bool = False, length_scale=1.0, phone_scale=None):
     """inference_plm.py:tts :126-201 from the prompt WAVEFORM on: resampling to 16 kHz when ``prompt_sr`` differs
     (:124-126, kaiser window), prompt mels (:130-150, `prompt_mels`; with ``denoise_ratio`` > 0 the second prompt mel
     comes from the denoised prompt and the style vectors are mixed by voice_conversion_noise_control), text -> w2v /
@@ -321,7 +367,11 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     ``prosody_codes`` (int64 [Ts] or [1, Ts]; ``prosody_lengths`` their frame count, None: Ts): given prosody codes
     instead of the prosody LM (see `tts`); excludes ``plm_sampling``, ``plm_prefix``, ``plm_causal`` and ``takes`` > 1.
     ``scale_norm`` ... ``return_stats``: the int16 stage, see `output.OutputStage`, every take converted over its own
-    length (stats: fp32 [takes] tensors)."""
+    length (stats: fp32 [takes] tensors).
+    ``pitch`` / ``lf0`` / ``return_lf0`` / ``length_scale`` / ``phone_scale``: the prosody controls of `tts`.
+    ``pitch`` holds one value per take or one for all; ``lf0`` (fp32 [4 * T2] or [1, 4 * T2]) is shared by the takes;
+    ``length_scale`` is one float and ``phone_scale`` one row of N factors (or a list holding it): the takes of a call
+    have one length.  ``return_lf0`` appends the vocoder's track, fp32 [4 * T2] ([N, 4 * T2] with takes), last."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
     takes = int(takes)
@@ -345,6 +395,13 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
     if denoise_ratio != 0 and denoiser is None:
         raise L.HspError("denoise_ratio > 0 needs the denoiser model (denoiser.generator.MPNet), as "
                          "inference_plm.py:144-147")
+    pitch = PC.check_pitch(pitch, takes)
+    if phone_scale is not None and not (isinstance(phone_scale, (list, tuple)) and len(phone_scale) == 1
+                                        and not isinstance(phone_scale[0], (int, float))):
+        phone_scale = [phone_scale]
+    if not isinstance(length_scale, (int, float)):
+        raise L.HspError("length_scale is one float here: the takes of a call have one length")
+    length_scale, scale = PC.check_scales(length_scale, phone_scale, [text.shape[1]], dur is not None)
     if int(prompt_sr) != 16000:
         prompt_audio = Fh.resample(prompt_audio, prompt_sr, 16000, resampling_method="kaiser_window")
     gain = stage.gain(prompt_audio)
@@ -358,16 +415,21 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
         src_mel = torch.cat([rep(src_mel[:1]), rep(src_mel[1:2])])     # the B prompt mels, then the B second mels
         if noise is not None and noise.shape[0] == 1:
             noise = rep(noise)
+        if scale is not None:
+            scale = scale.repeat(B, 0)
+        if lf0 is not None:
+            lf0 = lf0.reshape(1, -1).expand(B, -1)
     text_length = torch.full((B,), text.shape[1], dtype=torch.int64, device=dev)
     ttv_len = torch.full((B,), src_mel_ttv.shape[2], dtype=torch.int64, device=dev)
     src_length2 = torch.full((2 * B,), src_mel.shape[2], dtype=torch.int64, device=dev)
     seeds = int(seed) if plm_sampling is not None else None
-    wav, audio, stats, codes = _tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel,
-                                    src_length2, noise_scale_vc, float(denoise_ratio), output_sr, dur, noise, stage,
-                                    gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes, prosody_lengths,
-                                    noise_seeds=noise_seed)
+    wav, audio, stats, codes, track = _tts(models, text, text_length, tone, language, src_mel_ttv, ttv_len, src_mel,
+                                           src_length2, noise_scale_vc, float(denoise_ratio), output_sr, dur, noise,
+                                           stage, gain, plm_sampling, seeds, plm_causal, plm_prefix, prosody_codes,
+                                           prosody_lengths, noise_seeds=noise_seed, pitch=pitch, lf0=lf0,
+                                           length_scale=length_scale, scale=scale)
     if B == 1:
-        wav, codes = wav[0], codes[0]
+        wav, codes, track = wav[0], codes[0], track[0]
         if output_path is not None:
             write_wav(output_path, output_rate(output_sr), wav)
     elif output_path is not None:
@@ -375,24 +437,28 @@ def tts_from_prompt(models: TtsModels, mel_fn, text, tone, language, prompt_audi
         stem, ext = os.path.splitext(str(output_path))
         for k in range(B):
             write_wav(f"{stem}_take{k}{ext}", output_rate(output_sr), wav[k])
-    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes))
+    return pack(wav, (audio, return_float), (stats, return_stats), (codes, return_codes), (track, return_lf0))
 
 
 def tts_from_prompt_file(models: TtsModels, mel_fn, text, tone, language, prompt_path, output_path=None,
                          plm_sampling=None, seed: int = 0, takes: int = 1, plm_causal: bool = False, plm_prefix=None,
-                         return_codes: bool = False, prosody_codes=None, prosody_lengths=None, **kwargs):
+                         return_codes: bool = False, prosody_codes=None, prosody_lengths=None, pitch=None, lf0=None,
+                         return_lf0: bool = False, length_scale=1.0, phone_scale=None, **kwargs):
     """inference_plm.py:120-201 from the prompt FILE on: ``audio.load`` (torchaudio.load), channel 0 to the GPU of
     ``text``, then `tts_from_prompt` at the file's rate (resampled to 16 kHz there).  ``plm_sampling`` / ``seed`` /
     ``takes`` / ``plm_causal`` / ``plm_prefix`` / ``return_codes`` / ``prosody_codes`` / ``prosody_lengths`` and
+    ``pitch`` / ``lf0`` / ``return_lf0`` / ``length_scale`` / ``phone_scale`` and
     ``kwargs`` (the fields of `output.OutputStage`, ``noise`` / ``noise_seed``, ...) go to `tts_from_prompt`."""
     from . import audio as A
     OutputStage.of(kwargs).check()      # before the file is read
+    PC.check_pitch(pitch, int(takes))
     Fh.check_noise_seeds(kwargs.get("noise"), kwargs.get("noise_seed"), what="noise_seed")
     prompt, rate = A.load(prompt_path)
     return tts_from_prompt(models, mel_fn, text, tone, language, prompt[:1].to(text.device), output_path=output_path,
                            prompt_sr=rate, plm_sampling=plm_sampling, seed=seed, takes=takes, plm_causal=plm_causal,
                            plm_prefix=plm_prefix, return_codes=return_codes, prosody_codes=prosody_codes,
-                           prosody_lengths=prosody_lengths, **kwargs)
+                           prosody_lengths=prosody_lengths, pitch=pitch, lf0=lf0, return_lf0=return_lf0,
+                           length_scale=length_scale, phone_scale=phone_scale, **kwargs)
 
 
 # ---------------------------------------------------------------- a page of lines: ragged batches (DESIGN.md §4.3)
@@ -604,14 +670,19 @@ def _plm_codes(models, x_frame, frames, plm_sampling, seeds, plm_causal, plm_pre
 def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=1.0, noise=None, noise_scale_vc=0.333,
                denoise_ratio=0.0, denoised=None, denoiser=None, hps_denoiser=None, prompt_sr=16000, output_sr=16000,
                plm_sampling=None, seeds=0, plm_causal=False, plm_prefixes=None, prosody_codes=None,
-               prosody_lengths=None, row_exact=True, int16=True, encoded=None, noise_seeds=None):
+               prosody_lengths=None, row_exact=True, int16=True, encoded=None, noise_seeds=None, pitch=None, lf0=None,
+               phone_scale=None):
     """`tts_batch` behind the check of its output stage -> (wav or None, lengths int64 [B], audio, stats or None,
-    codes (a list of B), the frame counts on the host).  ``int16`` False: the int16 stage is left to the caller.
+    codes (a list of B), the frame counts on the host, the vocoder's log-F0 rows (a list of B [4 T_b])).  ``int16`` False: the int16 stage is left to the caller.
     ``encoded``: what `_encode_prompts` made of the lines' prompts (`tts_lines` encodes a page's prompts once)."""
     counts = check_lines(lines, prompts, dur, plm_sampling, plm_causal, plm_prefixes, prosody_codes, prosody_lengths,
                          denoised)
     _check_denoiser(denoise_ratio, denoised, denoiser, hps_denoiser, "tts_batch")
     B, N = len(lines), max(counts)
+    pitch = PC.check_pitch(pitch, B)
+    length_scale, scale = PC.check_scales(length_scale, phone_scale, counts, dur is not None)
+    if lf0 is not None and not isinstance(lf0, torch.Tensor):
+        lf0 = _per_line(lf0, B, "lf0")
     if isinstance(seeds, torch.Tensor) and seeds.shape != (B,):
         raise L.HspError(f"seeds must be an int or an int64 [{B}] tensor, got shape {tuple(seeds.shape)}")
     if noise is not None and (noise.dim() != 3 or noise.shape[0] != B or noise.shape[1] != 192):
@@ -634,10 +705,18 @@ def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=
     text, tone, language = (_pad_rows([line[i] for line in lines], N, torch.int64, dev) for i in range(3))
     text_length = _device_lengths(counts, dev)
     durs = None if dur is None else _pad_rows([d.to(torch.float32) for d in dur], N, torch.float32, dev)
+    pace = {} if scale is None else dict(phone_scale=torch.from_numpy(scale).to(dev))
     x_frame, g, x_lengths, x_mask, frame_lengths = models.ttv.inf_extract_tc_latent(
-        text, text_length, src_mel_ttv, ttv_len, tone, language, length_scale=length_scale, dur=durs, host_lengths=True)
+        text, text_length, src_mel_ttv, ttv_len, tone, language, length_scale=length_scale, dur=durs, host_lengths=True,
+        **pace)
     frames = [int(math.ceil(v)) for v in frame_lengths.tolist()]
     T2 = x_frame.shape[2]
+    if isinstance(lf0, list):          # per-line rows, as `return_lf0` hands them back: each its line's 4 * frames
+        for b, r in enumerate(lf0):
+            if _row(r).shape[0] != 4 * frames[b]:
+                raise L.HspError(f"line {b}: lf0 must hold {4 * frames[b]} values (4 per frame of the {frames[b]} "
+                                 f"frames these durations give), got {_row(r).shape[0]}")
+        lf0 = _pad_rows([r.to(torch.float32) for r in lf0], 4 * T2, torch.float32, dev)
     if noise is not None:
         if noise.shape[2] < T2:
             raise L.HspError(f"noise has {noise.shape[2]} columns; the longest line has {T2} frames")
@@ -646,18 +725,21 @@ def _tts_batch(models, mel_fn, lines, prompts, stage, *, dur=None, length_scale=
     codes = _plm_codes(models, x_frame, frames, plm_sampling, seeds, plm_causal, plm_prefixes, prosody_codes,
                        prosody_lengths)
     _stage("vocoder")
-    wav, audio, stats = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, None, None, noise_scale_vc,
-                                        float(denoise_ratio), output_sr, noise, stage if int16 else None,
-                                        0.999 if peaks is None else peaks, row_exact, style, noise_seeds)
+    wav, audio, stats, track = _tts_from_codes(models, x_frame, g, codes, x_lengths, x_mask, None, None, noise_scale_vc,
+                                               float(denoise_ratio), output_sr, noise, stage if int16 else None,
+                                               0.999 if peaks is None else peaks, row_exact, style, noise_seeds, pitch,
+                                               lf0)
     _stage("end")
     lengths = output_length(torch.ceil(x_lengths).to(torch.int64), output_sr)
-    return wav, lengths, audio, stats, [codes[b, :frames[b]] for b in range(B)], frames
+    return (wav, lengths, audio, stats, [codes[b, :frames[b]] for b in range(B)], frames,
+            [track[b, :4 * frames[b]] for b in range(B)])
 
 
 @torch.no_grad()
 def tts_batch(models: TtsModels, mel_fn, lines, prompts, *, return_float: bool = False, return_codes: bool = False,
               scale_norm: str = "max", target_lufs: float = -23.0, limiter: bool = False, ceiling_db: float = -1.0,
-              lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, **kw):
+              lookahead_ms: float = 1.5, limiter_passes: int = 2, return_stats: bool = False, pitch=None, lf0=None,
+              return_lf0: bool = False, length_scale=1.0, phone_scale=None, **kw):
     """`tts_from_prompt` for B different lines in one ragged batch; row b equals the one-line call on line b (same
     ``dur``, ``noise[b:b+1, :, :T_b]``, prompt and seed) -- DESIGN.md §4.3, INTEGRATION.md "reading a page".
 
@@ -667,6 +749,13 @@ def tts_batch(models: TtsModels, mel_fn, lines, prompts, *, return_float: bool =
              style vector are computed once, as `tts_from_prompt` computes them;
     dur      a list of B [N_b] pinned durations, None: predicted (``length_scale``: the speaking rate, as
              ``inf_extract_tc_latent`` takes it);
+    length_scale, phone_scale  the pace: a float for the page or a [B] sequence, one per line; a list of B rows of N_b
+             factors, one per phone (None entries: 1), or None.  Each in [0.25, 4]; row b equals the one-line call with
+             line b's values (`prosody_controls.check_scales`); pinned durations are scaled by ``phone_scale`` alone;
+    pitch    a `prosody_controls.PitchEdit` whose per-row values are per line: the vocoder's log-F0 track of every
+             line is edited over the line's own 4 * frames, as the one-line call edits it (one launch; None: none);
+    lf0      given tracks instead of the pitch predictor's: a list of B fp32 [4 T_b] rows (what ``return_lf0`` hands
+             back), or fp32 [B, 4 T_max]; a wrong width is an error that names the expected one;
     noise    fp32 [B, 192, >= T_max] (columns past the longest line's frames are ignored), None: drawn;
     noise_seeds  an int s (line b draws its prior noise with s + b) or an int64 [B] tensor, instead of ``noise``: the
              seeded stream of `tts`, so row b equals ``tts_from_prompt(noise_seed=s + b)`` and no noise tensor exists;
@@ -683,11 +772,13 @@ def tts_batch(models: TtsModels, mel_fn, lines, prompts, *, return_float: bool =
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b is wav[b, :lengths[b]], zeros after; then,
     where asked and in this order, the float audio [B, 1, n_max], the stats dict, the codes as a list of B int64
-    [T_b]."""
+    [T_b], and with ``return_lf0`` the log-F0 tracks the vocoder was given as a list of B fp32 [4 T_b]."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
-    wav, lengths, audio, stats, codes, _ = _tts_batch(models, mel_fn, lines, prompts, stage, **kw)
-    return pack(wav, (lengths, True), (audio, return_float), (stats, return_stats), (codes, return_codes))
+    wav, lengths, audio, stats, codes, _, tracks = _tts_batch(models, mel_fn, lines, prompts, stage, pitch=pitch, lf0=lf0,
+                                                              length_scale=length_scale, phone_scale=phone_scale, **kw)
+    return pack(wav, (lengths, True), (audio, return_float), (stats, return_stats), (codes, return_codes),
+                (tracks, return_lf0))
 
 
 def _take(arg, rows):
@@ -708,11 +799,13 @@ def _line_seeds(seeds, N: int, what: str):
 def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16, join: bool = False,
               pause_ms: float = 300.0, return_float: bool = False, return_codes: bool = False, dur=None, noise=None,
               seeds=0, plm_prefixes=None, prosody_codes=None, prosody_lengths=None, denoised=None, noise_seeds=None,
-              **kw):
+              pitch=None, lf0=None, return_lf0: bool = False, length_scale=1.0, phone_scale=None, **kw):
     """Any number of lines: sorted by phone count, cut into chunks of at most ``max_batch`` (`line_chunks`), one
     `tts_batch` per chunk (the per-line keywords ``dur``, ``noise`` rows, ``seeds``, ``noise_seeds``, ``plm_prefixes``,
-    ``prosody_codes`` / ``prosody_lengths`` sliced per chunk; an int ``seeds`` / ``noise_seeds`` = s gives the caller's
-    line k the seed s + k whatever chunk it lands in), results in the caller's order.  Every distinct prompt of the
+    ``prosody_codes`` / ``prosody_lengths``, the rows of ``pitch``, ``lf0`` (a list of N rows), a per-line
+    ``length_scale`` and ``phone_scale`` sliced per chunk; an int ``seeds`` / ``noise_seeds`` = s gives the caller's
+    line k the seed s + k whatever chunk it lands in), results in the caller's order.  ``return_lf0``: the lines'
+    log-F0 tracks (a list of N fp32 [4 T_k]) come last, after the codes.  Every distinct prompt of the
     page is encoded, and with a denoiser denoised, once per call, whatever chunks its lines fall into.  Other keywords
     go to `tts_batch`.
 
@@ -737,6 +830,11 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
     from .inference_vc import output_length
     N, output_sr = len(lines), kw.get("output_sr", 16000)
     Fh.check_noise_seeds(noise, noise_seeds, N)
+    if pitch is not None:
+        PC.check_pitch(pitch, N)
+    PC.check_scales(length_scale, phone_scale, counts, dur is not None)
+    lf0 = _per_line(lf0, N, "lf0")
+    per_scale = not isinstance(length_scale, (int, float))
     line_seeds = _line_seeds(seeds, N, "seeds")
     line_noise_seeds = None if noise_seeds is None else _line_seeds(noise_seeds, N, "noise_seeds")
     dev = lines[0][0].device
@@ -746,10 +844,10 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
     # every distinct prompt of the page is encoded (and denoised) once, whatever chunks its lines fall into
     encoded, index = _encode_prompts(models, mel_fn, prompts, N, kw.get("prompt_sr", 16000), kw.get("denoise_ratio", 0.0),
                                      denoised, kw.get("denoiser"), kw.get("hps_denoiser"))
-    wavs, floats, codes, n_out, part_stats = [], [], [], [], []
+    wavs, floats, codes, n_out, part_stats, tracks = [], [], [], [], [], []
     for rows in chunks:
         idx = torch.tensor(rows, dtype=torch.int64)
-        wav, _, audio, stats, cds, frames = _tts_batch(
+        wav, _, audio, stats, cds, frames, trk = _tts_batch(
             models, mel_fn, [lines[k] for k in rows], _take(prompts, rows) if per_prompt else prompts,
             stage, dur=_take(dur, rows), noise=None if noise is None else noise[idx.to(noise.device)],
             seeds=line_seeds[idx.to(line_seeds.device)].to(dev),
@@ -757,7 +855,9 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
             plm_prefixes=_take(plm_prefixes, rows),
             prosody_codes=_take(prosody_codes, rows), prosody_lengths=_take(prosody_lengths, rows),
             denoised=_take(denoised, rows) if per_denoised else denoised, int16=not join,
-            encoded=(encoded, [index[k] for k in rows]), **kw)
+            encoded=(encoded, [index[k] for k in rows]), pitch=None if pitch is None else pitch.rows(rows),
+            lf0=_take(lf0, rows), length_scale=[float(length_scale[k]) for k in rows] if per_scale else length_scale,
+            phone_scale=_take(phone_scale, rows), **kw)
         for i in range(len(rows)):
             n = output_length(frames[i], output_sr)
             n_out.append(n)
@@ -765,30 +865,35 @@ def tts_lines(models: TtsModels, mel_fn, lines, prompts, *, max_batch: int = 16,
             if not join:
                 wavs.append(wav[i, :n])
         codes += cds
+        tracks += trk
         part_stats.append(stats)
     inv = chunk_order(chunks)
     back = lambda flat: [flat[i] for i in inv]  # noqa: E731
-    floats, codes, n_out = back(floats), back(codes), back(n_out)
+    floats, codes, n_out, tracks = back(floats), back(codes), back(n_out), back(tracks)
     if not join:
         stats = None
         if stage.return_stats:
             order = torch.tensor(inv, device=dev)
             stats = {k: torch.cat([ps[k] for ps in part_stats])[order] for k in part_stats[0]}
-        return pack(back(wavs), (floats, return_float), (stats, stage.return_stats), (codes, return_codes))
+        return pack(back(wavs), (floats, return_float), (stats, stage.return_stats), (codes, return_codes),
+                    (tracks, return_lf0))
     rate = output_rate(output_sr)
     offsets, total = join_plan(n_out, rate, pause_ms)
     programme = torch.zeros(1, 1, total, dtype=torch.float32, device=dev)
     for off, n, row in zip(offsets, n_out, floats):
         programme[0, 0, off:off + n].copy_(row)
     wav, stats = stage.int16(programme, None, rate, 0.999)
-    return pack(wav.reshape(-1), (programme, return_float), (stats, stage.return_stats), (codes, return_codes))
+    return pack(wav.reshape(-1), (programme, return_float), (stats, stage.return_stats), (codes, return_codes),
+                (tracks, return_lf0))
 
 
-def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None, names=None, device=None, **kw):
+def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None, names=None, device=None, pitch=None,
+                    lf0=None, return_lf0: bool = False, length_scale=1.0, phone_scale=None, **kw):
     """`tts_lines` from prompt FILES: ``prompt_paths`` one WAV file for every line or a list of one per line, at any
     sample rate; every distinct file is loaded once (``audio.load_16k``: channel 0, kaiser-window resampling to
-    16 kHz) and shared by the lines that name it.  Keywords ``kw`` go to `tts_lines` (``noise`` rows and
-    ``noise_seeds`` are indexed by the caller's line order).  With ``out_dir`` the rows are
+    16 kHz) and shared by the lines that name it.  ``pitch`` / ``lf0`` / ``return_lf0`` / ``length_scale`` /
+    ``phone_scale`` and the keywords ``kw`` go to `tts_lines` (``noise`` rows, ``noise_seeds`` and the per-line prosody
+    controls are indexed by the caller's line order).  With ``out_dir`` the rows are
     written as ``<out_dir>/<names[k]>.wav`` (``names`` None: ``line_0000.wav``, ...) at the output rate, or as one
     ``programme.wav`` with ``join=True``.  Returns what `tts_lines` returns."""
     import os
@@ -798,6 +903,7 @@ def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None
         raise L.HspError("lines must be a non-empty list of (ids, tone, language) triples")
     N = len(lines)
     Fh.check_noise_seeds(kw.get("noise"), kw.get("noise_seeds"), N)
+    PC.check_pitch(pitch, N)
     per_line = isinstance(prompt_paths, (list, tuple))
     paths = [str(p) for p in prompt_paths] if per_line else [str(prompt_paths)]
     if len(paths) not in (1, N):
@@ -811,7 +917,8 @@ def tts_batch_files(models: TtsModels, mel_fn, lines, prompt_paths, out_dir=None
     if device is None:
         device = lines[0][0].device
     loaded = {p: A.load_16k(p, device) for p in dict.fromkeys(paths)}       # each distinct prompt file loaded once
-    out = tts_lines(models, mel_fn, lines, [loaded[p] for p in paths] if len(paths) > 1 else loaded[paths[0]], **kw)
+    out = tts_lines(models, mel_fn, lines, [loaded[p] for p in paths] if len(paths) > 1 else loaded[paths[0]],
+                    pitch=pitch, lf0=lf0, return_lf0=return_lf0, length_scale=length_scale, phone_scale=phone_scale, **kw)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         rate = output_rate(kw.get("output_sr", 16000))

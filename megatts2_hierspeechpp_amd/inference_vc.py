@@ -22,6 +22,7 @@ from torch import nn
 from . import _lib as L
 from . import functional as Fh
 from . import hip_layers
+from . import prosody_controls as PC
 from .output import OutputStage, output_rate, pack
 
 SOURCE_HOP = 1280   # pad_source's multiple (inference_vc.py:74-75)
@@ -74,7 +75,8 @@ def load_source(path, device):
 @torch.no_grad()
 def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noise_scale_vc=0.333, denoise_ratio=0.0,
        denoised_audio=None, noise=None, return_float=False, scale_norm="max", output_sr=16000, target_lufs=-23.0,
-       limiter=False, ceiling_db=-1.0, lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seed=None):
+       limiter=False, ceiling_db=-1.0, lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seed=None,
+       pitch=None, return_lf0=False):
     """source_audio [1, Ls] (16 kHz, already padded by pad_source), f0_src [1, Ls / 80] (YAAPT, 0 = unvoiced),
     target_audio [1, Lt], f0_trg [1, Lt / 80] -> int16 waveform [320 T] (and the float audio with return_float).
     ``output_sr`` 24000 / 48000: SpeechSR (``models.sr``) runs after the vocoder (:147-151) -> [480 T] / [960 T].
@@ -82,9 +84,12 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     is what the reference does at denoise_ratio == 0.  ``scale_norm`` ... ``return_stats``: the int16 stage, see
     `output.OutputStage`; the prompt of 'prompt' is ``target_audio`` (inference_vc.py:104-105).
     ``noise_seed`` (an int; excludes ``noise``): the vocoder's prior noise is the seeded stream of include/hsp.h "seeded
-    prior noise", so the same call gives the same waveform; None: ``noise``, or torch's process-wide generator."""
+    prior noise", so the same call gives the same waveform; None: ``noise``, or torch's process-wide generator.
+    ``pitch`` (a `prosody_controls.PitchEdit`): the converted log-F0 track is edited before the vocoder reads it (one
+    launch; None or an identity edit: none).  ``return_lf0``: the track the vocoder was given, fp32 [4 T], comes last."""
     stage = OutputStage(scale_norm, target_lufs, limiter, ceiling_db, lookahead_ms, limiter_passes,
                         return_stats).check()
+    pitch = PC.check_pitch(pitch, 1)
     if isinstance(noise_seed, torch.Tensor):
         raise L.HspError("noise_seed is one int")
     Fh.check_noise_seeds(noise, noise_seed, what="noise_seed")
@@ -99,13 +104,16 @@ def vc(models: VcModels, mel_fn, source_audio, f0_src, target_audio, f0_trg, noi
     both[1].copy_(second.reshape(-1)[:target_audio.shape[-1]])
     trg_mel = mel_fn(both)                                                     # [2, 80, Tm]  (:113-126)
     trg_len = torch.tensor([trg_mel.shape[2]] * 2, dtype=torch.int64, device=x_w2v.device)
-    audio = models.voc.voice_conversion_noise_control(x_w2v, x_length, trg_mel, trg_len, lf0.reshape(1, -1)[:, :4 * T],
+    lf0 = lf0.reshape(1, -1)[:, :4 * T]
+    if pitch is not None:
+        lf0 = pitch.apply(lf0)
+    audio = models.voc.voice_conversion_noise_control(x_w2v, x_length, trg_mel, trg_len, lf0,
                                                       noise_scale=noise_scale_vc, denoise_ratio=denoise_ratio,
                                                       noise=noise, noise_seeds=noise_seed)
     if output_sr in (24000, 48000):
         audio = _sr_model(models)(audio)                                       # :147-151
     wav, stats = stage.int16(audio.reshape(1, -1), None, output_rate(output_sr), gain)
-    return pack(wav.reshape(-1), (audio, return_float), (stats, return_stats))
+    return pack(wav.reshape(-1), (audio, return_float), (stats, return_stats), (lf0.reshape(-1), return_lf0))
 
 
 def _sr_model(models):
@@ -286,7 +294,7 @@ def denoise_prompts(prompts, denoiser, hps):
 def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, noise=None, noise_scale_vc=0.333,
              denoise_ratio=0.0, denoised=None, output_sr=16000, scale_norm="max", return_float=False,
              row_exact=False, denoiser=None, hps_denoiser=None, target_lufs=-23.0, limiter=False, ceiling_db=-1.0,
-             lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seeds=None):
+             lookahead_ms=1.5, limiter_passes=2, return_stats=False, noise_seeds=None, pitch=None, return_lf0=False):
     """``vc`` for B sources in one pass.
 
     sources  B 16 kHz rows padded by pad_source ([Ls_b] or [1, Ls_b] device tensors), or (padded fp32 [B, Ls],
@@ -305,7 +313,11 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
              seeded stream of ``vc(noise_seed=)``; with ``row_exact`` row b equals ``vc`` on it alone with its seed, and
              no noise tensor is built;
     scale_norm ... return_stats  the int16 stage, see `output.OutputStage`: every row over its own length, 'prompt'
-             with the peak of the row's own prompt (taken on the device: no norm reads anything back to the host).
+             with the peak of the row's own prompt (taken on the device: no norm reads anything back to the host);
+    pitch    a `prosody_controls.PitchEdit` whose per-row values are per source: every row's converted log-F0 track is
+             edited over its own 4 T_b frames, as ``vc(pitch=)`` edits it (one launch; None or an identity edit: none);
+    return_lf0  the tracks the vocoder was given, fp32 [B, 4 T_max] (row b: its first 4 T_b entries, zeros after), come
+             last.
 
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device): row b's valid samples are wav[b, :lengths[b]]
     (320 T_b at 16 kHz, x1.5 / x3 with SpeechSR), zeros after; with ``return_float`` also the float audio
@@ -317,6 +329,7 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
                         return_stats).check()
     if noise_seeds is not None:
         Fh.check_noise_seeds(noise, noise_seeds, sources[0].shape[0] if isinstance(sources, tuple) else len(sources))
+    pitch = PC.check_pitch(pitch, sources[0].shape[0] if isinstance(sources, tuple) else len(sources))
     voc = models.voc
     if denoised is not None and denoiser is not None:
         raise L.HspError("vc_batch: give the denoised prompts or a denoiser, not both")
@@ -380,6 +393,8 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
         ft_len = _device_lengths(ft_host, dev)
     lf0 = Fh.f0_convert_batch(fs, fs_len, ft, ft_len)[:, :4 * T].reshape(B, 1, 4 * T)
     lf0 = Fh.mask_mul(lf0, Fh.sequence_mask(4 * frames, 4 * T))
+    if pitch is not None:
+        lf0 = pitch.apply(lf0.reshape(B, 4 * T), 4 * frames).reshape(B, 1, 4 * T)
     _tap("lf0", lf0)
     # one style vector per distinct prompt, at the prompt's own length (:113-126); the ragged mel covers them all
     pm, _ = _stack([r for p in range(P) for r in (prompts[p], seconds[p])], dev)
@@ -415,12 +430,13 @@ def vc_batch(models: VcModels, mel_fn, sources, f0_srcs, targets, f0_trgs, *, no
         gain = peaks.expand(B).contiguous() if P == 1 else torch.cat([peaks[index[b]:index[b] + 1] for b in range(B)])
     wav, stats = stage.int16(audio, n_valid, output_rate(output_sr), gain)
     _stage("end")
-    return pack(wav, (n_valid, True), (audio, return_float), (stats, return_stats))
+    return pack(wav, (n_valid, True), (audio, return_float), (stats, return_stats),
+                (lf0.reshape(B, 4 * T), return_lf0))
 
 
 @torch.no_grad()
 def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir=None, f0=None, device=None,
-                   group_by_length: Optional[bool] = None, **kw):
+                   group_by_length: Optional[bool] = None, pitch=None, return_lf0=False, **kw):
     """The reference's per-file loop (inference_vc.py:70-170, one process call per file) as batches: every source and
     prompt WAV at any sample rate (``audio.load_16k``; sources padded by pad_source), F0 tracks from ``f0`` (a mapping
     path -> track) or else from the '.hf0.npy' file extract_f0.py writes beside each WAV (a missing track is an error
@@ -436,12 +452,16 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     flows' attention sees the batch's padding; contract item 3).  None (the default): True, unless ``row_exact=True``
     is given -- then ONE ragged batch whose rows each match their one-file conversion.
     The fields of `output.OutputStage` go to ``vc_batch`` with ``kw``; ``return_stats=True`` appends the limiter's
-    per-row stats (fp32 [B] tensors in the order of ``source_paths``).
+    per-row stats (fp32 [B] tensors in the order of ``source_paths``).  ``pitch`` (a `prosody_controls.PitchEdit`,
+    per-row values in the order of ``source_paths``) is sliced per batch; ``return_lf0`` appends the vocoder's log-F0
+    tracks, fp32 [B, 4 T_max], last.
     Returns (wav int16 [B, n_max], lengths int64 [B] on the device); the files hold wav[b, :lengths[b]]."""
     from .audio import load_16k
     from .inference_plm import write_wav
     return_stats = OutputStage.of(kw).check().return_stats                  # before any file is read
     Fh.check_noise_seeds(kw.get("noise"), kw.get("noise_seeds"), len(source_paths))
+    if pitch is not None:
+        PC.check_pitch(pitch, len(source_paths))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     source_paths = [str(p) for p in source_paths]
@@ -470,17 +490,20 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
     seeds = kw.pop("noise_seeds", None)
     if seeds is not None:                                                   # one seed per file, whatever batch it joins
         seeds = Fh.row_seeds(seeds, B, "cpu")
-    parts, part_stats = [], []
+    parts, part_stats, part_lf0 = [], [], []
     for rows in groups:
         T = max(sources[b].shape[-1] for b in rows) // FRAME
         nz = None if noise is None else noise[torch.tensor(rows, device=noise.device), :, :T].contiguous()
         sd = None if seeds is None else seeds[torch.tensor(rows)]
         parts.append(vc_batch(models, mel_fn, [sources[b] for b in rows], [f0_srcs[b] for b in rows],
                               [prompts[trg_paths[b]] for b in rows], [tracks[trg_paths[b]] for b in rows], noise=nz,
-                              noise_seeds=sd, **kw))
+                              noise_seeds=sd, pitch=None if pitch is None else pitch.rows(rows), return_lf0=return_lf0,
+                              **kw))
+        if return_lf0:
+            part_lf0.append(parts[-1][-1])
         if return_stats:
             part_stats.append(parts[-1][2])
-            parts[-1] = parts[-1][:2]
+        parts[-1] = parts[-1][:2]
     stats = None
     if return_stats:
         order = torch.tensor([b for rows in groups for b in rows], device=device).argsort()
@@ -501,4 +524,9 @@ def vc_batch_files(models: VcModels, mel_fn, source_paths, target_paths, out_dir
         host = wav.cpu()
         for b in range(B):
             write_wav(os.path.join(str(out_dir), output_name(source_paths[b], trg_paths[b])), rate, host[b, :n[b]])
-    return pack(wav, (lengths, True), (stats, return_stats))
+    tracks = None
+    if return_lf0:
+        tracks = torch.zeros(B, max(t.shape[1] for t in part_lf0), dtype=torch.float32, device=device)
+        for rows, t in zip(groups, part_lf0):
+            tracks[torch.tensor(rows, device=device), :t.shape[1]] = t
+    return pack(wav, (lengths, True), (stats, return_stats), (tracks, return_lf0))

@@ -778,9 +778,11 @@ class SynthesizerTrn(nn.Module):
         self.arena = _finalize(self, device, materialize)
         return self
 
-    def _tc_latent(self, x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur):
+    def _tc_latent(self, x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur, scale=None):
         """The text -> frame-rate front part shared by ``inf_extract_tc_latent`` and ``extract_tc_latent_code``: style and
         MRTE from ``ref_mel``, predicted or given durations, range clamp, Gaussian upsampling, ``dur_downsample``.
+        ``scale`` (fp32 [B, N] on the device, or None): a factor per phone on its duration before the ceil
+        (hsp_duration_scaled_f32); None: hsp_duration_f32, the launch there has always been.
         -> x_frame [B, 256, T2], g [B, 256, 1], frame_lengths (float, host) [B], mask2 float [B, 1, T2]."""
         B, N = x.shape
         C = self.inter_channels
@@ -800,8 +802,15 @@ class SynthesizerTrn(nn.Module):
         else:
             dcol.copy_(dur.to(torch.float32))
             lw = (None, 0)
-        L.call("hsp_duration_f32", lw[0], lw[1], L.ptr(x_lengths), float(length_scale), L.fptr(dcol), dcol.stride(0),
-               L.fptr(frames), B, N)
+        if scale is None:
+            L.call("hsp_duration_f32", lw[0], lw[1], L.ptr(x_lengths), float(length_scale), L.fptr(dcol), dcol.stride(0),
+                   L.fptr(frames), B, N)
+        else:
+            if scale.shape != (B, N) or scale.dtype != torch.float32 or not scale.is_contiguous():
+                raise L.HspError(f"the phone scales must be a contiguous fp32 [{B}, {N}] tensor, got "
+                                 f"{scale.dtype} {tuple(scale.shape)}")
+            L.call("hsp_duration_scaled_f32", lw[0], lw[1], L.ptr(x_lengths), float(length_scale), L.fptr(dcol),
+                   dcol.stride(0), L.fptr(frames), B, N, L.fptr(scale), N)
         rng = self.RangePredictor(xd, x_lengths)
         frames_h = frames.cpu()                       # the reference's `.item()` (Gaussian.py:53): T is data dependent
         T = int(frames_h.max().item())
@@ -816,15 +825,18 @@ class SynthesizerTrn(nn.Module):
     @_entry
     @torch.no_grad()
     def inf_extract_tc_latent(self, x, x_lengths, y_mel, y_length, tone, language, mrte_mel=None, mrte_mel_lengths=None,
-                              length_scale=1, dur=None, host_lengths=False):
+                              length_scale=1, dur=None, host_lengths=False, phone_scale=None):
         """(:937-982) ids/tone/language int64 [B, N], x_lengths [B], y_mel [B, 80, Tm], y_length [B] ->
         x_frame [B, 256, T2], g [B, 256, 1], x_lengths (float, frames / 2) [B], x_mask BOOL [B, 1, T2] (the
         reference's dtypes, :979-982; ``inf_plm_gen`` takes that mask or a float one).
         ``dur`` [B, N] (optional) overrides the predicted durations (BASELINE config 3 pins them).
         ``host_lengths``: a fifth result, the same x_lengths as the CPU tensor the front-end read back (callers that
-        slice rows by their frame counts need no second read-back)."""
+        slice rows by their frame counts need no second read-back).
+        ``phone_scale`` (fp32 [B, N] on the device, or None): a factor per phone on its duration, predicted or given,
+        before the ceil (include/hsp.h: hsp_duration_scaled_f32); entries past a row's length are not read."""
         ref_mel, ref_len = (mrte_mel, mrte_mel_lengths) if mrte_mel is not None else (y_mel, y_length)
-        x_frame, g, frame_lengths, mask2 = self._tc_latent(x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur)
+        x_frame, g, frame_lengths, mask2 = self._tc_latent(x, x_lengths, ref_mel, ref_len, tone, language, length_scale, dur,
+                                                           phone_scale)
         out = (x_frame, g, frame_lengths.to(x.device), mask2.to(torch.bool))   # a dtype cast, as the reference's (:982)
         return (*out, frame_lengths) if host_lengths else out
 
