@@ -7,294 +7,133 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HSP_LIB", os.path.join(_HERE, "libhsp.so"))  # HSP_LIB: kernel A/B builds
-
-# enums of include/hsp.h
-PRO_NONE, PRO_LRELU, PRO_ACT1D, PRO_SILU = 0, 1, 2, 3
-ACT_NONE, ACT_TANH, ACT_GELU_TANH, ACT_RELU, ACT_MISH, ACT_SILU, ACT_SOFTPLUS, ACT_GELU_ERF = 0, 1, 2, 3, 4, 5, 6, 7
-ACT_ACT1D = 8          # the next Activation1d from the conv epilogue (hsp.h: HSP_ACT_ACT1D)
-ROWS_PLAIN, ROWS_GATE_WN, ROWS_GATE_GLU, ROWS_SHUFFLE = 0, 1, 2, 3
-MASK_NONE, MASK_PRE, MASK_POST, MASK_BOTH = 0, 1, 2, 3
-EINVAL = -1
-MHA_TOK, MHA_MFMA_WHOLE, MHA_MFMA_SLAB, MHA_MFMA_STREAM, MHA_ROW, MHA_ROW_STREAM = range(6)   # hsp_mha_plan kernel ids
-
-_fp = C.c_void_p
-
-
-class Conv1dArgs(C.Structure):
-    """Mirror of ``hsp_conv1d_args`` (include/hsp.h) -- field order is the ABI."""
-    _fields_ = [
-        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64), ("x_ts", C.c_int64),
-        ("B", C.c_int32), ("Cin", C.c_int32), ("Lin", C.c_int32),
-        ("w", _fp), ("K", C.c_int32), ("M", C.c_int32), ("dil", C.c_int32), ("pad", C.c_int32), ("stride", C.c_int32),
-        ("zeros", _fp), ("w_ld", C.c_int32),
-        ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64),
-        ("Cout", C.c_int32), ("Lout", C.c_int32), ("ncols", C.c_int32),
-        ("prologue", C.c_int32), ("slope", C.c_float),
-        ("alpha_exp", _fp), ("beta_inv", _fp), ("filt", _fp),
-        ("rows", C.c_int32), ("gate_half", C.c_int32), ("up", C.c_int32), ("shuf_pad", C.c_int32),
-        ("bias", _fp), ("cbias", _fp), ("cbias_bs", C.c_int64),
-        ("act", C.c_int32),
-        ("mask", _fp), ("mask_bs", C.c_int64), ("mask_mode", C.c_int32),
-        ("cscale", _fp), ("cscale_bs", C.c_int64), ("scale", C.c_float),
-        ("res", _fp), ("res_bs", C.c_int64), ("res_cs", C.c_int64),
-        ("accumulate", C.c_int32), ("post_scale", C.c_float), ("debug", C.c_int32),
-        ("ln_c1", _fp), ("ln_eps", C.c_float),
-        ("split_row", C.c_int32), ("accumulate2", C.c_int32), ("mask_mode2", C.c_int32), ("y2", _fp),
-        ("y2_bs", C.c_int64), ("y2_cs", C.c_int64), ("res_ts", C.c_int64), ("w_bs", C.c_int64),
-        ("fold_cols", C.c_int32),
-    ]
-
-
-class MhaArgs(C.Structure):
-    """Mirror of ``hsp_mha_args``."""
-    _fields_ = [
-        ("q", _fp), ("k", _fp), ("v", _fp), ("o", _fp),
-        ("q_bs", C.c_int64), ("k_bs", C.c_int64), ("v_bs", C.c_int64), ("o_bs", C.c_int64),
-        ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("Tq", C.c_int32), ("Tk", C.c_int32),
-        ("qk_scale", C.c_float),
-        ("mask_q", _fp), ("mask_k", _fp), ("rel_k", _fp), ("rel_v", _fp), ("window", C.c_int32),
-        ("q_cs", C.c_int64), ("k_cs", C.c_int64), ("v_cs", C.c_int64), ("o_cs", C.c_int64),
-        ("mask_dense", _fp), ("mask_dense_bs", C.c_int64),
-    ]
-
-
-class MhaProjArgs(C.Structure):
-    """Mirror of ``hsp_mha_proj_args``."""
-    _fields_ = [
-        ("q", _fp), ("k", _fp), ("v", _fp),
-        ("q_bs", C.c_int64), ("q_cs", C.c_int64), ("k_bs", C.c_int64), ("k_cs", C.c_int64), ("v_bs", C.c_int64),
-        ("v_cs", C.c_int64),
-        ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("Tq", C.c_int32), ("Tk", C.c_int32),
-        ("qk_scale", C.c_float),
-        ("wt", _fp), ("M", C.c_int32), ("wt_ld", C.c_int32),
-        ("bias", _fp), ("mask", _fp), ("mask_bs", C.c_int64), ("cscale", _fp), ("cscale_bs", C.c_int64),
-        ("res", _fp), ("res_bs", C.c_int64), ("res_cs", C.c_int64), ("res_ts", C.c_int64),
-        ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64), ("y_ts", C.c_int64), ("debug", C.c_int32),
-        ("key_len", _fp),
-    ]
-
-
-class DftSegArgs(C.Structure):
-    """Mirror of ``hsp_dftseg_args``."""
-    _fields_ = [
-        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64),
-        ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64),
-        ("B", C.c_int32), ("C", C.c_int32), ("L", C.c_int32),
-        ("k", C.c_int32), ("dil", C.c_int32), ("pad", C.c_int32), ("nseg", C.c_int32), ("Np", C.c_int32),
-        ("xf", _fp), ("xf_bs", C.c_int64), ("dft", _fp),
-        ("bias", _fp), ("res", _fp), ("res_bs", C.c_int64), ("res_cs", C.c_int64),
-        ("accumulate", C.c_int32), ("post_scale", C.c_float),
-        ("act_alpha_exp", _fp), ("act_beta_inv", _fp), ("act_filt", _fp), ("prod3", C.c_int32),
-        ("act_len", _fp),
-    ]
-
-
-class Cprod3Args(C.Structure):
-    """Mirror of ``hsp_cprod3_args``."""
-    _fields_ = [
-        ("xf", _fp), ("yf", _fp), ("w", _fp), ("zeros", _fp), ("xf_bs", C.c_int64), ("yf_bs", C.c_int64),
-        ("bins", C.c_int32), ("C", C.c_int32), ("Np", C.c_int32), ("debug", C.c_int32),
-    ]
-
-
-class SampleArgs(C.Structure):
-    """Mirror of ``hsp_sample_args``."""
-    _fields_ = [
-        ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
-        ("seeds", _fp), ("probs", _fp), ("probs_bs", C.c_int64),
-    ]
-
-
-class PlmDecodeArgs(C.Structure):
-    """Mirror of ``hsp_plm_decode_args``."""
-    _fields_ = [
-        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64),
-        ("y", _fp), ("y_bs", C.c_int64), ("y_cs", C.c_int64),
-        ("k_cache", _fp), ("v_cache", _fp), ("bs", C.c_int64), ("cs", C.c_int64),
-        ("t", C.c_int32), ("B", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("F", C.c_int32), ("eps", C.c_float),
-        ("g1", _fp), ("b1", _fp), ("wqkv_t", _fp), ("bqkv", _fp), ("wo_t", _fp), ("bo", _fp), ("g2", _fp), ("b2", _fp),
-        ("w1_t", _fp), ("c1", _fp), ("w2_t", _fp), ("c2", _fp),
-        ("workspace", _fp), ("workspace_bytes", C.c_int64), ("debug", C.c_int32),
-    ]
-
-
-class PlmPrefillAttnArgs(C.Structure):
-    """Mirror of ``hsp_plm_prefill_attn_args``."""
-    _fields_ = [
-        ("qkv", _fp), ("q_rs", C.c_int64), ("out", _fp), ("o_rs", C.c_int64),
-        ("k_cache", _fp), ("v_cache", _fp), ("cs", C.c_int64),
-        ("n", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("debug", C.c_int32),
-    ]
-
-
-class ProsodyArgs(C.Structure):
-    """Mirror of ``hsp_prosody_args``."""
-    _fields_ = [
-        ("x", _fp), ("x_bs", C.c_int64), ("x_cs", C.c_int64), ("lengths", _fp),
-        ("B", C.c_int32), ("D", C.c_int32), ("T", C.c_int32), ("k", C.c_int32), ("w_ld", C.c_int32), ("bins", C.c_int32),
-        ("w1a", _fp), ("b1a", _fp), ("w1b", _fp), ("b1b", _fp), ("w2a", _fp), ("b2a", _fp), ("w2b", _fp), ("b2b", _fp),
-        ("embed", _fp), ("codes", _fp), ("c_bs", C.c_int64), ("pooled", _fp), ("p_bs", C.c_int64),
-    ]
-
-
-class LimiterArgs(C.Structure):
-    """Mirror of ``hsp_limiter_args``."""
-    _fields_ = [
-        ("x", _fp), ("x_bs", C.c_int64), ("lengths", _fp), ("gains", _fp), ("B", C.c_int32), ("n", C.c_int64),
-        ("bank", _fp), ("F", C.c_int32), ("Z", C.c_int32), ("W", C.c_int32), ("ceiling", C.c_float),
-        ("y", _fp), ("y_bs", C.c_int64), ("min_gain", _fp), ("tp", _fp),
-    ]
-
-
-class F0EditArgs(C.Structure):
-    """Mirror of ``hsp_f0_edit_args``."""
-    _fields_ = [
-        ("lf0", _fp), ("lf0_bs", C.c_int64), ("lengths", _fp), ("B", C.c_int32), ("n", C.c_int64),
-        ("shift", _fp), ("range", _fp), ("target_hz", _fp), ("offsets", _fp), ("off_bs", C.c_int64),
-        ("f_min", C.c_float), ("f_max", C.c_float), ("out", _fp), ("out_bs", C.c_int64), ("mean_hz", _fp),
-    ]
-
-
-WSPEC_BLOCK, WSPEC_THREE = 0, 1
-
-
-# symbol -> (restype, argtypes); every symbol include/hsp.h declares
-SIGNATURES = {
-    "hsp_version": (C.c_int, []),
-    "hsp_arch": (C.c_char_p, []),
-    "hsp_conv1d_mfma_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),
-    "hsp_conv1d_direct_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),
-    "hsp_conv1d_mfma_plan": (C.c_int, [C.POINTER(Conv1dArgs), C.POINTER(C.c_int32 * 4)]),
-    "hsp_act1d_snakebeta_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
-    "hsp_act1d_snakebeta_ragged_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
-    "hsp_snake_consts_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, _fp]),
-    "hsp_fold_weight_norm_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, _fp]),
-    "hsp_gather_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
-    "hsp_sequence_mask_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, _fp]),
-    "hsp_flip_channels_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_sample_prior_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
-    "hsp_randn_rows_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_sample_prior_seeded_f32": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp]),
-    "hsp_layernorm_mod_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp, _fp,
-                                        C.c_int64, _fp, _fp, _fp]),
-    "hsp_mha_f32": (C.c_int, [C.POINTER(MhaArgs), _fp]),
-    "hsp_mha_plan": (C.c_int, [C.POINTER(MhaArgs), C.POINTER(C.c_int32 * 4)]),
-    "hsp_mha_proj_f32": (C.c_int, [C.POINTER(MhaProjArgs), _fp]),
-    "hsp_dftseg_fwd_f32": (C.c_int, [C.POINTER(DftSegArgs), _fp]),
-    "hsp_dftseg_inv_f32": (C.c_int, [C.POINTER(DftSegArgs), _fp]),
-    "hsp_dftseg_tables_f32": (C.c_int, [_fp, _fp]),
-    "hsp_dftseg_pair_supported": (C.c_int, [C.POINTER(DftSegArgs), C.POINTER(DftSegArgs)]),
-    "hsp_dftseg_pair_f32": (C.c_int, [C.POINTER(DftSegArgs), C.POINTER(DftSegArgs), _fp]),
-    "hsp_dftseg_supported": (C.c_int, [C.POINTER(DftSegArgs)]),
-    "hsp_cprod3_f32": (C.c_int, [C.POINTER(Cprod3Args), _fp]),
-    "hsp_cprod3_supported": (C.c_int, [C.POINTER(Cprod3Args)]),
-    "hsp_dftseg_weight_spectrum_f32": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp]),
-    "hsp_mha_proj_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "hsp_masked_mean_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_mask_mul_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_linear_interp_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_linear_interp_ragged_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
-    "hsp_axpby_f32": (C.c_int, [_fp, _fp, _fp, C.c_float, C.c_float, C.c_int64, _fp]),
-    "hsp_plm_embed_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32, C.c_int32,
-                                    _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp]),
-    "hsp_plm_embed_step_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32, C.c_int32,
-                                         _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64,
-                                         C.c_int64, C.c_int32, _fp]),
-    "hsp_argmax_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, _fp]),
-    "hsp_plm_embed_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32,
-                                           C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32,
-                                           C.c_int32, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                           C.POINTER(SampleArgs), _fp]),
-    "hsp_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, C.c_int32,
-                                 C.POINTER(SampleArgs), _fp]),
-    "hsp_plm_decode_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
-    "hsp_plm_decode_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
-    "hsp_plm_decode_layer_f32": (C.c_int, [C.POINTER(PlmDecodeArgs), _fp]),
-    "hsp_plm_decode_layer_pos_f32": (C.c_int, [C.POINTER(PlmDecodeArgs), _fp, _fp]),
-    "hsp_plm_embed_pos_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int32, C.c_int32,
-                                        _fp, C.c_int32, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, _fp]),
-    "hsp_plm_choose_advance_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, _fp,
-                                             C.c_int32, C.POINTER(SampleArgs), _fp]),
-    "hsp_plm_prefill_attn_supported": (C.c_int, [C.c_int32, C.c_int32]),
-    "hsp_plm_prefill_attn_f32": (C.c_int, [C.POINTER(PlmPrefillAttnArgs), _fp]),
-    "hsp_embedding_sum_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp,
-                                        C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_lstm_bidir_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
-                                     C.c_int32, _fp]),
-    "hsp_duration_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp]),
-    "hsp_duration_scaled_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp,
-                                          C.c_int64, _fp]),
-    "hsp_gaussian_upsample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp,
-                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_act_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int32, _fp]),
-    "hsp_reflect_pad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_f0_convert_f32": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp]),
-    "hsp_reflect_pad_ragged_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, _fp]),
-    "hsp_f0_convert_batch_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int32, _fp, C.c_int64, C.c_int32,
-                                           C.c_int32, _fp]),
-    "hsp_stft_frames_ragged_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, _fp]),
-    "hsp_abs_max_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int64, _fp]),
-    "hsp_peak_int16_gains": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
-    "hsp_mag_pha_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int32, C.c_float, _fp]),
-    "hsp_lsigmoid_mul_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, _fp, C.c_int32, C.c_int32, _fp]),
-    "hsp_atan2_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
-    "hsp_polar_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, C.c_int32, _fp]),
-    "hsp_norm_factor_rows_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int32, C.c_int64, _fp]),
-    "hsp_stft_frames_packed_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int32, C.c_int64, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_instnorm_prelu_seg_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp,
-                                             _fp, C.c_float, _fp]),
-    "hsp_zero_gaps_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp]),
-    "hsp_dwconv_bn_silu_seg_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp]),
-    "hsp_istft_ola_seg_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _fp, _fp,
-                                        C.c_int32, C.c_int32, _fp]),
-    "hsp_maxpool1d_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_vq_nearest_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_prosody_encode_f32": (C.c_int, [C.POINTER(ProsodyArgs), _fp]),
-    "hsp_add_cbias_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
-    "hsp_zero_below_f32": (C.c_int, [_fp, C.c_float, _fp, C.c_int64, _fp]),
-    "hsp_peak_int16": (C.c_int, [_fp, C.c_int64, _fp, C.c_float, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
-    "hsp_f0_edit_rows_f32": (C.c_int, [C.POINTER(F0EditArgs), _fp]),
-    "hsp_loudness_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
-    "hsp_loudness_coefs_f64": (C.c_int, [C.c_int32, _fp]),
-    "hsp_loudness_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp]),
-    "hsp_loudness_gains_f32": (C.c_int, [_fp, _fp, C.c_float, C.c_float, _fp, _fp, C.c_int32, _fp]),
-    "hsp_true_peak_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int32, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp]),
-    "hsp_limiter_f32": (C.c_int, [C.POINTER(LimiterArgs), _fp]),
-    "hsp_gain_update_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, C.c_int32, _fp]),
-    "hsp_limiter_stats_f32": (C.c_int, [_fp, _fp, C.c_float, _fp, _fp, _fp, C.c_int32, _fp]),
-    "hsp_gain_int16_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int64, _fp]),
-    "hsp_resample_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
-                                   C.c_int32, _fp, C.c_int64, C.c_int32, _fp]),
-    "hsp_copy_strided_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_int32, C.c_int32,
-                                       _fp]),
-    "hsp_conv1d_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),
-    "hsp_convtr1d_f32": (C.c_int, [C.POINTER(Conv1dArgs), _fp]),
-    "hsp_wn_layer_f32": (C.c_int, [C.POINTER(Conv1dArgs), C.POINTER(Conv1dArgs), C.POINTER(Conv1dArgs), _fp]),
-    "hsp_ffn_conv_f32": (C.c_int, [C.POINTER(Conv1dArgs), C.POINTER(Conv1dArgs), _fp]),
-    "hsp_layernorm_modulate_f32": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp, _fp,
-                                             C.c_int64, _fp]),
-    "hsp_stft_frames_f32": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                      _fp]),
-    "hsp_power_mel_log_f32": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_int32, C.c_float, _fp]),
-}
-
-_lib: Optional[C.CDLL] = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hsp.h")   # the checkout's, as build.source_id finds it
 
 
 class HspError(RuntimeError):
     pass
+
+
+# ------------------------------------------------------------------ the reader of include/hsp.h
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_POINTEES = {*_SCALARS, "int16_t", "void"}     # a pointer to one of these travels as c_void_p
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char *": C.c_char_p}
+_DEFINE = re.compile(r"# ?define (HSP_\w+)(?: ([-+]?\d+)| \( ?([-+]?\d+) ?\))?")
+_DIRECTIVE = re.compile(r"# ?(include|ifdef|ifndef|if|endif|pragma)\b")
+_TOP = re.compile(r' ?(?:(extern "C" \{)|(\})|enum \{([^{}]*)\} ;|typedef struct(?: \w+)? \{([^{}]*)\} (\w+) ;|([^;{}]+);)')
+_PROTO = re.compile(r"(int|int64_t|const char \*) (\w+) \( (.*) \)")
+
+
+def _declare(decl, structs, where):
+    """One member line of a struct (``structs`` None) or one parameter of ``where``, its tokens one space apart:
+    ``[const] T a , b`` or ``[const] T * p , * q`` (and, as a parameter, ``T v [ n ]``) -> [(name, ctype), ...]."""
+    m = re.fullmatch(r"(?:const )?(\w+) (.+)", decl)
+    base, declarators = (m[1], m[2].split(" , ")) if m else (None, [""])
+    param, out = structs is not None, []
+    for d in declarators:
+        dm = re.fullmatch(r"(\* )?(\w+)(?: \[ (\d+) \])?", d)
+        star, name, dim = dm.groups() if dm else (None, None, None)
+        if star and not dim and base in _POINTEES:
+            ctype = C.c_void_p
+        elif star and not dim and param and base in structs:
+            ctype = C.POINTER(structs[base])
+        elif name and not star and not dim and base in _SCALARS:
+            ctype = _SCALARS[base]
+        elif name and not star and dim and param and base in _SCALARS:
+            ctype = C.POINTER(_SCALARS[base] * int(dim))
+        else:
+            raise HspError(f"hsp.h: {where}: unsupported declaration {decl!r}")
+        out.append((name, ctype))
+    return out
+
+
+def parse_header(text):
+    """(consts, structs, protos) of the text of include/hsp.h: {HSP_NAME: int}, {hsp_x_args: ctypes.Structure class},
+    {hsp_name: (restype, [argtypes])}.  It reads the forms the header uses -- anonymous enums and integer #defines;
+    typedef structs of scalars and pointers; prototypes over scalars, pointers, struct pointers and ``int32_t v[n]`` --
+    and raises HspError, naming the declaration, on anything else: nothing is skipped."""
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+    consts, structs, protos, body, depth, pos = {}, {}, {}, [], 0, 0
+    for line in (" ".join(ln.split()) for ln in text.split("\n")):
+        m = _DEFINE.fullmatch(line)
+        if m and (m[2] or m[3]):
+            consts[m[1]] = int(m[2] or m[3])
+        elif line.startswith("#") and not m and not _DIRECTIVE.match(line):     # m without a value: the include guard
+            raise HspError(f"hsp.h: unsupported directive {line!r}")
+        elif not line.startswith("#"):
+            body.append(line)
+    src = " ".join(re.sub(r"([*(),;=\[\]{}])", r" \1 ", " ".join(body)).split())
+    while pos < len(src):
+        m = _TOP.match(src, pos)
+        extern, close, enum, members, sname, decl = m.groups() if m else (None,) * 6
+        depth += 1 if extern else -1 if close else 0
+        if not m or depth < 0:
+            raise HspError(f"hsp.h: cannot classify the declaration at {src[pos:pos + 120]!r}")
+        pos = m.end()
+        for item in enum.split(" , ") if enum is not None else ():
+            em = re.fullmatch(r" ?(HSP_\w+) = ([-+]?\d+) ?", item)
+            if not em:
+                raise HspError(f"hsp.h: unsupported enum member {item!r}")
+            consts[em[1]] = int(em[2])
+        if sname:
+            fields = [f for d in members.split(" ; ") if d.strip() for f in _declare(d.strip(), None, sname)]
+            structs[sname] = type(sname, (C.Structure,), {"_fields_": fields})
+        elif decl:
+            pm = _PROTO.fullmatch(decl.strip())
+            if not pm or not pm[2].startswith("hsp_"):
+                raise HspError(f"hsp.h: not a prototype of an hsp_ function: {decl.strip()!r}")
+            params = [] if pm[3] == "void" else [t for p in pm[3].split(" , ") for _, t in _declare(p, structs, pm[2])]
+            protos[pm[2]] = (_RETURNS[pm[1]], params)
+    return consts, structs, protos
+
+
+# ------------------------------------------------------------------ the binding, built from the header at import
+try:
+    with open(HEADER_PATH) as _f:
+        _CONSTS, STRUCTS, SIGNATURES = parse_header(_f.read())    # SIGNATURES: symbol -> (restype, argtypes)
+except OSError as e:
+    raise HspError(f"{HEADER_PATH}: the C header the binding is derived from cannot be read ({e})") from None
+_unbound = set(STRUCTS)                                           # STRUCTS: C name -> class
+
+
+def _struct(cname, doc):
+    """The ctypes class of a struct of the header, claimed under a Python name (each struct exactly once)."""
+    if cname not in _unbound:
+        raise HspError(f"{HEADER_PATH} declares no struct {cname} (or it is bound twice)")
+    _unbound.remove(cname)
+    STRUCTS[cname].__doc__ = doc
+    return STRUCTS[cname]
+
+
+Conv1dArgs = _struct("hsp_conv1d_args", "Arguments of the fused conv launches -- field order is the ABI.")
+MhaArgs = _struct("hsp_mha_args", "Arguments of hsp_mha_f32 / hsp_mha_plan.")
+MhaProjArgs = _struct("hsp_mha_proj_args", "Arguments of hsp_mha_proj_f32: attention + output projection.")
+DftSegArgs = _struct("hsp_dftseg_args", "Arguments of the hsp_dftseg_* transforms.")
+Cprod3Args = _struct("hsp_cprod3_args", "Arguments of hsp_cprod3_f32.")
+SampleArgs = _struct("hsp_sample_args", "Sampling controls of the PLM decision kernels.")
+PlmDecodeArgs = _struct("hsp_plm_decode_args", "Arguments of hsp_plm_decode_layer_f32 / _pos_f32.")
+PlmPrefillAttnArgs = _struct("hsp_plm_prefill_attn_args", "Arguments of hsp_plm_prefill_attn_f32.")
+ProsodyArgs = _struct("hsp_prosody_args", "Arguments of hsp_prosody_encode_f32.")
+LimiterArgs = _struct("hsp_limiter_args", "Arguments of hsp_limiter_f32.")
+F0EditArgs = _struct("hsp_f0_edit_args", "Arguments of hsp_f0_edit_rows_f32.")
+if _unbound:
+    raise HspError(f"{HEADER_PATH}: no Python name is bound to {sorted(_unbound)}: add a _struct line above")
+for _name, _cls in list(globals().items()):          # a class answers to its Python name (launch hooks report it)
+    if isinstance(_cls, type) and issubclass(_cls, C.Structure):
+        _cls.__name__ = _cls.__qualname__ = _name
+
+# every enum member and integer #define of the header under its name without the HSP_ prefix: PRO_NONE, ACT_ACT1D,
+# ROWS_SHUFFLE, MASK_POST, EINVAL, VERSION, MHA_TOK, WSPEC_THREE, DFTSEG_TABLE_FLOATS, PLM_PREFILL_MAX_N, ...
+globals().update({k[len("HSP_"):]: v for k, v in _CONSTS.items()})
+
+_lib: Optional[C.CDLL] = None
 
 
 def lib() -> C.CDLL:

@@ -62,7 +62,7 @@ def _dft_tables(device):
     the radix-2 half-length transform + the 128-point twiddles), filled by the library, once per device."""
     t = _DFT.get(device)
     if t is None:
-        n = 4160  # HSP_DFTSEG_TABLE_FLOATS
+        n = L.DFTSEG_TABLE_FLOATS
         f = np.zeros(n, dtype=np.float32)
         finv = np.zeros(n, dtype=np.float32)
         L.check(L.lib().hsp_dftseg_tables_f32(f.ctypes.data, finv.ctypes.data), "hsp_dftseg_tables_f32")

@@ -31,6 +31,28 @@ DENOISER_H = types.SimpleNamespace(dense_channel=64, compress_factor=0.3, num_ts
                                    sampling_rate=16000, n_fft=400, hop_size=100, win_size=400)
 
 
+def header_values(tmp_path, exprs):
+    """The integer C expressions ``exprs`` as gcc evaluates them against include/hsp.h (write abi.c, compile, run)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src, exe = tmp_path / "abi.c", tmp_path / "abi"
+    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){"]
+                             + [f'printf("%lld\\n", (long long)({e}));' for e in exprs] + ["return 0;}"]))
+    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)])
+    return [int(v) for v in subprocess.check_output([str(exe)]).split()]
+
+
+def assert_struct_layouts(tmp_path, structs):
+    """sizeof and every offsetof of the structs {C name: ctypes class}, as gcc sees include/hsp.h == the ctypes classes."""
+    import ctypes
+    exprs, want = [], []
+    for cname, cls in structs.items():
+        fields = [f for f, _ in cls._fields_]
+        exprs += [f"sizeof({cname})"] + [f"offsetof({cname}, {f})" for f in fields]
+        want += [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    assert header_values(tmp_path, exprs) == want, list(structs)
+
+
 def fixture_names():
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
 

@@ -8,6 +8,7 @@ import pytest
 
 import conv_ref as R
 import epi_act_cases as EC
+import helpers
 
 
 @pytest.fixture(scope="module")
@@ -39,16 +40,9 @@ def _struct(L, c, Lc, k, d, nb=EC.B, fused=True):
 def test_struct_mirror(L, tmp_path):
     """The form adds no field: the struct is the parent's, the value is the header's HSP_ACT_ACT1D and a default struct
     does not ask for it."""
-    import os
-    import subprocess
     assert L.Conv1dArgs().act == L.ACT_NONE != L.ACT_ACT1D
     assert not any(n.startswith("epi_act") for n, _ in L.Conv1dArgs._fields_)
-    src = tmp_path / "e.c"
-    src.write_text('#include <stdio.h>\n#include "hsp.h"\nint main(void){printf("%d %zu\\n", (int)HSP_ACT_ACT1D, '
-                   'sizeof(hsp_conv1d_args));return 0;}\n')
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(tmp_path / "e")])
-    val, size = (int(v) for v in subprocess.check_output([str(tmp_path / "e")]).split())
+    val, size = helpers.header_values(tmp_path, ["HSP_ACT_ACT1D", "sizeof(hsp_conv1d_args)"])
     assert val == L.ACT_ACT1D and size == ctypes.sizeof(L.Conv1dArgs)
 
 

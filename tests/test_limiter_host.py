@@ -5,13 +5,13 @@ harnesses."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import limiter_ref as M
 import loudness_ref as LR
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hsp_true_peak_f32", "hsp_limiter_f32", "hsp_gain_update_f32", "hsp_limiter_stats_f32", "hsp_gain_int16_f32")
@@ -107,15 +107,7 @@ def test_header_binding_and_struct_layout_agree(tmp_path):
     src = open(os.path.join(ROOT, "megatts2_hierspeechpp_amd", "csrc", "hsp_limiter.hip")).read()
     assert int(re.search(r"constexpr int TILE = (\d+);", src).group(1)) == M.TILE     # the row lengths straddle this tile
     assert int(re.search(r"constexpr int WMAX = (\d+);", src).group(1)) == 480
-    fields = [f for f, _ in _lib.LimiterArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){",
-                              'printf("%zu\\n", sizeof(hsp_limiter_args));']
-                             + [f'printf("%zu\\n", offsetof(hsp_limiter_args, {f}));' for f in fields] + ["return 0;}"]))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals == [C.sizeof(_lib.LimiterArgs)] + [getattr(_lib.LimiterArgs, f).offset for f in fields]
+    helpers.assert_struct_layouts(tmp_path, {"hsp_limiter_args": _lib.LimiterArgs})
 
 
 def test_new_entry_points_reject_bad_arguments():

@@ -6,7 +6,6 @@ before any HIP call), and header, ctypes table, version script and library agree
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,6 +17,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import plm_causal_ref as R  # noqa: E402
 import plm_prefix_ref as PR  # noqa: E402
+import helpers  # noqa: E402
 
 TOL = 1e-4
 
@@ -159,12 +159,4 @@ def test_names_agree_across_header_ctypes_map_and_library(tmp_path):
     vmap = open(os.path.join(ROOT, "megatts2_hierspeechpp_amd", "csrc", "hsp.map")).read()
     assert "global: hsp_*;" in vmap and "local: *;" in vmap
     # the ctypes mirror of the argument block == the header as a C compiler sees it
-    fields = [f for f, _ in L.PlmPrefillAttnArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){",
-                              'printf("%zu\\n", sizeof(hsp_plm_prefill_attn_args));']
-                             + [f'printf("%zu\\n", offsetof(hsp_plm_prefill_attn_args, {f}));' for f in fields] + ["return 0;}"]))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals == [ctypes.sizeof(L.PlmPrefillAttnArgs)] + [getattr(L.PlmPrefillAttnArgs, f).offset for f in fields]
+    helpers.assert_struct_layouts(tmp_path, {"hsp_plm_prefill_attn_args": L.PlmPrefillAttnArgs})

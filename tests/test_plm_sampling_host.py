@@ -3,7 +3,6 @@ argument refusals (no GPU needed: the C entry points refuse before any launch) a
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import plm_sampling_ref as R  # noqa: E402
+import helpers  # noqa: E402
 
 GOLD = os.path.join(HERE, "golden", "sampling")
 
@@ -98,17 +98,7 @@ def test_c_entry_points_refuse_invalid_arguments():
 
 def test_sample_args_struct_matches_the_header(tmp_path):
     from megatts2_hierspeechpp_amd import _lib
-    fields = [f for f, _ in _lib.SampleArgs._fields_]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){",
-             'printf("%zu\\n", sizeof(hsp_sample_args));']
-    lines += [f'printf("%zu\\n", offsetof(hsp_sample_args, {f}));' for f in fields]
-    lines += ["return 0;}"]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals == [ctypes.sizeof(_lib.SampleArgs)] + [getattr(_lib.SampleArgs, f).offset for f in fields]
+    helpers.assert_struct_layouts(tmp_path, {"hsp_sample_args": _lib.SampleArgs})
 
 
 def test_seeds_helper_shapes():

@@ -6,13 +6,13 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import f0_edit_ref as R
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hsp_f0_edit_rows_f32", "hsp_duration_scaled_f32")
@@ -237,15 +237,7 @@ def test_header_binding_and_struct_layout_agree(tmp_path):
         [C.c_void_p, C.c_int64, C.c_void_p]                                # the same plus scale, sc_bs
     assert lib.hsp_version() == 104                                        # additive: the ABI number stays
     assert "NOT an identity row" in hdr and "bit-identical to hsp_duration_f32" in hdr
-    fields = [f for f, _ in _lib.F0EditArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){",
-                              'printf("%zu\\n", sizeof(hsp_f0_edit_args));']
-                             + [f'printf("%zu\\n", offsetof(hsp_f0_edit_args, {f}));' for f in fields] + ["return 0;}"]))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals == [C.sizeof(_lib.F0EditArgs)] + [getattr(_lib.F0EditArgs, f).offset for f in fields]
+    helpers.assert_struct_layouts(tmp_path, {"hsp_f0_edit_args": _lib.F0EditArgs})
 
 
 def einval_cases():

@@ -8,7 +8,6 @@ import glob
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ import torch.nn.functional as F
 
 import prosody_ref as R
 from oracle import hsp_oracle as O
+import helpers
 
 ROOT = R.ROOT
 POOL, D = R.POOL, R.D
@@ -225,15 +225,7 @@ def test_names_agree_across_header_ctypes_map_and_library(tmp_path):
     assert lib.hsp_version() == 104 and int(re.search(r"#define HSP_VERSION (\d+)", hdr).group(1)) == 104
     vmap = open(os.path.join(ROOT, "megatts2_hierspeechpp_amd", "csrc", "hsp.map")).read()
     assert "global: hsp_*;" in vmap and "prosody" not in vmap
-    fields = [f for f, _ in L.ProsodyArgs._fields_]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(['#include <stdio.h>', '#include <stddef.h>', '#include "hsp.h"', "int main(void){",
-                              'printf("%zu\\n", sizeof(hsp_prosody_args));']
-                             + [f'printf("%zu\\n", offsetof(hsp_prosody_args, {f}));' for f in fields] + ["return 0;}"]))
-    exe = tmp_path / "abi"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert vals == [ctypes.sizeof(L.ProsodyArgs)] + [getattr(L.ProsodyArgs, f).offset for f in fields]
+    helpers.assert_struct_layouts(tmp_path, {"hsp_prosody_args": L.ProsodyArgs})
 
 
 def test_the_distance_is_stated_once():
